@@ -20,7 +20,15 @@ collective.  Weak scaling: value = N * K / max-over-ranks(elapsed).  ``python be
 torchrun environment launches its own ranks (re-executes itself under ``torch.distributed.run`` on 127.0.0.1);
 rank 0 prints the one JSON line either way.
 
-The JSON line also carries:
+A plain run sets up, warms up, times K steps and prints the headline: `metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step` (+ the run's configuration and fallback counters).  ``--dump-outputs DIR`` also writes what the
+last timed step returned to its caller (tracked boxes / scores / ids of ``EMM.forward``, template features and search
+regions of ``EMM.extract_cache``) as DIR/<name>.npy (float32 / float64); the inputs are seeded, so two builds given the
+same arguments can be compared output for output.
+
+``--full`` adds every other leg below (each off in a plain run; the ``--no-*`` options still switch single legs off).
+With ``--full`` the timed loop carries the kernel event brackets of `roofline` on every 16th step, as it always has.
+The JSON line then also carries:
   roofline     — the kernel that runs the cross-correlation in the pipeline (search-region ROIAlign fused with the
                  depthwise xcorr): algorithmic bytes = window cells actually touched + templates + response
                  (SURVEY.md §8(d)-B restricted to that kernel, computed from the boxes) / the average launch duration
@@ -106,7 +114,7 @@ def other_config_runs(args):
             "configs[4]": ["--channels", "256", "--net-hw", "1056", "1920", "--tracks", "50"]}
     out = {}
     for name, extra in runs.items():
-        cmd = [sys.executable, os.path.abspath(__file__), "--steps", "200", "--warmup", "50", "--prewarm-ms", "200",
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--steps", "200", "--warmup", "50", "--prewarm-ms", "200",
                "--no-cpu-baseline", "--no-graph", "--extra-streams", "0", "--no-tracking-loop", "--no-other-configs", "--other-config-worker",
                "--argmax-pairs", "30" if name == "configs[2]" else "0"] + extra
         try:
@@ -760,6 +768,30 @@ def argmax_statistics(emm, ops, dev, n, pairs):
         "seconds": time.time() - t0}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, result, state):
+    """``--dump-outputs``: what one timed step hands its caller — ``EMM.forward``'s tracks and ``EMM.extract_cache``'s new
+    track memory — as <out_dir>/<name>.npy, float32 (float64 for the integer ids).  Above DUMP_LIMIT_BYTES in all, the
+    template features keep a fixed, seeded sample of their rows (tracks) and ``template_feature_rows.npy`` says which."""
+    import numpy as np
+    z, sr, _ = state
+    arrays = {"track_boxes": result[0].bbox, "track_scores": result[0].get_field("scores"),
+              "track_ids": result[0].get_field("ids"), "search_regions": sr[0].bbox, "template_features": z}
+    arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    arrays = {k: v.astype(np.float32 if v.dtype.kind == "f" and v.itemsize <= 4 else np.float64) for k, v in arrays.items()}
+    z = arrays["template_features"]
+    room = DUMP_LIMIT_BYTES - sum(v.nbytes for k, v in arrays.items() if k != "template_features")
+    if z.nbytes > room:
+        rows_fit = max(1, (room - 8 * z.shape[0]) // (z.nbytes // z.shape[0]))
+        keep = np.sort(np.random.RandomState(0).choice(z.shape[0], rows_fit, replace=False))
+        arrays["template_features"], arrays["template_feature_rows"] = z[keep], keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def self_launch(args):
     """``python bench.py --gpus N`` without a torchrun environment: start the N ranks ourselves (one process per
     GPU, rendezvous on 127.0.0.1) and let rank 0 print the JSON line."""
@@ -815,10 +847,19 @@ def main():
                          "collective backend becomes gloo and the JSON says so)")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the BASELINE.json configs[2] / configs[4] runs that follow the headline (`other_configs`)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every other leg: kernel rooflines, parity with the oracle and the "
+                         "reference golden, arg-max statistics, cache-warm / graph / multi-stream / tracking loops, host "
+                         "enqueue cost, the other BASELINE.json configs and the CPU baseline (several minutes)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned (EMM.forward's tracks, EMM.extract_cache's new track "
+                         "memory) as DIR/<name>.npy, float32 / float64")
     ap.add_argument("--other-config-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-budget", type=float, default=10.0, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     globals()["CHANNELS"] = args.channels            # the helpers above read the module constants
     globals()["NET_HW"] = tuple(args.net_hw)
     if args.cpu_baseline_worker:
@@ -852,6 +893,7 @@ def main():
         torch.set_num_threads(1)
         pinned = parallel.pin_rank_to_cores(local_rank, int(os.environ.get("LOCAL_WORLD_SIZE", world)))
     ops.load_library()
+    timer = args.full and not args.no_kernel_timer
 
     n = args.tracks
     image_wh = (NET_HW[1], NET_HW[0])
@@ -896,7 +938,7 @@ def main():
             torch.cuda.synchronize()
         for k in range(args.warmup):
             state, _ = step(k, state)
-        if not args.no_kernel_timer:
+        if timer:
             # events are created here, outside the timed region.  An event pair costs ~3 us of stream time, so the
             # two instrumented kernels are bracketed on every TIMER_STRIDE-th step only (bracketing all of them
             # slows the frame pair from 80 to 94 us); the samples still come from inside the timed region.
@@ -904,9 +946,11 @@ def main():
             ops.kernel_timer_begin(ops.TIMER_XCORR, cap, TIMER_STRIDE)
             ops.kernel_timer_begin(ops.TIMER_TOWER, cap, TIMER_STRIDE)
         elapsed, state_before_last, result = timed_run(args.steps)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, result, state)      # before any later step can reuse a buffer
         last_k = args.steps - 1
         post_steps = 0
-        if not args.no_kernel_timer:
+        if timer:
             # top the bracket samples up to MIN_TIMER_SAMPLES with a post-loop of the same frame pairs (NOT part of
             # `value`): the driver's default --steps 20 leaves two samples otherwise
             have = (args.steps + TIMER_STRIDE - 1) // TIMER_STRIDE
@@ -915,11 +959,11 @@ def main():
                 st_keep = state
                 timed_run(post_steps, k0=args.steps)
                 state = st_keep
-        xcorr_total_ms, xcorr_launches = (0.0, 0) if args.no_kernel_timer else ops.kernel_timer_end(ops.TIMER_XCORR)
-        tower_total_ms, tower_launches = (0.0, 0) if args.no_kernel_timer else ops.kernel_timer_end(ops.TIMER_TOWER)
+        xcorr_total_ms, xcorr_launches = ops.kernel_timer_end(ops.TIMER_XCORR) if timer else (0.0, 0)
+        tower_total_ms, tower_launches = ops.kernel_timer_end(ops.TIMER_TOWER) if timer else (0.0, 0)
         # cache-warm variant of the same loop (two alternating frames, as round 1 measured it): informational
         warm = None
-        if world == 1 and K > 2 and args.steps >= 100:
+        if args.full and world == 1 and K > 2 and args.steps >= 100:
             K_keep, K = K, 2
             timed_run(min(200, args.steps))
             w_elapsed, _, _ = timed_run(args.steps)
@@ -928,15 +972,15 @@ def main():
                     "ms_per_step": w_elapsed / args.steps * 1e3,
                     "note": "two alternating frames (77 MB) stay resident in the 256 MiB Infinity Cache"}
     multi = loop_stats = graph_stats = None
-    if world == 1 and args.graph and not args.no_graph:
+    if args.full and world == 1 and args.graph and not args.no_graph:
         try:
             with torch.no_grad():
                 graph_stats = hipgraph_loop_throughput(emm, feats, det, state, args.steps)
         except Exception as e:                      # a capture failure must not cost the run its headline
             graph_stats = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
-    if world == 1 and args.extra_streams > 1:
+    if args.full and world == 1 and args.extra_streams > 1:
         multi = multi_stream_throughput(emm, feats, det, args.extra_streams, dev)
-    if world == 1 and not args.no_tracking_loop:
+    if args.full and world == 1 and not args.no_tracking_loop:
         loop_stats = tracking_loop_throughput(n, dev, feats)
         loop_stats["with_refinement"] = tracking_loop_throughput(n, dev, feats, refine=True)
         # the same loops with every call shown the next frame's features (a streaming caller): the next head is launched a
@@ -967,15 +1011,16 @@ def main():
     # host cost of a step: the time to ENQUEUE frame pairs (no synchronisation), measured outside the timed region on
     # a burst short enough for the stream's queue; next to the GPU time per step it says how much host headroom a
     # rank has (eight ranks share one host)
-    with torch.no_grad():
-        torch.cuda.synchronize()
-        t_h = time.perf_counter()
-        for k in range(64):
-            state, _ = step(k, state)
-        host_enqueue_us = (time.perf_counter() - t_h) / 64 * 1e6
-        torch.cuda.synchronize()
-    rank_ms = parallel.gather_floats(elapsed / args.steps * 1e3, dev)
-    rank_host_us = parallel.gather_floats(host_enqueue_us, dev)
+    if args.full:
+        with torch.no_grad():
+            torch.cuda.synchronize()
+            t_h = time.perf_counter()
+            for k in range(64):
+                state, _ = step(k, state)
+            host_enqueue_us = (time.perf_counter() - t_h) / 64 * 1e6
+            torch.cuda.synchronize()
+        rank_ms = parallel.gather_floats(elapsed / args.steps * 1e3, dev)
+        rank_host_us = parallel.gather_floats(host_enqueue_us, dev)
     elapsed = parallel.max_over_ranks(elapsed, dev)
     backend = torch.distributed.get_backend() if parallel.is_distributed() else "none"
     dist_world = torch.distributed.get_world_size() if parallel.is_distributed() else 1
@@ -989,7 +1034,7 @@ def main():
         return
     fb_snapshot = dict(ops.FALLBACKS)        # (before the parity legs: those call the operators stand-alone, un-hinted)
     parity = None
-    if not args.no_parity:
+    if args.full and not args.no_parity:
         golden_ok = (CHANNELS, tuple(NET_HW), n) in ((128, (704, 1280), 30), (128, (704, 1280), 100),
                                                      (256, (1056, 1920), 50), (128, (800, 800), 4))
         parity = parity_report(emm, ops, feats[last_k % K], state_before_last, result,
@@ -1011,7 +1056,7 @@ def main():
     # the stand-alone xcorr operator (SURVEY.md §8d figure A) on the same search regions, timed the same way
     xcorr_bytes = 4.0 * n * CHANNELS * (rx * rx + rz * rz + ho * ho)
     xop = None
-    if not args.no_kernel_timer:
+    if timer:
         with torch.no_grad():
             z, sr, d = state
             x = ops.roi_align_levels(feats[0], sr[0].bbox, d[0].bbox, rx, emm.feature_extractor.pooler_x.scales, 2,
@@ -1032,14 +1077,14 @@ def main():
                        "runs the fused kernel)"}
     # an empty kernel of the graded kernel's launch shape under the same timer (see `empty_launch_event_bracket_us` below)
     floor_us = None
-    if not args.no_kernel_timer:
+    if timer:
         try:
             floor_us = ops.dispatch_floor_us(n * ((CHANNELS + 7) // 8), 512)
         except Exception:
             floor_us = None
     traffic = traffic_source = valu_insts = None
     tpath = os.path.join(ROOT, "profiles", "xcorr_traffic.json")
-    if os.path.exists(tpath):
+    if args.full and os.path.exists(tpath):
         try:
             tj = json.load(open(tpath))
             # the counters were taken on ONE kernel at ONE source state: refuse them for any other
@@ -1063,11 +1108,6 @@ def main():
         "ms_per_step": elapsed / args.steps * 1e3,
         "higher_is_better": True,
         "scaling": "weak",
-        "per_rank": {"ms_per_step_min": min(rank_ms), "ms_per_step_max": max(rank_ms),
-                     "host_enqueue_us_per_step_min": min(rank_host_us), "host_enqueue_us_per_step_max": max(rank_host_us),
-                     "cores_pinned_rank0": pinned, "omp_threads": torch.get_num_threads(),
-                     "note": "host_enqueue = Python + ctypes time to enqueue one frame pair (4 launches), no "
-                             "synchronisation; headroom = ms_per_step - host_enqueue"},
         "vs_baseline": None,
         # arithmetic type of the path: fp32 in and out of every kernel; the towers' transform-domain GEMMs run on the fp16 matrix
         # pipe with every fp32 operand as two fp16 parts of a power-of-two-scaled value (3 of 4 part products, fp32 accumulate):
@@ -1087,78 +1127,87 @@ def main():
                            % (world, bcast_bytes, {"nccl": "nccl (RCCL)"}.get(backend, backend), dist_world,
                               "; RANKS SHARE DEVICES (flow test, not a scaling measurement)" if shared else ""),
         },
-        "roofline": {
-            "bound": "hbm", "kernel": ops.fused_kernel_name() + " (search-region ROIAlign + depthwise xcorr)",
-            "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-            "traffic": traffic, "traffic_source": traffic_source,
-            # the same fraction by the bytes the counters saw instead of the algorithmic ones: at 100
-            # tracks overlapping search windows are served by L2 / MALL, so fewer bytes reach the fabric than the formula counts
-            "frac_by_counter_bytes": None if not traffic or xcorr_avg_s <= 0 else traffic / xcorr_avg_s / 1e9 / HBM_PEAK_GBS,
-            # the resource that actually binds this kernel: vector-instruction issue.  A wave64
-            # instruction occupies its SIMD's issue port for 4 cycles; SQ_INSTS_VALU (same counter passes and source stamp
-            # as `traffic`) x 4 cycles / (256 CUs x 4 SIMDs) / clock = the time the launch needs for vector issue alone,
-            # were it spread perfectly over the chip — `frac_of_duration` of the measured duration
-            "valu_issue": None if not valu_insts or xcorr_avg_s <= 0 else {
-                "wave_instructions_per_launch": valu_insts, "cycles_per_instruction": 4, "simds": 1024, "clock_ghz": CLOCK_GHZ,
-                "issue_bound_us": valu_insts * 4.0 / 1024.0 / (CLOCK_GHZ * 1e3),
-                "frac_of_duration": valu_insts * 4.0 / 1024.0 / (CLOCK_GHZ * 1e3) / (xcorr_avg_s * 1e6),
-                "note": "static counter (profiles/xcorr_traffic.json, SQ_INSTS_VALU of a separate --pmc pass at this source "
-                        "state), not measured by this run.  Since round 6 the correlation runs on the matrix pipe (45 fp16 matrix "
-                        "instructions per plane on two-part operands instead of 900 v_fmac_f32 per lane): vector issue is no longer "
-                        "what binds the kernel — its time is the start-up / pooling chain (dependent memory round trips) plus an "
-                        "LDS-bound correlation phase (DESIGN.md §3)"},
-            "algorithmic_bytes_per_launch": fused_bytes,
-            "avg_launch_us": xcorr_avg_s * 1e6, "launches_timed": xcorr_launches, "timer": TIMER_NOTE,
-            # an EMPTY kernel of the same launch shape bracketed by the same pair of events: an UPPER bound on the fixed cost
-            # inside `avg_launch_us` — rocprofv3's dispatch timestamps give 0.8-1.5 us for the same empty kernel
-            # (profiles/r04_loop_kernel_stats.md, smot::empty_kernel) and the same 17.5 us as the events for the graded
-            # kernel, so most of an empty bracket is the bracket.  No "fraction net of the floor" is derived from it.
-            "empty_launch_event_bracket_us": floor_us,
-            "timer_stride": TIMER_STRIDE, "post_loop_steps_for_timer_samples": post_steps,
-            "xcorr_op": xop,
-        },
-        # the kernel with the largest share of GPU time: the two conv3x3 towers, Winograd F(2x2,3x3) on the matrix cores
-        # (tower_roofline: which form ran, its multiply-adds against the fp32 pipe, effective_tflops = the direct
-        # convolution's FLOPs / time, the figure to compare implementations by).  At the 29 x 29 response of the second yaml
-        # family the timer brackets the blocked convolution kernel only (GroupNorm + heads run in a second kernel).
-        "roofline_tower": None if tower_launches == 0 else tower_roofline(n, tower_total_ms, tower_launches, rx - rz + 1),
-        # the whole frame pair against HBM: compulsory bytes / ms_per_step.  The path is issue-,
-        # matrix-pipe- and latency-bound, so this fraction is small by construction.
-        "roofline_path": (lambda pb: {"bound": "hbm", "algorithmic_bytes_per_step": pb,
-                                      "achieved": pb / (elapsed / args.steps) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                      "frac": pb / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS})(
-            path_algorithmic_bytes(boxes_cpu, image_wh, CHANNELS, rz, rx)),
-        "parity": parity,
-        "cache_warm_loop": warm,
-        "hipgraph_loop": graph_stats,
-        "multi_stream": multi,
-        "tracking_loop": loop_stats,
         # capacity cliffs that fell back to a slower path during THIS run (siammot_amd.ops.FALLBACKS; all zero = none)
         "fallbacks": {k: int(fb_snapshot.get(k, 0)) for k in ("refine_library_gemm", "host_solver", "unhinted_head",
                                                                 "general_frame")},
     }
-    if world == 1 and not args.no_other_configs and not args.other_config_worker:
-        out["other_configs"] = other_config_runs(args)
-    if world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(n)
-    # the last thing on the line (a log tail keeps it): the numbers a reviewer looks for first, compact
-    rt, am = out.get("roofline_tower") or {}, ((out.get("parity") or {}).get("argmax_statistics") or {})
-    out["summary"] = {
-        "frame_pairs_per_s": out["value"], "ms_per_step": out["ms_per_step"],
-        "graded_kernel_us": out["roofline"]["avg_launch_us"], "graded_kernel_frac_of_hbm_peak": out["roofline"]["frac"],
-        "tower_us": rt.get("avg_launch_us"), "tower_form": rt.get("form"),
-        "tower_f16_mfma_frac": (rt.get("f16_mfma") or {}).get("frac"),
-        "host_enqueue_us_per_step": max(rank_host_us),
-        "tracking_loop_ms_per_frame": None if not loop_stats else {
-            "plain": loop_stats.get("ms_per_frame"), "with_refinement": (loop_stats.get("with_refinement") or {}).get("ms_per_frame"),
-            "next_frame_shown": (loop_stats.get("next_frame_shown") or {}).get("ms_per_frame")},
-        "argmax_statistics": {k: am.get(k) for k in ("frame_pairs", "tracks_total", "argmax_exact", "min_iou",
-                                                     "tracks_below_1e-3_iou_bar")} if am else None,
-        "other_configs_ms_per_step": {k: v.get("ms_per_step") for k, v in (out.get("other_configs") or {}).items()},
-        "cpu_baseline_frame_pairs_per_s": (out.get("cpu_baseline") or {}).get("value"),
-        "methodology_version": "r06 (tracking_loop legs: median of three chunks, detections as ready-made BoxLists — as r05; "
-                               "r01-r04 built a BoxList per frame inside the timed loop: ~4 us per frame more)",
-    }
+    if args.full:
+        out.update({
+            "per_rank": {"ms_per_step_min": min(rank_ms), "ms_per_step_max": max(rank_ms),
+                         "host_enqueue_us_per_step_min": min(rank_host_us), "host_enqueue_us_per_step_max": max(rank_host_us),
+                         "cores_pinned_rank0": pinned, "omp_threads": torch.get_num_threads(),
+                         "note": "host_enqueue = Python + ctypes time to enqueue one frame pair (4 launches), no "
+                                 "synchronisation; headroom = ms_per_step - host_enqueue"},
+            "roofline": {
+                "bound": "hbm", "kernel": ops.fused_kernel_name() + " (search-region ROIAlign + depthwise xcorr)",
+                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                "traffic": traffic, "traffic_source": traffic_source,
+                # the same fraction by the bytes the counters saw instead of the algorithmic ones: at 100
+                # tracks overlapping search windows are served by L2 / MALL, so fewer bytes reach the fabric than the formula counts
+                "frac_by_counter_bytes": None if not traffic or xcorr_avg_s <= 0 else traffic / xcorr_avg_s / 1e9 / HBM_PEAK_GBS,
+                # the resource that actually binds this kernel: vector-instruction issue.  A wave64
+                # instruction occupies its SIMD's issue port for 4 cycles; SQ_INSTS_VALU (same counter passes and source stamp
+                # as `traffic`) x 4 cycles / (256 CUs x 4 SIMDs) / clock = the time the launch needs for vector issue alone,
+                # were it spread perfectly over the chip — `frac_of_duration` of the measured duration
+                "valu_issue": None if not valu_insts or xcorr_avg_s <= 0 else {
+                    "wave_instructions_per_launch": valu_insts, "cycles_per_instruction": 4, "simds": 1024, "clock_ghz": CLOCK_GHZ,
+                    "issue_bound_us": valu_insts * 4.0 / 1024.0 / (CLOCK_GHZ * 1e3),
+                    "frac_of_duration": valu_insts * 4.0 / 1024.0 / (CLOCK_GHZ * 1e3) / (xcorr_avg_s * 1e6),
+                    "note": "static counter (profiles/xcorr_traffic.json, SQ_INSTS_VALU of a separate --pmc pass at this source "
+                            "state), not measured by this run.  Since round 6 the correlation runs on the matrix pipe (45 fp16 matrix "
+                            "instructions per plane on two-part operands instead of 900 v_fmac_f32 per lane): vector issue is no longer "
+                            "what binds the kernel — its time is the start-up / pooling chain (dependent memory round trips) plus an "
+                            "LDS-bound correlation phase (DESIGN.md §3)"},
+                "algorithmic_bytes_per_launch": fused_bytes,
+                "avg_launch_us": xcorr_avg_s * 1e6, "launches_timed": xcorr_launches, "timer": TIMER_NOTE,
+                # an EMPTY kernel of the same launch shape bracketed by the same pair of events: an UPPER bound on the fixed cost
+                # inside `avg_launch_us` — rocprofv3's dispatch timestamps give 0.8-1.5 us for the same empty kernel
+                # (profiles/r04_loop_kernel_stats.md, smot::empty_kernel) and the same 17.5 us as the events for the graded
+                # kernel, so most of an empty bracket is the bracket.  No "fraction net of the floor" is derived from it.
+                "empty_launch_event_bracket_us": floor_us,
+                "timer_stride": TIMER_STRIDE, "post_loop_steps_for_timer_samples": post_steps,
+                "xcorr_op": xop,
+            },
+            # the kernel with the largest share of GPU time: the two conv3x3 towers, Winograd F(2x2,3x3) on the matrix cores
+            # (tower_roofline: which form ran, its multiply-adds against the fp32 pipe, effective_tflops = the direct
+            # convolution's FLOPs / time, the figure to compare implementations by).  At the 29 x 29 response of the second yaml
+            # family the timer brackets the blocked convolution kernel only (GroupNorm + heads run in a second kernel).
+            "roofline_tower": None if tower_launches == 0 else tower_roofline(n, tower_total_ms, tower_launches, rx - rz + 1),
+            # the whole frame pair against HBM: compulsory bytes / ms_per_step.  The path is issue-,
+            # matrix-pipe- and latency-bound, so this fraction is small by construction.
+            "roofline_path": (lambda pb: {"bound": "hbm", "algorithmic_bytes_per_step": pb,
+                                          "achieved": pb / (elapsed / args.steps) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                          "frac": pb / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS})(
+                path_algorithmic_bytes(boxes_cpu, image_wh, CHANNELS, rz, rx)),
+            "parity": parity,
+            "cache_warm_loop": warm,
+            "hipgraph_loop": graph_stats,
+            "multi_stream": multi,
+            "tracking_loop": loop_stats,
+        })
+    if args.full:
+        if world == 1 and not args.no_other_configs and not args.other_config_worker:
+            out["other_configs"] = other_config_runs(args)
+        if world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(n)
+        # the last thing on the line (a log tail keeps it): the numbers a reviewer looks for first, compact
+        rt, am = out.get("roofline_tower") or {}, ((out.get("parity") or {}).get("argmax_statistics") or {})
+        out["summary"] = {
+            "frame_pairs_per_s": out["value"], "ms_per_step": out["ms_per_step"],
+            "graded_kernel_us": out["roofline"]["avg_launch_us"], "graded_kernel_frac_of_hbm_peak": out["roofline"]["frac"],
+            "tower_us": rt.get("avg_launch_us"), "tower_form": rt.get("form"),
+            "tower_f16_mfma_frac": (rt.get("f16_mfma") or {}).get("frac"),
+            "host_enqueue_us_per_step": max(rank_host_us),
+            "tracking_loop_ms_per_frame": None if not loop_stats else {
+                "plain": loop_stats.get("ms_per_frame"), "with_refinement": (loop_stats.get("with_refinement") or {}).get("ms_per_frame"),
+                "next_frame_shown": (loop_stats.get("next_frame_shown") or {}).get("ms_per_frame")},
+            "argmax_statistics": {k: am.get(k) for k in ("frame_pairs", "tracks_total", "argmax_exact", "min_iou",
+                                                         "tracks_below_1e-3_iou_bar")} if am else None,
+            "other_configs_ms_per_step": {k: v.get("ms_per_step") for k, v in (out.get("other_configs") or {}).items()},
+            "cpu_baseline_frame_pairs_per_s": (out.get("cpu_baseline") or {}).get("value"),
+            "methodology_version": "r06 (tracking_loop legs: median of three chunks, detections as ready-made BoxLists — as r05; "
+                                   "r01-r04 built a BoxList per frame inside the timed loop: ~4 us per frame more)",
+        }
     print(json.dumps(out))
     sys.stdout.flush()
     parallel.shutdown()

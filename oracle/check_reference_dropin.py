@@ -14,7 +14,8 @@ registry.  No kernel is launched (CPU-only container): what is checked is the pl
   * with track memory it calls ``EMM.forward(features, template_boxes, sr=..., template_features=...)`` — the call is
     intercepted here and its argument structure checked (the kernels themselves are covered by ``pytest -m gpu``).
 
-Prints one JSON line; exit code 0 on success.  Build container only (needs /root/reference).
+Prints one JSON line; exit code 0 on success.  ``--golden`` also writes what was seen to tests/golden/reference_dropin.json,
+which tests/test_reference_dropin.py checks the package against where the reference is absent.  Build container only (needs /root/reference).
 """
 import json
 import os
@@ -30,6 +31,8 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
 import golden_inputs as gi            # noqa: E402
 import gen_golden as gg               # noqa: E402
+
+GOLDEN = os.path.join(ROOT, "tests", "golden", "reference_dropin.json")
 
 
 def main():
@@ -123,9 +126,19 @@ def main():
     _, tracks, _ = head(feats, track_memory=memory)                          # reference code, track_head.py:37-46
     assert calls["forward"] == dict(n_feat=5, n_boxes=2, sr_size=(W + 1024, H + 1024),
                                     z_shape=(2, case["channels"], 15, 15))
-    print(json.dumps({"ok": True, "tracker_class": "%s.%s" % (type(head.tracker).__module__, type(head.tracker).__name__),
-                      "track_head_class": "%s.%s" % (TrackHead.__module__, TrackHead.__name__),
-                      "state_dict_keys": len(sd), "tracks_started": started}))
+    res = {"ok": True, "tracker_class": "%s.%s" % (type(head.tracker).__module__, type(head.tracker).__name__),
+           "track_head_class": "%s.%s" % (TrackHead.__module__, TrackHead.__name__),
+           "state_dict_keys": len(sd), "tracks_started": started}
+    print(json.dumps(res))
+    if "--golden" in sys.argv:
+        # what tests/test_reference_dropin.py checks without the reference: its EMM's state_dict layout and the calls its
+        # TrackHead made on the tracker
+        res.update(state_dict={k: {"shape": list(v.shape), "dtype": str(v.dtype)} for k, v in sorted(sd.items())},
+                   calls={"extract_cache": list(calls["extract_cache"]),
+                          "forward": {k: list(v) if isinstance(v, tuple) else v for k, v in calls["forward"].items()}})
+        with open(GOLDEN, "w") as f:
+            json.dump(res, f, indent=1, sort_keys=True)
+            f.write("\n")
 
 
 if __name__ == "__main__":

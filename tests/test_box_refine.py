@@ -332,5 +332,7 @@ def test_yaml_sized_box_head_host_logic_matches_reference_golden():
         r = RefineTracks(head)(feats, [_proposals(inp["track_boxes"], inp["track_ids"], "cpu", inp["track_labels"],
                                                   inp["track_scores"], c["image_wh"])])[0]
     assert r.get_field("ids").numpy().tolist() == g["refine_ids"].tolist()
-    np.testing.assert_allclose(r.bbox.numpy(), g["refine_bbox"], rtol=0, atol=1e-3)
+    # the box bound of the GPU twin above (3e-3 px): the CPU BLAS sums fc6's 6,272 terms in an order that depends on the
+    # host's instruction set (MKL's SSE4.2 kernel moves one coordinate by 1.7e-3 px from the AVX-512 kernel the golden saw)
+    np.testing.assert_allclose(r.bbox.numpy(), g["refine_bbox"], rtol=0, atol=3e-3)
     np.testing.assert_allclose(r.get_field("scores").numpy(), g["refine_scores"], rtol=0, atol=1e-5)

@@ -119,7 +119,7 @@ def test_bench_gpus2_plain_command_launches_its_own_ranks():
     import subprocess
     n_dev = torch.cuda.device_count()
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "100", "--warmup", "10",
-           "--prewarm-ms", "50", "--no-cpu-baseline", "--extra-streams", "0"]
+           "--prewarm-ms", "50", "--full", "--no-cpu-baseline", "--extra-streams", "0"]
     if n_dev < 2:
         cmd.append("--allow-shared-gpu")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "SMOT_DIST_BACKEND")}

@@ -154,35 +154,42 @@ def test_container_readers_on_decoder_stand_ins(monkeypatch, rotate):
         video.CV2VideoIterator("missing.mp4")
 
 
-REFERENCE = os.environ.get("SIAMMOT_REFERENCE", "/root/reference")
+# the reference's demos/video_iterator.py on these stand-ins: rotation tag, the clip's seed, a read that fails (180 only),
+# each reader, all frames / a subset — its outputs are stored in tests/golden/video_iterators.npz (oracle/gen_golden_video.py)
+REFERENCE_ITERATOR_CASES = [(k, rotate, kind, idxs) for k, rotate in enumerate((0, 90, 180, 270))
+                            for kind in ("decord", "cv2") for idxs in (None, [4, 0, 3])]
 
 
-@pytest.mark.skipif(not os.path.isfile(os.path.join(REFERENCE, "demos", "video_iterator.py")), reason="reference checkout not present")
-def test_container_readers_equal_the_reference_iterators_on_the_same_stand_ins(monkeypatch):
-    """The reference's UNMODIFIED demos/video_iterator.py imported on the same decoder stand-ins (its top-level ``import
-    decord / cv2 / ffmpeg`` resolve to them): its ``DecordVideoIterator`` / ``CV2VideoIterator`` / ``build_video_iterator``
-    and this package's yield the same frame ids and the same arrays — every rotation tag, subsets, a failing read."""
-    import importlib.util
+def _reference_iterator_case(case):
+    """(clip path, frame_idxs, reader, golden key) of one case; (re)builds the clip from its seed."""
+    k, rotate, kind, idxs = case
+    path = "clip_%d.mp4" % rotate
+    _fake_clip(path, n=6, hw=(5, 9), rotate=rotate, fail_at=(4 if rotate == 180 else None), seed=10 + k)
+    return path, idxs, kind, "%s_r%d_%s" % (kind, rotate, "all" if idxs is None else "sub")
+
+
+def test_container_readers_equal_the_reference_iterators_on_the_same_stand_ins(monkeypatch, golden_dir):
+    """The reference's UNMODIFIED demos/video_iterator.py, run on the same decoder stand-ins (its top-level ``import
+    decord / cv2 / ffmpeg`` resolved to them; tests/golden/video_iterators.npz, oracle/gen_golden_video.py), and this
+    package's ``DecordVideoIterator`` / ``CV2VideoIterator`` / ``build_video_iterator`` yield the same length, frame ids
+    and arrays — every rotation tag, subsets, a failing read."""
     from siammot_amd import video
     _install_fake_decoders(monkeypatch)
-    spec = importlib.util.spec_from_file_location("ref_video_iterator", os.path.join(REFERENCE, "demos", "video_iterator.py"))
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
+    golden = np.load(os.path.join(golden_dir, "video_iterators.npz"))
     checked = 0
-    for k, rotate in enumerate((0, 90, 180, 270)):
-        path = "clip_%d.mp4" % rotate
-        _fake_clip(path, n=6, hw=(5, 9), rotate=rotate, fail_at=(4 if rotate == 180 else None), seed=10 + k)
-        for kind in ("decord", "cv2"):
-            for idxs in (None, [4, 0, 3]):
-                mine = video.build_video_iterator(path, video_decode=kind)
-                theirs = ref.build_video_iterator(path, video_decode=kind)
-                if idxs is not None:
-                    mine, theirs = type(mine)(path, frame_idxs=idxs), type(theirs)(path, frame_idxs=idxs)
-                a, b = list(mine()), list(theirs())
-                assert len(mine) == len(theirs) and [int(i) for i, _ in a] == [int(i) for i, _ in b]
-                for (_, fa), (_, fb) in zip(a, b):
-                    assert np.array_equal(fa, fb)
-                    checked += 1
+    for case in REFERENCE_ITERATOR_CASES:
+        path, idxs, kind, key = _reference_iterator_case(case)
+        mine = video.build_video_iterator(path, video_decode=kind)
+        if idxs is not None:
+            mine = type(mine)(path, frame_idxs=idxs)
+        a = list(mine())
+        assert len(mine) == int(golden[key + "/len"]), key
+        assert [int(i) for i, _ in a] == golden[key + "/ids"].tolist(), key
+        want = golden[key + "/frames"]
+        assert len(a) == len(want), key
+        for (_, fa), fb in zip(a, want):
+            assert np.array_equal(fa, fb), key
+            checked += 1
     assert checked > 60
 
 
