@@ -33,6 +33,7 @@ typedef void* smot_stream_t; /* hipStream_t */
 #define SMOT_ERR_UNSUPPORTED (-2)  /* legal in the reference but not implemented here (documented per call) */
 
 #define SMOT_MAX_LEVELS 8
+#define SMOT_MAX_IMAGES 64          /* images per call of the batched head (smot_emm_*_batched_fwd) */
 /* ABI history.
  * 10: the image of smot_emm_tower_pack grew (fp32 image + three-part bf16 image: ask smot_emm_tower_pack_floats), an image
  *     packed by a version-9 library is too short for this one; smot_emm_tower_form added.  (9: order-hint entries of 528 floats)
@@ -48,8 +49,10 @@ typedef void* smot_stream_t; /* hipStream_t */
  *     (one form); smot_emm_predictor_fwd may use the head of its `logits` output as scratch before it writes the logits;
  *     smot_sr_xcorr_fused_fwd / smot_emm_track_fwd correlate on the matrix cores (no signature change: responses equal
  *     smot_xcorr_dw_fwd's to rounding, not bit for bit).
+ * 14: smot_emm_track_batched_fwd / smot_emm_extract_cache_batched_fwd and SMOT_MAX_IMAGES added (several images per
+ *     call); existing entry points unchanged.
  */
-#define SMOT_ABI_VERSION 13
+#define SMOT_ABI_VERSION 14
 
 /* ABI version of the loaded library (checked by the host layer at load time). */
 int smot_abi_version(void);
@@ -405,6 +408,36 @@ int smot_emm_extract_cache_masked_fwd(const float* const* feats, const int* heig
                                       int sampling_ratio, float pad_pixels, float search_expansion,
                                       float min_search_wh, float* templates, float* sr, float* order_hint,
                                       smot_stream_t stream);
+
+/*
+ * The two halves of a frame pair over a BATCH of images in one set of launches (several video streams on one device).
+ * Arguments as in the single-image twins, plus num_images and row_start, a HOST array of num_images + 1 ints:
+ *   feats[l]  points at [num_images, C, H_l, W_l] contiguous maps; all images share one map size per level;
+ *   the rows of image b are [row_start[b], row_start[b+1]) of boxes / sr / templates / the outputs (N = row_start[num_images]);
+ *   1 <= num_images <= SMOT_MAX_IMAGES, row_start[0] == 0, row_start non-decreasing: anything else is SMOT_ERR_BAD_ARG
+ *   before any launch.  Images without rows and N == 0 are legal.
+ * The rows of image b get exactly what the single-image call gives on that image's maps with those rows (bit for bit).
+ * ws: smot_emm_track_ws_floats(N, C, rx, rz) floats.  clip_w / clip_h are the one image size of the batch.  An order hint
+ * of a batched extraction describes its rows whatever the split: the sample tables in it are relative to the image, and
+ * the consuming kernel takes the image of a row from ITS row_start.  Hints cover at most 256 rows, as for one image.
+ */
+int smot_emm_track_batched_fwd(const float* const* feats, const int* heights, const int* widths,
+                               const int* pad_cells, const float* scales, int num_levels, int C,
+                               const float* boxes, const float* sr, const float* templates, int N,
+                               int rx, int rz, int sampling_ratio,
+                               const float* const* predictor_params, int gn_groups, float gn_eps,
+                               const float* hann, int up, float pad_pixels,
+                               float one_minus_sigma, float sigma, int use_centerness,
+                               float clip_w, float clip_h,
+                               float* ws, float* bb, float* conf, int64_t* idx, const float* order_hint,
+                               smot_stream_t stream, int num_images, const int* row_start);
+
+int smot_emm_extract_cache_batched_fwd(const float* const* feats, const int* heights, const int* widths,
+                                       const float* scales, int num_levels, int C,
+                                       const float* boxes, int N, int rz, int sampling_ratio,
+                                       float pad_pixels, float search_expansion, float min_search_wh,
+                                       float* templates, float* sr, float* order_hint, smot_stream_t stream,
+                                       int num_images, const int* row_start);
 
 /*
  * Box-head post-processing of the propagated tracks + the score average of _refine_tracks, one launch, no host sync.

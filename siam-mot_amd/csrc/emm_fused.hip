@@ -5,6 +5,7 @@
 //   smot_emm_track_fwd         == the inference branch of EMM.forward          (reference EMM/track_core.py:28-79)
 //   smot_emm_extract_cache_fwd == EMM.extract_cache                             (reference EMM/track_core.py:81-98)
 #include "smot_common.h"
+#include "roi_common.h"
 #include "logit_src.h"
 #include "knobs.h"
 
@@ -32,6 +33,22 @@ int sr_xcorr_gather_impl(const float* const* feats, const int* heights, const in
                          const float* scales, int num_levels, int C, const float* boxes, const float* sr,
                          const float* templates, int N, int rx, int rz, int sampling_ratio, float* resp, hipStream_t st,
                          float* plane_max);
+// batched forms (smot_emm_*_batched_fwd)
+int launch_extract_cache_batched(const float* const* feats, const int* heights, const int* widths, const float* scales,
+                                 int num_levels, int C, const float* boxes, int N, int rz, float pad_pixels, float half_e,
+                                 float two_e, float min_wh, float* templates, float* sr, float* order_hint, hipStream_t st,
+                                 const ImageRows& I);
+int sr_xcorr_fused_batched_impl(const float* const* feats, const int* heights, const int* widths, const int* pad_cells,
+                                const float* scales, int num_levels, int C, const float* boxes, const float* sr,
+                                const float* templates, int N, float* resp, const float* order_hint, hipStream_t st,
+                                const int** hint_status, float* plane_max, const ImageRows& I);
+int sr_xcorr_gather_batched_impl(const float* const* feats, const int* heights, const int* widths, const int* pad_cells,
+                                 const float* scales, int num_levels, int C, const float* boxes, const float* sr,
+                                 const float* templates, int N, float* resp, hipStream_t st, float* plane_max,
+                                 const ImageRows& I);
+int roi_align_levels_batched(const float* const* feats, const int* heights, const int* widths, const int* pad_cells,
+                             const float* scales, int num_levels, int C, const float* rois, const float* level_boxes, int R,
+                             int out_hw, int sampling_ratio, float* out, hipStream_t st, const ImageRows& I);
 }  // namespace smot
 
 static inline bool p12_form3(int N, int C, int ho) { return smot_emm_tower_form(N, C, ho) == 3; }
@@ -45,17 +62,17 @@ extern "C" long long smot_emm_track_ws_floats(int N, int C, int rx, int rz) {
            n * smot_emm_decode_ws_floats((int)ho, 16);
 }
 
-extern "C" int smot_emm_track_fwd(const float* const* feats, const int* heights, const int* widths,
-                                  const int* pad_cells, const float* scales, int num_levels, int C,
-                                  const float* boxes, const float* sr, const float* templates, int N, int rx,
-                                  int rz, int sampling_ratio, const float* const* predictor_params, int gn_groups,
-                                  float gn_eps, const float* hann, int up, float pad_pixels,
-                                  float one_minus_sigma, float sigma, int use_centerness, float clip_w,
-                                  float clip_h, float* ws, float* bb, float* conf, int64_t* idx,
-                                  const float* order_hint, smot_stream_t stream) {
+// The head of smot_emm_track_fwd (I == nullptr) and of its batched twin (I = the validated row ranges of the batch): the
+// pooling launches take the batch's image of every row, the towers and the decode are per row and the same.
+static int emm_track_impl(const float* const* feats, const int* heights, const int* widths,
+                          const int* pad_cells, const float* scales, int num_levels, int C,
+                          const float* boxes, const float* sr, const float* templates, int N, int rx,
+                          int rz, int sampling_ratio, const float* const* predictor_params, int gn_groups,
+                          float gn_eps, const float* hann, int up, float pad_pixels,
+                          float one_minus_sigma, float sigma, int use_centerness, float clip_w,
+                          float clip_h, float* ws, float* bb, float* conf, int64_t* idx,
+                          const float* order_hint, smot_stream_t stream, const smot::ImageRows* I) {
     using namespace smot;
-    SMOT_REQUIRE(N >= 0 && C > 0 && rz > 0 && rx >= rz, "emm_track: bad sizes N=%d C=%d rx=%d rz=%d", N, C, rx, rz);
-    if (N == 0) return SMOT_OK;
     SMOT_REQUIRE(predictor_params && ws && boxes && sr && templates, "emm_track: null pointer");
     SMOT_REQUIRE(((uintptr_t)ws & 15) == 0, "emm_track: workspace must be 16-byte aligned");
     const int ho = rx - rz + 1;
@@ -74,20 +91,26 @@ extern "C" int smot_emm_track_fwd(const float* const* feats, const int* heights,
         // pooling feeds the correlation inside one kernel: the search-region tensor never reaches HBM
         // (a hint the kernel honours is VERIFIED against `boxes` / `sr` by it; `poison` = the list's status word)
         float* pm = (C <= 7 * ho * ho && p12_form3(N, C, ho)) ? logits : nullptr;
-        rc = sr_xcorr_fused_impl(feats, heights, widths, pad_cells, scales, num_levels, C, boxes, sr, templates, N, resp,
-                                 nullptr, order_hint, (hipStream_t)stream, &poison, pm);
+        rc = I ? sr_xcorr_fused_batched_impl(feats, heights, widths, pad_cells, scales, num_levels, C, boxes, sr, templates, N,
+                                             resp, order_hint, (hipStream_t)stream, &poison, pm, *I)
+               : sr_xcorr_fused_impl(feats, heights, widths, pad_cells, scales, num_levels, C, boxes, sr, templates, N, resp,
+                                     nullptr, order_hint, (hipStream_t)stream, &poison, pm);
         if (rc) return rc;
         plane_max = pm;
     } else if (rx == 35 && rz == 7 && sampling_ratio == 2 && !no_fuse) {
         // the second yaml family's shape: gathers + correlation in one kernel (sr_xcorr_small.hip), same arithmetic
         float* pm = (C <= 7 * ho * ho && p12_form3(N, C, ho)) ? logits : nullptr;
-        rc = sr_xcorr_gather_impl(feats, heights, widths, pad_cells, scales, num_levels, C, boxes, sr, templates, N, rx, rz,
-                                  sampling_ratio, resp, (hipStream_t)stream, pm);
+        rc = I ? sr_xcorr_gather_batched_impl(feats, heights, widths, pad_cells, scales, num_levels, C, boxes, sr, templates, N,
+                                              resp, (hipStream_t)stream, pm, *I)
+               : sr_xcorr_gather_impl(feats, heights, widths, pad_cells, scales, num_levels, C, boxes, sr, templates, N, rx, rz,
+                                      sampling_ratio, resp, (hipStream_t)stream, pm);
         if (rc) return rc;
         plane_max = pm;
     } else {
-        rc = smot_roi_align_levels_fwd(feats, heights, widths, pad_cells, scales, num_levels, C, sr, boxes, N, rx, rx,
-                                       sampling_ratio, x, nullptr, stream);
+        rc = I ? roi_align_levels_batched(feats, heights, widths, pad_cells, scales, num_levels, C, sr, boxes, N, rx,
+                                          sampling_ratio, x, (hipStream_t)stream, *I)
+               : smot_roi_align_levels_fwd(feats, heights, widths, pad_cells, scales, num_levels, C, sr, boxes, N, rx, rx,
+                                           sampling_ratio, x, nullptr, stream);
         if (rc) return rc;
         rc = smot_xcorr_dw_fwd(x, templates, resp, N, C, rx, rz, stream);
         if (rc) return rc;
@@ -113,6 +136,43 @@ extern "C" int smot_emm_track_fwd(const float* const* feats, const int* heights,
                        clip_w, clip_h, cand, bb, conf, idx, tickets_zeroed, (hipStream_t)stream, poison);
 }
 
+extern "C" int smot_emm_track_fwd(const float* const* feats, const int* heights, const int* widths,
+                                  const int* pad_cells, const float* scales, int num_levels, int C,
+                                  const float* boxes, const float* sr, const float* templates, int N, int rx,
+                                  int rz, int sampling_ratio, const float* const* predictor_params, int gn_groups,
+                                  float gn_eps, const float* hann, int up, float pad_pixels,
+                                  float one_minus_sigma, float sigma, int use_centerness, float clip_w,
+                                  float clip_h, float* ws, float* bb, float* conf, int64_t* idx,
+                                  const float* order_hint, smot_stream_t stream) {
+    using namespace smot;
+    SMOT_REQUIRE(N >= 0 && C > 0 && rz > 0 && rx >= rz, "emm_track: bad sizes N=%d C=%d rx=%d rz=%d", N, C, rx, rz);
+    if (N == 0) return SMOT_OK;
+    return emm_track_impl(feats, heights, widths, pad_cells, scales, num_levels, C, boxes, sr, templates, N, rx, rz,
+                          sampling_ratio, predictor_params, gn_groups, gn_eps, hann, up, pad_pixels, one_minus_sigma, sigma,
+                          use_centerness, clip_w, clip_h, ws, bb, conf, idx, order_hint, stream, nullptr);
+}
+
+// A batch of images in one set of launches (include/smot_emm.h): the row ranges are checked before anything is launched.
+extern "C" int smot_emm_track_batched_fwd(const float* const* feats, const int* heights, const int* widths,
+                                          const int* pad_cells, const float* scales, int num_levels, int C,
+                                          const float* boxes, const float* sr, const float* templates, int N, int rx,
+                                          int rz, int sampling_ratio, const float* const* predictor_params, int gn_groups,
+                                          float gn_eps, const float* hann, int up, float pad_pixels,
+                                          float one_minus_sigma, float sigma, int use_centerness, float clip_w,
+                                          float clip_h, float* ws, float* bb, float* conf, int64_t* idx,
+                                          const float* order_hint, smot_stream_t stream, int num_images,
+                                          const int* row_start) {
+    using namespace smot;
+    SMOT_REQUIRE(N >= 0 && C > 0 && rz > 0 && rx >= rz, "emm_track_batched: bad sizes N=%d C=%d rx=%d rz=%d", N, C, rx, rz);
+    ImageRows I;
+    const int rc = fill_image_rows(&I, num_images, row_start, N, "emm_track_batched");
+    if (rc) return rc;
+    if (N == 0) return SMOT_OK;
+    return emm_track_impl(feats, heights, widths, pad_cells, scales, num_levels, C, boxes, sr, templates, N, rx, rz,
+                          sampling_ratio, predictor_params, gn_groups, gn_eps, hann, up, pad_pixels, one_minus_sigma, sigma,
+                          use_centerness, clip_w, clip_h, ws, bb, conf, idx, order_hint, stream, &I);
+}
+
 extern "C" int smot_emm_extract_cache_fwd(const float* const* feats, const int* heights, const int* widths,
                                           const float* scales, int num_levels, int C, const float* boxes, int N,
                                           int rz, int sampling_ratio, float pad_pixels, float search_expansion,
@@ -131,6 +191,30 @@ extern "C" int smot_emm_extract_cache_fwd(const float* const* feats, const int* 
     int zero_pad[SMOT_MAX_LEVELS] = {0};
     int rc = smot_roi_align_levels_fwd(feats, heights, widths, zero_pad, scales, num_levels, C, boxes, boxes, N, rz, rz,
                                        sampling_ratio, templates, nullptr, stream);
+    if (rc) return rc;
+    return smot_search_region_fwd(boxes, N, pad_pixels, search_expansion, min_search_wh, sr, stream);
+}
+
+// EMM.extract_cache over a batch of images (include/smot_emm.h): same routing as smot_emm_extract_cache_fwd.
+extern "C" int smot_emm_extract_cache_batched_fwd(const float* const* feats, const int* heights, const int* widths,
+                                                  const float* scales, int num_levels, int C, const float* boxes, int N,
+                                                  int rz, int sampling_ratio, float pad_pixels, float search_expansion,
+                                                  float min_search_wh, float* templates, float* sr, float* order_hint,
+                                                  smot_stream_t stream, int num_images, const int* row_start) {
+    using namespace smot;
+    SMOT_REQUIRE(N >= 0 && num_levels >= 1 && num_levels <= SMOT_MAX_LEVELS, "emm_extract_cache_batched: bad sizes");
+    ImageRows I;
+    int rc = fill_image_rows(&I, num_images, row_start, N, "emm_extract_cache_batched");
+    if (rc) return rc;
+    if (N == 0) return SMOT_OK;
+    if ((rz == 15 || rz == 7) && sampling_ratio == 2 && !knobs().roi_generic) {
+        const float half_e = (float)((double)search_expansion / 2.0);
+        const float two_e = (float)((double)search_expansion * 2.0);
+        return launch_extract_cache_batched(feats, heights, widths, scales, num_levels, C, boxes, N, rz, pad_pixels, half_e,
+                                            two_e, min_search_wh, templates, sr, order_hint, (hipStream_t)stream, I);
+    }
+    rc = roi_align_levels_batched(feats, heights, widths, nullptr, scales, num_levels, C, boxes, boxes, N, rz, sampling_ratio,
+                                  templates, (hipStream_t)stream, I);
     if (rc) return rc;
     return smot_search_region_fwd(boxes, N, pad_pixels, search_expansion, min_search_wh, sr, stream);
 }

@@ -29,174 +29,19 @@ __global__ void __launch_bounds__(256)
 roi_align_levels_kernel(LevelParams P, int C, const float* __restrict__ rois,
                         const float* __restrict__ level_boxes, int PH, int PW, int ch_per_block,
                         float* __restrict__ out, int32_t* __restrict__ levels_out, int num_images) {
-    // num_images == 0: rois are [R,4] on the one image of the call (the level-routed pooler).
-    // num_images >= 1: rois are [R,5] = (image index, x1, y1, x2, y2) as upstream's _C.roi_align_forward takes them,
-    //                  P.feat[0] is [num_images, C, H, W]; a row whose index is out of range pools to zeros.
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    __shared__ int wbound[4];              // ymin, ymax, xmin, xmax of the cells with non-zero weight
-    const int ny = PH * G, nx = PW * G;
-    float* win = reinterpret_cast<float*>(smem);
-    int* y_lo = reinterpret_cast<int*>(win + RA_CH * RA_WIN_FLOATS);
-    int* y_hi = y_lo + ny;
-    float* wy_lo = reinterpret_cast<float*>(y_hi + ny);
-    float* wy_hi = wy_lo + ny;
-    int* x_lo = reinterpret_cast<int*>(wy_hi + ny);
-    int* x_hi = x_lo + nx;
-    float* wx_lo = reinterpret_cast<float*>(x_hi + nx);
-    float* wx_hi = wx_lo + nx;
+    constexpr bool BATCHED = false;
+    constexpr NoImages I{};
+#include "roi_align_body.h"
+}
 
-    const int r = blockIdx.x;
-    const float* roi = num_images ? rois + (size_t)r * 5 + 1 : rois + (size_t)r * 4;
-    const int image = num_images ? (int)rois[(size_t)r * 5] : 0;
-    int lvl = 0;
-    if (P.num_levels > 1) lvl = map_level(level_boxes + (size_t)r * 4, P.k_min, P.k_max);
-    if (levels_out != nullptr && blockIdx.y == 0 && threadIdx.x == 0) levels_out[r] = lvl;
-
-    const int H = P.H[lvl], W = P.W[lvl], pad = P.pad[lvl];
-    const float scale = P.scale[lvl];
-    const float x1 = mul_rn(roi[0], scale), y1 = mul_rn(roi[1], scale);
-    const float x2 = mul_rn(roi[2], scale), y2 = mul_rn(roi[3], scale);
-    const float roi_w = fmaxf(sub_rn(x2, x1), 1.0f);
-    const float roi_h = fmaxf(sub_rn(y2, y1), 1.0f);
-    const float bin_h = div_rn(roi_h, (float)PH);
-    const float bin_w = div_rn(roi_w, (float)PW);
-
-    if (threadIdx.x == 0) {
-        wbound[0] = 0x7fffffff;
-        wbound[1] = -1;
-        wbound[2] = 0x7fffffff;
-        wbound[3] = -1;
-    }
-    __syncthreads();
-    for (int s = threadIdx.x; s < ny + nx; s += blockDim.x) {
-        int lo, hi;
-        float wl, wh;
-        if (s < ny) {
-            axis_sample(y1, bin_h, G, s, H, pad, &lo, &hi, &wl, &wh);
-            y_lo[s] = lo;
-            y_hi[s] = hi;
-            wy_lo[s] = wl;
-            wy_hi[s] = wh;
-        } else {
-            const int sx = s - ny;
-            axis_sample(x1, bin_w, G, sx, W, pad, &lo, &hi, &wl, &wh);
-            x_lo[sx] = lo;
-            x_hi[sx] = hi;
-            wx_lo[sx] = wl;
-            wx_hi[sx] = wh;
-        }
-        const int b = (s < ny) ? 0 : 2;
-        if (wl != 0.0f) {
-            atomicMin(&wbound[b], lo);
-            atomicMax(&wbound[b + 1], lo);
-        }
-        if (wh != 0.0f) {
-            atomicMin(&wbound[b], hi);
-            atomicMax(&wbound[b + 1], hi);
-        }
-    }
-    __syncthreads();
-    const int ymin = wbound[0], ymax = wbound[1], xmin = wbound[2], xmax = wbound[3];
-    const int c0 = blockIdx.y * ch_per_block;
-    const int c1 = min(C, c0 + ch_per_block);
-    const int bins = PH * PW;
-    const float* __restrict__ f = P.feat[lvl] + (size_t)image * C * H * W;
-    if (ymax < ymin || xmax < xmin || image < 0 || image >= max(num_images, 1)) {
-        // every sample lies in the virtual zero border (or outside the padded map): exact zeros
-        for (int c = c0; c < c1; ++c)
-            for (int t = threadIdx.x; t < bins; t += blockDim.x) out[((size_t)r * C + c) * bins + t] = 0.0f;
-        return;
-    }
-    const int wh_ = ymax - ymin + 1, ww = xmax - xmin + 1;
-    const bool staged = (wh_ * ww <= RA_WIN_FLOATS);     // workgroup-uniform
-    // re-base the tables: window-relative when staged, map-relative row offsets otherwise
-    __syncthreads();
-    for (int s = threadIdx.x; s < ny + nx; s += blockDim.x) {
-        if (s < ny) {
-            const int lo = (wy_lo[s] != 0.0f) ? y_lo[s] : ymin;
-            const int hi = (wy_hi[s] != 0.0f) ? y_hi[s] : ymin;
-            y_lo[s] = staged ? (lo - ymin) * ww : lo * W;
-            y_hi[s] = staged ? (hi - ymin) * ww : hi * W;
-        } else {
-            const int sx = s - ny;
-            const int lo = (wx_lo[sx] != 0.0f) ? x_lo[sx] : xmin;
-            const int hi = (wx_hi[sx] != 0.0f) ? x_hi[sx] : xmin;
-            x_lo[sx] = staged ? lo - xmin : lo;
-            x_hi[sx] = staged ? hi - xmin : hi;
-        }
-    }
-    __syncthreads();
-
-    const int nch = c1 - c0;
-    if (staged) {
-        // ---- stage the (wh x ww) windows of all channels of this workgroup.  Wave w takes rows
-        // w, w+4, ...; lanes take columns (contiguous, coalesced row segments).  All loads of a pass
-        // (up to 16 rows x RA_CH channels per lane) are issued before the first LDS store, so one
-        // memory round trip covers the whole pass; co-resident workgroups cover the rest. ----
-        const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-        for (int col0 = 0; col0 < ww; col0 += 64) {
-            const int col = col0 + tx;
-            for (int row0 = 0; row0 < wh_; row0 += 64) {
-                float tmp[RA_CH][16];
-#pragma unroll
-                for (int cl = 0; cl < RA_CH; ++cl) {
-                    const float* __restrict__ fc = f + (size_t)(c0 + min(cl, nch - 1)) * H * W;
-#pragma unroll
-                    for (int k = 0; k < 16; ++k) {
-                        const int row = row0 + ty + 4 * k;
-                        tmp[cl][k] = (row < wh_ && col < ww) ? fc[(ymin + row) * W + xmin + col] : 0.0f;
-                    }
-                }
-#pragma unroll
-                for (int cl = 0; cl < RA_CH; ++cl) {
-#pragma unroll
-                    for (int k = 0; k < 16; ++k) {
-                        const int row = row0 + ty + 4 * k;
-                        if (row < wh_ && col < ww) win[cl * RA_WIN_FLOATS + row * ww + col] = tmp[cl][k];
-                    }
-                }
-            }
-        }
-        __syncthreads();
-    }
-    // bins outer (tables of one bin in registers), channels inner
-    for (int t = threadIdx.x; t < bins; t += 256) {
-        const int ph = t / PW;
-        const int pw = t - ph * PW;
-        int ylo[G], yhi[G], xlo[G], xhi[G];
-        float wyl[G], wyh[G], wxl[G], wxh[G];
-#pragma unroll
-        for (int i = 0; i < G; ++i) {
-            ylo[i] = y_lo[ph * G + i];
-            yhi[i] = y_hi[ph * G + i];
-            wyl[i] = wy_lo[ph * G + i];
-            wyh[i] = wy_hi[ph * G + i];
-            xlo[i] = x_lo[pw * G + i];
-            xhi[i] = x_hi[pw * G + i];
-            wxl[i] = wx_lo[pw * G + i];
-            wxh[i] = wx_hi[pw * G + i];
-        }
-        for (int cl = 0; cl < nch; ++cl) {
-            // window larger than the LDS budget (degenerate aspect ratios): gather straight from the map
-            const float* __restrict__ src = staged ? (const float*)(win + cl * RA_WIN_FLOATS)
-                                                   : f + (size_t)(c0 + cl) * H * W;
-            float acc = 0.0f;
-#pragma unroll
-            for (int iy = 0; iy < G; ++iy) {
-#pragma unroll
-                for (int ix = 0; ix < G; ++ix) {
-                    const float v1 = src[ylo[iy] + xlo[ix]];
-                    const float v2 = src[ylo[iy] + xhi[ix]];
-                    const float v3 = src[yhi[iy] + xlo[ix]];
-                    const float v4 = src[yhi[iy] + xhi[ix]];
-                    const float w1 = wyl[iy] * wxl[ix], w2 = wyl[iy] * wxh[ix];
-                    const float w3 = wyh[iy] * wxl[ix], w4 = wyh[iy] * wxh[ix];
-                    acc += w1 * v1 + w2 * v2 + w3 * v3 + w4 * v4;
-                }
-            }
-            out[((size_t)r * C + c0 + cl) * bins + t] = acc / (float)(G * G);
-        }
-    }
+// A batch of images: [R,4] rois, the rows of image b are [I.row_start[b], I.row_start[b+1]) (smot_emm_*_batched_fwd)
+template <int G>
+__global__ void __launch_bounds__(256)
+roi_align_levels_batched_kernel(LevelParams P, int C, const float* __restrict__ rois,
+                                const float* __restrict__ level_boxes, int PH, int PW, int ch_per_block,
+                                float* __restrict__ out, int32_t* __restrict__ levels_out, int num_images, ImageRows I) {
+    constexpr bool BATCHED = true;
+#include "roi_align_body.h"
 }
 
 __global__ void search_region_kernel(const float* __restrict__ boxes, int N, float pad, float half_e,
@@ -221,6 +66,47 @@ namespace smot {
 int launch_roi_pool_separable(const LevelParams& P, int C, const float* rois, const float* level_boxes, int R,
                               int out_size, float* out, int32_t* levels_out, hipStream_t st);   // sr_xcorr.hip
 }
+
+namespace smot {
+int launch_roi_pool_separable_batched(const LevelParams& P, int C, const float* rois, const float* level_boxes, int R,
+                                      int out_size, float* out, hipStream_t st, const ImageRows& I);   // sr_xcorr.hip
+
+// smot_roi_align_levels_fwd over a batch (the generic branches of smot_emm_*_batched_fwd): same routing, same kernels'
+// batched forms; the rows of image b are [I.row_start[b], I.row_start[b+1]) of rois / level_boxes / out
+int roi_align_levels_batched(const float* const* feats, const int* heights, const int* widths, const int* pad_cells,
+                             const float* scales, int num_levels, int C, const float* rois, const float* level_boxes, int R,
+                             int out_hw, int sampling_ratio, float* out, hipStream_t st, const ImageRows& I) {
+    SMOT_REQUIRE(C > 0 && out_hw > 0 && R >= 0, "roi_align_batched: bad sizes C=%d out=%d R=%d", C, out_hw, R);
+    if (sampling_ratio <= 0 || sampling_ratio > 4) {
+        set_error("roi_align_batched: sampling_ratio=%d unsupported (need 1..4)", sampling_ratio);
+        return SMOT_ERR_UNSUPPORTED;
+    }
+    if (R == 0) return SMOT_OK;
+    LevelParams P;
+    const int rc = fill_level_params(&P, feats, heights, widths, pad_cells, scales, num_levels, "roi_align_batched");
+    if (rc) return rc;
+    if ((out_hw == 7 || out_hw == 15 || out_hw == 30) && sampling_ratio == 2 && !knobs().roi_generic)
+        return launch_roi_pool_separable_batched(P, C, rois, num_levels > 1 ? level_boxes : rois, R, out_hw, out, st, I);
+    dim3 grid(R, (C + RA_CH - 1) / RA_CH);
+    const size_t smem = (size_t)(2 * out_hw) * sampling_ratio * 16 + (size_t)RA_CH * RA_WIN_FLOATS * sizeof(float);
+    SMOT_REQUIRE(smem <= 96 * 1024, "roi_align_batched: pooled size %d needs too much LDS", out_hw);
+#define LAUNCH(G)                                                                                                  \
+    {                                                                                                              \
+        const int rco = ensure_lds_optin((const void*)roi_align_levels_batched_kernel<G>, 96 * 1024, "roi_align");  \
+        if (rco) return rco;                                                                                       \
+        hipLaunchKernelGGL(roi_align_levels_batched_kernel<G>, grid, dim3(256), smem, st, P, C, rois, level_boxes,  \
+                           out_hw, out_hw, RA_CH, out, (int32_t*)nullptr, 0, I);                                  \
+    }
+    switch (sampling_ratio) {
+        case 1: LAUNCH(1); break;
+        case 2: LAUNCH(2); break;
+        case 3: LAUNCH(3); break;
+        default: LAUNCH(4); break;
+    }
+#undef LAUNCH
+    return check_launch("roi_align_batched");
+}
+}  // namespace smot
 
 extern "C" int smot_roi_align_levels_fwd(const float* const* feats, const int* heights,
                                          const int* widths, const int* pad_cells,

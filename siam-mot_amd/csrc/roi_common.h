@@ -15,6 +15,65 @@ struct LevelParams {
     float k_min, k_max;
 };
 
+// Rows of a batched call (smot_emm_*_batched_fwd): the rois of image b are [row_start[b], row_start[b+1]) and the maps are
+// [num_images, C, H_l, W_l].  A kernel argument of the batched instantiations only; the single-image kernels take NoImages
+// (nothing) and are unchanged.
+struct ImageRows {
+    static constexpr bool batched = true;
+    int num_images;
+    int row_start[SMOT_MAX_IMAGES + 1];
+};
+struct NoImages {                  // (members only so that code behind `if constexpr (BATCHED)` is well-formed; never read)
+    static constexpr bool batched = false;
+    static constexpr int num_images = 1;
+    static constexpr int row_start[SMOT_MAX_IMAGES + 1] = {};
+};
+
+// The image of (wave-uniform) row n: the largest b < num_images with row_start[b] <= n (images without rows are skipped),
+// by a binary search of scalar loads from the kernel-argument segment — at most 6 for 64 images.
+__device__ __forceinline__ int image_of_row(const ImageRows& I, int n) {
+    int lo = 0, hi = I.num_images - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (I.row_start[mid] <= n) {
+            lo = mid;
+        } else {
+            hi = mid - 1;
+        }
+    }
+    return lo;
+}
+__device__ __forceinline__ int image_of_row(const NoImages&, int) { return 0; }
+
+// Host side: check a batched call's row ranges (before any launch) and pack them.
+inline int fill_image_rows(ImageRows* I, int num_images, const int* row_start, int N, const char* who) {
+    if (num_images < 1 || num_images > SMOT_MAX_IMAGES) {
+        set_error("%s: num_images=%d not in [1,%d]", who, num_images, SMOT_MAX_IMAGES);
+        return SMOT_ERR_BAD_ARG;
+    }
+    if (row_start == nullptr) {
+        set_error("%s: null row_start", who);
+        return SMOT_ERR_BAD_ARG;
+    }
+    if (row_start[0] != 0) {
+        set_error("%s: row_start[0]=%d, expected 0", who, row_start[0]);
+        return SMOT_ERR_BAD_ARG;
+    }
+    for (int b = 0; b < num_images; ++b) {
+        if (row_start[b + 1] < row_start[b]) {
+            set_error("%s: row_start decreases at image %d (%d -> %d)", who, b, row_start[b], row_start[b + 1]);
+            return SMOT_ERR_BAD_ARG;
+        }
+    }
+    if (row_start[num_images] != N) {
+        set_error("%s: row_start[%d]=%d, expected N=%d", who, num_images, row_start[num_images], N);
+        return SMOT_ERR_BAD_ARG;
+    }
+    I->num_images = num_images;
+    for (int b = 0; b <= SMOT_MAX_IMAGES; ++b) I->row_start[b] = b <= num_images ? row_start[b] : N;
+    return SMOT_OK;
+}
+
 // [UPSTREAM] LevelMapper: floor(4 + log2(sqrt(area)/224 + 1e-6)), clamped, 0-based.
 __device__ __forceinline__ int map_level(const float* b, float k_min, float k_max) {
     const float w = add_rn(sub_rn(b[2], b[0]), 1.0f);

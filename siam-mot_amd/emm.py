@@ -146,6 +146,37 @@ class OrderHint(object):
         return None
 
 
+class _BatchHint(object):
+    """``OrderHint`` of a batched extraction: one list for the rows of all its images, left on each of its B search-region
+    BoxLists.  ``lookup`` hands it (and the extraction's concatenated boxes / search regions) back only for those very
+    BoxLists in that order, with the detection tensors of the same identity and version; anything else ranks again."""
+    __slots__ = ("data", "boxes", "sr", "sr_version", "parts", "part_versions", "sr_parts", "scales")
+
+    def __init__(self, data, boxes, sr, dets, srs, scales):
+        self.data, self.boxes, self.sr, self.scales = data, boxes, sr, scales
+        self.sr_version = sr._version
+        self.parts = [d.bbox for d in dets]
+        self.part_versions = [t._version for t in self.parts]
+        self.sr_parts = [s_.bbox for s_ in srs]
+        for b, s_ in enumerate(srs):
+            s_.batch_hint = (self, b)
+
+    @staticmethod
+    def lookup(boxes, sr, scales):
+        h = sr[0].__dict__.get("batch_hint")
+        if h is None or h[1] != 0:
+            return None
+        h = h[0]
+        if h.scales != scales or len(h.parts) != len(boxes) or h.sr._version != h.sr_version:
+            return None
+        for b in range(len(boxes)):
+            t = boxes[b].bbox
+            if (sr[b].__dict__.get("batch_hint") != (h, b) or sr[b].bbox is not h.sr_parts[b] or t is not h.parts[b]
+                    or t._version != h.part_versions[b]):
+                return None
+        return h
+
+
 class EMM(nn.Module):
     """Drop-in for the reference ``EMM`` (EMM/track_core.py:14-98)."""
 
@@ -167,7 +198,8 @@ class EMM(nn.Module):
         if self.training:
             raise NotImplementedError("siammot_amd.EMM is an inference path; training "
                                       "(track_core.py:45-47,56-67) is out of scope")
-        assert len(boxes) == 1                                           # track_core.py:75
+        if len(boxes) != 1:              # several images (video streams) in one set of launches
+            return self._forward_batched(features, boxes, sr, template_features)
         st = self.__dict__.get("_static")
         if st is None:                   # submodule / attribute lookups go through nn.Module.__getattr__: once
             fe, pr = self.feature_extractor.pooler_x, self.predictor
@@ -201,6 +233,48 @@ class EMM(nn.Module):
         else:
             track_result = wrap_results_to_boxlist(bb, bb_conf, boxes, amodal=True)   # already clamped
         return {}, track_result, {}
+
+    def _static_args(self):
+        st = self.__dict__.get("_static")
+        if st is None:
+            fe, pr = self.feature_extractor.pooler_x, self.predictor
+            st = self.__dict__["_static"] = (pr.param_dict(), tuple(fe.scales), fe.sampling_ratio, pr.gn_groups,
+                                             pr.gn_eps)
+        return st
+
+    def _forward_batched(self, features, boxes, sr, template_features):
+        """``forward`` over B = len(boxes) images: features ``[B, C, H_l, W_l]``, ``sr`` the B search-region BoxLists aligned
+        with ``boxes``, ``template_features`` the rows of all images in order.  One library call; the tracks of image b get
+        exactly what a one-image call on that image gives them."""
+        B = len(boxes)
+        fb = {int(f.shape[0]) for f in features}
+        if len(fb) != 1 or fb.pop() != B:
+            raise RuntimeError("siammot_amd.EMM: %d images of boxes, feature batch %s" % (B, [tuple(f.shape) for f in features]))
+        if len(sr) != B:
+            raise RuntimeError("siammot_amd.EMM: %d search-region lists for %d images" % (len(sr), B))
+        size = tuple(boxes[0].size)
+        if any(tuple(b.size) != size for b in boxes):
+            raise RuntimeError("siammot_amd.EMM: the images of a batch differ in size: %s" % ([tuple(b.size) for b in boxes],))
+        rows = [len(b) for b in boxes]
+        if any(len(s_) != r for s_, r in zip(sr, rows)):
+            raise RuntimeError("siammot_amd.EMM: search regions %s do not match the boxes %s per image"
+                               % ([len(s_) for s_ in sr], rows))
+        if template_features is None or template_features.shape[0] != sum(rows):
+            raise RuntimeError("siammot_amd.EMM: template_features has %s rows, the boxes %d"
+                               % (None if template_features is None else template_features.shape[0], sum(rows)))
+        params, scales, sampling_ratio, gn_groups, gn_eps = self._static_args()
+        bh = _BatchHint.lookup(boxes, sr, scales)
+        if bh is not None:
+            boxes_bbox, sr_bbox, hint = bh.boxes, bh.sr, bh.data
+        else:
+            boxes_bbox = cat([b.bbox for b in boxes], dim=0)
+            sr_bbox = cat([b.bbox for b in sr], dim=0)
+            hint = None
+        bb, bb_conf = ops.emm_track_batched(features, boxes_bbox, sr_bbox, template_features, rows, params, self.rx,
+                                            self.rz, scales, sampling_ratio, self.pad_pixels, sigma=self.sigma,
+                                            use_centerness=self.use_centerness, clip_wh=None if self.amodal else size,
+                                            gn_groups=gn_groups, gn_eps=gn_eps, order_hint=hint)
+        return {}, wrap_results_to_boxlist(bb, bb_conf, boxes, amodal=True), {}     # (already clamped)
 
     def _pair_plan(self, features, boxes_bbox, params, scales, sampling_ratio):
         """The cached host plan of this module's two per-frame calls (``ops.PairPlan``), made on first use and again when a
@@ -247,7 +321,12 @@ class EMM(nn.Module):
         return sz
 
     def extract_cache(self, features, detection):
-        """(template features, [search regions], [detections]) — track_core.py:81-98."""
+        """(template features, [search regions], [detections]) — track_core.py:81-98.  ``detection`` may also be a list of
+        B BoxLists, one per image of ``[B, C, H_l, W_l]`` features: (templates of all rows, [B search regions], [B detections])."""
+        if isinstance(detection, (list, tuple)):
+            if len(detection) != 1:
+                return self._extract_cache_batched(features, list(detection))
+            detection = detection[0]
         det = detection
         tu = self.track_utils
         sz = self._template_pooler()
@@ -261,6 +340,28 @@ class EMM(nn.Module):
             r = ops.emm_extract_cache(features, det.bbox, self.rz, sz[0], sz[1], tu.pad_pixels, tu.search_expansion,
                                       tu.min_search_wh, hint=self.use_order_hint)
         return self.wrap_cache(r[0], r[1], det, r[2] if len(r) > 2 else None)
+
+    def _extract_cache_batched(self, features, dets):
+        B = len(dets)
+        fb = {int(f.shape[0]) for f in features}
+        if len(fb) != 1 or fb.pop() != B:
+            raise RuntimeError("siammot_amd.EMM: %d images of detections, feature batch %s" % (B, [tuple(f.shape) for f in features]))
+        size = tuple(dets[0].size)
+        if any(tuple(d.size) != size for d in dets):
+            raise RuntimeError("siammot_amd.EMM: the images of a batch differ in size: %s" % ([tuple(d.size) for d in dets],))
+        tu = self.track_utils
+        sz = self._template_pooler()
+        rows = [len(d) for d in dets]
+        boxes = cat([d.bbox for d in dets], dim=0)
+        x, sr_bbox, hint = ops.emm_extract_cache_batched(features, boxes, rows, self.rz, sz[0], sz[1], tu.pad_pixels,
+                                                         tu.search_expansion, tu.min_search_wh, hint=self.use_order_hint)
+        srs, n0 = [], 0
+        for d, r in zip(dets, rows):
+            srs.append(self.wrap_cache(x, sr_bbox[n0:n0 + r], d)[1][0])
+            n0 += r
+        if hint is not None:
+            _BatchHint(hint, boxes, sr_bbox, dets, srs, sz[0])
+        return x, srs, list(dets)
 
     def wrap_cache(self, x, sr_bbox, det, hint=None):
         """(templates, search-region boxes) of ``det``'s rows -> the reference's cache tuple.  ``hint``: the order

@@ -23,7 +23,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libsmot_emm.so")
 # measurement build (-DSMOT_DEBUG): older kernel generations, A/B switches, timing ablations.  Never loaded
 # implicitly — only through ``debug_library()`` (tools/, A/B tests).
 DEBUG_LIB_PATH = os.path.join(_HERE, "csrc", "libsmot_emm_debug.so")
-ABI_VERSION = 13
+ABI_VERSION = 14
 UP_SCALE = 16          # reference track_core.py:69-73
 
 
@@ -91,6 +91,12 @@ _SIGNATURES = {
     "smot_track_solve_carry_fwd": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _f, _f, _i,
                                                   _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                   _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),
+    # several images per call (ABI 14): the single-image twins' arguments + num_images, row_start (host int array)
+    "smot_emm_track_batched_fwd": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i,
+                                                  _vp, _i, _f, _vp, _i, _f, _f, _f, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                  _i, _vp]),
+    "smot_emm_extract_cache_batched_fwd": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _f, _f, _f,
+                                                          _vp, _vp, _vp, _vp, _i, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 _DEBUG_SIGNATURES = {
@@ -721,6 +727,142 @@ def emm_extract_cache(features, boxes, rz, scales, sampling_ratio, pad_pixels, s
             torch.cuda.set_device(cur)
     if rc:
         _check(rc, "emm_extract_cache")
+    return (templates, sr, oh) if hint else (templates, sr)
+
+
+# ---- several images per call (smot_emm_*_batched_fwd) ------------------------------------------------------------------
+MAX_IMAGES = 64                      # SMOT_MAX_IMAGES (include/smot_emm.h)
+
+
+def _geometry_batched(features, scales, pad_pixels, device):
+    """``_geometry`` for ``[B, C, H, W]`` maps (one B, one C for every level) -> (geometry, B)."""
+    L = len(scales)
+    shapes = tuple(tuple(features[l].shape) for l in range(L))
+    key = ("batched", shapes, tuple(scales), pad_pixels)
+    g = _geom_cache.get(key)
+    if g is None:
+        for sh in shapes:
+            if len(sh) != 4 or sh[0] != shapes[0][0] or sh[1] != shapes[0][1]:
+                raise RuntimeError("siammot_amd: every level must be [B, C, H, W] with one B and one C, got feature shapes %s"
+                                   % (shapes,))
+        if len(_geom_cache) > 32:
+            _geom_cache.clear()
+        g = _geom_cache[key] = _LevelGeometry(shapes, scales, pad_pixels)
+    fp = g.fp
+    for l in range(L):
+        f = features[l]
+        if not (f.is_cuda and f.dtype is _F32 and f.is_contiguous()):
+            f = g.keep[l] = _dev_f32(f, "features[%d]" % l)
+        if f.device != device:
+            raise RuntimeError("siammot_amd: features[%d] lives on %s, the boxes on %s" % (l, f.device, device))
+        fp[l] = f.data_ptr()
+    return g, shapes[0][0]
+
+
+def _row_starts(rows_per_image, B, N):
+    """Host ``row_start[B + 1]`` of a batch from its per-image row counts (checked here and again by the library)."""
+    rows = [int(r) for r in rows_per_image]
+    if len(rows) != B:
+        raise RuntimeError("siammot_amd: %d row counts for a feature batch of %d images" % (len(rows), B))
+    if any(r < 0 for r in rows) or sum(rows) != N:
+        raise RuntimeError("siammot_amd: row counts %s do not split the %d rows" % (rows, N))
+    starts = [0]
+    for r in rows:
+        starts.append(starts[-1] + r)
+    return (ctypes.c_int * (B + 1))(*starts)
+
+
+def emm_track_batched(features, boxes, sr, templates, rows_per_image, params, rx, rz, scales, sampling_ratio, pad_pixels,
+                      sigma=0.4, use_centerness=True, clip_wh=None, gn_groups=32, gn_eps=1e-5, return_index=False,
+                      winograd=True, order_hint=None):
+    """``emm_track`` over B images in one library call: ``features`` are ``[B, C, H_l, W_l]`` per level, the rows of image b
+    are the ``rows_per_image[b]`` consecutive rows after those of images 0..b-1 (host ints).  Returns what ``emm_track``
+    returns for all rows; the rows of image b are exactly what ``emm_track`` gives on ``features[l][b:b+1]`` with them.
+    ``clip_wh``: the one image size of the batch.  ``order_hint``: as for ``emm_track``, from ``emm_extract_cache_batched``."""
+    lib = _lib or load_library()
+    if not (isinstance(boxes, torch.Tensor) and boxes.is_cuda):
+        _dev_f32(boxes, "boxes")
+    dev = boxes.device
+    g, B = _geometry_batched(features, scales, pad_pixels, dev)
+    N, C = boxes.shape[0], g.C
+    row_start = _row_starts(rows_per_image, B, N)
+    boxes = _chk(boxes, "boxes", (N, 4))
+    sr = _chk(sr, "sr", (N, 4))
+    templates = _chk(templates, "template_features", (N, C, rz, rz))
+    blk = _param_block(params)
+    _same_device(dev, ("sr", sr), ("template_features", templates), ("predictor weights", blk.tensors[0]))
+    if blk.C != C:
+        raise RuntimeError("siammot_amd.emm_track_batched: predictor has %d channels, features have %d" % (blk.C, C))
+    ho = rx - rz + 1
+    a_pp = blk.a_pp
+    if not (winograd and ho in (16, 29)) and blk.packed is not None:
+        pp = (ctypes.c_void_p * 13)(*([t.data_ptr() for t in blk.tensors] + [None]))
+        a_pp = ctypes.addressof(pp)
+    stream = _stream(dev)
+    work = _workspace(dev, lib.smot_emm_track_ws_floats(N, C, rx, rz), stream.value)
+    bb = torch.empty((N, 4), dtype=_F32, device=dev)
+    conf = torch.empty((N,), dtype=_F32, device=dev)
+    idx = torch.empty((N,), dtype=torch.int64, device=dev) if return_index else None
+    if order_hint is not None and (tuple(order_hint.shape) != (N, HINT_FLOATS) or order_hint.device != dev
+                                   or order_hint.dtype is not _F32 or not order_hint.is_contiguous()):
+        raise RuntimeError("siammot_amd.emm_track_batched: order_hint must be the contiguous fp32 [%d, %d] tensor of the "
+                           "extraction that made these boxes" % (N, HINT_FLOATS))
+    cur = torch.cuda.current_device()
+    if cur != dev.index:
+        torch.cuda.set_device(dev.index)
+    try:
+        rc = lib.smot_emm_track_batched_fwd(g.a_fp, g.a_hs, g.a_ws, g.a_pc, g.a_sc, g.L, C,
+                                            boxes.data_ptr(), sr.data_ptr(), templates.data_ptr(), N, rx, rz,
+                                            sampling_ratio, a_pp, gn_groups, gn_eps,
+                                            hann_window(ho * UP_SCALE, dev).data_ptr(), UP_SCALE, pad_pixels, 1 - sigma,
+                                            sigma, 1 if use_centerness else 0,
+                                            float(clip_wh[0]) if clip_wh is not None else 0.0,
+                                            float(clip_wh[1]) if clip_wh is not None else 0.0,
+                                            work.data_ptr(), bb.data_ptr(), conf.data_ptr(),
+                                            idx.data_ptr() if idx is not None else None,
+                                            order_hint.data_ptr() if order_hint is not None else None, stream, B,
+                                            row_start)
+    finally:
+        if cur != dev.index:
+            torch.cuda.set_device(cur)
+    if rc:
+        _check(rc, "emm_track_batched")
+    return (bb, conf, idx) if return_index else (bb, conf)
+
+
+def emm_extract_cache_batched(features, boxes, rows_per_image, rz, scales, sampling_ratio, pad_pixels, search_expansion,
+                              min_search_wh, hint=False):
+    """``emm_extract_cache`` over B images in one library call (``features`` ``[B, C, H_l, W_l]``, rows grouped by image as
+    in ``emm_track_batched``) -> (templates, sr) or, with ``hint=True``, (templates, sr, order hint or None)."""
+    lib = _lib or load_library()
+    if not (isinstance(boxes, torch.Tensor) and boxes.is_cuda):
+        _dev_f32(boxes, "boxes")
+    dev = boxes.device
+    g, B = _geometry_batched(features, scales, 0, dev)
+    N, C = boxes.shape[0], g.C
+    row_start = _row_starts(rows_per_image, B, N)
+    boxes = _chk(boxes, "boxes", (N, 4))
+    templates = torch.empty((N, C, rz, rz), dtype=_F32, device=dev)
+    oh = None
+    if hint and boxes.data_ptr() % 16 == 0 and order_hint_floats(N, rz, sampling_ratio) > 0:
+        both = torch.empty((N * (HINT_FLOATS + 4),), dtype=_F32, device=dev)       # one allocation: hint | sr
+        oh = both[:N * HINT_FLOATS].view(N, HINT_FLOATS)
+        sr = both[N * HINT_FLOATS:].view(N, 4)
+    else:
+        sr = torch.empty((N, 4), dtype=_F32, device=dev)
+    cur = torch.cuda.current_device()
+    if cur != dev.index:
+        torch.cuda.set_device(dev.index)
+    try:
+        rc = lib.smot_emm_extract_cache_batched_fwd(g.a_fp, g.a_hs, g.a_ws, g.a_sc, g.L, C, boxes.data_ptr(), N, rz,
+                                                    sampling_ratio, pad_pixels, search_expansion, min_search_wh,
+                                                    templates.data_ptr(), sr.data_ptr(),
+                                                    oh.data_ptr() if oh is not None else None, _stream(dev), B, row_start)
+    finally:
+        if cur != dev.index:
+            torch.cuda.set_device(cur)
+    if rc:
+        _check(rc, "emm_extract_cache_batched")
     return (templates, sr, oh) if hint else (templates, sr)
 
 
