@@ -7,8 +7,9 @@
  * reference's un-vendored native substrate).
  *
  * Conventions:
- *   - all tensors are contiguous fp32, NCHW; boxes are fp32 xyxy pixels; device pointers unless
- *     the parameter is documented as a HOST array;
+ *   - all tensors are contiguous fp32, NCHW (the *_typed_* entry points at the end also take fp16 / bf16
+ *     feature MAPS); boxes are fp32 xyxy pixels; device pointers unless the parameter is documented as
+ *     a HOST array;
  *   - the caller owns every buffer (outputs and workspaces included); nothing is allocated,
  *     nothing persists between calls, no host synchronisation happens inside;
  *   - kernels are enqueued on `stream` (a hipStream_t passed as void*; NULL = default stream);
@@ -691,6 +692,84 @@ int smot_memory_carry_fwd(const float* src_templates, const float* src_boxes, co
                           int64_t* dst_ids, int64_t* dst_labels, float* dst_scores, int dst_capacity,
                           const int* rows, int D, int dst_row0, const int* dst_row0_dev, int row_floats,
                           smot_stream_t stream);
+
+/*
+ * fp16 / bf16 FEATURE MAPS (a PyTorch backbone under torch.autocast or .half()).
+ *
+ * Every entry point above that reads the FPN maps has a `_typed_` twin that takes the maps as `const void*` and their
+ * element type `feat_type`; every other argument, and its order, is the twin's.  Only the MAPS have a type: boxes,
+ * templates / track memory, weights, workspaces, order hints and all outputs stay fp32.
+ *
+ * The contract: for T in {fp16, bf16}, a call on maps of element type T returns BIT FOR BIT what the same call returns
+ * on the maps converted to fp32 (T -> fp32 is exact; the kernels convert in registers right behind each load — fp16
+ * subnormals are kept — and every later instruction is the fp32 kernel's).  This holds for every output: pooled planes,
+ * responses, templates, search regions, order hints (an order hint holds no map data and no element size: one written
+ * from half maps and one written from their fp32 upcast are the same bytes, and a consumer of either type accepts
+ * either), boxes, scores, arg-max indices, solver records.  No fp32 copy of a map is made.
+ *
+ * SMOT_FEAT_F32 through a typed entry point runs the fp32 kernels (it IS the untyped call).  Any other `feat_type` is
+ * SMOT_ERR_BAD_ARG with a message that names the value, before any launch and before any pointer is looked at.
+ *
+ *   smot_emm_track_typed_fwd          the batched signature; one image = num_images 1, row_start {0, N}
+ *   smot_emm_extract_cache_typed_fwd  the batched signature plus n_valid: NULL, or the masked form's device count
+ *                                     (smot_emm_extract_cache_masked_fwd: N is then the capacity), legal with
+ *                                     num_images == 1 only (SMOT_ERR_BAD_ARG otherwise)
+ *   smot_track_frame_typed_fwd        args->feats[l] are read as maps of `feat_type` (the struct is unchanged)
+ */
+#define SMOT_FEAT_F32 0
+#define SMOT_FEAT_F16 1
+#define SMOT_FEAT_BF16 2
+
+int smot_roi_align_levels_typed_fwd(const void* const* feats, int feat_type, const int* heights, const int* widths,
+                                    const int* pad_cells, const float* scales, int num_levels, int C,
+                                    const float* rois, const float* level_boxes, int R,
+                                    int out_h, int out_w, int sampling_ratio,
+                                    float* out, int32_t* levels_out, smot_stream_t stream);
+
+int smot_roi_align_typed_fwd(const void* input, int feat_type, int num_images, int C, int H, int W, int pad_cells,
+                             const float* rois5, int R, float spatial_scale, int pooled_h, int pooled_w,
+                             int sampling_ratio, float* out, smot_stream_t stream);
+
+int smot_sr_xcorr_fused_typed_fwd(const void* const* feats, int feat_type, const int* heights, const int* widths,
+                                  const int* pad_cells, const float* scales, int num_levels, int C,
+                                  const float* boxes, const float* sr, const float* templates, int N,
+                                  int rx, int rz, int sampling_ratio, float* resp, float* x_debug,
+                                  smot_stream_t stream);
+
+int smot_sr_xcorr_gather_typed_fwd(const void* const* feats, int feat_type, const int* heights, const int* widths,
+                                   const int* pad_cells, const float* scales, int num_levels, int C,
+                                   const float* boxes, const float* sr, const float* templates, int N,
+                                   int rx, int rz, int sampling_ratio, float* resp, smot_stream_t stream);
+
+int smot_emm_track_typed_fwd(const void* const* feats, int feat_type, const int* heights, const int* widths,
+                             const int* pad_cells, const float* scales, int num_levels, int C,
+                             const float* boxes, const float* sr, const float* templates, int N,
+                             int rx, int rz, int sampling_ratio,
+                             const float* const* predictor_params, int gn_groups, float gn_eps,
+                             const float* hann, int up, float pad_pixels,
+                             float one_minus_sigma, float sigma, int use_centerness,
+                             float clip_w, float clip_h,
+                             float* ws, float* bb, float* conf, int64_t* idx, const float* order_hint,
+                             smot_stream_t stream, int num_images, const int* row_start);
+
+int smot_emm_extract_cache_typed_fwd(const void* const* feats, int feat_type, const int* heights, const int* widths,
+                                     const float* scales, int num_levels, int C,
+                                     const float* boxes, int N, int rz, int sampling_ratio,
+                                     float pad_pixels, float search_expansion, float min_search_wh,
+                                     float* templates, float* sr, float* order_hint, smot_stream_t stream,
+                                     int num_images, const int* row_start, const int* n_valid);
+
+int smot_box_refine_typed_fwd(const void* const* feats, int feat_type, const int* heights, const int* widths,
+                              const float* scales, int num_levels, int C, int pooled, int sampling_ratio,
+                              const float* boxes, const int64_t* labels, const int64_t* ids, const float* track_conf, int N,
+                              const float* fc6_w, const float* fc6_b, int dim6, const float* fc7_w, const float* fc7_b, int dim7,
+                              const float* cls_w, const float* cls_b, int num_classes,
+                              const float* reg_w, const float* reg_b, int reg_classes,
+                              float wx, float wy, float ww, float wh, float xform_clip, float clip_w, float clip_h,
+                              int tracktor, float* ws, float* out_boxes, float* out_scores, int64_t* out_ids,
+                              int64_t* out_labels, smot_stream_t stream);
+
+int smot_track_frame_typed_fwd(const smot_frame_args* args, int feat_type, smot_stream_t stream);
 
 #ifdef __cplusplus
 }

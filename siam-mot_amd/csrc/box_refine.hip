@@ -309,3 +309,22 @@ extern "C" int smot_box_refine_fwd(const float* const* feats, const int* heights
     hipLaunchKernelGGL(box_refine_post_kernel<true>, dim3(1), dim3(BR_MAXN), 0, st, A, N);
     return check_launch("box_refine_post");
 }
+
+// fp16 / bf16 maps (include/smot_emm.h, "fp16 / bf16 FEATURE MAPS"): only the 7x7 pooler reads them
+extern "C" int smot_box_refine_typed_fwd(const void* const* feats, int feat_type, const int* heights, const int* widths,
+                                         const float* scales, int num_levels, int C, int pooled, int sampling_ratio,
+                                         const float* boxes, const int64_t* labels, const int64_t* ids, const float* track_conf,
+                                         int N, const float* fc6_w, const float* fc6_b, int dim6, const float* fc7_w,
+                                         const float* fc7_b, int dim7, const float* cls_w, const float* cls_b, int num_classes,
+                                         const float* reg_w, const float* reg_b, int reg_classes, float wx, float wy, float ww,
+                                         float wh, float xform_clip, float clip_w, float clip_h, int tracktor, float* ws,
+                                         float* out_boxes, float* out_scores, int64_t* out_ids, int64_t* out_labels,
+                                         smot_stream_t stream) {
+    const int rc = smot::check_feat_type(feat_type, "box_refine_typed");
+    if (rc) return rc;
+    smot::FeatTypeScope scope(feat_type);
+    return smot_box_refine_fwd(reinterpret_cast<const float* const*>(feats), heights, widths, scales, num_levels, C, pooled,
+                               sampling_ratio, boxes, labels, ids, track_conf, N, fc6_w, fc6_b, dim6, fc7_w, fc7_b, dim7, cls_w,
+                               cls_b, num_classes, reg_w, reg_b, reg_classes, wx, wy, ww, wh, xform_clip, clip_w, clip_h,
+                               tracktor, ws, out_boxes, out_scores, out_ids, out_labels, stream);
+}

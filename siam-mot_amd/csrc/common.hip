@@ -17,6 +17,16 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
+static thread_local int g_feat_type = SMOT_FEAT_F32;
+int feat_type() { return g_feat_type; }
+FeatTypeScope::FeatTypeScope(int ft) : prev(g_feat_type) { g_feat_type = ft; }
+FeatTypeScope::~FeatTypeScope() { g_feat_type = prev; }
+int check_feat_type(int ft, const char* who) {
+    if (ft == SMOT_FEAT_F32 || ft == SMOT_FEAT_F16 || ft == SMOT_FEAT_BF16) return SMOT_OK;
+    set_error("%s: feat_type=%d is not SMOT_FEAT_F32 (0), SMOT_FEAT_F16 (1) or SMOT_FEAT_BF16 (2)", who, ft);
+    return SMOT_ERR_BAD_ARG;
+}
+
 }  // namespace smot
 
 extern "C" int smot_abi_version(void) { return SMOT_ABI_VERSION; }

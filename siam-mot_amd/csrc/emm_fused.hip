@@ -320,3 +320,56 @@ extern "C" int smot_track_frame_fwd(const smot_frame_args* a, smot_stream_t stre
                                 a->pool_state + 4, a->next_order_hint, (hipStream_t)stream,
                                 (stages & SMOT_STAGE_CARRY) ? a->carry_rows : 0);
 }
+
+
+// ---- fp16 / bf16 maps (include/smot_emm.h, "fp16 / bf16 FEATURE MAPS"): the element type is checked, set for the call's
+// duration (FeatTypeScope: the launch sites of the kernels that read the maps pick their instantiation by it) and the fp32
+// entry point's host code runs — towers, decode and solver never see the maps ------------------------------------------------
+extern "C" int smot_emm_track_typed_fwd(const void* const* feats, int feat_type, const int* heights, const int* widths,
+                                        const int* pad_cells, const float* scales, int num_levels, int C,
+                                        const float* boxes, const float* sr, const float* templates, int N, int rx,
+                                        int rz, int sampling_ratio, const float* const* predictor_params, int gn_groups,
+                                        float gn_eps, const float* hann, int up, float pad_pixels,
+                                        float one_minus_sigma, float sigma, int use_centerness, float clip_w,
+                                        float clip_h, float* ws, float* bb, float* conf, int64_t* idx,
+                                        const float* order_hint, smot_stream_t stream, int num_images,
+                                        const int* row_start) {
+    const int rc = smot::check_feat_type(feat_type, "emm_track_typed");
+    if (rc) return rc;
+    smot::FeatTypeScope scope(feat_type);
+    return smot_emm_track_batched_fwd(reinterpret_cast<const float* const*>(feats), heights, widths, pad_cells, scales,
+                                      num_levels, C, boxes, sr, templates, N, rx, rz, sampling_ratio, predictor_params,
+                                      gn_groups, gn_eps, hann, up, pad_pixels, one_minus_sigma, sigma, use_centerness, clip_w,
+                                      clip_h, ws, bb, conf, idx, order_hint, stream, num_images, row_start);
+}
+
+extern "C" int smot_emm_extract_cache_typed_fwd(const void* const* feats, int feat_type, const int* heights,
+                                                const int* widths, const float* scales, int num_levels, int C,
+                                                const float* boxes, int N, int rz, int sampling_ratio, float pad_pixels,
+                                                float search_expansion, float min_search_wh, float* templates, float* sr,
+                                                float* order_hint, smot_stream_t stream, int num_images,
+                                                const int* row_start, const int* n_valid) {
+    using namespace smot;
+    const int rc = check_feat_type(feat_type, "emm_extract_cache_typed");
+    if (rc) return rc;
+    FeatTypeScope scope(feat_type);
+    const float* const* f = reinterpret_cast<const float* const*>(feats);
+    if (n_valid == nullptr)
+        return smot_emm_extract_cache_batched_fwd(f, heights, widths, scales, num_levels, C, boxes, N, rz, sampling_ratio,
+                                                  pad_pixels, search_expansion, min_search_wh, templates, sr, order_hint,
+                                                  stream, num_images, row_start);
+    // the masked form: N is a capacity, the count is on the device — one image only
+    SMOT_REQUIRE(num_images == 1, "emm_extract_cache_typed: n_valid needs num_images == 1 (got %d)", num_images);
+    ImageRows I;
+    const int rci = fill_image_rows(&I, num_images, row_start, N, "emm_extract_cache_typed");
+    if (rci) return rci;
+    return smot_emm_extract_cache_masked_fwd(f, heights, widths, scales, num_levels, C, boxes, N, n_valid, rz, sampling_ratio,
+                                             pad_pixels, search_expansion, min_search_wh, templates, sr, order_hint, stream);
+}
+
+extern "C" int smot_track_frame_typed_fwd(const smot_frame_args* a, int feat_type, smot_stream_t stream) {
+    const int rc = smot::check_feat_type(feat_type, "track_frame_typed");
+    if (rc) return rc;
+    smot::FeatTypeScope scope(feat_type);
+    return smot_track_frame_fwd(a, stream);
+}

@@ -31,6 +31,7 @@ roi_align_levels_kernel(LevelParams P, int C, const float* __restrict__ rois,
                         float* __restrict__ out, int32_t* __restrict__ levels_out, int num_images) {
     constexpr bool BATCHED = false;
     constexpr NoImages I{};
+    using FT = float;
 #include "roi_align_body.h"
 }
 
@@ -40,6 +41,30 @@ __global__ void __launch_bounds__(256)
 roi_align_levels_batched_kernel(LevelParams P, int C, const float* __restrict__ rois,
                                 const float* __restrict__ level_boxes, int PH, int PW, int ch_per_block,
                                 float* __restrict__ out, int32_t* __restrict__ levels_out, int num_images, ImageRows I) {
+    constexpr bool BATCHED = true;
+    using FT = float;
+#include "roi_align_body.h"
+}
+
+// The same two kernels on fp16 / bf16 maps (FT = f16_t / bf16_t; smot_*_typed_fwd): P.feat[] is read as `const FT*`.
+// (The workgroups per CU of the fp32 twins asked for: left alone, the 3x3-sample forms took 188 registers.)
+template <typename FT, int G>
+__global__ void __launch_bounds__(256, G <= 2 ? 3 : (G == 3 ? 2 : 1))
+roi_align_levels_half_kernel(LevelParams P, int C, const float* __restrict__ rois,
+                             const float* __restrict__ level_boxes, int PH, int PW, int ch_per_block,
+                             float* __restrict__ out, int32_t* __restrict__ levels_out, int num_images) {
+    static_assert(sizeof(FT) == 2, "fp16 / bf16 maps");
+    constexpr bool BATCHED = false;
+    constexpr NoImages I{};
+#include "roi_align_body.h"
+}
+template <typename FT, int G>
+__global__ void __launch_bounds__(256, G <= 3 ? 3 : 1)
+roi_align_levels_half_batched_kernel(LevelParams P, int C, const float* __restrict__ rois,
+                                     const float* __restrict__ level_boxes, int PH, int PW, int ch_per_block,
+                                     float* __restrict__ out, int32_t* __restrict__ levels_out, int num_images,
+                                     ImageRows I) {
+    static_assert(sizeof(FT) == 2, "fp16 / bf16 maps");
     constexpr bool BATCHED = true;
 #include "roi_align_body.h"
 }
@@ -91,7 +116,14 @@ int roi_align_levels_batched(const float* const* feats, const int* heights, cons
     const size_t smem = (size_t)(2 * out_hw) * sampling_ratio * 16 + (size_t)RA_CH * RA_WIN_FLOATS * sizeof(float);
     SMOT_REQUIRE(smem <= 96 * 1024, "roi_align_batched: pooled size %d needs too much LDS", out_hw);
 #define LAUNCH(G)                                                                                                  \
-    {                                                                                                              \
+    if (feat_type() != SMOT_FEAT_F32) {                                                                            \
+        SMOT_HALF_TYPES(                                                                                           \
+            const int rco = ensure_lds_optin((const void*)roi_align_levels_half_batched_kernel<FT, G>, 96 * 1024,  \
+                                             "roi_align");                                                         \
+            if (rco) return rco;                                                                                   \
+            hipLaunchKernelGGL((roi_align_levels_half_batched_kernel<FT, G>), grid, dim3(256), smem, st, P, C,      \
+                               rois, level_boxes, out_hw, out_hw, RA_CH, out, (int32_t*)nullptr, 0, I))            \
+    } else {                                                                                                       \
         const int rco = ensure_lds_optin((const void*)roi_align_levels_batched_kernel<G>, 96 * 1024, "roi_align");  \
         if (rco) return rco;                                                                                       \
         hipLaunchKernelGGL(roi_align_levels_batched_kernel<G>, grid, dim3(256), smem, st, P, C, rois, level_boxes,  \
@@ -141,7 +173,13 @@ extern "C" int smot_roi_align_levels_fwd(const float* const* feats, const int* h
     const size_t smem = (size_t)(out_h + out_w) * sampling_ratio * 16 + (size_t)RA_CH * RA_WIN_FLOATS * sizeof(float);
     hipStream_t st = (hipStream_t)stream;
 #define LAUNCH(G)                                                                                        \
-    {                                                                                                    \
+    if (feat_type() != SMOT_FEAT_F32) {                                                                  \
+        SMOT_HALF_TYPES(                                                                                 \
+            const int rco = ensure_lds_optin((const void*)roi_align_levels_half_kernel<FT, G>, 96 * 1024, "roi_align"); \
+            if (rco) return rco;                                                                         \
+            hipLaunchKernelGGL((roi_align_levels_half_kernel<FT, G>), grid, dim3(256), smem, st, P, C, rois, \
+                               level_boxes, out_h, out_w, ch_per_block, out, levels_out, 0))             \
+    } else {                                                                                             \
         const int rco = ensure_lds_optin((const void*)roi_align_levels_kernel<G>, 96 * 1024, "roi_align");   \
         if (rco) return rco;                                                                             \
         hipLaunchKernelGGL(roi_align_levels_kernel<G>, grid, dim3(256), smem, st, P, C, rois, level_boxes, \
@@ -183,7 +221,13 @@ extern "C" int smot_roi_align_fwd(const float* input, int num_images, int C, int
     SMOT_REQUIRE(smem <= 96 * 1024, "roi_align: pooled size %dx%d needs too much LDS", pooled_h, pooled_w);
     hipStream_t st = (hipStream_t)stream;
 #define LAUNCH(G)                                                                                        \
-    {                                                                                                    \
+    if (feat_type() != SMOT_FEAT_F32) {                                                                  \
+        SMOT_HALF_TYPES(                                                                                 \
+            const int rco = ensure_lds_optin((const void*)roi_align_levels_half_kernel<FT, G>, 96 * 1024, "roi_align"); \
+            if (rco) return rco;                                                                         \
+            hipLaunchKernelGGL((roi_align_levels_half_kernel<FT, G>), grid, dim3(256), smem, st, P, C, rois5, \
+                               (const float*)nullptr, pooled_h, pooled_w, RA_CH, out, (int32_t*)nullptr, num_images)) \
+    } else {                                                                                             \
         const int rco = ensure_lds_optin((const void*)roi_align_levels_kernel<G>, 96 * 1024, "roi_align");   \
         if (rco) return rco;                                                                             \
         hipLaunchKernelGGL(roi_align_levels_kernel<G>, grid, dim3(256), smem, st, P, C, rois5,           \
@@ -211,4 +255,27 @@ extern "C" int smot_search_region_fwd(const float* boxes, int N, float pad_pixel
     hipLaunchKernelGGL(search_region_kernel, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, boxes, N,
                        pad_pixels, half_e, two_e, min_search_wh, sr);
     return check_launch("search_region");
+}
+
+// ---- fp16 / bf16 maps (include/smot_emm.h, "fp16 / bf16 FEATURE MAPS"): the element type is checked, set for the call's
+// duration (FeatTypeScope: the launch sites above pick the kernels by it) and the fp32 entry point's host code runs ----------
+extern "C" int smot_roi_align_levels_typed_fwd(const void* const* feats, int feat_type, const int* heights, const int* widths,
+                                               const int* pad_cells, const float* scales, int num_levels, int C,
+                                               const float* rois, const float* level_boxes, int R, int out_h, int out_w,
+                                               int sampling_ratio, float* out, int32_t* levels_out, smot_stream_t stream) {
+    const int rc = smot::check_feat_type(feat_type, "roi_align_levels_typed");
+    if (rc) return rc;
+    smot::FeatTypeScope scope(feat_type);
+    return smot_roi_align_levels_fwd(reinterpret_cast<const float* const*>(feats), heights, widths, pad_cells, scales, num_levels,
+                                     C, rois, level_boxes, R, out_h, out_w, sampling_ratio, out, levels_out, stream);
+}
+
+extern "C" int smot_roi_align_typed_fwd(const void* input, int feat_type, int num_images, int C, int H, int W, int pad_cells,
+                                        const float* rois5, int R, float spatial_scale, int pooled_h, int pooled_w,
+                                        int sampling_ratio, float* out, smot_stream_t stream) {
+    const int rc = smot::check_feat_type(feat_type, "roi_align_typed");
+    if (rc) return rc;
+    smot::FeatTypeScope scope(feat_type);
+    return smot_roi_align_fwd(reinterpret_cast<const float*>(input), num_images, C, H, W, pad_cells, rois5, R, spatial_scale,
+                              pooled_h, pooled_w, sampling_ratio, out, stream);
 }

@@ -1,6 +1,8 @@
 // The body of the generic level-routed ROIAlign kernel, shared by its single-image and batched forms (roi_align.hip):
 // included inside each kernel's braces, which define BATCHED and I (the batch's ImageRows, or NoImages) — one text in two
 // kernels, so that the single-image kernel compiles to the same code as before batching existed.
+// FT (defined by the kernel as well) is the maps' element type: float, or f16_t / bf16_t in the *_half_* kernels, which
+// convert every cell to fp32 where it is loaded (the staged window in LDS is fp32 for every type).
     // num_images == 0: rois are [R,4] on the one image of the call (the level-routed pooler).
     // num_images >= 1: rois are [R,5] = (image index, x1, y1, x2, y2) as upstream's _C.roi_align_forward takes them,
     //                  P.feat[0] is [num_images, C, H, W]; a row whose index is out of range pools to zeros.
@@ -73,7 +75,7 @@
     const int c0 = blockIdx.y * ch_per_block;
     const int c1 = min(C, c0 + ch_per_block);
     const int bins = PH * PW;
-    const float* __restrict__ f = P.feat[lvl] + (size_t)image * C * H * W;
+    const FT* __restrict__ f = reinterpret_cast<const FT*>(P.feat[lvl]) + (size_t)image * C * H * W;
     if (ymax < ymin || xmax < xmin || image < 0 || image >= (BATCHED ? I.num_images : max(num_images, 1))) {
         // every sample lies in the virtual zero border (or outside the padded map): exact zeros
         for (int c = c0; c < c1; ++c)
@@ -113,11 +115,11 @@
                 float tmp[RA_CH][16];
 #pragma unroll
                 for (int cl = 0; cl < RA_CH; ++cl) {
-                    const float* __restrict__ fc = f + (size_t)(c0 + min(cl, nch - 1)) * H * W;
+                    const FT* __restrict__ fc = f + (size_t)(c0 + min(cl, nch - 1)) * H * W;
 #pragma unroll
                     for (int k = 0; k < 16; ++k) {
                         const int row = row0 + ty + 4 * k;
-                        tmp[cl][k] = (row < wh_ && col < ww) ? fc[(ymin + row) * W + xmin + col] : 0.0f;
+                        tmp[cl][k] = (row < wh_ && col < ww) ? feat_ld<FT>(fc + ((ymin + row) * W + xmin + col)) : 0.0f;
                     }
                 }
 #pragma unroll
@@ -132,6 +134,7 @@
         }
         __syncthreads();
     }
+    if constexpr (sizeof(FT) == 4) {
     // bins outer (tables of one bin in registers), channels inner
     for (int t = threadIdx.x; t < bins; t += 256) {
         const int ph = t / PW;
@@ -152,7 +155,7 @@
         for (int cl = 0; cl < nch; ++cl) {
             // window larger than the LDS budget (degenerate aspect ratios): gather straight from the map
             const float* __restrict__ src = staged ? (const float*)(win + cl * RA_WIN_FLOATS)
-                                                   : f + (size_t)(c0 + cl) * H * W;
+                                                   : reinterpret_cast<const float*>(f + (size_t)(c0 + cl) * H * W);
             float acc = 0.0f;
 #pragma unroll
             for (int iy = 0; iy < G; ++iy) {
@@ -169,4 +172,50 @@
             }
             out[((size_t)r * C + c0 + cl) * bins + t] = acc / (float)(G * G);
         }
+    }
+    } else {
+    // 2-byte maps: the same loop over `src_of(cl)`, where channel cl's cells are read — the staged window (fp32) or the map
+    // itself (converted cell by cell); which one is workgroup-uniform, so the two sources get a loop each
+    auto pool_bins = [&](auto src_of) __attribute__((always_inline)) {
+    for (int t = threadIdx.x; t < bins; t += 256) {
+        const int ph = t / PW;
+        const int pw = t - ph * PW;
+        int ylo[G], yhi[G], xlo[G], xhi[G];
+        float wyl[G], wyh[G], wxl[G], wxh[G];
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            ylo[i] = y_lo[ph * G + i];
+            yhi[i] = y_hi[ph * G + i];
+            wyl[i] = wy_lo[ph * G + i];
+            wyh[i] = wy_hi[ph * G + i];
+            xlo[i] = x_lo[pw * G + i];
+            xhi[i] = x_hi[pw * G + i];
+            wxl[i] = wx_lo[pw * G + i];
+            wxh[i] = wx_hi[pw * G + i];
+        }
+        for (int cl = 0; cl < nch; ++cl) {
+            const auto* __restrict__ src = src_of(cl);
+            float acc = 0.0f;
+#pragma unroll
+            for (int iy = 0; iy < G; ++iy) {
+#pragma unroll
+                for (int ix = 0; ix < G; ++ix) {
+                    const float v1 = feat_ld(src + (ylo[iy] + xlo[ix]));
+                    const float v2 = feat_ld(src + (ylo[iy] + xhi[ix]));
+                    const float v3 = feat_ld(src + (yhi[iy] + xlo[ix]));
+                    const float v4 = feat_ld(src + (yhi[iy] + xhi[ix]));
+                    const float w1 = wyl[iy] * wxl[ix], w2 = wyl[iy] * wxh[ix];
+                    const float w3 = wyh[iy] * wxl[ix], w4 = wyh[iy] * wxh[ix];
+                    acc += w1 * v1 + w2 * v2 + w3 * v3 + w4 * v4;
+                }
+            }
+            out[((size_t)r * C + c0 + cl) * bins + t] = acc / (float)(G * G);
+        }
+    }
+    };
+    if (staged) {
+        pool_bins([&](int cl) { return (const float*)(win + cl * RA_WIN_FLOATS); });
+    } else {
+        pool_bins([&](int cl) { return f + (size_t)(c0 + cl) * H * W; });
+    }
     }

@@ -15,6 +15,46 @@ struct LevelParams {
     float k_min, k_max;
 };
 
+// Element types of the feature maps (SMOT_FEAT_*).  Only the maps have a type: the kernels that read them convert right
+// behind the load — fp16 with the exact hardware conversion (subnormals kept: the code objects run with fp16 denormals
+// on), bf16 by a 16-bit shift — and every later instruction is the fp32 kernel's, so a call on maps of type T returns
+// bit for bit what the fp32 call returns on the upcast maps.  LevelParams keeps its `const float*` slots for every type
+// (the fp32 kernels' argument layout is untouched); a typed kernel reads them as `const FT*`.
+struct f16_t {
+    unsigned short bits;
+};
+struct bf16_t {
+    unsigned short bits;
+};
+// one element from its 16 bits (the low half of `b`; the high half is ignored)
+template <typename FT>
+__device__ __forceinline__ float feat_cvt(unsigned b) {
+    if constexpr (sizeof(FT) == 4) {
+        return __uint_as_float(b);
+    } else if constexpr (__is_same(FT, f16_t)) {
+        return (float)__builtin_bit_cast(_Float16, (unsigned short)b);
+    } else {
+        return __uint_as_float(b << 16);
+    }
+}
+// element k (0 / 1) of a dword that holds two 2-byte elements
+template <typename FT, int K>
+__device__ __forceinline__ float feat_of_pair(unsigned d) {
+    if constexpr (__is_same(FT, f16_t)) {
+        return (float)__builtin_bit_cast(_Float16, (unsigned short)(K == 0 ? d : d >> 16));
+    } else {
+        return __uint_as_float(K == 0 ? d << 16 : d & 0xffff0000u);
+    }
+}
+template <typename FT>
+__device__ __forceinline__ float feat_ld(const FT* p) {
+    if constexpr (sizeof(FT) == 4) {
+        return *p;
+    } else {
+        return feat_cvt<FT>(p->bits);
+    }
+}
+
 // Rows of a batched call (smot_emm_*_batched_fwd): the rois of image b are [row_start[b], row_start[b+1]) and the maps are
 // [num_images, C, H_l, W_l].  A kernel argument of the batched instantiations only; the single-image kernels take NoImages
 // (nothing) and are unchanged.

@@ -64,6 +64,27 @@ int smot_debug_launch_flags();      // common.hip: hipExtAnyOrderLaunch when SMO
         }                                  \
     } while (0)
 
+// The element type of the call in progress on this thread (common.hip).  The typed C entry points validate their
+// `feat_type`, set it for the duration of the call and run the fp32 entry point's host code; the launch sites of the three
+// kernels that read the maps pick the instantiation by it.  Outside a typed call it is SMOT_FEAT_F32.
+int feat_type();
+struct FeatTypeScope {
+    int prev;
+    explicit FeatTypeScope(int ft);
+    ~FeatTypeScope();
+};
+// SMOT_ERR_BAD_ARG (with a message that names the value) for anything but SMOT_FEAT_F32 / F16 / BF16
+int check_feat_type(int ft, const char* who);
+// `STMT` with FT bound to the maps' element type of the call in progress (fp16 / bf16 only: the fp32 launches stand as written)
+#define SMOT_HALF_TYPES(...)                     \
+    if (smot::feat_type() == SMOT_FEAT_F16) {    \
+        using FT = smot::f16_t;                  \
+        __VA_ARGS__;                             \
+    } else {                                     \
+        using FT = smot::bf16_t;                 \
+        __VA_ARGS__;                             \
+    }
+
 // fp32 ops that must NOT be contracted into FMAs, so that the rounding sequence matches the
 // reference's separate torch mul / add kernels.  (In ROCm 7.2 __fmul_rn & co. are plain operators,
 // so the guarantee comes from building with -ffp-contract=off — see build.py.)

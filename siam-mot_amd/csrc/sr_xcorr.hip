@@ -116,6 +116,43 @@ __device__ __forceinline__ gptr_t uniform_base(const float* p) {
 // Arithmetic per output is generation 2's, term by term (same fmaf chains), so results are bit-identical to it.
 typedef int v4i_t __attribute__((ext_vector_type(4)));
 
+// The row loads of the pooling by the maps' element type FT (sr_xcorr_fused9_body.h): one column per lane (4 or 2 bytes),
+// or two adjacent columns (8 bytes at 4-byte alignment, or 4 bytes at 2-byte alignment: odd xmin, odd map width — the
+// runtime runs the memory pipeline in its unaligned access mode).  The conversion to fp32 is exact (roi_common.h).
+typedef int v2i_t __attribute__((ext_vector_type(2)));
+template <typename FT>
+struct fx_pair {
+    typedef int type;
+};
+template <>
+struct fx_pair<float> {
+    typedef v2i_t type;
+};
+template <typename FT>
+__device__ __forceinline__ typename fx_pair<FT>::type fx_load2(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, int soff) {
+    if constexpr (sizeof(FT) == 4) {
+        return __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff, soff, 0);
+    } else {
+        return __builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, soff, 0);
+    }
+}
+template <typename FT>
+__device__ __forceinline__ float fx_pair_elem(typename fx_pair<FT>::type v, int k) {
+    if constexpr (sizeof(FT) == 4) {
+        return __int_as_float(v[k]);
+    } else {
+        return k == 0 ? feat_of_pair<FT, 0>((unsigned)v) : feat_of_pair<FT, 1>((unsigned)v);
+    }
+}
+template <typename FT>
+__device__ __forceinline__ float fx_load1(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, int soff) {
+    if constexpr (sizeof(FT) == 4) {
+        return __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, soff, 0));
+    } else {
+        return feat_cvt<FT>((unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rsrc, voff, soff, 0));
+    }
+}
+
 __device__ __forceinline__ float rl_f(float v, int lane_const) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane_const));
 }
@@ -438,6 +475,7 @@ sr_xcorr_fused9_kernel(LevelParams P, int C, const float* __restrict__ sr, const
                        int32_t* __restrict__ levels_out, SrOut S) {
     constexpr bool BATCHED = false;
     constexpr NoImages I{};
+    using FT = float;
 #include "sr_xcorr_fused9_body.h"
 }
 
@@ -449,6 +487,33 @@ sr_xcorr_fused9_batched_kernel(LevelParams P, int C, const float* __restrict__ s
                                const float* __restrict__ z, float* __restrict__ resp, float* __restrict__ x_debug,
                                int32_t* __restrict__ levels_out, SrOut S, ImageRows I) {
     constexpr bool BATCHED = true;
+    constexpr bool P2 = false;
+    using FT = float;
+#include "sr_xcorr_fused9_body.h"
+}
+
+// The same two kernels on fp16 / bf16 maps (FT = f16_t / bf16_t; smot_*_typed_fwd): P.feat[] is read as `const FT*`, the
+// image offset of the batched form is in elements of FT.  Only the product's forms exist (no A/B variants).
+template <typename FT, int RX, int RZ, int G, bool XCORR, int MM = 0>
+__global__ void __launch_bounds__(64 * FX_CH, MM == 1 ? 4 : 6)
+sr_xcorr_fused9_half_kernel(LevelParams P, int C, const float* __restrict__ sr, const float* __restrict__ boxes,
+                            const float* __restrict__ z, float* __restrict__ resp, float* __restrict__ x_debug,
+                            int32_t* __restrict__ levels_out, SrOut S) {
+    static_assert(sizeof(FT) == 2, "fp16 / bf16 maps");
+    constexpr bool BATCHED = false;
+    constexpr NoImages I{};
+    constexpr int NCH = FX_CH;
+    constexpr bool P2 = false;
+#include "sr_xcorr_fused9_body.h"
+}
+template <typename FT, int RX, int RZ, int G, bool XCORR, int MM = 0>
+__global__ void __launch_bounds__(64 * FX_CH, MM == 1 ? 4 : 6)
+sr_xcorr_fused9_half_batched_kernel(LevelParams P, int C, const float* __restrict__ sr, const float* __restrict__ boxes,
+                                    const float* __restrict__ z, float* __restrict__ resp, float* __restrict__ x_debug,
+                                    int32_t* __restrict__ levels_out, SrOut S, ImageRows I) {
+    static_assert(sizeof(FT) == 2, "fp16 / bf16 maps");
+    constexpr bool BATCHED = true;
+    constexpr int NCH = FX_CH;
     constexpr bool P2 = false;
 #include "sr_xcorr_fused9_body.h"
 }
@@ -470,9 +535,30 @@ static inline bool order_hint_rois(int N, bool consumer) {
     if (knobs().fused_gen == 2 || knobs().no_hint >= (consumer ? 1 : 2)) return false;      // (constant false: product)
     return N >= 2 && N <= 256 && fused_order() == 1;
 }
+// fp16 / bf16 maps (a typed call in progress: feat_type()): the kernel the fp32 call takes, in its *_half_* form; I = the
+// batch's row ranges or nullptr
+template <int RX, bool XCORR, int MM>
+static void launch_fused_half(dim3 grid, hipStream_t st, const LevelParams& P, int C, const float* rois, const float* boxes,
+                              const float* z, float* resp, float* out, int32_t* levels_out, const SrOut& S,
+                              const ImageRows* I) {
+    SMOT_HALF_TYPES(
+        if (I != nullptr) {
+            SMOT_LAUNCH((sr_xcorr_fused9_half_batched_kernel<FT, RX, 15, 2, XCORR, MM>), grid, dim3(512), 0, st, P, C, rois,
+                        boxes, z, resp, out, levels_out, S, *I);
+        } else {
+            SMOT_LAUNCH((sr_xcorr_fused9_half_kernel<FT, RX, 15, 2, XCORR, MM>), grid, dim3(512), 0, st, P, C, rois, boxes, z,
+                        resp, out, levels_out, S);
+        })
+}
+static inline bool half_maps() { return feat_type() != SMOT_FEAT_F32; }
+
 template <int RX, bool XCORR>
 static void launch_fused(dim3 grid, hipStream_t st, const LevelParams& P, int C, const float* rois, const float* boxes,
                          const float* z, float* resp, float* out, int32_t* levels_out, const SrOut& S) {
+    if (half_maps()) {
+        launch_fused_half<RX, XCORR, (RX == 30 && XCORR) ? 1 : 0>(grid, st, P, C, rois, boxes, z, resp, out, levels_out, S, nullptr);
+        return;
+    }
 #ifdef SMOT_DEBUG
     if (knobs().fused_gen == 2 && S.n_valid == nullptr) {      // (generation 2 has no masked form)
         hipLaunchKernelGGL((sr_xcorr_fused8_kernel<RX, 15, 2, XCORR>), grid, dim3(512), 0, st, P, C, rois, boxes, z, resp,
@@ -515,6 +601,8 @@ int launch_roi_pool_separable(const LevelParams& P, int C, const float* rois, co
     SrOut none = {nullptr, 0.f, 0.f, 0.f, 0.f, g_trace, 0, nullptr, fused_order(), nullptr, nullptr, 0};
     if (out_size == 30) {
         launch_fused<30, false>(grid, st, P, C, rois, level_boxes, nullptr, nullptr, out, levels_out, none);
+    } else if (out_size == 7 && half_maps()) {
+        launch_fused_half<7, false, 0>(grid, st, P, C, rois, level_boxes, nullptr, nullptr, out, levels_out, none, nullptr);
     } else if (out_size == 7) {        // the box head's 7x7 pooler (box_head.py:46, roi_heads.py:60-84): same kernel
         SMOT_LAUNCH((sr_xcorr_fused9_kernel<7, 15, 2, false>), grid, dim3(512), 0, st, P, C, rois, level_boxes,
                     (const float*)nullptr, (float*)nullptr, out, levels_out, none);
@@ -542,7 +630,9 @@ int launch_extract_cache(const float* const* feats, const int* heights, const in
     // the next frame's search-region pooling runs on maps zero-padded by int(pad_pixels / stride) cells per level
     // (track_utils.py:94-96); the hint's finished tables are built against exactly that
     for (int l = 0; l < num_levels && l < SMOT_MAX_LEVELS; ++l) S.plan_pad[l] = (int)(pad_pixels * scales[l]);
-    if (rz == 7) {                 // the second yaml family's template (DLA_34_FPN_EMM_AOT.yaml:52-63): same kernel, 7x7 bins
+    if (rz == 7 && half_maps()) {
+        launch_fused_half<7, false, 0>(grid, st, P, C, boxes, boxes, nullptr, nullptr, templates, nullptr, S, nullptr);
+    } else if (rz == 7) {          // the second yaml family's template (DLA_34_FPN_EMM_AOT.yaml:52-63): same kernel, 7x7 bins
         SMOT_LAUNCH((sr_xcorr_fused9_kernel<7, 15, 2, false>), grid, dim3(512), 0, st, P, C, boxes, boxes, (const float*)nullptr,
                     (float*)nullptr, templates, (int32_t*)nullptr, S);
     } else {
@@ -558,7 +648,11 @@ int launch_roi_pool_separable_batched(const LevelParams& P, int C, const float* 
                                       int out_size, float* out, hipStream_t st, const ImageRows& I) {
     dim3 grid(R, (C + FX_CH - 1) / FX_CH);
     SrOut none = {nullptr, 0.f, 0.f, 0.f, 0.f, g_trace, 0, nullptr, fused_order(), nullptr, nullptr, 0};
-    if (out_size == 30) {
+    if (half_maps()) {
+        if (out_size == 30) launch_fused_half<30, false, 0>(grid, st, P, C, rois, level_boxes, nullptr, nullptr, out, nullptr, none, &I);
+        else if (out_size == 7) launch_fused_half<7, false, 0>(grid, st, P, C, rois, level_boxes, nullptr, nullptr, out, nullptr, none, &I);
+        else launch_fused_half<15, false, 0>(grid, st, P, C, rois, level_boxes, nullptr, nullptr, out, nullptr, none, &I);
+    } else if (out_size == 30) {
         SMOT_LAUNCH((sr_xcorr_fused9_batched_kernel<30, 15, 2, false>), grid, dim3(512), 0, st, P, C, rois, level_boxes,
                     (const float*)nullptr, (float*)nullptr, out, (int32_t*)nullptr, none, I);
     } else if (out_size == 7) {
@@ -586,7 +680,10 @@ int launch_extract_cache_batched(const float* const* feats, const int* heights, 
     dim3 grid(N, (C + FX_CH - 1) / FX_CH + (order_hint != nullptr ? 1 : 0));
     SrOut S = {sr, pad_pixels, half_e, two_e, min_wh, g_trace, 0, nullptr, fused_order(), order_hint, nullptr, 0};
     for (int l = 0; l < num_levels && l < SMOT_MAX_LEVELS; ++l) S.plan_pad[l] = (int)(pad_pixels * scales[l]);
-    if (rz == 7) {
+    if (half_maps()) {
+        if (rz == 7) launch_fused_half<7, false, 0>(grid, st, P, C, boxes, boxes, nullptr, nullptr, templates, nullptr, S, &I);
+        else launch_fused_half<15, false, 0>(grid, st, P, C, boxes, boxes, nullptr, nullptr, templates, nullptr, S, &I);
+    } else if (rz == 7) {
         SMOT_LAUNCH((sr_xcorr_fused9_batched_kernel<7, 15, 2, false>), grid, dim3(512), 0, st, P, C, boxes, boxes,
                     (const float*)nullptr, (float*)nullptr, templates, (int32_t*)nullptr, S, I);
     } else {
@@ -613,8 +710,11 @@ int sr_xcorr_fused_batched_impl(const float* const* feats, const int* heights, c
     SrOut none = {nullptr, 0.f, 0.f, 0.f, 0.f, g_trace, 0, nullptr, fused_order(), nullptr, order_hint, 0};
     none.plane_max = plane_max;
     timer_mark(0, 0, st);
-    SMOT_LAUNCH((sr_xcorr_fused9_batched_kernel<30, 15, 2, true, FX_CH, 1>), grid, dim3(512), 0, st, P, C, sr, boxes,
-                templates, resp, (float*)nullptr, (int32_t*)nullptr, none, I);
+    if (half_maps())
+        launch_fused_half<30, true, 1>(grid, st, P, C, sr, boxes, templates, resp, nullptr, nullptr, none, &I);
+    else
+        SMOT_LAUNCH((sr_xcorr_fused9_batched_kernel<30, 15, 2, true, FX_CH, 1>), grid, dim3(512), 0, st, P, C, sr, boxes,
+                    templates, resp, (float*)nullptr, (int32_t*)nullptr, none, I);
     timer_mark(0, 1, st);
     return check_launch("sr_xcorr_fused_batched");
 }
@@ -742,4 +842,16 @@ extern "C" int smot_sr_xcorr_fused_fwd(const float* const* feats, const int* hei
     SMOT_REQUIRE(boxes && sr && templates && resp, "sr_xcorr_fused: null pointer");
     return sr_xcorr_fused_impl(feats, heights, widths, pad_cells, scales, num_levels, C, boxes, sr, templates, N, resp,
                                x_debug, nullptr, (hipStream_t)stream, nullptr, nullptr);
+}
+
+// fp16 / bf16 maps (include/smot_emm.h, "fp16 / bf16 FEATURE MAPS")
+extern "C" int smot_sr_xcorr_fused_typed_fwd(const void* const* feats, int feat_type, const int* heights, const int* widths,
+                                             const int* pad_cells, const float* scales, int num_levels, int C,
+                                             const float* boxes, const float* sr, const float* templates, int N, int rx,
+                                             int rz, int sampling_ratio, float* resp, float* x_debug, smot_stream_t stream) {
+    const int rc = smot::check_feat_type(feat_type, "sr_xcorr_fused_typed");
+    if (rc) return rc;
+    smot::FeatTypeScope scope(feat_type);
+    return smot_sr_xcorr_fused_fwd(reinterpret_cast<const float* const*>(feats), heights, widths, pad_cells, scales, num_levels,
+                                   C, boxes, sr, templates, N, rx, rz, sampling_ratio, resp, x_debug, stream);
 }

@@ -2,6 +2,9 @@
 // inside each kernel's braces, which define BATCHED and the kernel arguments (I = the batch's ImageRows, or NoImages).
 // One text in two kernels instead of one inlined device function: the single-image kernels compile to the same code as
 // before batching existed (an inlined body schedules differently).
+// FT (defined by the kernel as well) is the maps' element type: float, or f16_t / bf16_t in the *_half_* kernels, which
+// load 2-byte elements and convert them right behind the load (fx_load1 / fx_load2 / fx_pair_elem); everything else,
+// the sample tables and the order hint's row BYTE offsets of an fp32 map included, is the same text.
     constexpr int HO = XCORR ? RX - RZ + 1 : 16;
     constexpr int NS = RX * G;                   // samples per axis
     // LDS image of the one-plane-per-wave correlation (xcorr_patch1.h): row stride 40, one plane per slot
@@ -272,10 +275,12 @@
     FX_TRACE(2)
 
     // ---- pooling ----------------------------------------------------------------------------------------------
-    const float* __restrict__ fbase = P.feat[lvl];
+    const FT* __restrict__ fbase = reinterpret_cast<const FT*>(P.feat[lvl]);
     // batched: the image's offset goes into the 64-bit base (a batch of maps passes 4 GiB; lane offsets stay 32-bit)
     if constexpr (BATCHED) fbase += (size_t)img * ((size_t)C * H * W);
-    const unsigned plane_bytes = (unsigned)(H * W) * 4u;
+    const unsigned plane_bytes = (unsigned)(H * W) * (unsigned)sizeof(FT);
+    // the tables (and a hint's) hold row offsets in bytes of an fp32 map: 2-byte maps halve them where they are used
+    constexpr int ROW_SHIFT = sizeof(FT) == 2 ? 1 : 0;
     // One batch = ROWS pooled rows of one plane (or of a plane pair side by side).  `PAIR`: lanes 32..63 pool the
     // wave's second plane and the two waves of the pair split the pooled rows; `CHUNKED`: windows wider than 64
     // columns (rare: small batches keep its loop-carried accumulators out of the register peak).
@@ -298,7 +303,7 @@
         const unsigned lane_plane = (PAIR && half == 1 && has1) ? plane_bytes : 0u;
         float* xdst = sm + ((pl0 + half) >> 1) * (2 * XP + 2 * ZP) + ((pl0 + half) & 1) * XP;
         // buffer resource of the (first) plane: wave-uniform base, offsets are 32-bit
-        const float* pbase = fbase + (size_t)(c0 + pl0) * H * W;
+        const FT* pbase = fbase + (size_t)(c0 + pl0) * H * W;
         unsigned long long pa = reinterpret_cast<unsigned long long>(pbase);
         const unsigned pa_lo = __builtin_amdgcn_readfirstlane((unsigned)pa);
         const unsigned pa_hi = __builtin_amdgcn_readfirstlane((unsigned)(pa >> 32));
@@ -324,20 +329,21 @@
             // registers, so that their memory round trip runs beside this batch's staging and horizontal taps instead of
             // behind them: ONE exposed round trip per wave instead of one per batch.  Three batches of five rows (40 load
             // registers in flight; two of eight rows spilled 30 registers).  Same loads, same FMA chains: bit-identical.
-            typedef int v2i_t __attribute__((ext_vector_type(2)));
             constexpr int GR = (ROWS + 1) / 2, SW = 64;
             static_assert(RH % ROWS == 0 && GR * SW <= ROWS * XS, "full batches; staging fits a batch's own rows");
             const int wcol = min(2 * col, ww - 2);
-            const unsigned voff = (unsigned)(xmin + wcol) * 4u + lane_plane;
-            v2i_t vl[ROWS][G], vh[ROWS][G];
+            const unsigned voff = (unsigned)(xmin + wcol) * (unsigned)sizeof(FT) + lane_plane;
+            typename fx_pair<FT>::type vl[ROWS][G], vh[ROWS][G];
             // (fast: the wave's own 30 y entries sit in ye_early, batch b's at lanes 10 b ..; else a batch's entries from LDS)
             int4 ye = fast ? ye_early : tab[0][min(lane + row0 * G, 63 + 2 * RH * G)];
+            ye.x = (int)((unsigned)ye.x >> ROW_SHIFT);
+            ye.y = (int)((unsigned)ye.y >> ROW_SHIFT);
             int yoff = 0;
 #define SMOT_FX_ISSUE()                                                                                             \
             _Pragma("unroll") for (int b = 0; b < ROWS; ++b)                                                        \
                 _Pragma("unroll") for (int iy = 0; iy < G; ++iy) {                                                  \
-                    vl[b][iy] = __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff, __builtin_amdgcn_readlane(ye.x, yoff + b * G + iy), 0); \
-                    vh[b][iy] = __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff, __builtin_amdgcn_readlane(ye.y, yoff + b * G + iy), 0); \
+                    vl[b][iy] = fx_load2<FT>(rsrc, voff, __builtin_amdgcn_readlane(ye.x, yoff + b * G + iy));         \
+                    vh[b][iy] = fx_load2<FT>(rsrc, voff, __builtin_amdgcn_readlane(ye.y, yoff + b * G + iy));         \
                 }
             SMOT_FX_ISSUE()
             __builtin_amdgcn_sched_barrier(0);
@@ -358,15 +364,19 @@
 #pragma unroll
                         for (int iy = 0; iy < G; ++iy) {
                             const int e = yoff + b * G + iy;
-                            c_ = fmaf(rl_f(wl, e), __int_as_float(vl[b][iy][k]), c_);
-                            c_ = fmaf(rl_f(wh, e), __int_as_float(vh[b][iy][k]), c_);
+                            c_ = fmaf(rl_f(wl, e), fx_pair_elem<FT>(vl[b][iy], k), c_);
+                            c_ = fmaf(rl_f(wh, e), fx_pair_elem<FT>(vh[b][iy], k), c_);
                         }
                         cs[b][k] = c_;
                     }
                 __builtin_amdgcn_sched_barrier(0);
                 if (r0 + ROWS < row0 + nrows) {                      // (wave-uniform) the next batch's entries and row loads
                     if (fast) yoff += ROWS * G;
-                    else ye = tab[0][min(lane + (r0 + ROWS) * G, 63 + 2 * RH * G)];
+                    else {
+                        ye = tab[0][min(lane + (r0 + ROWS) * G, 63 + 2 * RH * G)];
+                        ye.x = (int)((unsigned)ye.x >> ROW_SHIFT);
+                        ye.y = (int)((unsigned)ye.y >> ROW_SHIFT);
+                    }
                     SMOT_FX_ISSUE()
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -411,7 +421,7 @@
             // the table (masked tail rows) read the zero pad: weight 0, offset 0
             // (fast: only the narrow plane-pair form comes here — ONE batch at r0 == row0, the entries ye_early holds)
             const int4 ye = (fast && PAIR && !CHUNKED) ? ye_early : tab[0][min(lane + r0 * G, 63 + 2 * RH * G)];
-            const unsigned ol = (unsigned)ye.x, oh = (unsigned)ye.y;
+            const unsigned ol = (unsigned)ye.x >> ROW_SHIFT, oh = (unsigned)ye.y >> ROW_SHIFT;
             const float wl = __int_as_float(ye.z), wh = __int_as_float(ye.w);
             float acc[ROWS];
             if (CHUNKED) {
@@ -424,7 +434,7 @@
                 // first window column this lane loads.  X2: columns (wcol, wcol + 1); the last pair of an odd-width
                 // window is (ww-2, ww-1) — lanes past the window repeat it (same values to the same staging slots)
                 const int wcol = CHUNKED ? min(cbase + col, ww - 1) : (X2 ? min(2 * col, ww - 2) : min(col, ww - 1));
-                const unsigned voff = (unsigned)(xmin + wcol) * 4u + lane_plane;
+                const unsigned voff = (unsigned)(xmin + wcol) * (unsigned)sizeof(FT) + lane_plane;
                 float v[ROWS][G][2][NV];
 #pragma unroll
                 for (int b = 0; b < ROWS; ++b)
@@ -432,18 +442,15 @@
                     for (int iy = 0; iy < G; ++iy) {
                         const int e = b * G + iy;
                         if constexpr (X2) {
-                            typedef int v2i_t __attribute__((ext_vector_type(2)));
-                            const v2i_t l2 = __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff, __builtin_amdgcn_readlane((int)ol, e), 0);
-                            const v2i_t h2 = __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff, __builtin_amdgcn_readlane((int)oh, e), 0);
-                            v[b][iy][0][0] = __int_as_float(l2.x);
-                            v[b][iy][0][NV - 1] = __int_as_float(l2.y);
-                            v[b][iy][1][0] = __int_as_float(h2.x);
-                            v[b][iy][1][NV - 1] = __int_as_float(h2.y);
+                            const auto l2 = fx_load2<FT>(rsrc, voff, __builtin_amdgcn_readlane((int)ol, e));
+                            const auto h2 = fx_load2<FT>(rsrc, voff, __builtin_amdgcn_readlane((int)oh, e));
+                            v[b][iy][0][0] = fx_pair_elem<FT>(l2, 0);
+                            v[b][iy][0][NV - 1] = fx_pair_elem<FT>(l2, 1);
+                            v[b][iy][1][0] = fx_pair_elem<FT>(h2, 0);
+                            v[b][iy][1][NV - 1] = fx_pair_elem<FT>(h2, 1);
                         } else {
-                            v[b][iy][0][0] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-                                rsrc, voff, __builtin_amdgcn_readlane((int)ol, e), 0));
-                            v[b][iy][1][0] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-                                rsrc, voff, __builtin_amdgcn_readlane((int)oh, e), 0));
+                            v[b][iy][0][0] = fx_load1<FT>(rsrc, voff, __builtin_amdgcn_readlane((int)ol, e));
+                            v[b][iy][1][0] = fx_load1<FT>(rsrc, voff, __builtin_amdgcn_readlane((int)oh, e));
                         }
                     }
                 // fences: hipcc otherwise sinks the loads to their first use (4 loads, wait, use, next 4 loads ...)

@@ -1,6 +1,8 @@
 // The body of the 35 / 7 gathers + correlation kernel, shared by its single-image and batched forms (sr_xcorr_small.hip):
 // included inside each kernel's braces, which define BATCHED and I (the batch's ImageRows, or NoImages) — one text in two
 // kernels, so that the single-image kernel compiles to the same code as before batching existed.
+// FT (defined by the kernel as well) is the maps' element type: float, or f16_t / bf16_t in the *_half_* kernels, whose
+// gathers fetch 2-byte cells (four of them in 8 bytes) and convert them right behind the load.
     constexpr int HO = RX - RZ + 1;
     constexpr int NQ = (HO + 3) / 4;                     // column groups per response row
     constexpr int XS = ((4 * NQ + RZ - 1 + 3) / 4) * 4;  // padded LDS row of a pooled plane (floats)
@@ -104,7 +106,7 @@
     // The gathers are what this phase costs (the address path takes a wave instruction's 64 addresses at a fixed rate,
     // whatever their width: 16 four-byte gathers per bin and channel 205 us per frame pair, 8 eight-byte ones 192), so the
     // cells are fetched in the widest pieces that hold them; the values, products and sums are the generic kernel's.
-    const float* __restrict__ f = P.feat[lvl];
+    const FT* __restrict__ f = reinterpret_cast<const FT*>(P.feat[lvl]);
     // batched: the roi's image in the 64-bit base (a batch of maps passes 4 GiB; the per-plane resources below keep it)
     if constexpr (BATCHED) f += (size_t)image_of_row(I, r) * ((size_t)C * H * W);
     // one buffer resource per PLANE (its size is the bound the hardware checks the lane offsets against — a scalar offset
@@ -117,7 +119,7 @@
         const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)fa);
         const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(fa >> 32));
         return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
-                                                 (int)((unsigned)(H * W) * 4u), 0x00020000);
+                                                 (int)((unsigned)(H * W) * (unsigned)sizeof(FT)), 0x00020000);
     };
     typedef int v2i_t __attribute__((ext_vector_type(2)));
     for (int t0 = 0; t0 < RX * RX; t0 += 256) {
@@ -146,13 +148,39 @@
         // wave needs those is decided once per bin (wave-uniform: no divergent memory code).
         static_assert(G == 2, "two samples per bin and axis");
         const int d1 = xlo[1] - xlo[0];
-        const bool quad = (xhi[0] == xlo[0] + 1) && (xhi[1] == xlo[1] + 1) && d1 >= 0 && d1 <= 2;
+        bool quad_ = (xhi[0] == xlo[0] + 1) && (xhi[1] == xlo[1] + 1) && d1 >= 0 && d1 <= 2;
+        if constexpr (sizeof(FT) == 2) {
+            // 2-byte cells: the hardware checks the plane's bound per DWORD, so a dword that straddles the plane's end would
+            // read as zeros together with the last cell in it — a bin whose 8-byte piece reaches past the end takes the
+            // exact 2-byte gathers instead
+            quad_ = quad_ && max(max(ylo[0], ylo[1]), max(yhi[0], yhi[1])) + xlo[0] + 4 <= H * W;
+        }
+        const bool quad = quad_;
         const bool any_odd = __any(!quad);
         typedef int v4i_t __attribute__((ext_vector_type(4)));
         for (int cl = 0; cl < nch; ++cl) {
             const auto rsrc = plane_rsrc(c0 + cl);
             const int soff = 0;
             float vl[G][G][2], vh[G][G][2];        // [iy][ix][low / high column] of the low / high row
+            if constexpr (sizeof(FT) == 2) {
+#pragma unroll
+                for (int iy = 0; iy < G; ++iy) {
+                    const v2i_t a2 = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (unsigned)(ylo[iy] + xlo[0]) * 2u, soff, 0);
+                    const v2i_t b2 = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (unsigned)(yhi[iy] + xlo[0]) * 2u, soff, 0);
+                    const float a[4] = {feat_of_pair<FT, 0>((unsigned)a2.x), feat_of_pair<FT, 1>((unsigned)a2.x),
+                                        feat_of_pair<FT, 0>((unsigned)a2.y), feat_of_pair<FT, 1>((unsigned)a2.y)};
+                    const float b4[4] = {feat_of_pair<FT, 0>((unsigned)b2.x), feat_of_pair<FT, 1>((unsigned)b2.x),
+                                         feat_of_pair<FT, 0>((unsigned)b2.y), feat_of_pair<FT, 1>((unsigned)b2.y)};
+                    vl[iy][0][0] = a[0];
+                    vl[iy][0][1] = a[1];
+                    vh[iy][0][0] = b4[0];
+                    vh[iy][0][1] = b4[1];
+                    vl[iy][1][0] = d1 == 0 ? a[0] : (d1 == 1 ? a[1] : a[2]);
+                    vl[iy][1][1] = d1 == 0 ? a[1] : (d1 == 1 ? a[2] : a[3]);
+                    vh[iy][1][0] = d1 == 0 ? b4[0] : (d1 == 1 ? b4[1] : b4[2]);
+                    vh[iy][1][1] = d1 == 0 ? b4[1] : (d1 == 1 ? b4[2] : b4[3]);
+                }
+            } else {
 #pragma unroll
             for (int iy = 0; iy < G; ++iy) {
                 const v4i_t a = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (unsigned)(ylo[iy] + xlo[0]) * 4u, soff, 0);
@@ -166,15 +194,16 @@
                 vh[iy][1][0] = __int_as_float(d1 == 0 ? b4[0] : (d1 == 1 ? b4[1] : b4[2]));
                 vh[iy][1][1] = __int_as_float(d1 == 0 ? b4[1] : (d1 == 1 ? b4[2] : b4[3]));
             }
+            }
             if (any_odd) {
 #pragma unroll
                 for (int iy = 0; iy < G; ++iy)
 #pragma unroll
                     for (int ix = 0; ix < G; ++ix) {
-                        const float o1 = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, (unsigned)(ylo[iy] + xlo[ix]) * 4u, soff, 0));
-                        const float o2 = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, (unsigned)(ylo[iy] + xhi[ix]) * 4u, soff, 0));
-                        const float o3 = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, (unsigned)(yhi[iy] + xlo[ix]) * 4u, soff, 0));
-                        const float o4 = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, (unsigned)(yhi[iy] + xhi[ix]) * 4u, soff, 0));
+                        const float o1 = sx_load1<FT>(rsrc, (unsigned)(ylo[iy] + xlo[ix]) * (unsigned)sizeof(FT));
+                        const float o2 = sx_load1<FT>(rsrc, (unsigned)(ylo[iy] + xhi[ix]) * (unsigned)sizeof(FT));
+                        const float o3 = sx_load1<FT>(rsrc, (unsigned)(yhi[iy] + xlo[ix]) * (unsigned)sizeof(FT));
+                        const float o4 = sx_load1<FT>(rsrc, (unsigned)(yhi[iy] + xhi[ix]) * (unsigned)sizeof(FT));
                         if (!quad) {
                             vl[iy][ix][0] = o1;
                             vl[iy][ix][1] = o2;

@@ -27,12 +27,23 @@ namespace smot {
 
 constexpr int SX_CH = 4;             // channels per workgroup
 
+// one cell of a plane by the maps' element type (the gathers of lanes whose cells do not lie in one piece)
+template <typename FT>
+__device__ __forceinline__ float sx_load1(__amdgpu_buffer_rsrc_t rsrc, unsigned voff) {
+    if constexpr (sizeof(FT) == 4) {
+        return __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, 0, 0));
+    } else {
+        return feat_cvt<FT>((unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rsrc, voff, 0, 0));
+    }
+}
+
 template <int RX, int RZ, int G>
 __global__ void __launch_bounds__(256)
 sr_xcorr_gather_kernel(LevelParams P, int C, const float* __restrict__ rois, const float* __restrict__ level_boxes,
                        const float* __restrict__ z, float* __restrict__ resp, float* __restrict__ plane_max) {
     constexpr bool BATCHED = false;
     constexpr NoImages I{};
+    using FT = float;
 #include "sr_xcorr_gather_body.h"
 }
 
@@ -42,6 +53,27 @@ __global__ void __launch_bounds__(256)
 sr_xcorr_gather_batched_kernel(LevelParams P, int C, const float* __restrict__ rois, const float* __restrict__ level_boxes,
                                const float* __restrict__ z, float* __restrict__ resp, float* __restrict__ plane_max,
                                ImageRows I) {
+    constexpr bool BATCHED = true;
+    using FT = float;
+#include "sr_xcorr_gather_body.h"
+}
+
+// The same two kernels on fp16 / bf16 maps (FT = f16_t / bf16_t; smot_*_typed_fwd): P.feat[] is read as `const FT*`
+template <typename FT, int RX, int RZ, int G>
+__global__ void __launch_bounds__(256)
+sr_xcorr_gather_half_kernel(LevelParams P, int C, const float* __restrict__ rois, const float* __restrict__ level_boxes,
+                            const float* __restrict__ z, float* __restrict__ resp, float* __restrict__ plane_max) {
+    static_assert(sizeof(FT) == 2, "fp16 / bf16 maps");
+    constexpr bool BATCHED = false;
+    constexpr NoImages I{};
+#include "sr_xcorr_gather_body.h"
+}
+template <typename FT, int RX, int RZ, int G>
+__global__ void __launch_bounds__(256)
+sr_xcorr_gather_half_batched_kernel(LevelParams P, int C, const float* __restrict__ rois,
+                                    const float* __restrict__ level_boxes, const float* __restrict__ z,
+                                    float* __restrict__ resp, float* __restrict__ plane_max, ImageRows I) {
+    static_assert(sizeof(FT) == 2, "fp16 / bf16 maps");
     constexpr bool BATCHED = true;
 #include "sr_xcorr_gather_body.h"
 }
@@ -53,7 +85,12 @@ int launch_sr_xcorr_gather(const LevelParams& P, int C, const float* sr, const f
     if (N == 0) return SMOT_OK;
     dim3 grid(N, (C + SX_CH - 1) / SX_CH);
     timer_mark(0, 0, st);
-    SMOT_LAUNCH((sr_xcorr_gather_kernel<35, 7, 2>), grid, dim3(256), 0, st, P, C, sr, boxes, templates, resp, plane_max);
+    if (feat_type() != SMOT_FEAT_F32) {
+        SMOT_HALF_TYPES(SMOT_LAUNCH((sr_xcorr_gather_half_kernel<FT, 35, 7, 2>), grid, dim3(256), 0, st, P, C, sr, boxes,
+                                    templates, resp, plane_max))
+    } else {
+        SMOT_LAUNCH((sr_xcorr_gather_kernel<35, 7, 2>), grid, dim3(256), 0, st, P, C, sr, boxes, templates, resp, plane_max);
+    }
     timer_mark(0, 1, st);
     return check_launch("sr_xcorr_gather");
 }
@@ -79,7 +116,13 @@ int sr_xcorr_gather_batched_impl(const float* const* feats, const int* heights, 
     if (N == 0) return SMOT_OK;
     dim3 grid(N, (C + SX_CH - 1) / SX_CH);
     timer_mark(0, 0, st);
-    SMOT_LAUNCH((sr_xcorr_gather_batched_kernel<35, 7, 2>), grid, dim3(256), 0, st, P, C, sr, boxes, templates, resp, plane_max, I);
+    if (feat_type() != SMOT_FEAT_F32) {
+        SMOT_HALF_TYPES(SMOT_LAUNCH((sr_xcorr_gather_half_batched_kernel<FT, 35, 7, 2>), grid, dim3(256), 0, st, P, C, sr,
+                                    boxes, templates, resp, plane_max, I))
+    } else {
+        SMOT_LAUNCH((sr_xcorr_gather_batched_kernel<35, 7, 2>), grid, dim3(256), 0, st, P, C, sr, boxes, templates, resp,
+                    plane_max, I);
+    }
     timer_mark(0, 1, st);
     return check_launch("sr_xcorr_gather_batched");
 }
@@ -102,4 +145,16 @@ extern "C" int smot_sr_xcorr_gather_fwd(const float* const* feats, const int* he
     SMOT_REQUIRE(boxes && sr && templates && resp, "sr_xcorr_gather: null pointer");
     return sr_xcorr_gather_impl(feats, heights, widths, pad_cells, scales, num_levels, C, boxes, sr, templates, N, rx, rz,
                                 sampling_ratio, resp, (hipStream_t)stream, nullptr);
+}
+
+// fp16 / bf16 maps (include/smot_emm.h, "fp16 / bf16 FEATURE MAPS")
+extern "C" int smot_sr_xcorr_gather_typed_fwd(const void* const* feats, int feat_type, const int* heights, const int* widths,
+                                              const int* pad_cells, const float* scales, int num_levels, int C,
+                                              const float* boxes, const float* sr, const float* templates, int N, int rx,
+                                              int rz, int sampling_ratio, float* resp, smot_stream_t stream) {
+    const int rc = smot::check_feat_type(feat_type, "sr_xcorr_gather_typed");
+    if (rc) return rc;
+    smot::FeatTypeScope scope(feat_type);
+    return smot_sr_xcorr_gather_fwd(reinterpret_cast<const float* const*>(feats), heights, widths, pad_cells, scales, num_levels,
+                                    C, boxes, sr, templates, N, rx, rz, sampling_ratio, resp, stream);
 }

@@ -280,10 +280,16 @@ class EMM(nn.Module):
         """The cached host plan of this module's two per-frame calls (``ops.PairPlan``), made on first use and again when a
         configuration value, the parameter dict, the library or the device changed; None when the inputs are not plain
         device tensors (the general binding then raises or converts)."""
-        plan = self.__dict__.get("_plan")
+        # one plan per element type of the maps (fp32 / fp16 / bf16): a caller that alternates them keeps all of them; other
+        # map shapes make the type's plan stale (PairPlan.stale watches dtype and shapes)
+        plans = self.__dict__.get("_plan")
+        if plans is None:
+            plans = self.__dict__["_plan"] = {}
+        dt = features[0].dtype if len(features) and isinstance(features[0], torch.Tensor) else None
+        plan = plans.get(dt)
         tu = self.track_utils
         if plan is not None and plan.dev == boxes_bbox.device and not plan.stale(params, self.rx, self.rz, scales,
-                                                                                 sampling_ratio, self.pad_pixels, tu):
+                                                                                 sampling_ratio, self.pad_pixels, tu, features):
             return plan
         if not (isinstance(boxes_bbox, torch.Tensor) and boxes_bbox.is_cuda and self.rx - self.rz + 1 in (16, 29)):
             return None
@@ -292,7 +298,7 @@ class EMM(nn.Module):
                                 self.pad_pixels, tu)
         except (RuntimeError, IndexError, TypeError, AttributeError):
             return None                  # the general binding reports what is wrong with the inputs
-        self.__dict__["_plan"] = plan
+        plans[dt] = plan
         return plan
 
     def track_raw(self, features, boxes, sr, template_features, image_wh, sr_boxlist=None):

@@ -1,7 +1,9 @@
 """ctypes binding of ``csrc/libsmot_emm.so`` (C ABI: include/smot_emm.h) + tensor-level operators.
 
 This is the ONLY compute path of the package: there is no CPU / eager fallback.  If the HIP
-library is missing or a tensor is not a contiguous fp32 device tensor, the call raises.
+library is missing or a tensor is not a contiguous fp32 device tensor, the call raises.  The FPN maps alone may also be
+fp16 or bf16 (a backbone under ``torch.autocast`` or ``.half()``): the ``smot_*_typed_fwd`` entry points read them as
+they are and return bit for bit what the call returns on ``maps.float()``; everything else stays fp32.
 
 Operator ↔ reference map (reference paths relative to amazon-science/siam-mot):
     roi_align_levels   SRPooler.forward            EMM/sr_pool.py:53-91 (+ track_utils.py:87-107 pad)
@@ -97,6 +99,24 @@ _SIGNATURES = {
                                                   _i, _vp]),
     "smot_emm_extract_cache_batched_fwd": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _f, _f, _f,
                                                           _vp, _vp, _vp, _vp, _i, _vp]),
+    # fp16 / bf16 feature maps: the twins' arguments with `feat_type` behind the maps (track / extract_cache: the batched
+    # signatures; extract_cache + n_valid)
+    "smot_roi_align_levels_typed_fwd": (ctypes.c_int, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i,
+                                                       _vp, _vp, _vp]),
+    "smot_roi_align_typed_fwd": (ctypes.c_int, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _f, _i, _i, _i, _vp, _vp]),
+    "smot_sr_xcorr_fused_typed_fwd": (ctypes.c_int, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i,
+                                                     _vp, _vp, _vp]),
+    "smot_sr_xcorr_gather_typed_fwd": (ctypes.c_int, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i,
+                                                      _vp, _vp]),
+    "smot_emm_track_typed_fwd": (ctypes.c_int, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i,
+                                                _vp, _i, _f, _vp, _i, _f, _f, _f, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                _i, _vp]),
+    "smot_emm_extract_cache_typed_fwd": (ctypes.c_int, [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _f, _f, _f,
+                                                        _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "smot_box_refine_typed_fwd": (ctypes.c_int, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i,
+                                                 _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i,
+                                                 _f, _f, _f, _f, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "smot_track_frame_typed_fwd": (ctypes.c_int, [_vp, _i, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 _DEBUG_SIGNATURES = {
@@ -183,6 +203,34 @@ def _dev_f32(t, name):
     return t if t.is_contiguous() else t.contiguous()
 
 
+# element types of the feature MAPS (SMOT_FEAT_* of include/smot_emm.h); everything else is fp32
+FEAT_TYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+
+
+def _dev_feat(t, name):
+    """``_dev_f32`` for a feature map: fp16 and bf16 pass as they are (no copy, no cast)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError("siammot_amd: %s must be a device (ROCm) tensor — no CPU path exists" % name)
+    if t.dtype not in FEAT_TYPES:
+        raise RuntimeError("siammot_amd: %s must be float32 (or a float16 / bfloat16 feature map), got %s" % (name, t.dtype))
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _feat_type(feats):
+    """The one element type of a call's maps (each passed ``_dev_feat``) -> SMOT_FEAT_*; mixed levels raise."""
+    dt = feats[0].dtype
+    for l, f in enumerate(feats):
+        if f.dtype is not dt:
+            raise RuntimeError("siammot_amd: all feature levels of one call must share one dtype, got %s (features[0]) and %s "
+                               "(features[%d])" % (dt, f.dtype, l))
+    return FEAT_TYPES[dt]
+
+
+def _one_image_rows(N):
+    """``row_start`` of a typed call on one image."""
+    return (ctypes.c_int * 2)(0, N)
+
+
 try:
     _raw_stream = torch._C._cuda_getCurrentRawStream         # (device index) -> hipStream_t as int, ~0.2 us
 except AttributeError:                                        # pragma: no cover - older torch
@@ -251,7 +299,8 @@ def roi_align_levels(features, rois, level_boxes, out_size, scales, sampling_rat
     """
     lib = load_library()
     L = len(scales)
-    feats = [_dev_f32(features[l], "features[%d]" % l) for l in range(L)]
+    feats = [_dev_feat(features[l], "features[%d]" % l) for l in range(L)]
+    ft = _feat_type(feats)
     for f in feats:
         if f.dim() != 4 or f.shape[0] != 1:
             raise RuntimeError("siammot_amd.roi_align_levels: one image per call, got feature shape %s"
@@ -271,9 +320,9 @@ def roi_align_levels(features, rois, level_boxes, out_size, scales, sampling_rat
     sc = (ctypes.c_float * L)(*[float(s) for s in scales])
     cast = lambda a: ctypes.cast(a, ctypes.c_void_p)
     with _Launch(rois, level_boxes, *feats) as ln:
-        rc = lib.smot_roi_align_levels_fwd(cast(fp), cast(hs), cast(ws), cast(pc), cast(sc), L, C,
-                                           _ptr(rois), _ptr(level_boxes), R, out_size, out_size,
-                                           int(sampling_ratio), _ptr(out), _ptr(levels), ln.stream)
+        rc = lib.smot_roi_align_levels_typed_fwd(cast(fp), ft, cast(hs), cast(ws), cast(pc), cast(sc), L, C,
+                                                 _ptr(rois), _ptr(level_boxes), R, out_size, out_size,
+                                                 int(sampling_ratio), _ptr(out), _ptr(levels), ln.stream)
     _check(rc, "roi_align_levels")
     return (out, levels) if return_levels else out
 
@@ -281,9 +330,9 @@ def roi_align_levels(features, rois, level_boxes, out_size, scales, sampling_rat
 def roi_align(input, rois, spatial_scale, pooled_h, pooled_w, sampling_ratio, pad_cells=0):
     """[UPSTREAM] ``_C.roi_align_forward(input, rois, spatial_scale, pooled_h, pooled_w, sampling_ratio)``: one feature
     level ``[B,C,H,W]``, rois ``[R,5]`` = (image index, x1, y1, x2, y2) -> ``[R,C,pooled_h,pooled_w]``, allocated here
-    with the input's options as upstream does.  ``pad_cells`` > 0: virtual zero border (rois in padded coordinates)."""
+    in fp32 (a half ``input`` is read as it is; upstream's ``ROIAlign.forward`` is an ``amp.float_function``).  ``pad_cells`` > 0: virtual zero border (rois in padded coordinates)."""
     lib = load_library()
-    input = _dev_f32(input, "input")
+    input = _dev_feat(input, "input")
     rois = _dev_f32(rois, "rois")
     if input.dim() != 4 or rois.dim() != 2 or rois.shape[1] != 5:
         raise RuntimeError("siammot_amd.roi_align: input must be [B,C,H,W] and rois [R,5], got %s and %s"
@@ -292,8 +341,9 @@ def roi_align(input, rois, spatial_scale, pooled_h, pooled_w, sampling_ratio, pa
     R = rois.shape[0]
     out = torch.empty((R, C, int(pooled_h), int(pooled_w)), dtype=torch.float32, device=input.device)
     with _Launch(input, rois) as ln:
-        rc = lib.smot_roi_align_fwd(_ptr(input), B, C, H, W, int(pad_cells), _ptr(rois), R, float(spatial_scale),
-                                    int(pooled_h), int(pooled_w), int(sampling_ratio), _ptr(out), ln.stream)
+        rc = lib.smot_roi_align_typed_fwd(_ptr(input), FEAT_TYPES[input.dtype], B, C, H, W, int(pad_cells), _ptr(rois), R,
+                                          float(spatial_scale), int(pooled_h), int(pooled_w), int(sampling_ratio),
+                                          _ptr(out), ln.stream)
     _check(rc, "roi_align")
     return out
 
@@ -439,7 +489,8 @@ _cast = lambda a: ctypes.cast(a, ctypes.c_void_p)
 
 def _level_arrays(features, scales):
     L = len(scales)
-    feats = [_dev_f32(features[l], "features[%d]" % l) for l in range(L)]
+    feats = [_dev_feat(features[l], "features[%d]" % l) for l in range(L)]
+    _feat_type(feats)                      # (one dtype per call: raises otherwise)
     for f in feats:
         if f.dim() != 4 or f.shape[0] != 1:
             raise RuntimeError("siammot_amd: one image per call, got feature shape %s" % (tuple(f.shape),))
@@ -475,11 +526,12 @@ _F32 = torch.float32
 class _LevelGeometry(object):
     """ctypes arrays of one FPN geometry: heights / widths / scales / virtual pad cells, plus the pointer array
     that is refilled every call."""
-    __slots__ = ("shapes", "L", "C", "fp", "hs", "ws", "sc", "pc", "a_fp", "a_hs", "a_ws", "a_sc", "a_pc", "keep")
+    __slots__ = ("shapes", "L", "C", "fp", "hs", "ws", "sc", "pc", "a_fp", "a_hs", "a_ws", "a_sc", "a_pc", "keep", "dtype", "ft")
 
-    def __init__(self, shapes, scales, pad_pixels):
+    def __init__(self, shapes, scales, pad_pixels, dtype=torch.float32):
         L = len(scales)
         self.shapes, self.L, self.C = shapes, L, shapes[0][1]
+        self.dtype, self.ft = dtype, FEAT_TYPES[dtype]      # the maps' one element type (part of the cache key)
         self.fp = (ctypes.c_void_p * L)()
         self.hs = (ctypes.c_int * L)(*[sh[2] for sh in shapes])
         self.ws = (ctypes.c_int * L)(*[sh[3] for sh in shapes])
@@ -493,12 +545,24 @@ class _LevelGeometry(object):
 _geom_cache = {}
 
 
+def _maps_dtype(features, L):
+    """The element type of a call's maps (levels must agree; anything but fp32 / fp16 / bf16 raises)."""
+    dt = features[0].dtype if isinstance(features[0], torch.Tensor) else None
+    if dt not in FEAT_TYPES:
+        _dev_feat(features[0], "features[0]")               # raises
+    for l in range(1, L):
+        if features[l].dtype is not dt:
+            _feat_type([_dev_feat(features[k], "features[%d]" % k) for k in range(l + 1)])     # raises either way
+    return dt
+
+
 def _geometry(features, scales, pad_pixels, device):
     """Validate the per-level feature tensors (all on ``device``) and return the cached geometry with fresh
     pointers."""
     L = len(scales)
     shapes = tuple(tuple(features[l].shape) for l in range(L))
-    key = (shapes, tuple(scales), pad_pixels)
+    dt = _maps_dtype(features, L)
+    key = (shapes, tuple(scales), pad_pixels, dt)
     g = _geom_cache.get(key)
     if g is None:
         for sh in shapes:
@@ -507,12 +571,12 @@ def _geometry(features, scales, pad_pixels, device):
                                    % (shapes,))
         if len(_geom_cache) > 32:
             _geom_cache.clear()
-        g = _geom_cache[key] = _LevelGeometry(shapes, scales, pad_pixels)
+        g = _geom_cache[key] = _LevelGeometry(shapes, scales, pad_pixels, dt)
     fp = g.fp
     for l in range(L):
         f = features[l]
-        if not (f.is_cuda and f.dtype is _F32 and f.is_contiguous()):
-            f = g.keep[l] = _dev_f32(f, "features[%d]" % l)         # raises, or copies a strided view
+        if not (f.is_cuda and f.is_contiguous()):
+            f = g.keep[l] = _dev_feat(f, "features[%d]" % l)        # raises, or copies a strided view
         if f.device != device:
             raise RuntimeError("siammot_amd: features[%d] lives on %s, the boxes on %s" % (l, f.device, device))
         fp[l] = f.data_ptr()
@@ -520,15 +584,15 @@ def _geometry(features, scales, pad_pixels, device):
 
 
 def _geometry_refresh(g, features, device):
-    """The per-frame part of ``_geometry`` for a caller that keeps ``g``: same shapes, fp32, contiguous, on ``device`` ->
+    """The per-frame part of ``_geometry`` for a caller that keeps ``g``: same shapes, same dtype, contiguous, on ``device`` ->
     the pointer array is refilled and True is returned; anything else returns False (the caller takes the full path,
     which raises or rebuilds)."""
-    fp, shapes = g.fp, g.shapes
+    fp, shapes, dt = g.fp, g.shapes, g.dtype
     if len(features) < g.L:
         return False
     for l in range(g.L):                 # validate every level first: a mismatch must leave the pointer array as it was
         f = features[l]
-        if f.shape != shapes[l] or not (f.is_cuda and f.dtype is _F32 and f.is_contiguous()) or f.device != device:
+        if f.shape != shapes[l] or not (f.is_cuda and f.dtype is dt and f.is_contiguous()) or f.device != device:
             return False
     for l in range(g.L):
         fp[l] = features[l].data_ptr()
@@ -643,15 +707,18 @@ def emm_track(features, boxes, sr, templates, params, rx, rz, scales, sampling_r
     if cur != dev.index:
         torch.cuda.set_device(dev.index)
     try:
-        rc = lib.smot_emm_track_fwd(g.a_fp, g.a_hs, g.a_ws, g.a_pc, g.a_sc, g.L, C,
-                                boxes.data_ptr(), sr.data_ptr(), templates.data_ptr(), N, rx, rz, sampling_ratio,
-                                a_pp, gn_groups, gn_eps, hann_window(ho * UP_SCALE, dev).data_ptr(),
-                                UP_SCALE, pad_pixels, 1 - sigma, sigma, 1 if use_centerness else 0,
-                                float(clip_wh[0]) if clip_wh is not None else 0.0,
-                                float(clip_wh[1]) if clip_wh is not None else 0.0,
-                                work.data_ptr(), bb.data_ptr(), conf.data_ptr(),
-                                idx.data_ptr() if idx is not None else None,
-                                order_hint.data_ptr() if order_hint is not None else None, stream)
+        tail = (boxes.data_ptr(), sr.data_ptr(), templates.data_ptr(), N, rx, rz, sampling_ratio,
+                a_pp, gn_groups, gn_eps, hann_window(ho * UP_SCALE, dev).data_ptr(),
+                UP_SCALE, pad_pixels, 1 - sigma, sigma, 1 if use_centerness else 0,
+                float(clip_wh[0]) if clip_wh is not None else 0.0,
+                float(clip_wh[1]) if clip_wh is not None else 0.0,
+                work.data_ptr(), bb.data_ptr(), conf.data_ptr(),
+                idx.data_ptr() if idx is not None else None,
+                order_hint.data_ptr() if order_hint is not None else None, stream)
+        if g.ft == 0:
+            rc = lib.smot_emm_track_fwd(g.a_fp, g.a_hs, g.a_ws, g.a_pc, g.a_sc, g.L, C, *tail)
+        else:                                     # fp16 / bf16 maps: read as they are
+            rc = lib.smot_emm_track_typed_fwd(g.a_fp, g.ft, g.a_hs, g.a_ws, g.a_pc, g.a_sc, g.L, C, *tail, 1, _one_image_rows(N))
     finally:
         if cur != dev.index:
             torch.cuda.set_device(cur)
@@ -711,7 +778,13 @@ def emm_extract_cache(features, boxes, rz, scales, sampling_ratio, pad_pixels, s
     if cur != dev.index:
         torch.cuda.set_device(dev.index)
     try:
-        if n_valid is None:
+        if g.ft != 0:                             # fp16 / bf16 maps: read as they are (masked or not)
+            rc = lib.smot_emm_extract_cache_typed_fwd(g.a_fp, g.ft, g.a_hs, g.a_ws, g.a_sc, g.L, C, boxes.data_ptr(), N,
+                                                      rz, sampling_ratio, pad_pixels, search_expansion, min_search_wh,
+                                                      templates.data_ptr(), sr.data_ptr(),
+                                                      oh.data_ptr() if oh is not None else None, _stream(dev), 1,
+                                                      _one_image_rows(N), n_valid.data_ptr() if n_valid is not None else None)
+        elif n_valid is None:
             rc = lib.smot_emm_extract_cache_fwd(g.a_fp, g.a_hs, g.a_ws, g.a_sc, g.L, C, boxes.data_ptr(), N,
                                                 rz, sampling_ratio, pad_pixels, search_expansion, min_search_wh,
                                                 templates.data_ptr(), sr.data_ptr(),
@@ -738,7 +811,8 @@ def _geometry_batched(features, scales, pad_pixels, device):
     """``_geometry`` for ``[B, C, H, W]`` maps (one B, one C for every level) -> (geometry, B)."""
     L = len(scales)
     shapes = tuple(tuple(features[l].shape) for l in range(L))
-    key = ("batched", shapes, tuple(scales), pad_pixels)
+    dt = _maps_dtype(features, L)
+    key = ("batched", shapes, tuple(scales), pad_pixels, dt)
     g = _geom_cache.get(key)
     if g is None:
         for sh in shapes:
@@ -747,12 +821,12 @@ def _geometry_batched(features, scales, pad_pixels, device):
                                    % (shapes,))
         if len(_geom_cache) > 32:
             _geom_cache.clear()
-        g = _geom_cache[key] = _LevelGeometry(shapes, scales, pad_pixels)
+        g = _geom_cache[key] = _LevelGeometry(shapes, scales, pad_pixels, dt)
     fp = g.fp
     for l in range(L):
         f = features[l]
-        if not (f.is_cuda and f.dtype is _F32 and f.is_contiguous()):
-            f = g.keep[l] = _dev_f32(f, "features[%d]" % l)
+        if not (f.is_cuda and f.is_contiguous()):
+            f = g.keep[l] = _dev_feat(f, "features[%d]" % l)
         if f.device != device:
             raise RuntimeError("siammot_amd: features[%d] lives on %s, the boxes on %s" % (l, f.device, device))
         fp[l] = f.data_ptr()
@@ -811,7 +885,7 @@ def emm_track_batched(features, boxes, sr, templates, rows_per_image, params, rx
     if cur != dev.index:
         torch.cuda.set_device(dev.index)
     try:
-        rc = lib.smot_emm_track_batched_fwd(g.a_fp, g.a_hs, g.a_ws, g.a_pc, g.a_sc, g.L, C,
+        rc = lib.smot_emm_track_typed_fwd(g.a_fp, g.ft, g.a_hs, g.a_ws, g.a_pc, g.a_sc, g.L, C,
                                             boxes.data_ptr(), sr.data_ptr(), templates.data_ptr(), N, rx, rz,
                                             sampling_ratio, a_pp, gn_groups, gn_eps,
                                             hann_window(ho * UP_SCALE, dev).data_ptr(), UP_SCALE, pad_pixels, 1 - sigma,
@@ -854,10 +928,11 @@ def emm_extract_cache_batched(features, boxes, rows_per_image, rz, scales, sampl
     if cur != dev.index:
         torch.cuda.set_device(dev.index)
     try:
-        rc = lib.smot_emm_extract_cache_batched_fwd(g.a_fp, g.a_hs, g.a_ws, g.a_sc, g.L, C, boxes.data_ptr(), N, rz,
-                                                    sampling_ratio, pad_pixels, search_expansion, min_search_wh,
-                                                    templates.data_ptr(), sr.data_ptr(),
-                                                    oh.data_ptr() if oh is not None else None, _stream(dev), B, row_start)
+        rc = lib.smot_emm_extract_cache_typed_fwd(g.a_fp, g.ft, g.a_hs, g.a_ws, g.a_sc, g.L, C, boxes.data_ptr(), N, rz,
+                                                  sampling_ratio, pad_pixels, search_expansion, min_search_wh,
+                                                  templates.data_ptr(), sr.data_ptr(),
+                                                  oh.data_ptr() if oh is not None else None, _stream(dev), B, row_start,
+                                                  None)
     finally:
         if cur != dev.index:
             torch.cuda.set_device(cur)
@@ -884,7 +959,7 @@ class PairPlan(object):
     the caller then takes the general functions above, which raise or convert.  Results are the general functions', bit
     for bit — same library entry points, same arguments.  There is still no CPU or eager path."""
     __slots__ = ("dev", "dev_index", "g", "gz", "params", "blk", "rx", "rz", "ho", "scales", "sampling_ratio", "pad_pixels",
-                 "hann_ptr", "ws", "ws_n", "C", "hint_n", "hint_ok", "lib", "f_track", "f_extract", "tu")
+                 "hann_ptr", "ws", "ws_n", "C", "hint_n", "hint_ok", "lib", "f_track", "f_extract", "tu", "ft")
 
     def __init__(self, features, dev, params, rx, rz, scales, sampling_ratio, pad_pixels, tu):
         self.lib = lib = _lib or load_library()
@@ -900,10 +975,24 @@ class PairPlan(object):
         self.hann_ptr = hann_window(self.ho * UP_SCALE, dev).data_ptr()
         self.ws, self.ws_n = None, -1
         self.hint_n, self.hint_ok = -1, False
-        self.f_track, self.f_extract = lib.smot_emm_track_fwd, lib.smot_emm_extract_cache_fwd
+        self.ft = self.g.ft                       # the maps' element type the plan was made for (SMOT_FEAT_*)
+        if self.ft == 0:
+            self.f_track, self.f_extract = lib.smot_emm_track_fwd, lib.smot_emm_extract_cache_fwd
+        else:
+            self.f_track, self.f_extract = lib.smot_emm_track_typed_fwd, lib.smot_emm_extract_cache_typed_fwd
         self.tu = (float(tu.pad_pixels), float(tu.search_expansion), float(tu.min_search_wh))
 
-    def stale(self, params, rx, rz, scales, sampling_ratio, pad_pixels, tu):
+    def stale(self, params, rx, rz, scales, sampling_ratio, pad_pixels, tu, features=None):
+        """True when the plan does not describe this call.  ``features``: the call's maps — another dtype or other shapes
+        than the plan's geometry make it stale too (a caller that switches between fp32 and half maps, or between map
+        sizes, gets a new plan instead of falling to the general functions on every call)."""
+        if features is not None:
+            g = self.g
+            if len(features) < g.L:
+                return True
+            for l in range(g.L):
+                if features[l].dtype is not g.dtype or features[l].shape != g.shapes[l]:
+                    return True
         return (params is not self.params or rx != self.rx or rz != self.rz or scales != self.scales or
                 sampling_ratio != self.sampling_ratio or pad_pixels != self.pad_pixels or self.lib is not _lib or
                 self.tu != (float(tu.pad_pixels), float(tu.search_expansion), float(tu.min_search_wh)))
@@ -938,10 +1027,17 @@ class PairPlan(object):
             hint_ptr = order_hint.data_ptr()
         elif self.rx == 30 and rz == 15 and 2 <= N <= 256:
             FALLBACKS["unhinted_head"] += 1
-        rc = self.f_track(g.a_fp, g.a_hs, g.a_ws, g.a_pc, g.a_sc, g.L, self.C, boxes.data_ptr(), sr.data_ptr(),
-                          templates.data_ptr(), N, self.rx, rz, self.sampling_ratio, blk.a_pp, gn_groups, gn_eps,
-                          self.hann_ptr, UP_SCALE, self.pad_pixels, 1 - sigma, sigma, 1 if use_centerness else 0, clip_w,
-                          clip_h, self.ws.data_ptr(), bb.data_ptr(), conf.data_ptr(), None, hint_ptr, stream)
+        if self.ft == 0:
+            rc = self.f_track(g.a_fp, g.a_hs, g.a_ws, g.a_pc, g.a_sc, g.L, self.C, boxes.data_ptr(), sr.data_ptr(),
+                              templates.data_ptr(), N, self.rx, rz, self.sampling_ratio, blk.a_pp, gn_groups, gn_eps,
+                              self.hann_ptr, UP_SCALE, self.pad_pixels, 1 - sigma, sigma, 1 if use_centerness else 0, clip_w,
+                              clip_h, self.ws.data_ptr(), bb.data_ptr(), conf.data_ptr(), None, hint_ptr, stream)
+        else:
+            rc = self.f_track(g.a_fp, self.ft, g.a_hs, g.a_ws, g.a_pc, g.a_sc, g.L, self.C, boxes.data_ptr(), sr.data_ptr(),
+                              templates.data_ptr(), N, self.rx, rz, self.sampling_ratio, blk.a_pp, gn_groups, gn_eps,
+                              self.hann_ptr, UP_SCALE, self.pad_pixels, 1 - sigma, sigma, 1 if use_centerness else 0, clip_w,
+                              clip_h, self.ws.data_ptr(), bb.data_ptr(), conf.data_ptr(), None, hint_ptr, stream, 1,
+                              _one_image_rows(N))
         if rc:
             _check(rc, "emm_track")
         return bb, conf
@@ -967,9 +1063,15 @@ class PairPlan(object):
         if oh is None:
             sr = torch.empty((N, 4), dtype=_F32, device=dev)
         tu = self.tu
-        rc = self.f_extract(g.a_fp, g.a_hs, g.a_ws, g.a_sc, g.L, self.C, boxes.data_ptr(), N, rz, self.sampling_ratio,
-                            tu[0], tu[1], tu[2], templates.data_ptr(), sr.data_ptr(),
-                            oh.data_ptr() if oh is not None else None, _raw_stream(self.dev_index))
+        if self.ft == 0:
+            rc = self.f_extract(g.a_fp, g.a_hs, g.a_ws, g.a_sc, g.L, self.C, boxes.data_ptr(), N, rz, self.sampling_ratio,
+                                tu[0], tu[1], tu[2], templates.data_ptr(), sr.data_ptr(),
+                                oh.data_ptr() if oh is not None else None, _raw_stream(self.dev_index))
+        else:
+            rc = self.f_extract(g.a_fp, self.ft, g.a_hs, g.a_ws, g.a_sc, g.L, self.C, boxes.data_ptr(), N, rz,
+                                self.sampling_ratio, tu[0], tu[1], tu[2], templates.data_ptr(), sr.data_ptr(),
+                                oh.data_ptr() if oh is not None else None, _raw_stream(self.dev_index), 1,
+                                _one_image_rows(N), None)
         if rc:
             _check(rc, "emm_extract_cache")
         return templates, sr, oh
@@ -1062,6 +1164,7 @@ def sr_xcorr_fused(features, boxes, sr, templates, rx, rz, scales, sampling_rati
     templates = _dev_f32(templates, "template_features")
     N = boxes.shape[0]
     feats, fp, hs, ws_, sc = _level_arrays(features, scales)
+    ft = FEAT_TYPES[feats[0].dtype]
     C = feats[0].shape[1]
     L = len(scales)
     pc = (ctypes.c_int * L)(*[int(pad_pixels / ((2 ** i) * 4)) for i in range(L)])
@@ -1070,11 +1173,11 @@ def sr_xcorr_fused(features, boxes, sr, templates, rx, rz, scales, sampling_rati
     pooled = torch.empty((N, C, rx, rx), dtype=torch.float32, device=boxes.device) if return_pooled else None
     with _Launch(boxes, sr, templates, *feats) as ln:
         if (int(rx), int(rz)) == (35, 7) and pooled is None:        # the second yaml family's shape: its own entry
-            rc = lib.smot_sr_xcorr_gather_fwd(_cast(fp), _cast(hs), _cast(ws_), _cast(pc), _cast(sc), L, C, _ptr(boxes),
+            rc = lib.smot_sr_xcorr_gather_typed_fwd(_cast(fp), ft, _cast(hs), _cast(ws_), _cast(pc), _cast(sc), L, C, _ptr(boxes),
                                               _ptr(sr), _ptr(templates), N, int(rx), int(rz), int(sampling_ratio),
                                               _ptr(resp), ln.stream)
         else:
-            rc = lib.smot_sr_xcorr_fused_fwd(_cast(fp), _cast(hs), _cast(ws_), _cast(pc), _cast(sc), L, C, _ptr(boxes),
+            rc = lib.smot_sr_xcorr_fused_typed_fwd(_cast(fp), ft, _cast(hs), _cast(ws_), _cast(pc), _cast(sc), L, C, _ptr(boxes),
                                              _ptr(sr), _ptr(templates), N, int(rx), int(rz), int(sampling_ratio),
                                              _ptr(resp), _ptr(pooled), ln.stream)
     _check(rc, "sr_xcorr_fused")
@@ -1335,7 +1438,8 @@ def box_refine(features, scales, pooled, sampling_ratio, boxes, labels, ids, tra
     labels)`` in the box head's output order."""
     lib = _lib or load_library()
     L = len(scales)
-    feats = [_dev_f32(features[l], "features[%d]" % l) for l in range(L)]
+    feats = [_dev_feat(features[l], "features[%d]" % l) for l in range(L)]
+    ft = _feat_type(feats)
     boxes = _dev_f32(boxes, "boxes")
     track_conf = _dev_f32(track_conf, "track_conf")
     w6, b6, w7, b7, wc, bc, wr, br = [_dev_f32(t, "box head parameter") for t in layers]
@@ -1359,13 +1463,13 @@ def box_refine(features, scales, pooled, sampling_ratio, boxes, labels, ids, tra
     cast = lambda a: ctypes.cast(a, ctypes.c_void_p)
     cw, ch = (0.0, 0.0) if clip_wh is None else (float(clip_wh[0]), float(clip_wh[1]))
     with _Launch(boxes, track_conf, labels, ids, w6, *feats) as ln:
-        rc = lib.smot_box_refine_fwd(cast(fp), cast(hs), cast(wsz), cast(sc), L, C, int(pooled), int(sampling_ratio),
-                                     _ptr(boxes), _ptr(labels), _ptr(ids), _ptr(track_conf), N,
-                                     _ptr(w6), _ptr(b6), w6.shape[0], _ptr(w7), _ptr(b7), w7.shape[0],
-                                     _ptr(wc), _ptr(bc), K, _ptr(wr), _ptr(br), KR,
-                                     float(weights[0]), float(weights[1]), float(weights[2]), float(weights[3]),
-                                     float(xform_clip), cw, ch, int(bool(tracktor)), _ptr(ws), _ptr(out_boxes),
-                                     _ptr(out_scores), _ptr(out_ids), _ptr(out_labels), ln.stream)
+        rc = lib.smot_box_refine_typed_fwd(cast(fp), ft, cast(hs), cast(wsz), cast(sc), L, C, int(pooled), int(sampling_ratio),
+                                           _ptr(boxes), _ptr(labels), _ptr(ids), _ptr(track_conf), N,
+                                           _ptr(w6), _ptr(b6), w6.shape[0], _ptr(w7), _ptr(b7), w7.shape[0],
+                                           _ptr(wc), _ptr(bc), K, _ptr(wr), _ptr(br), KR,
+                                           float(weights[0]), float(weights[1]), float(weights[2]), float(weights[3]),
+                                           float(xform_clip), cw, ch, int(bool(tracktor)), _ptr(ws), _ptr(out_boxes),
+                                           _ptr(out_scores), _ptr(out_ids), _ptr(out_labels), ln.stream)
     _check(rc, "box_refine")
     return out_boxes, out_scores, out_ids, out_labels
 
@@ -1486,16 +1590,20 @@ class FrameArgs(object):
         return self._addr
 
 
-def track_frame(args, dev, addr=None):
+def track_frame(args, dev, addr=None, feat_type=0):
     """``smot_track_frame_fwd``: head [+ box-head refinement] + solver + masked template extraction of ONE tracking frame
     (the stages ``args.stages`` selects) enqueued by one call.  ``args``: a filled ``FrameArgs``, packed here unless the
-    caller packed / poked it already and passes the block's address.  Launch only."""
+    caller packed / poked it already and passes the block's address.  ``feat_type``: the element type of the maps
+    ``args.feats`` names (``FEAT_TYPES``).  Launch only."""
     lib = _lib or load_library()
     cur = torch.cuda.current_device()
     if cur != dev.index:
         torch.cuda.set_device(dev.index)
     try:
-        rc = lib.smot_track_frame_fwd(args.pack() if addr is None else addr, _stream(dev))
+        if feat_type == 0:
+            rc = lib.smot_track_frame_fwd(args.pack() if addr is None else addr, _stream(dev))
+        else:
+            rc = lib.smot_track_frame_typed_fwd(args.pack() if addr is None else addr, feat_type, _stream(dev))
     finally:
         if cur != dev.index:
             torch.cuda.set_device(cur)
@@ -1503,17 +1611,21 @@ def track_frame(args, dev, addr=None):
         _check(rc, "track_frame")
 
 
-def track_frame_addr(lib, addr, dev, stream):
-    """``smot_track_frame_fwd`` on a block the caller keeps packed (``FrameArgs.poke_head`` / ``poke_rest``)."""
+def track_frame_addr(lib, addr, dev, stream, feat_type=0):
+    """``smot_track_frame_fwd`` on a block the caller keeps packed (``FrameArgs.poke_head`` / ``poke_rest``);
+    ``feat_type``: the element type of the maps the block's ``feats`` name (``FEAT_TYPES``; the struct has no field for it)."""
     cur = torch.cuda.current_device()
     if cur != dev.index:
         torch.cuda.set_device(dev.index)
         try:
-            rc = lib.smot_track_frame_fwd(addr, stream)
+            rc = (lib.smot_track_frame_fwd(addr, stream) if feat_type == 0
+                  else lib.smot_track_frame_typed_fwd(addr, feat_type, stream))
         finally:
             torch.cuda.set_device(cur)
-    else:
+    elif feat_type == 0:
         rc = lib.smot_track_frame_fwd(addr, stream)
+    else:
+        rc = lib.smot_track_frame_typed_fwd(addr, feat_type, stream)
     if rc:
         _check(rc, "track_frame")
 

@@ -201,7 +201,15 @@ def _memory_rows(mem):
 class _FramePlan(object):
     """What ``TrackingLoop._frame_plan`` keeps between frames (see there)."""
     __slots__ = ("dev", "emm", "solver", "pool", "refine", "g", "scales", "params", "hann", "rz", "rx", "C", "amodal",
-                 "ws_need", "lib", "args", "box_params", "box_ptrs", "box_amodal", "image_wh", "a_pp", "state")
+                 "ws_need", "lib", "args", "box_params", "box_ptrs", "box_amodal", "image_wh", "a_pp", "state", "ft")
+
+
+def _frame_call(P, addr, dev, stream):
+    """The frame entry point on plan ``P``'s block: fp32 maps as ever, fp16 / bf16 maps (``P.ft``) through its typed twin."""
+    if P.ft:
+        ops.track_frame_addr(P.lib, addr, dev, stream, P.ft)
+    else:
+        ops.track_frame_addr(P.lib, addr, dev, stream)
 
 
 def _GLOBAL_HOOKS():
@@ -594,7 +602,8 @@ class TrackingLoop(torch.nn.Module):
 
     def _frame_plan(self, dev, features):
         """Everything of a frame's argument block that stands while the video's geometry and the model stand: packed once
-        (``ops.FrameArgs``), re-packed when a feature shape, a weight pointer or the device changes."""
+        (``ops.FrameArgs``), re-packed when a feature shape or dtype, a weight pointer or the device changes.  The maps'
+        element type (fp32 / fp16 / bf16) is not a field of the block: ``P.ft`` goes to the frame call beside it (``_frame_call``)."""
         P = self.__dict__.get("_plan")
         if P is not None and P.dev == dev and ops._geometry_refresh(P.g, features, dev):
             return P
@@ -604,6 +613,7 @@ class TrackingLoop(torch.nn.Module):
         P = _FramePlan()
         P.dev, P.emm, P.solver, P.pool, P.refine = dev, emm, solver, pool, self.refine_tracks
         P.g = g = ops._geometry(features, tuple(fe.scales), emm.pad_pixels, dev)       # validates (raises) and caches
+        P.ft = ops.FEAT_TYPES.get(features[0].dtype, 0)       # (a dtype the library does not take was refused just above)
         P.scales = tuple(fe.scales)
         P.params = pr.param_dict()
         P.hann = ops.hann_window((emm.rx - emm.rz + 1) * ops.UP_SCALE, dev)
@@ -738,7 +748,7 @@ class TrackingLoop(torch.nn.Module):
                 ops.FALLBACKS["unhinted_head"] += 1
             addr = a.poke_head((ops._workspace(dev, need[0], stream.value).data_ptr(), p_tbb, p_sr, p_z, p_hint, p_ids,
                                 p_lab, p, p + 16 * n_trk), n_trk, ops.STAGE_HEAD)
-            ops.track_frame_addr(P.lib, addr, dev, stream)                         # the head is running from here on
+            _frame_call(P, addr, dev, stream)                         # the head is running from here on
         if self._probed and n_trk > 0:              # (a test-only subclass: tests/sequence_replay.ProbedTrackingLoop)
             self._head_output_enqueued(tf[:4 * n_trk].view(n_trk, 4), tf[4 * tf_cap:4 * tf_cap + n_trk])
         # ---- while the head runs: detections, output buffers, the remaining stages --------------------------------------
@@ -794,7 +804,7 @@ class TrackingLoop(torch.nn.Module):
                             rec_host.data_ptr(), templates.data_ptr(), sr_next.data_ptr(), (fp + 4 * hint_off) if hint_off else 0,
                             cz, cb, cs, ci, cl, cc),
                            stages, n_det, (solver.track_thresh, solver.start_thresh, solver.resume_track_thresh), carry, n_trk)
-        ops.track_frame_addr(P.lib, addr, dev, stream)
+        _frame_call(P, addr, dev, stream)
         if self._probed and n_trk > 0 and a.refine:
             self._refined_output_enqueued(tf[5 * tf_cap:5 * tf_cap + 4 * n_trk].view(n_trk, 4), tf[9 * tf_cap:9 * tf_cap + n_trk],
                                           ti[:n_trk], ti[n_trk:])
@@ -819,7 +829,7 @@ class TrackingLoop(torch.nn.Module):
             addr = a.poke_head((ops._workspace(dev, need[0], stream.value).data_ptr(), fp + 16 * M, sr_next.data_ptr(),
                                 templates.data_ptr(), spec_hint, ip + 16 * M,
                                 ip + 24 * M, p, p + 16 * n_trk), n_trk, ops.STAGE_HEAD)
-            ops.track_frame_addr(P.lib, addr, dev, stream)
+            _frame_call(P, addr, dev, stream)
             ops.SPECULATION["launched"] += 1
             ops._geometry_refresh(P.g, features, dev)     # the plan's pointer array names THIS frame's maps again
         early = None
@@ -918,7 +928,7 @@ class TrackingLoop(torch.nn.Module):
             stream = ops._stream(P.dev)
             if (eh[0] is mem and mem._val is None and P is self.__dict__.get("_plan")
                     and stream.value == eh[3] and ops._geometry_refresh(P.g, features, P.dev)):
-                ops.track_frame_addr(P.lib, P.args._addr, P.dev, stream)
+                _frame_call(P, P.args._addr, P.dev, stream)
                 ops.SPECULATION["early_launched"] += 1
                 self.__dict__["_spec_head"] = (mem, eh[1], features, eh[4], eh[2], eh[5], eh[6], True)
         if self._lean_ok(detections):
