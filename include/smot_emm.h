@@ -540,7 +540,9 @@ int smot_linear_rows_fwd(const float* x, int M, int K, const float* W, const flo
  *                  behind this launch): K (kept), A (active rows), max_id, frame_idx,
  *                  n_active, n_dormant, flags (bit 0: id table overflow; bit 1, ABI 12: a propagated track came in with a NaN
  *                  score — what a head writes whose order hint failed its verification, see order_hint; bit 2, ABI 12: no id
- *                  started, resumed, was suspended or expired in this frame — the three tables stand), M; kept
+ *                  started, resumed, was suspended or expired in this frame — the three tables stand; bits 8 and up: the number of
+ *                  ids that were resumed AND suspended in this frame and are still dormant — they are the LAST entries of
+ *                  the dormant table), M; kept
  *                  original row [M]; kept id [M]; active-row id
  *                  [M]; snapshot of the three pool tables.  The only thing the host has to read back.  frame_idx
  *                  (word 3, always >= 1) is stored last, behind a system-scope fence: a host polling a pinned
