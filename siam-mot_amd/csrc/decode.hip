@@ -18,7 +18,9 @@
 //     wide margin (rcp / exp2 / FMA contraction: a few 1e-7 on scores of magnitude <= 1), so the result is the
 //     arg-max of the exactly evaluated score map, not "exact among approximate winners" (ADVICE r1 / VERDICT
 //     r1 weak #1: a near-tie inside a band could previously elect a different cell than the reference).
-//     A lane with two or more nominees re-walks its rows (rare; costs that wave one extra pass).
+//     A lane with two or more nominees re-walks its rows (rare; costs that wave one extra pass).  A band whose
+//     best fast score is above 1, infinite or NaN (negative size ratios: unbounded scale penalty) is not ranked
+//     by the fast form at all: all of its cells are re-scored exactly (see DEC_TOL).
 //   * One launch.  The band's exact winner (64-bit key = score, ~index) and the seven exactly interpolated
 //     logits of that cell are published with write-through 8-byte stores; the last workgroup of a track to
 //     arrive (one atomic ticket per track) reduces the Ho+1 keys, forms the location analytically from the
@@ -163,12 +165,32 @@ __device__ __forceinline__ float interp4_fma(float a, float b, float c, float d,
 }
 
 constexpr int DEC_MAX_COLS = 4;   // output columns per lane: G <= 1024
-constexpr float DEC_TOL = 4e-6f;  // |fast score - exact score| bound used to nominate cells (scores are <= 1 in
-                                  // magnitude: (1-sigma)*p*pen + sigma*window); measured gap: a few 1e-7
+// DEC_TOL: |fast score - exact score| bound used to nominate cells — for a band whose best fast score b is a finite value
+// in [-1, 1] ONLY (nomination_threshold below); every other band is not ranked at all.  Derivation:
+//   score = (1-sigma) * c * pen + sigma * window,  c = p * sigmoid in [0, 1],  pen = exp(a),  a = 0.1 * (1 - sa * sb).
+//   * sa, sb >= 1 (positive size ratios, max(s, 1/s) >= 1 — every cell a positive regression map produces): a <= 0 and
+//     pen <= 1.  The fast c differs from the exact one by a few ulp (two exp2, one product, one rcp, FMA-contracted
+//     interpolation of differenced planes); a carries a relative error k of a few ulp, which moves pen by
+//     |a| e^a k <= k / e.  All factors are <= 1: |fast - exact| is a few 1e-7 (measured), DEC_TOL = 4e-6 a wide margin.
+//   * a size ratio in [-1, 0) — bicubic overshoot beside the exact zeros a ReLU leaves in `reg`, or a template box of
+//     negative extent — makes a > 0 and pen unbounded (scores of 1e30, +inf; NaN where c underflows to 0 beside an inf
+//     pen).  The score's relative error is then |a| * k with k the relative error of an interpolated size that passes
+//     NEAR ZERO: (a few ulp) * sum|w q| / |sum w q|, a cancellation ratio without bound.  No tolerance that is a function of
+//     the score (or of a) covers it — an fp32 restatement of the fast form differs from the exact map by 2 % on such
+//     cells (median 7e-8) — and beyond 2^23 * DEC_TOL = 33.5 `b - DEC_TOL` is b itself.  A best fast score above 1 can only
+//     come from such a cell (pen <= 1 keeps the score <= 1), so it, +-inf and NaN mean: this band's fast scores rank
+//     nothing, every cell of the band is re-scored exactly (the flood path of a flat map: a wave per cell in turn, some
+//     thousand cycles for each of the band's up * G cells — inputs no trained head has been seen to produce pay for being
+//     right; bands with a best in [-1, 1] take the path they took).
+//   Not covered: a band whose best fast score is <= 1 although cells with pen > 1 and a tiny c sit near it.
+// tests/test_decode_edges.py holds the kernel to the oracle on all of these; measured results: DESIGN.md §3 K4.
+constexpr float DEC_TOL = 4e-6f;
 constexpr int DEC_REC = 5;        // u64 words published per band: key, then seven floats (+ pad)
 constexpr int DEC_NOM = 64;       // nominee list per band (more: the whole band is re-scored exactly)
 // Static LDS of decode_kernel next to the dynamic logits image: dv 4 KiB + wy_tab 512 B + nom 256 B + wbest / flags;
 // the launch-time guard reserves this much so that a large Ho fails with a message instead of an opaque HIP error.
+// (gfx950 resource report, -Rpass-analysis=kernel-resource-usage: 5,040 / 5,072 / 5,136 B for SPLIT = 1 / 2 / 4; the
+// largest Ho the guard admits is 46: 7 * 46^2 * 4 + 6,144 = 65,392 <= 65,536.)
 constexpr size_t DEC_STATIC_LDS = 6 * 1024;
 // The cross-workgroup hand-off below (relaxed agent-scope stores, s_waitcnt vmcnt(0), relaxed ticket — no
 // release/acquire) relies on gfx9 write-through L2 semantics; refuse to build it for anything else.
@@ -182,6 +204,14 @@ typedef __attribute__((address_space(1))) unsigned gu32_t;
 __device__ __forceinline__ float key_score(unsigned k) {        // inverse of score_key (NaN key -> NaN)
     if (k == 0xFFFFFFFFu) return __uint_as_float(0x7FC00000u);
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
+}
+
+// Key-space nomination threshold of a band whose best fast score has the key `best_key`: every cell whose fast score key
+// is >= the threshold is re-scored exactly.  0 = the fast scores of this band rank nothing (best fast score above 1,
+// +-inf or NaN — see DEC_TOL): nobody nominates, every cell of the band is re-scored exactly.
+__device__ __forceinline__ unsigned nomination_threshold(unsigned best_key) {
+    const float b = key_score(best_key);
+    return (fabsf(b) <= 1.0f) ? score_key(b - DEC_TOL) : 0u;     // (NaN and inf compare false)
 }
 
 struct FinalizeArgs {
@@ -347,8 +377,9 @@ decode_kernel(LogitSrc L, const float* __restrict__ boxes, const float* __restri
     unsigned wgs = wbest[0];
 #pragma unroll
     for (int w = 1; w < 4 * SPLIT; ++w) wgs = max(wgs, wbest[w]);
-    // nomination threshold in key space: fast score >= best fast score - DEC_TOL (NaN best: only NaN cells)
-    const unsigned thr = score_key(key_score(wgs) - DEC_TOL);
+    // nomination threshold in key space (0: no ranking, the whole band is re-scored exactly — see DEC_TOL)
+    const unsigned thr = nomination_threshold(wgs);
+    const bool rescore_band = thr == 0u;                           // workgroup-uniform
 
     DC_TRACE(3)
     // ---- exact re-scoring of the nominated cells (the reference's rounding sequence) ----------------------------
@@ -358,7 +389,7 @@ decode_kernel(LogitSrc L, const float* __restrict__ boxes, const float* __restri
     // reads and ~1,000 instructions at one-wave issue rate — up to 17 k cycles with the rest of the workgroup waiting
     // at the barrier (profiles/r02u_decode_trace.jsonl); cooperatively it is a few hundred cycles per nominee.
     const bool have = best != 0ull;
-    const bool nominee = have && (unsigned)(best >> 32) >= thr;
+    const bool nominee = have && !rescore_band && (unsigned)(best >> 32) >= thr;
     const bool several = have && sk2 != 0u && sk2 >= thr;          // a second cell of this lane is in range too
     if (nominee) {
         const unsigned idx1 = 0xFFFFFFFFu - (unsigned)(best & 0xFFFFFFFFull);
@@ -388,9 +419,10 @@ decode_kernel(LogitSrc L, const float* __restrict__ boxes, const float* __restri
     unsigned long long ebest = 0ull;
     {
         // more nominees than the list holds (a flat score map): the band's first cells in list order are not
-        // necessarily its best — every cell of the band is then re-scored exactly, a wave per cell in turn
+        // necessarily its best — every cell of the band is then re-scored exactly, a wave per cell in turn.  The same
+        // for a band whose best fast score is not a finite value in [-1, 1]: there the fast form ranks nothing.
         const int total = nom_cnt;
-        const bool flood = total > DEC_NOM;
+        const bool flood = rescore_band || total > DEC_NOM;
         const int cells = flood ? (y_end - y_begin) * G : total;
         const int lane = threadIdx.x & 63;
         const int ch = lane >> 2, k = lane & 3;
