@@ -722,6 +722,33 @@ int smot_memory_carry_fwd(const float* src_templates, const float* src_boxes, co
 #define SMOT_FEAT_F16 1
 #define SMOT_FEAT_BF16 2
 
+/*
+ * CHANNELS-LAST FEATURE MAPS (a backbone run with .to(memory_format=torch.channels_last): [B, C, H, W] tensors whose
+ * memory is [B, H, W, C]).
+ *
+ * SMOT_FEAT_CHANNELS_LAST is a LAYOUT flag OR'ed into the `feat_type` of the `_typed_` entry points: the legal values are
+ * {0, 1, 2, 16, 17, 18}; every other value (3, 19, 32, -1, ...) is SMOT_ERR_BAD_ARG as above.  With the flag, every level
+ * of the call is read as [num_images, H_l, W_l, C] — cell (img, c, y, x) at element ((img * H_l + y) * W_l + x) * C + c —
+ * and must be 16-byte aligned (SMOT_ERR_BAD_ARG otherwise), with C % 8 == 0 (SMOT_ERR_UNSUPPORTED otherwise: pass NCHW maps).  The untyped symbols
+ * stay NCHW fp32.
+ *
+ * The contract: a call on channels-last maps returns, for EVERY output, exactly the bits the same call returns on the
+ * NCHW copy of the maps — pooled planes, responses, templates, search regions, order hints, boxes, scores, arg-max
+ * indices, ids / labels, solver records.  The kernels read the channel runs of a pixel (8 channels = 32 bytes of fp32,
+ * 16 of fp16 / bf16) and repeat the NCHW kernels' arithmetic in the NCHW kernels' order; no NCHW copy of a map is made.
+ * An order hint holds no layout: one written from channels-last maps is the same bytes as one written from the NCHW
+ * copy, and a head of either layout accepts either (its row offsets stay bytes of an fp32 NCHW row; the channels-last
+ * kernels rescale them where they use them).  Everything but the maps stays fp32-contiguous.
+ *
+ *   honour the flag:   smot_roi_align_levels_typed_fwd, smot_roi_align_typed_fwd, smot_sr_xcorr_fused_typed_fwd (30 / 15,
+ *                      x_debug included), smot_emm_extract_cache_typed_fwd (plain, hinted, masked, batched),
+ *                      smot_emm_track_typed_fwd (one image and batched, hinted; every shape but 35 / 7),
+ *                      smot_box_refine_typed_fwd, smot_track_frame_typed_fwd (all stages)
+ *   SMOT_ERR_UNSUPPORTED with the flag (for N > 0):  smot_sr_xcorr_gather_typed_fwd, and the 35 / 7 shape through
+ *                      smot_emm_track_typed_fwd / smot_track_frame_typed_fwd — callers pass the NCHW copy there
+ */
+#define SMOT_FEAT_CHANNELS_LAST 16
+
 int smot_roi_align_levels_typed_fwd(const void* const* feats, int feat_type, const int* heights, const int* widths,
                                     const int* pad_cells, const float* scales, int num_levels, int C,
                                     const float* rois, const float* level_boxes, int R,

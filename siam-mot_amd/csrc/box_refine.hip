@@ -238,7 +238,7 @@ extern "C" int smot_box_refine_fwd(const float* const* feats, const int* heights
     SMOT_REQUIRE(boxes && ws && fc6_w && fc7_w && cls_w && reg_w, "box_refine: null pointer");
     SMOT_REQUIRE(((uintptr_t)ws & 15) == 0, "box_refine: ws must be 16-byte aligned");
     LevelParams P;
-    int rc = fill_level_params(&P, feats, heights, widths, nullptr, scales, num_levels, "box_refine");
+    int rc = fill_level_params(&P, feats, heights, widths, nullptr, scales, num_levels, "box_refine", C);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int NH = num_classes + 4 * reg_classes;

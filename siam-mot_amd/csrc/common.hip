@@ -18,12 +18,16 @@ void set_error(const char* fmt, ...) {
 }
 
 static thread_local int g_feat_type = SMOT_FEAT_F32;
-int feat_type() { return g_feat_type; }
+// (the element type and the layout flag of the call in progress travel in one word, as the entry point received them)
+int feat_type() { return g_feat_type & ~SMOT_FEAT_CHANNELS_LAST; }
+bool channels_last() { return (g_feat_type & SMOT_FEAT_CHANNELS_LAST) != 0; }
 FeatTypeScope::FeatTypeScope(int ft) : prev(g_feat_type) { g_feat_type = ft; }
 FeatTypeScope::~FeatTypeScope() { g_feat_type = prev; }
 int check_feat_type(int ft, const char* who) {
-    if (ft == SMOT_FEAT_F32 || ft == SMOT_FEAT_F16 || ft == SMOT_FEAT_BF16) return SMOT_OK;
-    set_error("%s: feat_type=%d is not SMOT_FEAT_F32 (0), SMOT_FEAT_F16 (1) or SMOT_FEAT_BF16 (2)", who, ft);
+    const int et = ft & ~SMOT_FEAT_CHANNELS_LAST;
+    if (ft >= 0 && (et == SMOT_FEAT_F32 || et == SMOT_FEAT_F16 || et == SMOT_FEAT_BF16)) return SMOT_OK;
+    set_error("%s: feat_type=%d is not SMOT_FEAT_F32 (0), SMOT_FEAT_F16 (1) or SMOT_FEAT_BF16 (2), alone or with "
+              "SMOT_FEAT_CHANNELS_LAST (16)", who, ft);
     return SMOT_ERR_BAD_ARG;
 }
 

@@ -32,6 +32,7 @@ roi_align_levels_kernel(LevelParams P, int C, const float* __restrict__ rois,
     constexpr bool BATCHED = false;
     constexpr NoImages I{};
     using FT = float;
+    constexpr bool NHWC = false;
 #include "roi_align_body.h"
 }
 
@@ -43,6 +44,7 @@ roi_align_levels_batched_kernel(LevelParams P, int C, const float* __restrict__ 
                                 float* __restrict__ out, int32_t* __restrict__ levels_out, int num_images, ImageRows I) {
     constexpr bool BATCHED = true;
     using FT = float;
+    constexpr bool NHWC = false;
 #include "roi_align_body.h"
 }
 
@@ -56,6 +58,7 @@ roi_align_levels_half_kernel(LevelParams P, int C, const float* __restrict__ roi
     static_assert(sizeof(FT) == 2, "fp16 / bf16 maps");
     constexpr bool BATCHED = false;
     constexpr NoImages I{};
+    constexpr bool NHWC = false;
 #include "roi_align_body.h"
 }
 template <typename FT, int G>
@@ -66,7 +69,56 @@ roi_align_levels_half_batched_kernel(LevelParams P, int C, const float* __restri
                                      ImageRows I) {
     static_assert(sizeof(FT) == 2, "fp16 / bf16 maps");
     constexpr bool BATCHED = true;
+    constexpr bool NHWC = false;
 #include "roi_align_body.h"
+}
+
+// The same kernel on CHANNELS-LAST maps of every element type (SMOT_FEAT_CHANNELS_LAST; FT = float / f16_t / bf16_t): the
+// window is staged from the pixels' channel runs into the same LDS image, the pooling behind it is the NCHW kernels' text —
+// bit-identical results.  BATCHED_ = false: I is not read.
+template <typename FT, int G, bool BATCHED_>
+__global__ void __launch_bounds__(256, (sizeof(FT) == 2 && G <= 3) ? 2 : 1)
+roi_align_levels_nhwc_kernel(LevelParams P, int C, const float* __restrict__ rois, const float* __restrict__ level_boxes,
+                             int PH, int PW, int ch_per_block, float* __restrict__ out, int32_t* __restrict__ levels_out,
+                             int num_images, ImageRows I) {
+    constexpr bool BATCHED = BATCHED_;
+    constexpr bool NHWC = true;
+#include "roi_align_body.h"
+}
+
+template <typename FT, int G, bool B>
+static int launch_roi_align_nhwc_one(dim3 grid, size_t smem, hipStream_t st, const LevelParams& P, int C, const float* rois,
+                                     const float* level_boxes, int PH, int PW, float* out, int32_t* levels_out,
+                                     int num_images, const ImageRows& I) {
+    const int rco = ensure_lds_optin((const void*)roi_align_levels_nhwc_kernel<FT, G, B>, 96 * 1024, "roi_align");
+    if (rco) return rco;
+    hipLaunchKernelGGL((roi_align_levels_nhwc_kernel<FT, G, B>), grid, dim3(256), smem, st, P, C, rois, level_boxes, PH, PW,
+                       RA_CH, out, levels_out, num_images, I);
+    return SMOT_OK;
+}
+// the channels-last launch of a typed call in progress (channels_last()): I = the batch's row ranges, or nullptr
+static int launch_roi_align_nhwc(int sampling_ratio, dim3 grid, size_t smem, hipStream_t st, const LevelParams& P, int C,
+                                 const float* rois, const float* level_boxes, int PH, int PW, float* out,
+                                 int32_t* levels_out, int num_images, const ImageRows* I) {
+    ImageRows none;
+    none.num_images = 1;
+    for (int b = 0; b <= SMOT_MAX_IMAGES; ++b) none.row_start[b] = 0;
+#define SMOT_RA_NHWC(FT_, G_)                                                                                          \
+    (I != nullptr ? launch_roi_align_nhwc_one<FT_, G_, true>(grid, smem, st, P, C, rois, level_boxes, PH, PW, out,      \
+                                                             levels_out, num_images, *I)                              \
+                  : launch_roi_align_nhwc_one<FT_, G_, false>(grid, smem, st, P, C, rois, level_boxes, PH, PW, out,     \
+                                                              levels_out, num_images, none))
+#define SMOT_RA_NHWC_G(G_)                                                                                             \
+    (feat_type() == SMOT_FEAT_F32 ? SMOT_RA_NHWC(float, G_)                                                            \
+                                  : (feat_type() == SMOT_FEAT_F16 ? SMOT_RA_NHWC(f16_t, G_) : SMOT_RA_NHWC(bf16_t, G_)))
+    switch (sampling_ratio) {
+        case 1: return SMOT_RA_NHWC_G(1);
+        case 2: return SMOT_RA_NHWC_G(2);
+        case 3: return SMOT_RA_NHWC_G(3);
+        default: return SMOT_RA_NHWC_G(4);
+    }
+#undef SMOT_RA_NHWC_G
+#undef SMOT_RA_NHWC
 }
 
 __global__ void search_region_kernel(const float* __restrict__ boxes, int N, float pad, float half_e,
@@ -108,7 +160,7 @@ int roi_align_levels_batched(const float* const* feats, const int* heights, cons
     }
     if (R == 0) return SMOT_OK;
     LevelParams P;
-    const int rc = fill_level_params(&P, feats, heights, widths, pad_cells, scales, num_levels, "roi_align_batched");
+    const int rc = fill_level_params(&P, feats, heights, widths, pad_cells, scales, num_levels, "roi_align_batched", C);
     if (rc) return rc;
     if ((out_hw == 7 || out_hw == 15 || out_hw == 30) && sampling_ratio == 2 && !knobs().roi_generic)
         return launch_roi_pool_separable_batched(P, C, rois, num_levels > 1 ? level_boxes : rois, R, out_hw, out, st, I);
@@ -128,6 +180,11 @@ int roi_align_levels_batched(const float* const* feats, const int* heights, cons
         if (rco) return rco;                                                                                       \
         hipLaunchKernelGGL(roi_align_levels_batched_kernel<G>, grid, dim3(256), smem, st, P, C, rois, level_boxes,  \
                            out_hw, out_hw, RA_CH, out, (int32_t*)nullptr, 0, I);                                  \
+    }
+    if (channels_last()) {
+        const int rcn = launch_roi_align_nhwc(sampling_ratio, grid, smem, st, P, C, rois, level_boxes, out_hw, out_hw, out,
+                                              nullptr, 0, &I);
+        return rcn ? rcn : check_launch("roi_align_batched");
     }
     switch (sampling_ratio) {
         case 1: LAUNCH(1); break;
@@ -159,7 +216,7 @@ extern "C" int smot_roi_align_levels_fwd(const float* const* feats, const int* h
     SMOT_REQUIRE(num_levels == 1 || level_boxes, "roi_align: level_boxes required for num_levels>1");
     LevelParams P;
     {
-        const int rc = fill_level_params(&P, feats, heights, widths, pad_cells, scales, num_levels, "roi_align");
+        const int rc = fill_level_params(&P, feats, heights, widths, pad_cells, scales, num_levels, "roi_align", C);
         if (rc) return rc;
     }
 
@@ -186,6 +243,11 @@ extern "C" int smot_roi_align_levels_fwd(const float* const* feats, const int* h
                            out_h, out_w, ch_per_block, out, levels_out, 0);                              \
     }
     SMOT_REQUIRE(smem <= 96 * 1024, "roi_align: pooled size %dx%d needs too much LDS", out_h, out_w);
+    if (channels_last()) {
+        const int rcn = launch_roi_align_nhwc(sampling_ratio, grid, smem, st, P, C, rois, level_boxes, out_h, out_w, out,
+                                              levels_out, 0, nullptr);
+        return rcn ? rcn : check_launch("roi_align");
+    }
     switch (sampling_ratio) {
         case 1: LAUNCH(1); break;
         case 2: LAUNCH(2); break;
@@ -213,7 +275,7 @@ extern "C" int smot_roi_align_fwd(const float* input, int num_images, int C, int
     SMOT_REQUIRE(input && rois5 && out, "roi_align: null pointer");
     LevelParams P;
     {
-        const int rc = fill_level_params(&P, &input, &H, &W, &pad_cells, &spatial_scale, 1, "roi_align");
+        const int rc = fill_level_params(&P, &input, &H, &W, &pad_cells, &spatial_scale, 1, "roi_align", C);
         if (rc) return rc;
     }
     dim3 grid(R, (C + RA_CH - 1) / RA_CH);
@@ -232,6 +294,11 @@ extern "C" int smot_roi_align_fwd(const float* input, int num_images, int C, int
         if (rco) return rco;                                                                             \
         hipLaunchKernelGGL(roi_align_levels_kernel<G>, grid, dim3(256), smem, st, P, C, rois5,           \
                            (const float*)nullptr, pooled_h, pooled_w, RA_CH, out, (int32_t*)nullptr, num_images); \
+    }
+    if (channels_last()) {
+        const int rcn = launch_roi_align_nhwc(sampling_ratio, grid, smem, st, P, C, rois5, nullptr, pooled_h, pooled_w, out,
+                                              nullptr, num_images, nullptr);
+        return rcn ? rcn : check_launch("roi_align");
     }
     switch (sampling_ratio) {
         case 1: LAUNCH(1); break;

@@ -3,6 +3,8 @@
 // kernels, so that the single-image kernel compiles to the same code as before batching existed.
 // FT (defined by the kernel as well) is the maps' element type: float, or f16_t / bf16_t in the *_half_* kernels, which
 // convert every cell to fp32 where it is loaded (the staged window in LDS is fp32 for every type).
+// NHWC (defined by the kernel too; false in the NCHW kernels): channels-last maps — only the staging of the window and the
+// addressing of the unstaged fallback differ; the pooling behind them is the same text.
     // num_images == 0: rois are [R,4] on the one image of the call (the level-routed pooler).
     // num_images >= 1: rois are [R,5] = (image index, x1, y1, x2, y2) as upstream's _C.roi_align_forward takes them,
     //                  P.feat[0] is [num_images, C, H, W]; a row whose index is out of range pools to zeros.
@@ -108,6 +110,31 @@
         // w, w+4, ...; lanes take columns (contiguous, coalesced row segments).  All loads of a pass
         // (up to 16 rows x RA_CH channels per lane) are issued before the first LDS store, so one
         // memory round trip covers the whole pass; co-resident workgroups cover the rest. ----
+        if constexpr (NHWC) {
+            // channels-last maps: lanes run along the window's pixels (row-major, as the LDS image is), each takes the run of
+            // the workgroup's RA_CH channels of its pixel in one 16-byte (fp32) or 8-byte (fp16 / bf16) load and writes it
+            // into the same per-channel LDS images; four pixels per lane are in flight before the first LDS store
+            static_assert(RA_CH == 4, "a channel run of 16 / 8 bytes");
+            const FT* __restrict__ fr = f + c0;
+            const int npix = wh_ * ww;
+            for (int p0 = 0; p0 < npix; p0 += 4 * 256) {
+                float tmp[4][RA_CH];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int p = min(p0 + 256 * k + (int)threadIdx.x, npix - 1);
+                    const int row = p / ww, col = p - row * ww;
+                    feat_ld_run<FT, RA_CH>(fr + ((size_t)(ymin + row) * W + xmin + col) * C, tmp[k]);
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int p = p0 + 256 * k + (int)threadIdx.x;
+                    if (p < npix) {
+#pragma unroll
+                        for (int cl = 0; cl < RA_CH; ++cl) win[cl * RA_WIN_FLOATS + p] = tmp[k][cl];
+                    }
+                }
+            }
+        } else {
         const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
         for (int col0 = 0; col0 < ww; col0 += 64) {
             const int col = col0 + tx;
@@ -132,8 +159,11 @@
                 }
             }
         }
+        }
         __syncthreads();
     }
+    // channels-last maps read in place (windows past the LDS budget): cell (y, x) of channel c at ((y * W + x) * C + c)
+    const int cell = NHWC ? (staged ? 1 : C) : 1;
     if constexpr (sizeof(FT) == 4) {
     // bins outer (tables of one bin in registers), channels inner
     for (int t = threadIdx.x; t < bins; t += 256) {
@@ -155,16 +185,16 @@
         for (int cl = 0; cl < nch; ++cl) {
             // window larger than the LDS budget (degenerate aspect ratios): gather straight from the map
             const float* __restrict__ src = staged ? (const float*)(win + cl * RA_WIN_FLOATS)
-                                                   : reinterpret_cast<const float*>(f + (size_t)(c0 + cl) * H * W);
+                                                   : reinterpret_cast<const float*>(f + (NHWC ? (size_t)(c0 + cl) : (size_t)(c0 + cl) * H * W));
             float acc = 0.0f;
 #pragma unroll
             for (int iy = 0; iy < G; ++iy) {
 #pragma unroll
                 for (int ix = 0; ix < G; ++ix) {
-                    const float v1 = src[ylo[iy] + xlo[ix]];
-                    const float v2 = src[ylo[iy] + xhi[ix]];
-                    const float v3 = src[yhi[iy] + xlo[ix]];
-                    const float v4 = src[yhi[iy] + xhi[ix]];
+                    const float v1 = src[(ylo[iy] + xlo[ix]) * cell];
+                    const float v2 = src[(ylo[iy] + xhi[ix]) * cell];
+                    const float v3 = src[(yhi[iy] + xlo[ix]) * cell];
+                    const float v4 = src[(yhi[iy] + xhi[ix]) * cell];
                     const float w1 = wyl[iy] * wxl[ix], w2 = wyl[iy] * wxh[ix];
                     const float w3 = wyh[iy] * wxl[ix], w4 = wyh[iy] * wxh[ix];
                     acc += w1 * v1 + w2 * v2 + w3 * v3 + w4 * v4;
@@ -200,10 +230,10 @@
             for (int iy = 0; iy < G; ++iy) {
 #pragma unroll
                 for (int ix = 0; ix < G; ++ix) {
-                    const float v1 = feat_ld(src + (ylo[iy] + xlo[ix]));
-                    const float v2 = feat_ld(src + (ylo[iy] + xhi[ix]));
-                    const float v3 = feat_ld(src + (yhi[iy] + xlo[ix]));
-                    const float v4 = feat_ld(src + (yhi[iy] + xhi[ix]));
+                    const float v1 = feat_ld(src + (ylo[iy] + xlo[ix]) * cell);
+                    const float v2 = feat_ld(src + (ylo[iy] + xhi[ix]) * cell);
+                    const float v3 = feat_ld(src + (yhi[iy] + xlo[ix]) * cell);
+                    const float v4 = feat_ld(src + (yhi[iy] + xhi[ix]) * cell);
                     const float w1 = wyl[iy] * wxl[ix], w2 = wyl[iy] * wxh[ix];
                     const float w3 = wyh[iy] * wxl[ix], w4 = wyh[iy] * wxh[ix];
                     acc += w1 * v1 + w2 * v2 + w3 * v3 + w4 * v4;
@@ -216,6 +246,6 @@
     if (staged) {
         pool_bins([&](int cl) { return (const float*)(win + cl * RA_WIN_FLOATS); });
     } else {
-        pool_bins([&](int cl) { return f + (size_t)(c0 + cl) * H * W; });
+        pool_bins([&](int cl) { return f + (NHWC ? (size_t)(c0 + cl) : (size_t)(c0 + cl) * H * W); });
     }
     }

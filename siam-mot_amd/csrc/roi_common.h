@@ -55,6 +55,42 @@ __device__ __forceinline__ float feat_ld(const FT* p) {
     }
 }
 
+// Channels-last maps (SMOT_FEAT_CHANNELS_LAST): N consecutive channels of one pixel, N * sizeof(FT) = 8, 16 or 32 bytes at
+// that alignment (C % 8 == 0, a channel group's first channel a multiple of N), as 8- or 16-byte loads; converted like feat_ld.
+template <typename FT, int N>
+__device__ __forceinline__ void feat_ld_run(const FT* p, float* out) {
+    constexpr int DW = N * (int)sizeof(FT) / 4;
+    static_assert(DW == 2 || DW == 4 || DW == 8, "a run of 8, 16 or 32 bytes");
+    unsigned d[DW];
+    if constexpr (DW == 2) {
+        const uint2 a = *reinterpret_cast<const uint2*>(p);
+        d[0] = a.x;
+        d[1] = a.y;
+    } else {
+#pragma unroll
+        for (int q = 0; q < DW / 4; ++q) {
+            const uint4 a = reinterpret_cast<const uint4*>(p)[q];
+            d[4 * q + 0] = a.x;
+            d[4 * q + 1] = a.y;
+            d[4 * q + 2] = a.z;
+            d[4 * q + 3] = a.w;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < DW; ++q) {
+        if constexpr (sizeof(FT) == 4) {
+            out[q] = __uint_as_float(d[q]);
+        } else {
+            out[2 * q] = feat_of_pair<FT, 0>(d[q]);
+            out[2 * q + 1] = feat_of_pair<FT, 1>(d[q]);
+        }
+    }
+}
+template <typename FT>
+__device__ __forceinline__ void feat_ld8(const FT* p, float* out) {
+    feat_ld_run<FT, 8>(p, out);
+}
+
 // Rows of a batched call (smot_emm_*_batched_fwd): the rois of image b are [row_start[b], row_start[b+1]) and the maps are
 // [num_images, C, H_l, W_l].  A kernel argument of the batched instantiations only; the single-image kernels take NoImages
 // (nothing) and are unchanged.
@@ -156,8 +192,15 @@ __device__ __forceinline__ void axis_sample(float start, float bin, int G, int s
 }
 
 // Host side: validate the per-level HOST arrays of the C ABI and pack them into kernel parameters.
+// `nhwc_C`: the channel count when the caller has kernels for channels-last maps, 0 when it has none — a typed call with
+// SMOT_FEAT_CHANNELS_LAST is then refused here (SMOT_ERR_UNSUPPORTED), as are C % 8 != 0 and maps that are not 16-byte aligned.
 inline int fill_level_params(LevelParams* P, const float* const* feats, const int* heights, const int* widths,
-                             const int* pad_cells, const float* scales, int num_levels, const char* who) {
+                             const int* pad_cells, const float* scales, int num_levels, const char* who, int nhwc_C = 0) {
+    if (channels_last() && (nhwc_C <= 0 || nhwc_C % 8 != 0)) {
+        if (nhwc_C <= 0) set_error("%s: no channels-last (SMOT_FEAT_CHANNELS_LAST) form; pass NCHW maps", who);
+        else set_error("%s: channels-last maps need C %% 8 == 0 (got C=%d); pass NCHW maps", who, nhwc_C);
+        return SMOT_ERR_UNSUPPORTED;
+    }
     if (!(feats && heights && widths && scales)) {
         set_error("%s: null level array", who);
         return SMOT_ERR_BAD_ARG;
@@ -170,6 +213,10 @@ inline int fill_level_params(LevelParams* P, const float* const* feats, const in
         const int pad = pad_cells ? pad_cells[l] : 0;
         if (!(feats[l] && heights[l] > 0 && widths[l] > 0 && pad >= 0 && scales[l] > 0.f)) {
             set_error("%s: bad level %d", who, l);
+            return SMOT_ERR_BAD_ARG;
+        }
+        if (channels_last() && (reinterpret_cast<uintptr_t>(feats[l]) & 15) != 0) {
+            set_error("%s: channels-last level %d is not 16-byte aligned", who, l);
             return SMOT_ERR_BAD_ARG;
         }
         P->feat[l] = feats[l];

@@ -68,12 +68,17 @@ int smot_debug_launch_flags();      // common.hip: hipExtAnyOrderLaunch when SMO
 // `feat_type`, set it for the duration of the call and run the fp32 entry point's host code; the launch sites of the three
 // kernels that read the maps pick the instantiation by it.  Outside a typed call it is SMOT_FEAT_F32.
 int feat_type();
+// ... and their layout: true while a typed call with SMOT_FEAT_CHANNELS_LAST is in progress ([B, H, W, C] in memory).  The
+// launch sites that have a channels-last kernel pick it; every other site that reads the maps refuses the call
+// (fill_level_params) — a channels-last map is never read as NCHW.
+bool channels_last();
 struct FeatTypeScope {
     int prev;
     explicit FeatTypeScope(int ft);
     ~FeatTypeScope();
 };
-// SMOT_ERR_BAD_ARG (with a message that names the value) for anything but SMOT_FEAT_F32 / F16 / BF16
+// SMOT_ERR_BAD_ARG (with a message that names the value) for anything but SMOT_FEAT_F32 / F16 / BF16, alone or OR'ed with
+// SMOT_FEAT_CHANNELS_LAST
 int check_feat_type(int ft, const char* who);
 // `STMT` with FT bound to the maps' element type of the call in progress (fp16 / bf16 only: the fp32 launches stand as written)
 #define SMOT_HALF_TYPES(...)                     \

@@ -476,6 +476,7 @@ sr_xcorr_fused9_kernel(LevelParams P, int C, const float* __restrict__ sr, const
     constexpr bool BATCHED = false;
     constexpr NoImages I{};
     using FT = float;
+    constexpr bool NHWC = false;
 #include "sr_xcorr_fused9_body.h"
 }
 
@@ -489,6 +490,7 @@ sr_xcorr_fused9_batched_kernel(LevelParams P, int C, const float* __restrict__ s
     constexpr bool BATCHED = true;
     constexpr bool P2 = false;
     using FT = float;
+    constexpr bool NHWC = false;
 #include "sr_xcorr_fused9_body.h"
 }
 
@@ -504,6 +506,7 @@ sr_xcorr_fused9_half_kernel(LevelParams P, int C, const float* __restrict__ sr, 
     constexpr NoImages I{};
     constexpr int NCH = FX_CH;
     constexpr bool P2 = false;
+    constexpr bool NHWC = false;
 #include "sr_xcorr_fused9_body.h"
 }
 template <typename FT, int RX, int RZ, int G, bool XCORR, int MM = 0>
@@ -515,6 +518,24 @@ sr_xcorr_fused9_half_batched_kernel(LevelParams P, int C, const float* __restric
     constexpr bool BATCHED = true;
     constexpr int NCH = FX_CH;
     constexpr bool P2 = false;
+    constexpr bool NHWC = false;
+#include "sr_xcorr_fused9_body.h"
+}
+
+// The product's forms on CHANNELS-LAST maps of every element type (SMOT_FEAT_CHANNELS_LAST; FT = float / f16_t / bf16_t):
+// the body's pooling stage is sr_pool_nhwc_stage.h, everything else — assignment, order hint, sample tables, LDS images,
+// correlation, write-out — is the NCHW kernels' text, and the static LDS is theirs (76,176 B for the 30 / 15 matrix form).
+// One kernel per form: a single image is a batch of one.  (The stage keeps a row's 8 channels of column sums and taps in
+// registers: 128 VGPRs, two workgroups of eight waves per CU, for every form.)
+template <typename FT, int RX, int RZ, int G, bool XCORR, int MM = 0>
+__global__ void __launch_bounds__(64 * FX_CH, 4)
+sr_xcorr_fused9_nhwc_kernel(LevelParams P, int C, const float* __restrict__ sr, const float* __restrict__ boxes,
+                            const float* __restrict__ z, float* __restrict__ resp, float* __restrict__ x_debug,
+                            int32_t* __restrict__ levels_out, SrOut S, ImageRows I) {
+    constexpr bool BATCHED = true;
+    constexpr int NCH = FX_CH;
+    constexpr bool P2 = false;
+    constexpr bool NHWC = true;
 #include "sr_xcorr_fused9_body.h"
 }
 
@@ -552,9 +573,42 @@ static void launch_fused_half(dim3 grid, hipStream_t st, const LevelParams& P, i
 }
 static inline bool half_maps() { return feat_type() != SMOT_FEAT_F32; }
 
+// channels-last maps (a typed call with SMOT_FEAT_CHANNELS_LAST in progress: channels_last()): the form the NCHW call takes,
+// in its channels-last kernel, by the maps' element type; I = the batch's row ranges, or nullptr for one image of R rois
+template <int RX, bool XCORR, int MM>
+static void launch_fused_nhwc(dim3 grid, hipStream_t st, const LevelParams& P, int C, const float* rois, const float* boxes,
+                              const float* z, float* resp, float* out, int32_t* levels_out, const SrOut& S,
+                              const ImageRows* I) {
+    ImageRows one;
+    if (I == nullptr) {
+        one.num_images = 1;
+        one.row_start[0] = 0;
+        for (int b = 1; b <= SMOT_MAX_IMAGES; ++b) one.row_start[b] = (int)grid.x;
+        I = &one;
+    }
+    if (feat_type() == SMOT_FEAT_F32) {
+        SMOT_LAUNCH((sr_xcorr_fused9_nhwc_kernel<float, RX, 15, 2, XCORR, MM>), grid, dim3(512), 0, st, P, C, rois, boxes, z,
+                    resp, out, levels_out, S, *I);
+    } else {
+        SMOT_HALF_TYPES(SMOT_LAUNCH((sr_xcorr_fused9_nhwc_kernel<FT, RX, 15, 2, XCORR, MM>), grid, dim3(512), 0, st, P, C,
+                                    rois, boxes, z, resp, out, levels_out, S, *I))
+    }
+}
+// (the pool-only forms by pooled size: 7, 15 or 30)
+static void launch_pool_nhwc(int out_size, dim3 grid, hipStream_t st, const LevelParams& P, int C, const float* rois,
+                             const float* boxes, float* out, int32_t* levels_out, const SrOut& S, const ImageRows* I) {
+    if (out_size == 30) launch_fused_nhwc<30, false, 0>(grid, st, P, C, rois, boxes, nullptr, nullptr, out, levels_out, S, I);
+    else if (out_size == 7) launch_fused_nhwc<7, false, 0>(grid, st, P, C, rois, boxes, nullptr, nullptr, out, levels_out, S, I);
+    else launch_fused_nhwc<15, false, 0>(grid, st, P, C, rois, boxes, nullptr, nullptr, out, levels_out, S, I);
+}
+
 template <int RX, bool XCORR>
 static void launch_fused(dim3 grid, hipStream_t st, const LevelParams& P, int C, const float* rois, const float* boxes,
                          const float* z, float* resp, float* out, int32_t* levels_out, const SrOut& S) {
+    if (channels_last()) {
+        launch_fused_nhwc<RX, XCORR, (RX == 30 && XCORR) ? 1 : 0>(grid, st, P, C, rois, boxes, z, resp, out, levels_out, S, nullptr);
+        return;
+    }
     if (half_maps()) {
         launch_fused_half<RX, XCORR, (RX == 30 && XCORR) ? 1 : 0>(grid, st, P, C, rois, boxes, z, resp, out, levels_out, S, nullptr);
         return;
@@ -599,7 +653,9 @@ int launch_roi_pool_separable(const LevelParams& P, int C, const float* rois, co
                               int out_size, float* out, int32_t* levels_out, hipStream_t st) {
     dim3 grid(R, (C + FX_CH - 1) / FX_CH);
     SrOut none = {nullptr, 0.f, 0.f, 0.f, 0.f, g_trace, 0, nullptr, fused_order(), nullptr, nullptr, 0};
-    if (out_size == 30) {
+    if (channels_last()) {
+        launch_pool_nhwc(out_size, grid, st, P, C, rois, level_boxes, out, levels_out, none, nullptr);
+    } else if (out_size == 30) {
         launch_fused<30, false>(grid, st, P, C, rois, level_boxes, nullptr, nullptr, out, levels_out, none);
     } else if (out_size == 7 && half_maps()) {
         launch_fused_half<7, false, 0>(grid, st, P, C, rois, level_boxes, nullptr, nullptr, out, levels_out, none, nullptr);
@@ -617,7 +673,7 @@ int launch_extract_cache(const float* const* feats, const int* heights, const in
                          float two_e, float min_wh, float* templates, float* sr, const int* n_valid, float* order_hint,
                          hipStream_t st, int hint_extra_rows) {
     LevelParams P;
-    const int rc = fill_level_params(&P, feats, heights, widths, nullptr, scales, num_levels, "emm_extract_cache");
+    const int rc = fill_level_params(&P, feats, heights, widths, nullptr, scales, num_levels, "emm_extract_cache", C);
     if (rc) return rc;
     SMOT_REQUIRE(boxes && templates && sr, "emm_extract_cache: null pointer");
     if (!order_hint_rois(N, false) || rz != 15) order_hint = nullptr;     // (the hint's consumer is the 30/15 head)
@@ -630,7 +686,9 @@ int launch_extract_cache(const float* const* feats, const int* heights, const in
     // the next frame's search-region pooling runs on maps zero-padded by int(pad_pixels / stride) cells per level
     // (track_utils.py:94-96); the hint's finished tables are built against exactly that
     for (int l = 0; l < num_levels && l < SMOT_MAX_LEVELS; ++l) S.plan_pad[l] = (int)(pad_pixels * scales[l]);
-    if (rz == 7 && half_maps()) {
+    if (channels_last()) {
+        launch_pool_nhwc(rz, grid, st, P, C, boxes, boxes, templates, nullptr, S, nullptr);
+    } else if (rz == 7 && half_maps()) {
         launch_fused_half<7, false, 0>(grid, st, P, C, boxes, boxes, nullptr, nullptr, templates, nullptr, S, nullptr);
     } else if (rz == 7) {          // the second yaml family's template (DLA_34_FPN_EMM_AOT.yaml:52-63): same kernel, 7x7 bins
         SMOT_LAUNCH((sr_xcorr_fused9_kernel<7, 15, 2, false>), grid, dim3(512), 0, st, P, C, boxes, boxes, (const float*)nullptr,
@@ -648,7 +706,9 @@ int launch_roi_pool_separable_batched(const LevelParams& P, int C, const float* 
                                       int out_size, float* out, hipStream_t st, const ImageRows& I) {
     dim3 grid(R, (C + FX_CH - 1) / FX_CH);
     SrOut none = {nullptr, 0.f, 0.f, 0.f, 0.f, g_trace, 0, nullptr, fused_order(), nullptr, nullptr, 0};
-    if (half_maps()) {
+    if (channels_last()) {
+        launch_pool_nhwc(out_size, grid, st, P, C, rois, level_boxes, out, nullptr, none, &I);
+    } else if (half_maps()) {
         if (out_size == 30) launch_fused_half<30, false, 0>(grid, st, P, C, rois, level_boxes, nullptr, nullptr, out, nullptr, none, &I);
         else if (out_size == 7) launch_fused_half<7, false, 0>(grid, st, P, C, rois, level_boxes, nullptr, nullptr, out, nullptr, none, &I);
         else launch_fused_half<15, false, 0>(grid, st, P, C, rois, level_boxes, nullptr, nullptr, out, nullptr, none, &I);
@@ -671,7 +731,7 @@ int launch_extract_cache_batched(const float* const* feats, const int* heights, 
                                  float two_e, float min_wh, float* templates, float* sr, float* order_hint, hipStream_t st,
                                  const ImageRows& I) {
     LevelParams P;
-    const int rc = fill_level_params(&P, feats, heights, widths, nullptr, scales, num_levels, "emm_extract_cache_batched");
+    const int rc = fill_level_params(&P, feats, heights, widths, nullptr, scales, num_levels, "emm_extract_cache_batched", C);
     if (rc) return rc;
     SMOT_REQUIRE(boxes && templates && sr, "emm_extract_cache_batched: null pointer");
     if (!order_hint_rois(N, false) || rz != 15) order_hint = nullptr;
@@ -680,7 +740,9 @@ int launch_extract_cache_batched(const float* const* feats, const int* heights, 
     dim3 grid(N, (C + FX_CH - 1) / FX_CH + (order_hint != nullptr ? 1 : 0));
     SrOut S = {sr, pad_pixels, half_e, two_e, min_wh, g_trace, 0, nullptr, fused_order(), order_hint, nullptr, 0};
     for (int l = 0; l < num_levels && l < SMOT_MAX_LEVELS; ++l) S.plan_pad[l] = (int)(pad_pixels * scales[l]);
-    if (half_maps()) {
+    if (channels_last()) {
+        launch_pool_nhwc(rz, grid, st, P, C, boxes, boxes, templates, nullptr, S, &I);
+    } else if (half_maps()) {
         if (rz == 7) launch_fused_half<7, false, 0>(grid, st, P, C, boxes, boxes, nullptr, nullptr, templates, nullptr, S, &I);
         else launch_fused_half<15, false, 0>(grid, st, P, C, boxes, boxes, nullptr, nullptr, templates, nullptr, S, &I);
     } else if (rz == 7) {
@@ -699,7 +761,7 @@ int sr_xcorr_fused_batched_impl(const float* const* feats, const int* heights, c
                                 const float* templates, int N, float* resp, const float* order_hint, hipStream_t st,
                                 const int** hint_status, float* plane_max, const ImageRows& I) {
     LevelParams P;
-    const int rc = fill_level_params(&P, feats, heights, widths, pad_cells, scales, num_levels, "sr_xcorr_fused_batched");
+    const int rc = fill_level_params(&P, feats, heights, widths, pad_cells, scales, num_levels, "sr_xcorr_fused_batched", C);
     if (rc) return rc;
     if (!order_hint_rois(N, true)) order_hint = nullptr;
     if (hint_status != nullptr)
@@ -710,7 +772,9 @@ int sr_xcorr_fused_batched_impl(const float* const* feats, const int* heights, c
     SrOut none = {nullptr, 0.f, 0.f, 0.f, 0.f, g_trace, 0, nullptr, fused_order(), nullptr, order_hint, 0};
     none.plane_max = plane_max;
     timer_mark(0, 0, st);
-    if (half_maps())
+    if (channels_last())
+        launch_fused_nhwc<30, true, 1>(grid, st, P, C, sr, boxes, templates, resp, nullptr, nullptr, none, &I);
+    else if (half_maps())
         launch_fused_half<30, true, 1>(grid, st, P, C, sr, boxes, templates, resp, nullptr, nullptr, none, &I);
     else
         SMOT_LAUNCH((sr_xcorr_fused9_batched_kernel<30, 15, 2, true, FX_CH, 1>), grid, dim3(512), 0, st, P, C, sr, boxes,
@@ -734,7 +798,7 @@ int sr_xcorr_fused_impl(const float* const* feats, const int* heights, const int
                         const float* templates, int N, float* resp, float* x_debug, const float* order_hint,
                         hipStream_t st, const int** hint_status, float* plane_max) {
     LevelParams P;
-    const int rc = fill_level_params(&P, feats, heights, widths, pad_cells, scales, num_levels, "sr_xcorr_fused");
+    const int rc = fill_level_params(&P, feats, heights, widths, pad_cells, scales, num_levels, "sr_xcorr_fused", C);
     if (rc) return rc;
     if (!order_hint_rois(N, true)) order_hint = nullptr;
     // the status word of a hint this launch honours (and verifies: fx_verify_hint) — for the head's decode kernel
@@ -744,7 +808,7 @@ int sr_xcorr_fused_impl(const float* const* feats, const int* heights, const int
                  "sr_xcorr_fused: the order hint must be 32-byte aligned");
     dim3 grid(N, (C + FX_CH - 1) / FX_CH);
 #ifdef SMOT_DEBUG
-    if (knobs().fused_gen == 10) {             // stage 1 (measurement library): generation 4 with a stand-alone plan launch
+    if (knobs().fused_gen == 10 && !channels_last()) {             // stage 1 (measurement library): generation 4 with a stand-alone plan launch
         static float* plans = nullptr;
         if (plans == nullptr && hipMalloc(&plans, (size_t)4096 * fused10_plan_floats() * 4) != hipSuccess) return SMOT_ERR_BAD_ARG;
         SMOT_REQUIRE(N <= 4096, "fused10 debug: at most 4096 rois");

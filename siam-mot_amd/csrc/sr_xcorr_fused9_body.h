@@ -5,6 +5,8 @@
 // FT (defined by the kernel as well) is the maps' element type: float, or f16_t / bf16_t in the *_half_* kernels, which
 // load 2-byte elements and convert them right behind the load (fx_load1 / fx_load2 / fx_pair_elem); everything else,
 // the sample tables and the order hint's row BYTE offsets of an fp32 map included, is the same text.
+// NHWC (defined by the kernel too; false in every NCHW kernel): the maps are channels-last and the pooling stage is
+// sr_pool_nhwc_stage.h; tables, hint, assignment, LDS images and the correlation are the same text.
     constexpr int HO = XCORR ? RX - RZ + 1 : 16;
     constexpr int NS = RX * G;                   // samples per axis
     // LDS image of the one-plane-per-wave correlation (xcorr_patch1.h): row stride 40, one plane per slot
@@ -189,7 +191,7 @@
     const int hb[4] = {g8[0], g8[1], g8[2], g8[3]};
     // the entries every wave fetched for itself are enough (no LDS tables, no barrier): a verified-geometry hint and a window
     // the plane-pair forms take (workgroup-uniform)
-    const bool fast = MM == 1 && hent && hb[3] - hb[2] + 1 <= 64
+    const bool fast = !NHWC && MM == 1 && hent && hb[3] - hb[2] + 1 <= 64
 #ifdef SMOT_DEBUG
                       && S.abl != 3 && S.abl != 12        // (3: the one-plane-per-wave A/B form reads the LDS tables; 12: A/B of this path)
 #endif
@@ -566,6 +568,10 @@
     // instructions of a narrow one (it was one plane per wave in two batches of 15 rows — twice the load, FMA and
     // tap instructions per plane, and those workgroups set the kernel's makespan: 25 k vs 12 k cycles of pooling).
     // Wider than 64 (degenerate aspect ratios): one plane per wave in 64-column chunks.
+    if constexpr (NHWC) {
+        // channels-last maps: one stage for every window width, same plane images (sr_pool_nhwc_stage.h)
+#include "sr_pool_nhwc_stage.h"
+    } else
     if (ww <= 32) {
         pool(std::true_type{}, std::false_type{}, std::false_type{}, std::integral_constant<int, RH>{});
 #ifdef SMOT_DEBUG

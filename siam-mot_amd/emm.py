@@ -286,6 +286,10 @@ class EMM(nn.Module):
         if plans is None:
             plans = self.__dict__["_plan"] = {}
         dt = features[0].dtype if len(features) and isinstance(features[0], torch.Tensor) else None
+        # ... and one more per type for channels-last maps (read in place: ops.FEAT_CHANNELS_LAST), under a key of its own
+        if dt is not None and not features[0].is_contiguous() and ops._head_reads_channels_last(self.rx, self.rz) \
+                and ops._levels_layout(features, len(scales)):
+            dt = (dt, ops.FEAT_CHANNELS_LAST)
         plan = plans.get(dt)
         tu = self.track_utils
         if plan is not None and plan.dev == boxes_bbox.device and not plan.stale(params, self.rx, self.rz, scales,

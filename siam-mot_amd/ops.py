@@ -216,6 +216,47 @@ def _dev_feat(t, name):
     return t if t.is_contiguous() else t.contiguous()
 
 
+# layout flag of the maps, OR'ed into the typed entry points' ``feat_type`` (SMOT_FEAT_CHANNELS_LAST): the levels are
+# ``[B, C, H, W]`` tensors whose memory is ``[B, H, W, C]`` and are read in place
+FEAT_CHANNELS_LAST = 16
+_CL = torch.channels_last
+
+
+def maps_layout(t):
+    """``FEAT_CHANNELS_LAST`` for a map the library reads as channels-last, 0 for NCHW and for everything else (which is
+    passed as NCHW: contiguous as it is, a strided view through a copy).  Channels-last: 4-D, NOT contiguous, and
+    contiguous in ``torch.channels_last`` — a tensor that is both (C == 1, or H == W == 1) is NCHW."""
+    return FEAT_CHANNELS_LAST if (t.dim() == 4 and not t.is_contiguous() and t.is_contiguous(memory_format=_CL)) else 0
+
+
+def _levels_layout(features, L):
+    """The layout word of a call: ``FEAT_CHANNELS_LAST`` only when EVERY level is channels-last, C % 8 == 0 and the level
+    starts at a 16-byte boundary (a pixel's channel runs are then 16-byte aligned); any mix of layouts, other strides,
+    another C or a view at an odd offset -> 0, the call as it ever was (such maps are copied)."""
+    for l in range(L):
+        f = features[l]
+        if not (isinstance(f, torch.Tensor) and f.dim() == 4 and f.shape[1] % 8 == 0 and not f.is_contiguous()
+                and f.is_contiguous(memory_format=_CL) and f.data_ptr() % 16 == 0):
+            return 0
+    return FEAT_CHANNELS_LAST
+
+
+def _dev_feats(features, L, nhwc=True):
+    """The ``L`` levels as the library takes them, and their ``feat_type`` word: channels-last levels (``_levels_layout``;
+    ``nhwc=False``: the entry has no channels-last form) pass as they are with the flag set, anything else through
+    ``_dev_feat``."""
+    if nhwc and _levels_layout(features, L):
+        feats = [features[l] for l in range(L)]
+        for l, f in enumerate(feats):
+            if not f.is_cuda:
+                raise RuntimeError("siammot_amd: features[%d] must be a device (ROCm) tensor — no CPU path exists" % l)
+            if f.dtype not in FEAT_TYPES:
+                _dev_feat(f, "features[%d]" % l)            # raises
+        return feats, _feat_type(feats) | FEAT_CHANNELS_LAST
+    feats = [_dev_feat(features[l], "features[%d]" % l) for l in range(L)]
+    return feats, _feat_type(feats)
+
+
 def _feat_type(feats):
     """The one element type of a call's maps (each passed ``_dev_feat``) -> SMOT_FEAT_*; mixed levels raise."""
     dt = feats[0].dtype
@@ -299,8 +340,7 @@ def roi_align_levels(features, rois, level_boxes, out_size, scales, sampling_rat
     """
     lib = load_library()
     L = len(scales)
-    feats = [_dev_feat(features[l], "features[%d]" % l) for l in range(L)]
-    ft = _feat_type(feats)
+    feats, ft = _dev_feats(features, L)
     for f in feats:
         if f.dim() != 4 or f.shape[0] != 1:
             raise RuntimeError("siammot_amd.roi_align_levels: one image per call, got feature shape %s"
@@ -332,7 +372,8 @@ def roi_align(input, rois, spatial_scale, pooled_h, pooled_w, sampling_ratio, pa
     level ``[B,C,H,W]``, rois ``[R,5]`` = (image index, x1, y1, x2, y2) -> ``[R,C,pooled_h,pooled_w]``, allocated here
     in fp32 (a half ``input`` is read as it is; upstream's ``ROIAlign.forward`` is an ``amp.float_function``).  ``pad_cells`` > 0: virtual zero border (rois in padded coordinates)."""
     lib = load_library()
-    input = _dev_feat(input, "input")
+    _dev_feat(input, "input") if not isinstance(input, torch.Tensor) else None        # (raises: not a tensor)
+    (input,), ft = _dev_feats((input,), 1)
     rois = _dev_f32(rois, "rois")
     if input.dim() != 4 or rois.dim() != 2 or rois.shape[1] != 5:
         raise RuntimeError("siammot_amd.roi_align: input must be [B,C,H,W] and rois [R,5], got %s and %s"
@@ -341,7 +382,7 @@ def roi_align(input, rois, spatial_scale, pooled_h, pooled_w, sampling_ratio, pa
     R = rois.shape[0]
     out = torch.empty((R, C, int(pooled_h), int(pooled_w)), dtype=torch.float32, device=input.device)
     with _Launch(input, rois) as ln:
-        rc = lib.smot_roi_align_typed_fwd(_ptr(input), FEAT_TYPES[input.dtype], B, C, H, W, int(pad_cells), _ptr(rois), R,
+        rc = lib.smot_roi_align_typed_fwd(_ptr(input), ft, B, C, H, W, int(pad_cells), _ptr(rois), R,
                                           float(spatial_scale), int(pooled_h), int(pooled_w), int(sampling_ratio),
                                           _ptr(out), ln.stream)
     _check(rc, "roi_align")
@@ -487,10 +528,9 @@ def emm_decode(logits, sr, boxes, rx, rz, pad_pixels, sigma=0.4, use_centerness=
 _cast = lambda a: ctypes.cast(a, ctypes.c_void_p)
 
 
-def _level_arrays(features, scales):
+def _level_arrays(features, scales, nhwc=True):
     L = len(scales)
-    feats = [_dev_feat(features[l], "features[%d]" % l) for l in range(L)]
-    _feat_type(feats)                      # (one dtype per call: raises otherwise)
+    feats, ft = _dev_feats(features, L, nhwc)      # (one dtype per call: raises otherwise)
     for f in feats:
         if f.dim() != 4 or f.shape[0] != 1:
             raise RuntimeError("siammot_amd: one image per call, got feature shape %s" % (tuple(f.shape),))
@@ -498,7 +538,7 @@ def _level_arrays(features, scales):
     hs = (ctypes.c_int * L)(*[f.shape[2] for f in feats])
     ws = (ctypes.c_int * L)(*[f.shape[3] for f in feats])
     sc = (ctypes.c_float * L)(*[float(s) for s in scales])
-    return feats, fp, hs, ws, sc
+    return feats, fp, hs, ws, sc, ft
 
 
 _ws_cache = {}
@@ -528,10 +568,11 @@ class _LevelGeometry(object):
     that is refilled every call."""
     __slots__ = ("shapes", "L", "C", "fp", "hs", "ws", "sc", "pc", "a_fp", "a_hs", "a_ws", "a_sc", "a_pc", "keep", "dtype", "ft")
 
-    def __init__(self, shapes, scales, pad_pixels, dtype=torch.float32):
+    def __init__(self, shapes, scales, pad_pixels, dtype=torch.float32, layout=0):
         L = len(scales)
         self.shapes, self.L, self.C = shapes, L, shapes[0][1]
-        self.dtype, self.ft = dtype, FEAT_TYPES[dtype]      # the maps' one element type (part of the cache key)
+        # the maps' one element type and layout (parts of the cache key): ``ft`` is the typed entry points' ``feat_type``
+        self.dtype, self.ft = dtype, FEAT_TYPES[dtype] | layout
         self.fp = (ctypes.c_void_p * L)()
         self.hs = (ctypes.c_int * L)(*[sh[2] for sh in shapes])
         self.ws = (ctypes.c_int * L)(*[sh[3] for sh in shapes])
@@ -556,13 +597,15 @@ def _maps_dtype(features, L):
     return dt
 
 
-def _geometry(features, scales, pad_pixels, device):
+def _geometry(features, scales, pad_pixels, device, nhwc=True):
     """Validate the per-level feature tensors (all on ``device``) and return the cached geometry with fresh
-    pointers."""
+    pointers.  Channels-last levels (``_levels_layout``) are passed as they are and the geometry says so (``g.ft``);
+    ``nhwc=False``: the caller's entry has no channels-last form, such maps are copied like any strided view."""
     L = len(scales)
     shapes = tuple(tuple(features[l].shape) for l in range(L))
     dt = _maps_dtype(features, L)
-    key = (shapes, tuple(scales), pad_pixels, dt)
+    cl = _levels_layout(features, L) if nhwc else 0
+    key = (shapes, tuple(scales), pad_pixels, dt, cl)
     g = _geom_cache.get(key)
     if g is None:
         for sh in shapes:
@@ -571,11 +614,11 @@ def _geometry(features, scales, pad_pixels, device):
                                    % (shapes,))
         if len(_geom_cache) > 32:
             _geom_cache.clear()
-        g = _geom_cache[key] = _LevelGeometry(shapes, scales, pad_pixels, dt)
+        g = _geom_cache[key] = _LevelGeometry(shapes, scales, pad_pixels, dt, cl)
     fp = g.fp
     for l in range(L):
         f = features[l]
-        if not (f.is_cuda and f.is_contiguous()):
+        if not (f.is_cuda and (cl or f.is_contiguous())):
             f = g.keep[l] = _dev_feat(f, "features[%d]" % l)        # raises, or copies a strided view
         if f.device != device:
             raise RuntimeError("siammot_amd: features[%d] lives on %s, the boxes on %s" % (l, f.device, device))
@@ -583,16 +626,26 @@ def _geometry(features, scales, pad_pixels, device):
     return g
 
 
+def _head_reads_channels_last(rx, rz):
+    """False for the 35 / 7 head shape: its gather kernel has no channels-last form (the maps go through the NCHW copy)."""
+    return not (int(rx) == 35 and int(rz) == 7)
+
+
 def _geometry_refresh(g, features, device):
-    """The per-frame part of ``_geometry`` for a caller that keeps ``g``: same shapes, same dtype, contiguous, on ``device`` ->
-    the pointer array is refilled and True is returned; anything else returns False (the caller takes the full path,
-    which raises or rebuilds)."""
+    """The per-frame part of ``_geometry`` for a caller that keeps ``g``: same shapes, same dtype, the geometry's own layout
+    (contiguous, or channels-last for a channels-last geometry), on ``device`` -> the pointer array is refilled and True is
+    returned; anything else returns False (the caller takes the full path, which raises or rebuilds)."""
     fp, shapes, dt = g.fp, g.shapes, g.dtype
     if len(features) < g.L:
         return False
+    cl = g.ft & FEAT_CHANNELS_LAST
     for l in range(g.L):                 # validate every level first: a mismatch must leave the pointer array as it was
         f = features[l]
-        if f.shape != shapes[l] or not (f.is_cuda and f.dtype is dt and f.is_contiguous()) or f.device != device:
+        if f.shape != shapes[l] or not (f.is_cuda and f.dtype is dt) or f.device != device:
+            return False
+        if f.is_contiguous() if cl else not f.is_contiguous():      # (channels-last: not contiguous, and ...)
+            return False
+        if cl and not (f.is_contiguous(memory_format=_CL) and f.data_ptr() % 16 == 0):
             return False
     for l in range(g.L):
         fp[l] = features[l].data_ptr()
@@ -678,7 +731,7 @@ def emm_track(features, boxes, sr, templates, params, rx, rz, scales, sampling_r
     if not (isinstance(boxes, torch.Tensor) and boxes.is_cuda):
         _dev_f32(boxes, "boxes")                 # raises: no CPU path
     dev = boxes.device
-    g = _geometry(features, scales, pad_pixels, dev)
+    g = _geometry(features, scales, pad_pixels, dev, nhwc=_head_reads_channels_last(rx, rz))
     N, C = boxes.shape[0], g.C
     boxes = _chk(boxes, "boxes", (N, 4))
     sr = _chk(sr, "sr", (N, 4))
@@ -807,12 +860,13 @@ def emm_extract_cache(features, boxes, rz, scales, sampling_ratio, pad_pixels, s
 MAX_IMAGES = 64                      # SMOT_MAX_IMAGES (include/smot_emm.h)
 
 
-def _geometry_batched(features, scales, pad_pixels, device):
+def _geometry_batched(features, scales, pad_pixels, device, nhwc=True):
     """``_geometry`` for ``[B, C, H, W]`` maps (one B, one C for every level) -> (geometry, B)."""
     L = len(scales)
     shapes = tuple(tuple(features[l].shape) for l in range(L))
     dt = _maps_dtype(features, L)
-    key = ("batched", shapes, tuple(scales), pad_pixels, dt)
+    cl = _levels_layout(features, L) if nhwc else 0
+    key = ("batched", shapes, tuple(scales), pad_pixels, dt, cl)
     g = _geom_cache.get(key)
     if g is None:
         for sh in shapes:
@@ -821,11 +875,11 @@ def _geometry_batched(features, scales, pad_pixels, device):
                                    % (shapes,))
         if len(_geom_cache) > 32:
             _geom_cache.clear()
-        g = _geom_cache[key] = _LevelGeometry(shapes, scales, pad_pixels, dt)
+        g = _geom_cache[key] = _LevelGeometry(shapes, scales, pad_pixels, dt, cl)
     fp = g.fp
     for l in range(L):
         f = features[l]
-        if not (f.is_cuda and f.is_contiguous()):
+        if not (f.is_cuda and (cl or f.is_contiguous())):
             f = g.keep[l] = _dev_feat(f, "features[%d]" % l)
         if f.device != device:
             raise RuntimeError("siammot_amd: features[%d] lives on %s, the boxes on %s" % (l, f.device, device))
@@ -857,7 +911,7 @@ def emm_track_batched(features, boxes, sr, templates, rows_per_image, params, rx
     if not (isinstance(boxes, torch.Tensor) and boxes.is_cuda):
         _dev_f32(boxes, "boxes")
     dev = boxes.device
-    g, B = _geometry_batched(features, scales, pad_pixels, dev)
+    g, B = _geometry_batched(features, scales, pad_pixels, dev, nhwc=_head_reads_channels_last(rx, rz))
     N, C = boxes.shape[0], g.C
     row_start = _row_starts(rows_per_image, B, N)
     boxes = _chk(boxes, "boxes", (N, 4))
@@ -964,8 +1018,9 @@ class PairPlan(object):
     def __init__(self, features, dev, params, rx, rz, scales, sampling_ratio, pad_pixels, tu):
         self.lib = lib = _lib or load_library()
         self.dev, self.dev_index = dev, dev.index
-        self.g = _geometry(features, scales, pad_pixels, dev)           # full validation (raises)
-        self.gz = _geometry(features, scales, 0, dev)
+        nhwc = _head_reads_channels_last(rx, rz)                        # (one layout for the plan's two calls)
+        self.g = _geometry(features, scales, pad_pixels, dev, nhwc)     # full validation (raises)
+        self.gz = _geometry(features, scales, 0, dev, nhwc)
         self.params, self.blk = params, _param_block(params)
         self.rx, self.rz, self.ho = rx, rz, rx - rz + 1
         self.scales, self.sampling_ratio, self.pad_pixels = scales, sampling_ratio, pad_pixels
@@ -983,9 +1038,10 @@ class PairPlan(object):
         self.tu = (float(tu.pad_pixels), float(tu.search_expansion), float(tu.min_search_wh))
 
     def stale(self, params, rx, rz, scales, sampling_ratio, pad_pixels, tu, features=None):
-        """True when the plan does not describe this call.  ``features``: the call's maps — another dtype or other shapes
-        than the plan's geometry make it stale too (a caller that switches between fp32 and half maps, or between map
-        sizes, gets a new plan instead of falling to the general functions on every call)."""
+        """True when the plan does not describe this call.  ``features``: the call's maps — another dtype, another layout or
+        other shapes than the plan's geometry make it stale too (a caller that switches between fp32 and half maps, between
+        NCHW and channels-last maps, or between map sizes, gets a new plan instead of falling to the general functions on
+        every call)."""
         if features is not None:
             g = self.g
             if len(features) < g.L:
@@ -993,6 +1049,13 @@ class PairPlan(object):
             for l in range(g.L):
                 if features[l].dtype is not g.dtype or features[l].shape != g.shapes[l]:
                     return True
+            # ... and another layout (NCHW maps on a channels-last plan, or maps the library reads as channels-last on an
+            # NCHW plan): a caller that alternates gets a plan per layout
+            if features[0].is_contiguous():
+                if g.ft & FEAT_CHANNELS_LAST:
+                    return True
+            elif not (g.ft & FEAT_CHANNELS_LAST) and _head_reads_channels_last(rx, rz) and _levels_layout(features, g.L):
+                return True
         return (params is not self.params or rx != self.rx or rz != self.rz or scales != self.scales or
                 sampling_ratio != self.sampling_ratio or pad_pixels != self.pad_pixels or self.lib is not _lib or
                 self.tu != (float(tu.pad_pixels), float(tu.search_expansion), float(tu.min_search_wh)))
@@ -1163,8 +1226,8 @@ def sr_xcorr_fused(features, boxes, sr, templates, rx, rz, scales, sampling_rati
     sr = _dev_f32(sr, "sr")
     templates = _dev_f32(templates, "template_features")
     N = boxes.shape[0]
-    feats, fp, hs, ws_, sc = _level_arrays(features, scales)
-    ft = FEAT_TYPES[feats[0].dtype]
+    # (the 35 / 7 shape's kernel has no channels-last form: such maps go through the NCHW copy there)
+    feats, fp, hs, ws_, sc, ft = _level_arrays(features, scales, nhwc=not ((int(rx), int(rz)) == (35, 7) and not return_pooled))
     C = feats[0].shape[1]
     L = len(scales)
     pc = (ctypes.c_int * L)(*[int(pad_pixels / ((2 ** i) * 4)) for i in range(L)])
@@ -1438,8 +1501,7 @@ def box_refine(features, scales, pooled, sampling_ratio, boxes, labels, ids, tra
     labels)`` in the box head's output order."""
     lib = _lib or load_library()
     L = len(scales)
-    feats = [_dev_feat(features[l], "features[%d]" % l) for l in range(L)]
-    ft = _feat_type(feats)
+    feats, ft = _dev_feats(features, L)
     boxes = _dev_f32(boxes, "boxes")
     track_conf = _dev_f32(track_conf, "track_conf")
     w6, b6, w7, b7, wc, bc, wr, br = [_dev_f32(t, "box head parameter") for t in layers]

@@ -613,7 +613,11 @@ class TrackingLoop(torch.nn.Module):
         P = _FramePlan()
         P.dev, P.emm, P.solver, P.pool, P.refine = dev, emm, solver, pool, self.refine_tracks
         P.g = g = ops._geometry(features, tuple(fe.scales), emm.pad_pixels, dev)       # validates (raises) and caches
-        P.ft = ops.FEAT_TYPES.get(features[0].dtype, 0)       # (a dtype the library does not take was refused just above)
+        cl = getattr(g, "ft", 0) & ops.FEAT_CHANNELS_LAST        # channels-last maps are read in place ...
+        if cl and not ops._head_reads_channels_last(emm.rx, emm.rz):
+            P.g = g = ops._geometry(features, tuple(fe.scales), emm.pad_pixels, dev, False)      # ... but not by the 35 / 7 head
+            cl = 0
+        P.ft = ops.FEAT_TYPES.get(features[0].dtype, 0) | cl     # (a dtype the library does not take was refused just above)
         P.scales = tuple(fe.scales)
         P.params = pr.param_dict()
         P.hann = ops.hann_window((emm.rx - emm.rz + 1) * ops.UP_SCALE, dev)
