@@ -15,12 +15,20 @@
 // INPUT order (roi_heads.py:66,70,75), so out_scores[p] = (det[p] + (track_conf[p] + 1)) / 2.
 //
 // One workgroup (N <= 512 rows, one thread per row); arithmetic in the reference's op order, fp32, separately rounded.
+// Any number of classes: a row's logits are read in a loop, nothing per class is held in registers.
+//
+// Non-finite inputs.  The reference has no contract here (a row whose probabilities are NaN fails its threshold, and
+// _refine_tracks then raises on the length mismatch); this kernel's is: the output keeps N rows, and a row's rank, id
+// and label never depend on its values.  A row whose soft-max is NaN in torch (a NaN or +inf among its class logits,
+// -inf in all of them) gets a NaN score; a lone -inf logit is an ordinary probability of 0.  A NaN among the label's
+// deltas gives NaN in exactly the coordinates where BoxCoder.decode followed by torch.clamp gives NaN (dx, dw: x1 and
+// x2; dy, dh: y1 and y2), clipped or not: the clamps of dw / dh and of clip_to_image keep a NaN (min_nan, clamp_nan).
+// No other row is affected (tests/test_box_refine_edges.py).
 #include "smot_common.h"
 
 namespace smot {
 
 constexpr int BR_MAXN = 512;
-constexpr int BR_MAXK = 16;       // classes incl. background held in registers per row
 
 struct BoxRefineArgs {
     const float* logits;     // [N, ldo] : columns [0, K) class logits, columns [K, K + 4*KR) box deltas
@@ -100,7 +108,8 @@ __global__ void __launch_bounds__(BR_MAXN) box_refine_post_kernel(BoxRefineArgs 
         const float w = add_rn(sub_rn(x2, x1), 1.0f), h = add_rn(sub_rn(y2, y1), 1.0f);
         const float cx = add_rn(x1, mul_rn(0.5f, w)), cy = add_rn(y1, mul_rn(0.5f, h));
         const float dx = div_rn(d[0], A.wx), dy = div_rn(d[1], A.wy);
-        const float dw = fminf(div_rn(d[2], A.ww), A.xform_clip), dh = fminf(div_rn(d[3], A.wh), A.xform_clip);
+        // torch.clamp(..., max=clip): a NaN delta stays NaN (fminf would return the clip: a finite box exp(clip) times too wide)
+        const float dw = min_nan(div_rn(d[2], A.ww), A.xform_clip), dh = min_nan(div_rn(d[3], A.wh), A.xform_clip);
         const float pcx = add_rn(mul_rn(dx, w), cx), pcy = add_rn(mul_rn(dy, h), cy);
         const float pw = mul_rn(expf(dw), w), ph = mul_rn(expf(dh), h);
         bx1 = sub_rn(pcx, mul_rn(0.5f, pw));

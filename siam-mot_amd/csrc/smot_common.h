@@ -105,6 +105,10 @@ __device__ __forceinline__ float relu_nan(float v) { return v < 0.0f ? 0.0f : v;
 __device__ __forceinline__ float max_nan(float a, float b) {
     return (a != a) ? a : ((b != b) ? b : fmaxf(a, b));
 }
+// torch.clamp(v, max=b) / torch.minimum semantics: NaN propagates (fminf returns the OTHER operand for a NaN)
+__device__ __forceinline__ float min_nan(float a, float b) {
+    return (a != a) ? a : ((b != b) ? b : fminf(a, b));
+}
 
 // torch.clamp semantics: NaN stays NaN
 __device__ __forceinline__ float clamp_nan(float v, float lo, float hi) {

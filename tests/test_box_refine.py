@@ -195,22 +195,35 @@ def test_linear_rows_matches_the_library_gemm(M, K, N, relu):
         ops.linear_rows(torch.randn((3, 6), device="cuda"), torch.randn((4, 6), device="cuda"))      # K % 4 != 0
 
 
+# (n, dim6, dim7, classes) of per-class heads, clipped, averaged scores — and (..., agnostic, amodal, tracktor)
+_ONE_CALL_SHAPES = [(30, 1024, 1024, 2), (64, 1024, 1024, 2), (1, 1024, 1024, 2), (17, 128, 64, 3), (30, 96, 100, 2),
+                    (9, 256, 1024, 14), (30, 64, 128, 16), (100, 1024, 1024, 2), (128, 1024, 1024, 2), (71, 128, 64, 3)]
+_ONE_CALL_FORMS = [(30, 128, 64, 3, True, False, False), (64, 128, 64, 56, True, True, False), (33, 128, 64, 57, True, False, True),
+                   (128, 128, 64, 12, False, True, True), (30, 1024, 1024, 2, True, True, True), (17, 128, 64, 3, False, True, False),
+                   (71, 128, 64, 3, False, False, True)]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("n,dim6,dim7,classes", [(30, 1024, 1024, 2), (64, 1024, 1024, 2), (1, 1024, 1024, 2), (17, 128, 64, 3),
-                                                 (30, 96, 100, 2), (9, 256, 1024, 14), (30, 64, 128, 16),
-                                                 (100, 1024, 1024, 2), (128, 1024, 1024, 2), (71, 128, 64, 3)])
-def test_one_call_refinement_equals_the_stage_wise_composition_bitwise(n, dim6, dim7, classes):
+@pytest.mark.parametrize("n,dim6,dim7,classes,agnostic,amodal,tracktor",
+                         [pytest.param(*s, False, False, False, id="%d-%d-%d-%d" % s) for s in _ONE_CALL_SHAPES] +
+                         [pytest.param(*s, id="%d-%d-%d-%d-%s" % (s[:4] + ("".join(c for c, on in zip("AMT", s[4:]) if on),)))
+                          for s in _ONE_CALL_FORMS])
+def test_one_call_refinement_equals_the_stage_wise_composition_bitwise(n, dim6, dim7, classes, agnostic, amodal, tracktor):
     """``smot_box_refine_fwd`` skips two reduction launches where the layer shapes allow (the head's launch adds fc7's K
     slices while it loads, the post-processing kernel adds the head's): the slices are added in the order and with the
     bias / ReLU placement of the reduction kernel, so the result must equal pooler -> linear_rows x 3 -> box_refine_post
     bit for bit — at the yaml's 1024-1024 head, at 64 rows and one row, at widths where the chain applies with fewer
     slices, where it does not (fc7 width not a multiple of 64), and at heads of 70 / 80 columns (more than one neuron
-    block: both reductions are launches again)."""
+    block: both reductions are launches again); with class-agnostic heads (A: 3 classes = 11 columns, 56 = 64 columns,
+    the last shape the post kernel sums itself, 57 = 65 columns, a reduction launch again), a per-class head of 60
+    columns at 128 rows, amodal inference (M: no clipping) and TRACKTOR scores (T)."""
     import siammot_amd.ops as ops
     g = torch.Generator().manual_seed(n * 7 + dim7)
     C, scales = 16, (0.25, 0.125, 0.0625, 0.03125)
     feats = tuple(torch.randn((1, C, 352 // s_, 640 // s_), generator=g).cuda() for s_ in (1, 2, 4, 8))
     xy = torch.rand((n, 2), generator=g) * torch.tensor([1000.0, 500.0])
+    if amodal:
+        xy = xy + torch.tensor([600.0, 0.0])                 # many boxes reach beyond the right border
     wh = 20.0 + torch.rand((n, 2), generator=g) * 200.0
     boxes = torch.cat((xy, xy + wh), 1).cuda()
     labels = torch.randint(1, classes, (n,), generator=g).cuda()
@@ -222,19 +235,23 @@ def test_one_call_refinement_equals_the_stage_wise_composition_bitwise(n, dim6, 
     w6, b6 = lin(dim6, C * 49)
     w7, b7 = lin(dim7, dim6)
     wc, bc = lin(classes, dim7)
-    wr, br = lin(4 * classes, dim7)
+    reg_classes = 2 if agnostic else classes
+    wr, br = lin(4 * reg_classes, dim7)
     weights, clip = (10.0, 10.0, 5.0, 5.0), 4.135
+    clip_wh = None if amodal else (1280, 704)
     one = ops.box_refine(feats, scales, 7, 2, boxes, labels, ids, conf, (w6, b6, w7, b7, wc, bc, wr, br), weights, clip,
-                         (1280, 704))
+                         clip_wh, tracktor)
     x = ops.roi_align_levels(feats, boxes, boxes, 7, scales, 2).reshape(n, -1)
     h6 = ops.linear_rows(x, w6, b6, relu=True)
     h7 = ops.linear_rows(h6, w7, b7, relu=True)
-    ho = torch.empty((n, 5 * classes), device="cuda")
+    ho = torch.empty((n, classes + 4 * reg_classes), device="cuda")
     ops.linear_rows(h7, wc, bc, out=ho[:, :classes])
     ops.linear_rows(h7, wr, br, out=ho[:, classes:])
-    staged = ops.box_refine_post(ho, classes, classes, boxes, labels, ids, conf, weights, clip, (1280, 704))
+    staged = ops.box_refine_post(ho, classes, reg_classes, boxes, labels, ids, conf, weights, clip, clip_wh, tracktor)
     for a, b in zip(one, staged):
         assert torch.equal(a, b)
+    if amodal:
+        assert bool((one[0][:, 2] > 1279).any() or (one[0][:, 3] > 703).any() or (one[0] < 0).any())      # nothing was clipped
 
 
 @pytest.mark.gpu
