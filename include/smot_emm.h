@@ -800,6 +800,53 @@ int smot_box_refine_typed_fwd(const void* const* feats, int feat_type, const int
 
 int smot_track_frame_typed_fwd(const smot_frame_args* args, int feat_type, smot_stream_t stream);
 
+/*
+ * RPN PROPOSAL SELECTION (the NMS's third caller): reference operator_patch/rpn_patch.py:15-60 on
+ * [UPSTREAM] RPNPostProcessor.forward / select_over_all_levels (inference only), for all images and FPN levels of a call in
+ * one memset + nine launches (their number depends on neither num_images nor num_levels) and without a host synchronisation.
+ *
+ *   objectness[l]  [num_images, A_l, H_l, W_l] logits, regression[l] [num_images, 4 A_l, H_l, W_l] (channel of coordinate c
+ *                  of anchor a: 4a + c), contiguous, all of element type `feat_type` (SMOT_FEAT_F32 / F16 / BF16; the layout
+ *                  flag is SMOT_ERR_BAD_ARG).  A half call returns bit for bit what the call returns on the upcast tensors.
+ *   num_anchors / heights / widths   host arrays [num_levels]: A_l, H_l, W_l
+ *   anchors        HOST array [num_images * num_levels] (image-major) of DEVICE pointers to fp32 [A_l H_l W_l, 4] xyxy rows in
+ *                  the reference's flattened order (h W + w) A + a; read in place.  At most 128 DISTINCT pointers per call
+ *                  (upstream's generator shares one tensor per level among the images): SMOT_ERR_UNSUPPORTED beyond.
+ *   image_wh       host array [num_images][2]: width, height of each image (the clip; ignored when `amodal`)
+ *   per (image, level): the k = min(pre_nms_top_n, A H W) largest LOGITS in descending order, ties to the lower flat index
+ *                  (= objectness.sigmoid().topk(k) wherever the selected sigmoid values are distinct); BoxCoder.decode with
+ *                  weights (wx, wy, ww, wh), TO_REMOVE = 1, dw / dh clamped at xform_clip with NaN kept; unless `amodal`
+ *                  the clamp to [0, W - 1] x [0, H - 1]; rows with a side x2 - x1 + 1 or y2 - y1 + 1 not >= min_size dropped;
+ *                  greedy NMS (+1 IoU, suppressed when IoU > nms_thresh) in score order, first post_nms_top_n kept.
+ *   per image:     num_levels > 1: the levels concatenated in level order, the min(fpn_post_nms_top_n, total) best by logit
+ *                  in descending order, ties to the lower concatenated position.  num_levels == 1: upstream makes no
+ *                  selection; the level's list is copied (pass its capacity as fpn_post_nms_top_n).
+ *   outputs        out_boxes [num_images, fpn_post_nms_top_n, 4], out_objectness [num_images, fpn_post_nms_top_n] (the
+ *                  sigmoid, evaluated for these rows only), out_count [num_images] int32; rows beyond the count are zero.
+ *   capacities     num_images <= SMOT_MAX_IMAGES, num_levels <= SMOT_MAX_LEVELS, pre_nms_top_n <= 2048,
+ *                  fpn_post_nms_top_n <= 2048 (SMOT_ERR_BAD_ARG beyond); SMOT_ERR_UNSUPPORTED for nms_thresh <= 0 and for
+ *                  num_levels * min(post_nms_top_n, pre_nms_top_n) * 4 + 64 > 65536 (the merge keeps one key per level row
+ *                  in LDS: 8 levels x 2048 rows do not fit, 8 x 2032 and 7 x 2048 do).
+ *   ws             smot_rpn_proposals_ws_bytes(...) bytes (-1 for shapes the call refuses), 16-byte aligned.  Its largest
+ *                  part is the NMS bitmask, NL * P * ceil(P / 64) * 8 bytes (2.6 MB at 4 x 5 x 1000; 268 MB at 64 x 8 x 2048).  Its head is part
+ *                  of the contract — the per-level candidates, in 4-byte words, every section padded to a multiple of 4
+ *                  words, NL = num_images * num_levels, P = pre_nms_top_n, row il = image * num_levels + level:
+ *                      int32 count[NL]        candidates of the pair (k)
+ *                      int32 index[NL][P]     their flat indices, sorted (best first)
+ *                      float logit[NL][P]     their logits
+ *                      float box[NL][P][4]    their decoded boxes BEFORE the clip
+ *                  What follows is scratch.
+ */
+long long smot_rpn_proposals_ws_bytes(int num_images, int num_levels, const int* num_anchors, const int* heights,
+                                      const int* widths, int pre_nms_top_n, int post_nms_top_n);
+int smot_rpn_proposals_fwd(const void* const* objectness, const void* const* regression, int feat_type,
+                           const int* num_anchors, const int* heights, const int* widths, int num_levels,
+                           int num_images, const float* const* anchors, const float* image_wh,
+                           int pre_nms_top_n, int post_nms_top_n, int fpn_post_nms_top_n, float nms_thresh,
+                           float min_size, int amodal, float wx, float wy, float ww, float wh, float xform_clip,
+                           void* ws, float* out_boxes, float* out_objectness, int32_t* out_count,
+                           smot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,10 @@ def get_default_cfg(conv_body="DLA-34-FPN", channels=128):
     cfg.MODEL.DLA = CfgNode(BACKBONE_OUT_CHANNELS=channels)
     cfg.MODEL.RESNETS = CfgNode(BACKBONE_OUT_CHANNELS=256)
     cfg.MODEL.GROUP_NORM = CfgNode(DIM_PER_GP=-1, NUM_GROUPS=32, EPSILON=1e-5)
+    # what rpn.make_rpn_postprocessor reads at inference: the three counts from siammot/configs/defaults.py:13-15, the
+    # rest [UPSTREAM] maskrcnn_benchmark defaults (with INPUT.AMODAL above)
+    cfg.MODEL.RPN = CfgNode(PRE_NMS_TOP_N_TEST=1000, POST_NMS_TOP_N_TEST=300, FPN_POST_NMS_TOP_N_TEST=300,
+                            NMS_THRESH=0.7, MIN_SIZE=0, FPN_POST_NMS_PER_BATCH=True)
     th = CfgNode()
     th.TRACKTOR = False
     th.POOLER_SCALES = (0.25, 0.125, 0.0625, 0.03125)

@@ -13,21 +13,9 @@
 //         slabs of the mask are staged in LDS; inside a slab one wave walks the 64 candidates in order,
 //         OR-ing the rows of kept boxes into a `removed` bitset held one 64-bit word per lane.
 // Output: keep[i] in {0,1} per box (score order).  No host synchronisation.
-#include "smot_common.h"
+#include "nms_common.h"
 
 namespace smot {
-
-constexpr int NMS_T = 64;
-
-__device__ __forceinline__ float iou_plus1(const float* a, const float* b) {
-    const float left = fmaxf(a[0], b[0]), right = fminf(a[2], b[2]);
-    const float top = fmaxf(a[1], b[1]), bottom = fminf(a[3], b[3]);
-    const float w = fmaxf(right - left + 1.0f, 0.0f), h = fmaxf(bottom - top + 1.0f, 0.0f);
-    const float inter = w * h;
-    const float sa = (a[2] - a[0] + 1.0f) * (a[3] - a[1] + 1.0f);
-    const float sb = (b[2] - b[0] + 1.0f) * (b[3] - b[1] + 1.0f);
-    return inter / (sa + sb - inter);
-}
 
 __global__ void __launch_bounds__(NMS_T)
 nms_mask_kernel(const float* __restrict__ boxes, int n, float thresh, unsigned long long* __restrict__ mask) {

@@ -117,6 +117,10 @@ _SIGNATURES = {
                                                  _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i,
                                                  _f, _f, _f, _f, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "smot_track_frame_typed_fwd": (ctypes.c_int, [_vp, _i, _vp]),
+    # RPN proposal selection: all images and levels of a call in one set of launches
+    "smot_rpn_proposals_ws_bytes": (ctypes.c_longlong, [_i, _i, _vp, _vp, _vp, _i, _i]),
+    "smot_rpn_proposals_fwd": (ctypes.c_int, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _f, _f, _i,
+                                              _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 _DEBUG_SIGNATURES = {
@@ -1149,6 +1153,7 @@ TIMER_XCORR, TIMER_TOWER = 0, 1
 #   host_solver          a frame beyond the one-launch solver's capacity (or with fields it does not carry): host path
 #   unhinted_head        a pooling + correlation launch that ranked its rois itself although an order hint could exist
 #   general_frame        a tracking-loop frame that did not take the one-launch path at all
+#   rpn_torch            an RPN proposal selection on device tensors beyond ``rpn_proposals``' capacities (torch composition)
 import collections as _collections
 FALLBACKS = _collections.Counter()
 # speculative next-frame heads of the tracking loop (TrackingLoop.forward(..., next_features=...)): launched / used as they
@@ -1286,6 +1291,106 @@ def nms(boxes, scores, thresh):
         rc = lib.smot_nms_fwd(_ptr(sorted_boxes), n, float(thresh), _ptr(ws), _ptr(keep), ln.stream)
     _check(rc, "nms")
     return order[keep.bool()].sort()[0]
+
+
+# capacities of ``rpn_proposals`` (include/smot_emm.h): beyond them ``siammot_amd.rpn.RPNPostProcessor`` takes its torch path
+RPN_MAX_TOP_N = 2048
+RPN_MAX_IMAGES = 64
+RPN_MAX_LEVELS = 8
+RPN_MAX_ANCHOR_TENSORS = 128
+RPN_MERGE_LDS_BYTES = 64 * 1024      # levels x rows per level x 4 + 64 must fit (the merge's keys and counters)
+RPN_MAX_MASK_BYTES = 64 << 20        # NMS bitmask scratch the module accepts (see rpn_mask_bytes); larger calls take the torch path
+
+
+def rpn_mask_bytes(num_images, num_levels, pre_nms_top_n):
+    """Size of the largest part of ``rpn_proposals``' workspace, the NMS bitmasks: 8 bytes per (candidate row, 64-column
+    tile) of every (image, level), allocated for ``pre_nms_top_n`` rows whether or not they survive the size filter —
+    2.6 MB at 4 images x 5 levels x 1000, 268 MB at the capacities 64 x 8 x 2048."""
+    return num_images * num_levels * pre_nms_top_n * ((pre_nms_top_n + 63) // 64) * 8
+
+
+def _al4(words):
+    return (words + 3) & ~3
+
+
+def rpn_proposals(objectness, box_regression, anchors, image_sizes, pre_nms_top_n, post_nms_top_n, fpn_post_nms_top_n,
+                  nms_thresh, min_size, amodal=False, weights=(1.0, 1.0, 1.0, 1.0), xform_clip=None,
+                  return_candidates=False):
+    """RPN proposal selection of all images and levels in one library call, free of host synchronisation
+    (``smot_rpn_proposals_fwd``).
+
+    objectness: L tensors ``[N, A, H, W]`` (logits); box_regression: L tensors ``[N, 4A, H, W]``; one dtype per call (fp32,
+    fp16 or bf16; a half call returns the bits of the call on ``.float()``); strided inputs are copied.  anchors: per image
+    a sequence of L fp32 ``[A*H*W, 4]`` tensors in the reference's flattened order, read in place.  image_sizes: per image
+    ``(width, height)``.
+
+    Returns ``(boxes [N, cap, 4], objectness [N, cap], count [N] int32)``, rows beyond ``count`` zero, with
+    ``cap = fpn_post_nms_top_n`` — or, with one level, where upstream makes no selection across levels,
+    ``min(post_nms_top_n, pre_nms_top_n)``.  ``return_candidates=True`` adds a dict of the per-level candidates
+    ``count [N, L]``, ``index [N, L, pre]``, ``logit [N, L, pre]``, ``box [N, L, pre, 4]`` (sorted flat indices, their
+    logits, the decoded boxes before clipping): views of this call's own workspace."""
+    import math
+    lib = _lib or load_library()
+    L = len(objectness)
+    N = len(anchors)
+    if L < 1 or len(box_regression) != L or len(image_sizes) != N:
+        raise RuntimeError("siammot_amd.rpn_proposals: %d objectness levels, %d regression levels, %d images with anchors, "
+                           "%d image sizes" % (L, len(box_regression), N, len(image_sizes)))
+    obj = [_dev_feat(o, "objectness[%d]" % l) for l, o in enumerate(objectness)]
+    reg = [_dev_feat(r, "box_regression[%d]" % l) for l, r in enumerate(box_regression)]
+    ft = _feat_type(obj + reg)
+    dev = obj[0].device
+    shapes = []
+    for l in range(L):
+        if obj[l].dim() != 4 or obj[l].shape[0] != N or tuple(reg[l].shape) != (N, 4 * obj[l].shape[1]) + tuple(obj[l].shape[2:]):
+            raise RuntimeError("siammot_amd.rpn_proposals: level %d has objectness %s and regression %s for %d images"
+                               % (l, tuple(obj[l].shape), tuple(reg[l].shape), N))
+        shapes.append(tuple(obj[l].shape[1:]))
+    anc = []
+    for i in range(N):
+        if len(anchors[i]) != L:
+            raise RuntimeError("siammot_amd.rpn_proposals: image %d has %d anchor levels, expected %d" % (i, len(anchors[i]), L))
+        for l in range(L):
+            a, h, w = shapes[l]
+            anc.append(_chk(anchors[i][l], "anchors[%d][%d]" % (i, l), (a * h * w, 4)))
+    pre, post, fpn = int(pre_nms_top_n), int(post_nms_top_n), int(fpn_post_nms_top_n)
+    cap = fpn if L > 1 else min(post, pre)
+    ia = (ctypes.c_int * L)(*[s[0] for s in shapes])
+    ih = (ctypes.c_int * L)(*[s[1] for s in shapes])
+    iw = (ctypes.c_int * L)(*[s[2] for s in shapes])
+    nbytes = lib.smot_rpn_proposals_ws_bytes(N, L, _cast(ia), _cast(ih), _cast(iw), pre, post)
+    if nbytes < 0:
+        _check(-1, "rpn_proposals")
+    stream = _stream(dev)
+    if return_candidates:
+        work = torch.empty((nbytes // 4,), dtype=_F32, device=dev)
+    else:
+        work = _workspace(dev, nbytes // 4, stream.value)
+    boxes = torch.empty((N, cap, 4), dtype=_F32, device=dev)
+    scores = torch.empty((N, cap), dtype=_F32, device=dev)
+    count = torch.empty((N,), dtype=torch.int32, device=dev)
+    po = (ctypes.c_void_p * L)(*[t.data_ptr() for t in obj])
+    pr = (ctypes.c_void_p * L)(*[t.data_ptr() for t in reg])
+    pa = (ctypes.c_void_p * (N * L))(*[t.data_ptr() for t in anc])
+    wh = (ctypes.c_float * (2 * N))(*[float(v) for s in image_sizes for v in (s[0], s[1])])
+    wx, wy, ww, wh_ = [float(v) for v in weights]
+    with _Launch(*(obj + reg + anc)) as ln:
+        rc = lib.smot_rpn_proposals_fwd(_cast(po), _cast(pr), ft, _cast(ia), _cast(ih), _cast(iw), L, N, _cast(pa), _cast(wh),
+                                        pre, post, cap, float(nms_thresh), float(min_size), 1 if amodal else 0,
+                                        wx, wy, ww, wh_, float(math.log(1000.0 / 16) if xform_clip is None else xform_clip),
+                                        _ptr(work), _ptr(boxes), _ptr(scores), _ptr(count), ln.stream)
+    _check(rc, "rpn_proposals")
+    if not return_candidates:
+        return boxes, scores, count
+    NL = N * L
+    o1 = _al4(NL)
+    o2 = o1 + _al4(NL * pre)
+    o3 = o2 + _al4(NL * pre)
+    cand = {"count": work[:NL].view(torch.int32).view(N, L),
+            "index": work[o1:o1 + NL * pre].view(torch.int32).view(N, L, pre),
+            "logit": work[o2:o2 + NL * pre].view(N, L, pre),
+            "box": work[o3:o3 + NL * pre * 4].view(N, L, pre, 4)}
+    return boxes, scores, count, cand
 
 
 _rec_pinned = {}
