@@ -14,7 +14,7 @@ def wrap(obj, name, key=None):
     def g(*a, **k):
         t0 = time.perf_counter(); r = f(*a, **k); acc[key] = acc.get(key, 0.0) + time.perf_counter() - t0; return r
     setattr(obj, name, g)
-for n in ("emm_track", "box_refine", "track_solve", "emm_extract_cache", "track_frame", "_geometry", "_param_block"):
+for n in ("emm_track", "box_refine", "track_solve", "emm_extract_cache", "track_frame_addr", "_geometry", "_param_block"):
     wrap(ops, n)
 wrap(ops.HostRecordRing, "wait", "record_wait")
 wrap(ops.FrameArgs, "pack", "args_pack")

@@ -200,12 +200,7 @@ class EMM(nn.Module):
                                       "(track_core.py:45-47,56-67) is out of scope")
         if len(boxes) != 1:              # several images (video streams) in one set of launches
             return self._forward_batched(features, boxes, sr, template_features)
-        st = self.__dict__.get("_static")
-        if st is None:                   # submodule / attribute lookups go through nn.Module.__getattr__: once
-            fe, pr = self.feature_extractor.pooler_x, self.predictor
-            st = self.__dict__["_static"] = (pr.param_dict(), tuple(fe.scales), fe.sampling_ratio, pr.gn_groups,
-                                             pr.gn_eps)
-        params, scales, sampling_ratio, gn_groups, gn_eps = st
+        params, scales, sampling_ratio, gn_groups, gn_eps = self._static_args()
         # one library call: pooling -> xcorr -> predictor -> decode (+ the clamp of clip_to_image)
         one = len(sr) == 1
         b0 = boxes[0]
@@ -236,7 +231,7 @@ class EMM(nn.Module):
 
     def _static_args(self):
         st = self.__dict__.get("_static")
-        if st is None:
+        if st is None:                   # submodule / attribute lookups go through nn.Module.__getattr__: once
             fe, pr = self.feature_extractor.pooler_x, self.predictor
             st = self.__dict__["_static"] = (pr.param_dict(), tuple(fe.scales), fe.sampling_ratio, pr.gn_groups,
                                              pr.gn_eps)
@@ -310,12 +305,7 @@ class EMM(nn.Module):
         templates ``[N,C,rz,rz]`` -> (boxes ``[N,4]``, scores ``[N]``), clamped to the image unless amodal.  No
         BoxList in or out — the tracking loop's per-frame fast path (track_head.TrackingLoop).  ``sr_boxlist``: the
         BoxList ``sr`` came from (it may carry the extraction's order hint)."""
-        st = self.__dict__.get("_static")
-        if st is None:
-            fe, pr = self.feature_extractor.pooler_x, self.predictor
-            st = self.__dict__["_static"] = (pr.param_dict(), tuple(fe.scales), fe.sampling_ratio, pr.gn_groups,
-                                             pr.gn_eps)
-        params, scales, sampling_ratio, gn_groups, gn_eps = st
+        params, scales, sampling_ratio, gn_groups, gn_eps = self._static_args()
         hint = OrderHint.lookup(sr_boxlist, boxes, sr, scales) if sr_boxlist is not None else None
         out = ops.emm_track(features, boxes, sr, template_features, params, self.rx, self.rz, scales, sampling_ratio,
                             self.pad_pixels, sigma=self.sigma, use_centerness=self.use_centerness,

@@ -344,11 +344,7 @@ def roi_align_levels(features, rois, level_boxes, out_size, scales, sampling_rat
     """
     lib = load_library()
     L = len(scales)
-    feats, ft = _dev_feats(features, L)
-    for f in feats:
-        if f.dim() != 4 or f.shape[0] != 1:
-            raise RuntimeError("siammot_amd.roi_align_levels: one image per call, got feature shape %s"
-                               % (tuple(f.shape),))
+    feats, fp, hs, ws, sc, ft = _level_arrays(features, scales, what=".roi_align_levels")
     C = feats[0].shape[1]
     rois = _dev_f32(rois, "rois")
     level_boxes = rois if level_boxes is None else _dev_f32(level_boxes, "level_boxes")
@@ -357,14 +353,9 @@ def roi_align_levels(features, rois, level_boxes, out_size, scales, sampling_rat
         pad_cells = [0] * L
     out = torch.empty((R, C, out_size, out_size), dtype=torch.float32, device=rois.device)
     levels = torch.empty((R,), dtype=torch.int32, device=rois.device) if return_levels else None
-    fp = (ctypes.c_void_p * L)(*[f.data_ptr() for f in feats])
-    hs = (ctypes.c_int * L)(*[f.shape[2] for f in feats])
-    ws = (ctypes.c_int * L)(*[f.shape[3] for f in feats])
     pc = (ctypes.c_int * L)(*[int(p) for p in pad_cells[:L]])
-    sc = (ctypes.c_float * L)(*[float(s) for s in scales])
-    cast = lambda a: ctypes.cast(a, ctypes.c_void_p)
     with _Launch(rois, level_boxes, *feats) as ln:
-        rc = lib.smot_roi_align_levels_typed_fwd(cast(fp), ft, cast(hs), cast(ws), cast(pc), cast(sc), L, C,
+        rc = lib.smot_roi_align_levels_typed_fwd(_cast(fp), ft, _cast(hs), _cast(ws), _cast(pc), _cast(sc), L, C,
                                                  _ptr(rois), _ptr(level_boxes), R, out_size, out_size,
                                                  int(sampling_ratio), _ptr(out), _ptr(levels), ln.stream)
     _check(rc, "roi_align_levels")
@@ -532,12 +523,14 @@ def emm_decode(logits, sr, boxes, rx, rz, pad_pixels, sigma=0.4, use_centerness=
 _cast = lambda a: ctypes.cast(a, ctypes.c_void_p)
 
 
-def _level_arrays(features, scales, nhwc=True):
+def _level_arrays(features, scales, nhwc=True, what=""):
+    """The first ``len(scales)`` levels as the library takes them and their ctypes arrays -> (maps, pointers, heights, widths,
+    scales, ``feat_type``).  ``what``: the caller's name in the error text (".roi_align_levels")."""
     L = len(scales)
     feats, ft = _dev_feats(features, L, nhwc)      # (one dtype per call: raises otherwise)
     for f in feats:
         if f.dim() != 4 or f.shape[0] != 1:
-            raise RuntimeError("siammot_amd: one image per call, got feature shape %s" % (tuple(f.shape),))
+            raise RuntimeError("siammot_amd%s: one image per call, got feature shape %s" % (what, tuple(f.shape)))
     fp = (ctypes.c_void_p * L)(*[f.data_ptr() for f in feats])
     hs = (ctypes.c_int * L)(*[f.shape[2] for f in feats])
     ws = (ctypes.c_int * L)(*[f.shape[3] for f in feats])
@@ -601,21 +594,23 @@ def _maps_dtype(features, L):
     return dt
 
 
-def _geometry(features, scales, pad_pixels, device, nhwc=True):
+def _geometry(features, scales, pad_pixels, device, nhwc=True, batched=False):
     """Validate the per-level feature tensors (all on ``device``) and return the cached geometry with fresh
     pointers.  Channels-last levels (``_levels_layout``) are passed as they are and the geometry says so (``g.ft``);
-    ``nhwc=False``: the caller's entry has no channels-last form, such maps are copied like any strided view."""
+    ``nhwc=False``: the caller's entry has no channels-last form, such maps are copied like any strided view.
+    ``batched``: ``[B, C, H, W]`` maps with one B (``g.shapes[0][0]``) for every level instead of one image."""
     L = len(scales)
     shapes = tuple(tuple(features[l].shape) for l in range(L))
     dt = _maps_dtype(features, L)
     cl = _levels_layout(features, L) if nhwc else 0
-    key = (shapes, tuple(scales), pad_pixels, dt, cl)
+    key = ("batched", shapes, tuple(scales), pad_pixels, dt, cl) if batched else (shapes, tuple(scales), pad_pixels, dt, cl)
     g = _geom_cache.get(key)
     if g is None:
         for sh in shapes:
-            if len(sh) != 4 or sh[0] != 1 or sh[1] != shapes[0][1]:
-                raise RuntimeError("siammot_amd: one image per call and one channel count, got feature shapes %s"
-                                   % (shapes,))
+            if len(sh) != 4 or sh[0] != (shapes[0][0] if batched else 1) or sh[1] != shapes[0][1]:
+                raise RuntimeError(("siammot_amd: every level must be [B, C, H, W] with one B and one C, got feature shapes %s"
+                                    if batched else
+                                    "siammot_amd: one image per call and one channel count, got feature shapes %s") % (shapes,))
         if len(_geom_cache) > 32:
             _geom_cache.clear()
         g = _geom_cache[key] = _LevelGeometry(shapes, scales, pad_pixels, dt, cl)
@@ -722,28 +717,55 @@ def _chk(t, name, shape):
     return t if t.is_contiguous() else t.contiguous()
 
 
-def emm_track(features, boxes, sr, templates, params, rx, rz, scales, sampling_ratio, pad_pixels,
-              sigma=0.4, use_centerness=True, clip_wh=None, gn_groups=32, gn_eps=1e-5, return_index=False,
-              winograd=True, order_hint=None):
-    """The inference branch of ``EMM.forward`` in ONE library call.  Returns (bb ``[N,4]``, conf ``[N]``).
+def _head_call(lib, g, batched=False):
+    """The head's library call (``smot_emm_track*_fwd``) bound to the geometry ``g``: the ONE place that spells its argument
+    order and chooses its entry point.  The entry also selects the kernels (csrc/emm_fused.hip): the untyped entry runs the
+    single-image kernels, the typed entry the batched ones even for one image.
 
-    ``order_hint``: the ``[N, HINT_FLOATS]`` tensor ``emm_extract_cache(..., hint=True)`` returned TOGETHER WITH exactly
-    these ``boxes`` / ``sr`` (include/smot_emm.h: a scheduling side channel, VERIFIED by the kernel against these very
-    tensors: a hint of other boxes raises its status word — ``order_hint_status`` — and every returned row is NaN;
-    ``siammot_amd.emm.EMM`` also checks tensor identity and versions before it passes one), or None."""
+        one image, fp32 NCHW maps (``g.ft == 0``)     smot_emm_track_fwd
+        one image, any other ``g.ft``                 smot_emm_track_typed_fwd(..., 1, [0, N])
+        ``batched``, any ``g.ft`` (0 included)        smot_emm_track_typed_fwd(..., num_images, row_start)
+
+    The callable takes addresses (None = NULL) and returns the library's status."""
+    a_fp, ft, a_hs, a_ws, a_pc, a_sc, L, C = g.a_fp, g.ft, g.a_hs, g.a_ws, g.a_pc, g.a_sc, g.L, g.C
+    if not batched and ft == 0:
+        fn = lib.smot_emm_track_fwd
+
+        def call(boxes, sr, templates, N, rx, rz, sampling_ratio, a_pp, gn_groups, gn_eps, hann, pad_pixels, sigma,
+                 use_centerness, clip_w, clip_h, work, bb, conf, idx, hint, stream):
+            return fn(a_fp, a_hs, a_ws, a_pc, a_sc, L, C, boxes, sr, templates, N, rx, rz, sampling_ratio, a_pp, gn_groups,
+                      gn_eps, hann, UP_SCALE, pad_pixels, 1 - sigma, sigma, 1 if use_centerness else 0, clip_w, clip_h,
+                      work, bb, conf, idx, hint, stream)
+    else:
+        fn = lib.smot_emm_track_typed_fwd
+
+        def call(boxes, sr, templates, N, rx, rz, sampling_ratio, a_pp, gn_groups, gn_eps, hann, pad_pixels, sigma,
+                 use_centerness, clip_w, clip_h, work, bb, conf, idx, hint, stream, num_images=1, row_start=None):
+            return fn(a_fp, ft, a_hs, a_ws, a_pc, a_sc, L, C, boxes, sr, templates, N, rx, rz, sampling_ratio, a_pp, gn_groups,
+                      gn_eps, hann, UP_SCALE, pad_pixels, 1 - sigma, sigma, 1 if use_centerness else 0, clip_w, clip_h,
+                      work, bb, conf, idx, hint, stream, num_images,
+                      row_start if row_start is not None else _one_image_rows(N))
+    return call
+
+
+def _emm_track(batched, features, boxes, sr, templates, rows_per_image, params, rx, rz, scales, sampling_ratio, pad_pixels,
+               sigma, use_centerness, clip_wh, gn_groups, gn_eps, return_index, winograd, order_hint):
+    """The one body of ``emm_track`` and ``emm_track_batched``."""
+    what = "emm_track_batched" if batched else "emm_track"
     lib = _lib or load_library()
     if not (isinstance(boxes, torch.Tensor) and boxes.is_cuda):
         _dev_f32(boxes, "boxes")                 # raises: no CPU path
     dev = boxes.device
-    g = _geometry(features, scales, pad_pixels, dev, nhwc=_head_reads_channels_last(rx, rz))
+    g = _geometry(features, scales, pad_pixels, dev, nhwc=_head_reads_channels_last(rx, rz), batched=batched)
     N, C = boxes.shape[0], g.C
+    rows = (g.shapes[0][0], _row_starts(rows_per_image, g.shapes[0][0], N)) if batched else ()
     boxes = _chk(boxes, "boxes", (N, 4))
     sr = _chk(sr, "sr", (N, 4))
     templates = _chk(templates, "template_features", (N, C, rz, rz))
     blk = _param_block(params)
     _same_device(dev, ("sr", sr), ("template_features", templates), ("predictor weights", blk.tensors[0]))
     if blk.C != C:
-        raise RuntimeError("siammot_amd.emm_track: predictor has %d channels, features have %d" % (blk.C, C))
+        raise RuntimeError("siammot_amd.%s: predictor has %d channels, features have %d" % (what, blk.C, C))
     ho = rx - rz + 1
     a_pp = blk.a_pp
     if not (winograd and ho in (16, 29)) and blk.packed is not None:
@@ -754,34 +776,41 @@ def emm_track(features, boxes, sr, templates, params, rx, rz, scales, sampling_r
     bb = torch.empty((N, 4), dtype=_F32, device=dev)
     conf = torch.empty((N,), dtype=_F32, device=dev)
     idx = torch.empty((N,), dtype=torch.int64, device=dev) if return_index else None
-    if order_hint is None and rx == 30 and rz == 15 and 2 <= N <= 256:
+    if not batched and order_hint is None and rx == 30 and rz == 15 and 2 <= N <= 256:
         FALLBACKS["unhinted_head"] += 1
     if order_hint is not None and (tuple(order_hint.shape) != (N, HINT_FLOATS) or order_hint.device != dev
                                    or order_hint.dtype is not _F32 or not order_hint.is_contiguous()):
-        raise RuntimeError("siammot_amd.emm_track: order_hint must be the contiguous fp32 [%d, %d] tensor of the "
-                           "extraction that made these boxes" % (N, HINT_FLOATS))
+        raise RuntimeError("siammot_amd.%s: order_hint must be the contiguous fp32 [%d, %d] tensor of the "
+                           "extraction that made these boxes" % (what, N, HINT_FLOATS))
     cur = torch.cuda.current_device()           # kernels launch on the CURRENT device: make it the tensors' device
     if cur != dev.index:
         torch.cuda.set_device(dev.index)
     try:
-        tail = (boxes.data_ptr(), sr.data_ptr(), templates.data_ptr(), N, rx, rz, sampling_ratio,
-                a_pp, gn_groups, gn_eps, hann_window(ho * UP_SCALE, dev).data_ptr(),
-                UP_SCALE, pad_pixels, 1 - sigma, sigma, 1 if use_centerness else 0,
-                float(clip_wh[0]) if clip_wh is not None else 0.0,
-                float(clip_wh[1]) if clip_wh is not None else 0.0,
-                work.data_ptr(), bb.data_ptr(), conf.data_ptr(),
-                idx.data_ptr() if idx is not None else None,
-                order_hint.data_ptr() if order_hint is not None else None, stream)
-        if g.ft == 0:
-            rc = lib.smot_emm_track_fwd(g.a_fp, g.a_hs, g.a_ws, g.a_pc, g.a_sc, g.L, C, *tail)
-        else:                                     # fp16 / bf16 maps: read as they are
-            rc = lib.smot_emm_track_typed_fwd(g.a_fp, g.ft, g.a_hs, g.a_ws, g.a_pc, g.a_sc, g.L, C, *tail, 1, _one_image_rows(N))
+        rc = _head_call(lib, g, batched)(
+            boxes.data_ptr(), sr.data_ptr(), templates.data_ptr(), N, rx, rz, sampling_ratio, a_pp, gn_groups, gn_eps,
+            hann_window(ho * UP_SCALE, dev).data_ptr(), pad_pixels, sigma, use_centerness,
+            float(clip_wh[0]) if clip_wh is not None else 0.0, float(clip_wh[1]) if clip_wh is not None else 0.0,
+            work.data_ptr(), bb.data_ptr(), conf.data_ptr(), idx.data_ptr() if idx is not None else None,
+            order_hint.data_ptr() if order_hint is not None else None, stream, *rows)
     finally:
         if cur != dev.index:
             torch.cuda.set_device(cur)
     if rc:
-        _check(rc, "emm_track")
+        _check(rc, what)
     return (bb, conf, idx) if return_index else (bb, conf)
+
+
+def emm_track(features, boxes, sr, templates, params, rx, rz, scales, sampling_ratio, pad_pixels,
+              sigma=0.4, use_centerness=True, clip_wh=None, gn_groups=32, gn_eps=1e-5, return_index=False,
+              winograd=True, order_hint=None):
+    """The inference branch of ``EMM.forward`` in ONE library call.  Returns (bb ``[N,4]``, conf ``[N]``).
+
+    ``order_hint``: the ``[N, HINT_FLOATS]`` tensor ``emm_extract_cache(..., hint=True)`` returned TOGETHER WITH exactly
+    these ``boxes`` / ``sr`` (include/smot_emm.h: a scheduling side channel, VERIFIED by the kernel against these very
+    tensors: a hint of other boxes raises its status word — ``order_hint_status`` — and every returned row is NaN;
+    ``siammot_amd.emm.EMM`` also checks tensor identity and versions before it passes one), or None."""
+    return _emm_track(False, features, boxes, sr, templates, None, params, rx, rz, scales, sampling_ratio, pad_pixels,
+                      sigma, use_centerness, clip_wh, gn_groups, gn_eps, return_index, winograd, order_hint)
 
 
 HINT_FLOATS = 536                    # SMOT_HINT_FLOATS (include/smot_emm.h): entry header + both finished sample tables + by-roi record
@@ -807,6 +836,79 @@ def order_hint_floats(N, rz, sampling_ratio):
     return v
 
 
+def _extract_call(lib, g, batched=False, masked=False):
+    """The extraction's library call (``smot_emm_extract_cache*_fwd``) bound to the geometry ``g``: the ONE place that spells
+    its argument order and chooses its entry point (and with it the kernels, as for ``_head_call``).
+
+        one image, ``g.ft == 0``, no ``n_valid``      smot_emm_extract_cache_fwd
+        one image, ``g.ft == 0``, ``masked``          smot_emm_extract_cache_masked_fwd(..., n_valid, ...)
+        one image, any other ``g.ft``                 smot_emm_extract_cache_typed_fwd(..., 1, [0, N], n_valid or NULL)
+        ``batched``, any ``g.ft``                     smot_emm_extract_cache_typed_fwd(..., num_images, row_start, NULL)
+
+    The callable takes addresses (None = NULL) and returns the library's status."""
+    a_fp, ft, a_hs, a_ws, a_sc, L, C = g.a_fp, g.ft, g.a_hs, g.a_ws, g.a_sc, g.L, g.C
+    if batched or ft != 0:
+        fn = lib.smot_emm_extract_cache_typed_fwd
+
+        def call(boxes, N, rz, sampling_ratio, pad_pixels, search_expansion, min_search_wh, templates, sr, hint, stream,
+                 n_valid=None, num_images=1, row_start=None):
+            return fn(a_fp, ft, a_hs, a_ws, a_sc, L, C, boxes, N, rz, sampling_ratio, pad_pixels, search_expansion,
+                      min_search_wh, templates, sr, hint, stream, num_images,
+                      row_start if row_start is not None else _one_image_rows(N), n_valid)
+    elif masked:
+        fn = lib.smot_emm_extract_cache_masked_fwd
+
+        def call(boxes, N, rz, sampling_ratio, pad_pixels, search_expansion, min_search_wh, templates, sr, hint, stream,
+                 n_valid):
+            return fn(a_fp, a_hs, a_ws, a_sc, L, C, boxes, N, n_valid, rz, sampling_ratio, pad_pixels, search_expansion,
+                      min_search_wh, templates, sr, hint, stream)
+    else:
+        fn = lib.smot_emm_extract_cache_fwd
+
+        def call(boxes, N, rz, sampling_ratio, pad_pixels, search_expansion, min_search_wh, templates, sr, hint, stream,
+                 n_valid=None):
+            return fn(a_fp, a_hs, a_ws, a_sc, L, C, boxes, N, rz, sampling_ratio, pad_pixels, search_expansion,
+                      min_search_wh, templates, sr, hint, stream)
+    return call
+
+
+def _sr_and_hint(N, dev, with_hint):
+    """The extraction's search-region output and, ``with_hint``, its order hint, in one allocation: hint | sr."""
+    if not with_hint:
+        return torch.empty((N, 4), dtype=_F32, device=dev), None
+    both = torch.empty((N * (HINT_FLOATS + 4),), dtype=_F32, device=dev)
+    return both[N * HINT_FLOATS:].view(N, 4), both[:N * HINT_FLOATS].view(N, HINT_FLOATS)
+
+
+def _emm_extract_cache(batched, features, boxes, rows_per_image, rz, scales, sampling_ratio, pad_pixels, search_expansion,
+                       min_search_wh, n_valid, hint):
+    """The one body of ``emm_extract_cache`` and ``emm_extract_cache_batched``."""
+    lib = _lib or load_library()
+    if not (isinstance(boxes, torch.Tensor) and boxes.is_cuda):
+        _dev_f32(boxes, "boxes")                 # raises: no CPU path
+    dev = boxes.device
+    g = _geometry(features, scales, 0, dev, batched=True) if batched else _geometry(features, scales, 0, dev)
+    N = boxes.shape[0]
+    rows = (g.shapes[0][0], _row_starts(rows_per_image, g.shapes[0][0], N)) if batched else ()
+    boxes = _chk(boxes, "boxes", (N, 4))
+    templates = torch.empty((N, g.C, rz, rz), dtype=_F32, device=dev)
+    sr, oh = _sr_and_hint(N, dev, hint and boxes.data_ptr() % 16 == 0 and order_hint_floats(N, rz, sampling_ratio) > 0)
+    cur = torch.cuda.current_device()
+    if cur != dev.index:
+        torch.cuda.set_device(dev.index)
+    try:
+        rc = _extract_call(lib, g, batched, n_valid is not None)(
+            boxes.data_ptr(), N, rz, sampling_ratio, pad_pixels, search_expansion, min_search_wh, templates.data_ptr(),
+            sr.data_ptr(), oh.data_ptr() if oh is not None else None, _stream(dev),
+            n_valid.data_ptr() if n_valid is not None else None, *rows)
+    finally:
+        if cur != dev.index:
+            torch.cuda.set_device(cur)
+    if rc:
+        _check(rc, "emm_extract_cache_batched" if batched else "emm_extract_cache")
+    return (templates, sr, oh) if hint else (templates, sr)
+
+
 def emm_extract_cache(features, boxes, rz, scales, sampling_ratio, pad_pixels, search_expansion, min_search_wh,
                       n_valid=None, hint=False):
     """``EMM.extract_cache`` in one library call → (templates ``[N,C,rz,rz]``, sr ``[N,4]``); with ``hint=True`` →
@@ -816,79 +918,12 @@ def emm_extract_cache(features, boxes, rz, scales, sampling_ratio, pad_pixels, s
     ``n_valid``: a device int32 tensor (1 element) holding the number of REAL rows among ``boxes`` (a capacity): rows
     beyond it are skipped on the device and their outputs stay unwritten — the call can be enqueued before the
     host knows the count (ops.track_solve_launch)."""
-    lib = _lib or load_library()
-    if not (isinstance(boxes, torch.Tensor) and boxes.is_cuda):
-        _dev_f32(boxes, "boxes")                 # raises: no CPU path
-    dev = boxes.device
-    g = _geometry(features, scales, 0, dev)
-    N, C = boxes.shape[0], g.C
-    boxes = _chk(boxes, "boxes", (N, 4))
-    templates = torch.empty((N, C, rz, rz), dtype=_F32, device=dev)
-    oh = None
-    if hint and boxes.data_ptr() % 16 == 0 and order_hint_floats(N, rz, sampling_ratio) > 0:
-        both = torch.empty((N * (HINT_FLOATS + 4),), dtype=_F32, device=dev)       # one allocation: hint | sr
-        oh = both[:N * HINT_FLOATS].view(N, HINT_FLOATS)
-        sr = both[N * HINT_FLOATS:].view(N, 4)
-    else:
-        sr = torch.empty((N, 4), dtype=_F32, device=dev)
-    cur = torch.cuda.current_device()
-    if cur != dev.index:
-        torch.cuda.set_device(dev.index)
-    try:
-        if g.ft != 0:                             # fp16 / bf16 maps: read as they are (masked or not)
-            rc = lib.smot_emm_extract_cache_typed_fwd(g.a_fp, g.ft, g.a_hs, g.a_ws, g.a_sc, g.L, C, boxes.data_ptr(), N,
-                                                      rz, sampling_ratio, pad_pixels, search_expansion, min_search_wh,
-                                                      templates.data_ptr(), sr.data_ptr(),
-                                                      oh.data_ptr() if oh is not None else None, _stream(dev), 1,
-                                                      _one_image_rows(N), n_valid.data_ptr() if n_valid is not None else None)
-        elif n_valid is None:
-            rc = lib.smot_emm_extract_cache_fwd(g.a_fp, g.a_hs, g.a_ws, g.a_sc, g.L, C, boxes.data_ptr(), N,
-                                                rz, sampling_ratio, pad_pixels, search_expansion, min_search_wh,
-                                                templates.data_ptr(), sr.data_ptr(),
-                                                oh.data_ptr() if oh is not None else None, _stream(dev))
-        else:
-            rc = lib.smot_emm_extract_cache_masked_fwd(g.a_fp, g.a_hs, g.a_ws, g.a_sc, g.L, C, boxes.data_ptr(), N,
-                                                       n_valid.data_ptr(), rz, sampling_ratio, pad_pixels,
-                                                       search_expansion, min_search_wh, templates.data_ptr(),
-                                                       sr.data_ptr(), oh.data_ptr() if oh is not None else None,
-                                                       _stream(dev))
-    finally:
-        if cur != dev.index:
-            torch.cuda.set_device(cur)
-    if rc:
-        _check(rc, "emm_extract_cache")
-    return (templates, sr, oh) if hint else (templates, sr)
+    return _emm_extract_cache(False, features, boxes, None, rz, scales, sampling_ratio, pad_pixels, search_expansion,
+                              min_search_wh, n_valid, hint)
 
 
-# ---- several images per call (smot_emm_*_batched_fwd) ------------------------------------------------------------------
+# ---- several images per call (smot_emm_*_typed_fwd with num_images, row_start) ----------------------------------------
 MAX_IMAGES = 64                      # SMOT_MAX_IMAGES (include/smot_emm.h)
-
-
-def _geometry_batched(features, scales, pad_pixels, device, nhwc=True):
-    """``_geometry`` for ``[B, C, H, W]`` maps (one B, one C for every level) -> (geometry, B)."""
-    L = len(scales)
-    shapes = tuple(tuple(features[l].shape) for l in range(L))
-    dt = _maps_dtype(features, L)
-    cl = _levels_layout(features, L) if nhwc else 0
-    key = ("batched", shapes, tuple(scales), pad_pixels, dt, cl)
-    g = _geom_cache.get(key)
-    if g is None:
-        for sh in shapes:
-            if len(sh) != 4 or sh[0] != shapes[0][0] or sh[1] != shapes[0][1]:
-                raise RuntimeError("siammot_amd: every level must be [B, C, H, W] with one B and one C, got feature shapes %s"
-                                   % (shapes,))
-        if len(_geom_cache) > 32:
-            _geom_cache.clear()
-        g = _geom_cache[key] = _LevelGeometry(shapes, scales, pad_pixels, dt, cl)
-    fp = g.fp
-    for l in range(L):
-        f = features[l]
-        if not (f.is_cuda and (cl or f.is_contiguous())):
-            f = g.keep[l] = _dev_feat(f, "features[%d]" % l)
-        if f.device != device:
-            raise RuntimeError("siammot_amd: features[%d] lives on %s, the boxes on %s" % (l, f.device, device))
-        fp[l] = f.data_ptr()
-    return g, shapes[0][0]
 
 
 def _row_starts(rows_per_image, B, N):
@@ -911,92 +946,16 @@ def emm_track_batched(features, boxes, sr, templates, rows_per_image, params, rx
     are the ``rows_per_image[b]`` consecutive rows after those of images 0..b-1 (host ints).  Returns what ``emm_track``
     returns for all rows; the rows of image b are exactly what ``emm_track`` gives on ``features[l][b:b+1]`` with them.
     ``clip_wh``: the one image size of the batch.  ``order_hint``: as for ``emm_track``, from ``emm_extract_cache_batched``."""
-    lib = _lib or load_library()
-    if not (isinstance(boxes, torch.Tensor) and boxes.is_cuda):
-        _dev_f32(boxes, "boxes")
-    dev = boxes.device
-    g, B = _geometry_batched(features, scales, pad_pixels, dev, nhwc=_head_reads_channels_last(rx, rz))
-    N, C = boxes.shape[0], g.C
-    row_start = _row_starts(rows_per_image, B, N)
-    boxes = _chk(boxes, "boxes", (N, 4))
-    sr = _chk(sr, "sr", (N, 4))
-    templates = _chk(templates, "template_features", (N, C, rz, rz))
-    blk = _param_block(params)
-    _same_device(dev, ("sr", sr), ("template_features", templates), ("predictor weights", blk.tensors[0]))
-    if blk.C != C:
-        raise RuntimeError("siammot_amd.emm_track_batched: predictor has %d channels, features have %d" % (blk.C, C))
-    ho = rx - rz + 1
-    a_pp = blk.a_pp
-    if not (winograd and ho in (16, 29)) and blk.packed is not None:
-        pp = (ctypes.c_void_p * 13)(*([t.data_ptr() for t in blk.tensors] + [None]))
-        a_pp = ctypes.addressof(pp)
-    stream = _stream(dev)
-    work = _workspace(dev, lib.smot_emm_track_ws_floats(N, C, rx, rz), stream.value)
-    bb = torch.empty((N, 4), dtype=_F32, device=dev)
-    conf = torch.empty((N,), dtype=_F32, device=dev)
-    idx = torch.empty((N,), dtype=torch.int64, device=dev) if return_index else None
-    if order_hint is not None and (tuple(order_hint.shape) != (N, HINT_FLOATS) or order_hint.device != dev
-                                   or order_hint.dtype is not _F32 or not order_hint.is_contiguous()):
-        raise RuntimeError("siammot_amd.emm_track_batched: order_hint must be the contiguous fp32 [%d, %d] tensor of the "
-                           "extraction that made these boxes" % (N, HINT_FLOATS))
-    cur = torch.cuda.current_device()
-    if cur != dev.index:
-        torch.cuda.set_device(dev.index)
-    try:
-        rc = lib.smot_emm_track_typed_fwd(g.a_fp, g.ft, g.a_hs, g.a_ws, g.a_pc, g.a_sc, g.L, C,
-                                            boxes.data_ptr(), sr.data_ptr(), templates.data_ptr(), N, rx, rz,
-                                            sampling_ratio, a_pp, gn_groups, gn_eps,
-                                            hann_window(ho * UP_SCALE, dev).data_ptr(), UP_SCALE, pad_pixels, 1 - sigma,
-                                            sigma, 1 if use_centerness else 0,
-                                            float(clip_wh[0]) if clip_wh is not None else 0.0,
-                                            float(clip_wh[1]) if clip_wh is not None else 0.0,
-                                            work.data_ptr(), bb.data_ptr(), conf.data_ptr(),
-                                            idx.data_ptr() if idx is not None else None,
-                                            order_hint.data_ptr() if order_hint is not None else None, stream, B,
-                                            row_start)
-    finally:
-        if cur != dev.index:
-            torch.cuda.set_device(cur)
-    if rc:
-        _check(rc, "emm_track_batched")
-    return (bb, conf, idx) if return_index else (bb, conf)
+    return _emm_track(True, features, boxes, sr, templates, rows_per_image, params, rx, rz, scales, sampling_ratio,
+                      pad_pixels, sigma, use_centerness, clip_wh, gn_groups, gn_eps, return_index, winograd, order_hint)
 
 
 def emm_extract_cache_batched(features, boxes, rows_per_image, rz, scales, sampling_ratio, pad_pixels, search_expansion,
                               min_search_wh, hint=False):
     """``emm_extract_cache`` over B images in one library call (``features`` ``[B, C, H_l, W_l]``, rows grouped by image as
     in ``emm_track_batched``) -> (templates, sr) or, with ``hint=True``, (templates, sr, order hint or None)."""
-    lib = _lib or load_library()
-    if not (isinstance(boxes, torch.Tensor) and boxes.is_cuda):
-        _dev_f32(boxes, "boxes")
-    dev = boxes.device
-    g, B = _geometry_batched(features, scales, 0, dev)
-    N, C = boxes.shape[0], g.C
-    row_start = _row_starts(rows_per_image, B, N)
-    boxes = _chk(boxes, "boxes", (N, 4))
-    templates = torch.empty((N, C, rz, rz), dtype=_F32, device=dev)
-    oh = None
-    if hint and boxes.data_ptr() % 16 == 0 and order_hint_floats(N, rz, sampling_ratio) > 0:
-        both = torch.empty((N * (HINT_FLOATS + 4),), dtype=_F32, device=dev)       # one allocation: hint | sr
-        oh = both[:N * HINT_FLOATS].view(N, HINT_FLOATS)
-        sr = both[N * HINT_FLOATS:].view(N, 4)
-    else:
-        sr = torch.empty((N, 4), dtype=_F32, device=dev)
-    cur = torch.cuda.current_device()
-    if cur != dev.index:
-        torch.cuda.set_device(dev.index)
-    try:
-        rc = lib.smot_emm_extract_cache_typed_fwd(g.a_fp, g.ft, g.a_hs, g.a_ws, g.a_sc, g.L, C, boxes.data_ptr(), N, rz,
-                                                  sampling_ratio, pad_pixels, search_expansion, min_search_wh,
-                                                  templates.data_ptr(), sr.data_ptr(),
-                                                  oh.data_ptr() if oh is not None else None, _stream(dev), B, row_start,
-                                                  None)
-    finally:
-        if cur != dev.index:
-            torch.cuda.set_device(cur)
-    if rc:
-        _check(rc, "emm_extract_cache_batched")
-    return (templates, sr, oh) if hint else (templates, sr)
+    return _emm_extract_cache(True, features, boxes, rows_per_image, rz, scales, sampling_ratio, pad_pixels,
+                              search_expansion, min_search_wh, None, hint)
 
 
 try:
@@ -1015,7 +974,8 @@ class PairPlan(object):
     version), allocates its outputs and makes the ONE library call.  ``track`` / ``extract`` return None for anything they
     do not recognise (another geometry, a strided tensor, another device, a count the plan was not made for is re-planned):
     the caller then takes the general functions above, which raise or convert.  Results are the general functions', bit
-    for bit — same library entry points, same arguments.  There is still no CPU or eager path."""
+    for bit — same library entry points, same arguments: both go through ``_head_call`` / ``_extract_call``
+    (tests/test_binding_paths.py).  There is still no CPU or eager path."""
     __slots__ = ("dev", "dev_index", "g", "gz", "params", "blk", "rx", "rz", "ho", "scales", "sampling_ratio", "pad_pixels",
                  "hann_ptr", "ws", "ws_n", "C", "hint_n", "hint_ok", "lib", "f_track", "f_extract", "tu", "ft")
 
@@ -1034,11 +994,8 @@ class PairPlan(object):
         self.hann_ptr = hann_window(self.ho * UP_SCALE, dev).data_ptr()
         self.ws, self.ws_n = None, -1
         self.hint_n, self.hint_ok = -1, False
-        self.ft = self.g.ft                       # the maps' element type the plan was made for (SMOT_FEAT_*)
-        if self.ft == 0:
-            self.f_track, self.f_extract = lib.smot_emm_track_fwd, lib.smot_emm_extract_cache_fwd
-        else:
-            self.f_track, self.f_extract = lib.smot_emm_track_typed_fwd, lib.smot_emm_extract_cache_typed_fwd
+        self.ft = self.g.ft                       # the maps' element type and layout the plan was made for (SMOT_FEAT_*)
+        self.f_track, self.f_extract = _head_call(lib, self.g), _extract_call(lib, self.gz)     # (entries resolved once)
         self.tu = (float(tu.pad_pixels), float(tu.search_expansion), float(tu.min_search_wh))
 
     def stale(self, params, rx, rz, scales, sampling_ratio, pad_pixels, tu, features=None):
@@ -1094,17 +1051,9 @@ class PairPlan(object):
             hint_ptr = order_hint.data_ptr()
         elif self.rx == 30 and rz == 15 and 2 <= N <= 256:
             FALLBACKS["unhinted_head"] += 1
-        if self.ft == 0:
-            rc = self.f_track(g.a_fp, g.a_hs, g.a_ws, g.a_pc, g.a_sc, g.L, self.C, boxes.data_ptr(), sr.data_ptr(),
-                              templates.data_ptr(), N, self.rx, rz, self.sampling_ratio, blk.a_pp, gn_groups, gn_eps,
-                              self.hann_ptr, UP_SCALE, self.pad_pixels, 1 - sigma, sigma, 1 if use_centerness else 0, clip_w,
-                              clip_h, self.ws.data_ptr(), bb.data_ptr(), conf.data_ptr(), None, hint_ptr, stream)
-        else:
-            rc = self.f_track(g.a_fp, self.ft, g.a_hs, g.a_ws, g.a_pc, g.a_sc, g.L, self.C, boxes.data_ptr(), sr.data_ptr(),
-                              templates.data_ptr(), N, self.rx, rz, self.sampling_ratio, blk.a_pp, gn_groups, gn_eps,
-                              self.hann_ptr, UP_SCALE, self.pad_pixels, 1 - sigma, sigma, 1 if use_centerness else 0, clip_w,
-                              clip_h, self.ws.data_ptr(), bb.data_ptr(), conf.data_ptr(), None, hint_ptr, stream, 1,
-                              _one_image_rows(N))
+        rc = self.f_track(boxes.data_ptr(), sr.data_ptr(), templates.data_ptr(), N, self.rx, rz, self.sampling_ratio, blk.a_pp,
+                          gn_groups, gn_eps, self.hann_ptr, self.pad_pixels, sigma, use_centerness, clip_w, clip_h,
+                          self.ws.data_ptr(), bb.data_ptr(), conf.data_ptr(), None, hint_ptr, stream)
         if rc:
             _check(rc, "emm_track")
         return bb, conf
@@ -1119,26 +1068,12 @@ class PairPlan(object):
             return None
         N = boxes.shape[0]
         templates = torch.empty((N, self.C, rz, rz), dtype=_F32, device=dev)
-        oh = None
-        if hint:
-            if N != self.hint_n:
-                self.hint_n, self.hint_ok = N, order_hint_floats(N, rz, self.sampling_ratio) > 0
-            if self.hint_ok and boxes.data_ptr() % 16 == 0:
-                both = torch.empty((N * (HINT_FLOATS + 4),), dtype=_F32, device=dev)       # one allocation: hint | sr
-                oh = both[:N * HINT_FLOATS].view(N, HINT_FLOATS)
-                sr = both[N * HINT_FLOATS:].view(N, 4)
-        if oh is None:
-            sr = torch.empty((N, 4), dtype=_F32, device=dev)
+        if hint and N != self.hint_n:
+            self.hint_n, self.hint_ok = N, order_hint_floats(N, rz, self.sampling_ratio) > 0
+        sr, oh = _sr_and_hint(N, dev, hint and self.hint_ok and boxes.data_ptr() % 16 == 0)
         tu = self.tu
-        if self.ft == 0:
-            rc = self.f_extract(g.a_fp, g.a_hs, g.a_ws, g.a_sc, g.L, self.C, boxes.data_ptr(), N, rz, self.sampling_ratio,
-                                tu[0], tu[1], tu[2], templates.data_ptr(), sr.data_ptr(),
-                                oh.data_ptr() if oh is not None else None, _raw_stream(self.dev_index))
-        else:
-            rc = self.f_extract(g.a_fp, self.ft, g.a_hs, g.a_ws, g.a_sc, g.L, self.C, boxes.data_ptr(), N, rz,
-                                self.sampling_ratio, tu[0], tu[1], tu[2], templates.data_ptr(), sr.data_ptr(),
-                                oh.data_ptr() if oh is not None else None, _raw_stream(self.dev_index), 1,
-                                _one_image_rows(N), None)
+        rc = self.f_extract(boxes.data_ptr(), N, rz, self.sampling_ratio, tu[0], tu[1], tu[2], templates.data_ptr(),
+                            sr.data_ptr(), oh.data_ptr() if oh is not None else None, _raw_stream(self.dev_index))
         if rc:
             _check(rc, "emm_extract_cache")
         return templates, sr, oh
@@ -1252,15 +1187,15 @@ def sr_xcorr_fused(features, boxes, sr, templates, rx, rz, scales, sampling_rati
     return (resp, pooled) if return_pooled else resp
 
 
-def nms_keep_mask(boxes, scores, thresh):
-    """Greedy NMS as a device-resident boolean mask in the ORIGINAL box order (True = kept) — no host
-    synchronisation; ``nms`` below turns it into upstream's index list."""
+def _nms_sorted(boxes, scores, thresh):
+    """The part ``nms_keep_mask`` and ``nms`` share: sort by descending score (stable) and one suppression launch ->
+    (device, order, keep flags uint8 in sorted order); (device, None, None) for no boxes."""
     lib = load_library()
     boxes = _dev_f32(boxes, "boxes")
     scores = _dev_f32(scores, "scores")
     n = boxes.shape[0]
     if n == 0:
-        return torch.empty((0,), dtype=torch.bool, device=boxes.device)
+        return boxes.device, None, None
     order = torch.argsort(scores, descending=True, stable=True)
     sorted_boxes = boxes[order].contiguous()
     ws = torch.empty((max(lib.smot_nms_ws_bytes(n) // 8, 1),), dtype=torch.int64, device=boxes.device)
@@ -1268,7 +1203,16 @@ def nms_keep_mask(boxes, scores, thresh):
     with _Launch(boxes, scores) as ln:
         rc = lib.smot_nms_fwd(_ptr(sorted_boxes), n, float(thresh), _ptr(ws), _ptr(keep), ln.stream)
     _check(rc, "nms")
-    mask = torch.empty((n,), dtype=torch.bool, device=boxes.device)
+    return boxes.device, order, keep
+
+
+def nms_keep_mask(boxes, scores, thresh):
+    """Greedy NMS as a device-resident boolean mask in the ORIGINAL box order (True = kept) — no host
+    synchronisation; ``nms`` below turns it into upstream's index list."""
+    dev, order, keep = _nms_sorted(boxes, scores, thresh)
+    if order is None:
+        return torch.empty((0,), dtype=torch.bool, device=dev)
+    mask = torch.empty((order.shape[0],), dtype=torch.bool, device=dev)
     mask[order] = keep.bool()
     return mask
 
@@ -1277,19 +1221,9 @@ def nms(boxes, scores, thresh):
     """[UPSTREAM] ``_C.nms(dets, scores, thresh)`` semantics: indices of the kept boxes, ascending (original
     order), after greedy suppression in descending-score order with the +1 IoU convention.  One host sync
     (the number of kept boxes), as in the reference."""
-    lib = load_library()
-    boxes = _dev_f32(boxes, "boxes")
-    scores = _dev_f32(scores, "scores")
-    n = boxes.shape[0]
-    if n == 0:
-        return torch.empty((0,), dtype=torch.int64, device=boxes.device)
-    order = torch.argsort(scores, descending=True, stable=True)
-    sorted_boxes = boxes[order].contiguous()
-    ws = torch.empty((max(lib.smot_nms_ws_bytes(n) // 8, 1),), dtype=torch.int64, device=boxes.device)
-    keep = torch.empty((n,), dtype=torch.uint8, device=boxes.device)
-    with _Launch(boxes, scores) as ln:
-        rc = lib.smot_nms_fwd(_ptr(sorted_boxes), n, float(thresh), _ptr(ws), _ptr(keep), ln.stream)
-    _check(rc, "nms")
+    dev, order, keep = _nms_sorted(boxes, scores, thresh)
+    if order is None:
+        return torch.empty((0,), dtype=torch.int64, device=dev)
     return order[keep.bool()].sort()[0]
 
 
@@ -1416,7 +1350,7 @@ class HostRecordRing(object):
     def next(self):
         self.k ^= 1
         if self.in_flight[self.k]:
-            torch.cuda.current_stream(self.dev).synchronize()
+            self._drain()
             self.in_flight = [False, False]
         rec = self.bufs[self.k]
         self.views[self.k][3] = 0     # the kernel stores the frame index (>= 1) here last: the host's completion flag
@@ -1433,22 +1367,15 @@ class HostRecordRing(object):
         return self.event
 
     def wait(self, rec, event=True):
-        """The frame's one synchronisation: poll the completion word of ``rec``; if it does not show up, fall back to the
-        event recorded behind the launch (``record_event``) or — ``event=False``, nothing was recorded — to draining the
-        stream (a kernel fault would otherwise spin for ever)."""
+        """The frame's one synchronisation (``wait_host_record``): poll the completion word of ``rec``; if it does not show
+        up, fall back to the event recorded behind the launch (``record_event``) or — ``event=False``, nothing was
+        recorded — to draining the stream."""
         i = 0 if rec is self.bufs[0] else 1
-        flag = self.views[i]
-        for _ in range(20000):
-            if flag[3] != 0:
-                break
-        else:
-            if event:
-                self.event.synchronize()
-            else:
-                torch.cuda.current_stream(self.dev).synchronize()
-            if flag[3] == 0:
-                raise RuntimeError("siammot_amd.track_solve: the solver kernel finished without completing its record")
+        wait_host_record(self.views[i], self.event.synchronize if event else self._drain)
         self.in_flight[i] = False
+
+    def _drain(self):
+        torch.cuda.current_stream(self.dev).synchronize()
 
 
 def track_solve(det, trk, trk_score_bias, thresholds, nms_thresh, max_dormant_frames, pool_state, pool_capacity,
@@ -1525,42 +1452,15 @@ def track_solve_record(rec):
     return host.numpy().copy()
 
 
-_rec_events = {}
-
-
-def track_solve_record_begin(rec):
-    """Enqueue the record's copy to a pinned buffer and an event behind it; ``track_solve_record_wait`` blocks on that
-    event only.  Launches enqueued in between (the masked template extraction) run while the host is already woken
-    up and doing its bookkeeping — they are off the frame's critical path."""
-    dev, nrec = rec.device, rec.shape[0]
-    host = _rec_pinned.get((dev, nrec))
-    if host is None:
-        if len(_rec_pinned) > 64:
-            _rec_pinned.clear()
-        host = _rec_pinned[(dev, nrec)] = torch.empty((nrec,), dtype=torch.int32).pin_memory()
-    ev = _rec_events.get(dev)
-    if ev is None:
-        ev = _rec_events[dev] = torch.cuda.Event()
-    host.copy_(rec, non_blocking=True)
-    ev.record(torch.cuda.current_stream(dev))
-    return host, ev
-
-
-def track_solve_record_wait(handle):
-    host, ev = handle
-    ev.synchronize()
-    return host.numpy().copy()
-
-
-def wait_host_record(rec, event, spins=20000):
-    """Block until the solver kernel has completed a pinned-memory record: poll its completion word (stored last,
-    behind a system-scope fence), falling back to the event behind the launch if it does not show up (a kernel
-    fault would otherwise spin for ever).  Polling sees the record ~10 us earlier than an event wake-up."""
-    flag = rec.numpy()
+def wait_host_record(flag, fallback, spins=20000):
+    """Block until the solver kernel has completed a pinned-memory record (``flag``: its numpy view): poll its completion
+    word (stored last, behind a system-scope fence); if it does not show up within ``spins`` reads, call ``fallback`` — a
+    synchronisation behind the launch (a kernel fault would otherwise spin for ever) — and raise if even that leaves the
+    record incomplete.  Polling sees the record ~10 us earlier than an event wake-up."""
     for _ in range(spins):
         if flag[3] != 0:
             return
-    event.synchronize()
+    fallback()
     if flag[3] == 0:
         raise RuntimeError("siammot_amd.track_solve: the solver kernel finished without completing its record")
 
@@ -1606,7 +1506,7 @@ def box_refine(features, scales, pooled, sampling_ratio, boxes, labels, ids, tra
     labels)`` in the box head's output order."""
     lib = _lib or load_library()
     L = len(scales)
-    feats, ft = _dev_feats(features, L)
+    feats, fp, hs, wsz, sc, ft = _level_arrays(features, scales, what=".box_refine")
     boxes = _dev_f32(boxes, "boxes")
     track_conf = _dev_f32(track_conf, "track_conf")
     w6, b6, w7, b7, wc, bc, wr, br = [_dev_f32(t, "box head parameter") for t in layers]
@@ -1623,14 +1523,9 @@ def box_refine(features, scales, pooled, sampling_ratio, boxes, labels, ids, tra
     out_scores = torch.empty((N,), dtype=_F32, device=dev)
     out_ids = torch.empty((N,), dtype=torch.int64, device=dev)
     out_labels = torch.empty((N,), dtype=torch.int64, device=dev)
-    fp = (ctypes.c_void_p * L)(*[f.data_ptr() for f in feats])
-    hs = (ctypes.c_int * L)(*[f.shape[2] for f in feats])
-    wsz = (ctypes.c_int * L)(*[f.shape[3] for f in feats])
-    sc = (ctypes.c_float * L)(*[float(s_) for s_ in scales])
-    cast = lambda a: ctypes.cast(a, ctypes.c_void_p)
     cw, ch = (0.0, 0.0) if clip_wh is None else (float(clip_wh[0]), float(clip_wh[1]))
     with _Launch(boxes, track_conf, labels, ids, w6, *feats) as ln:
-        rc = lib.smot_box_refine_typed_fwd(cast(fp), ft, cast(hs), cast(wsz), cast(sc), L, C, int(pooled), int(sampling_ratio),
+        rc = lib.smot_box_refine_typed_fwd(_cast(fp), ft, _cast(hs), _cast(wsz), _cast(sc), L, C, int(pooled), int(sampling_ratio),
                                            _ptr(boxes), _ptr(labels), _ptr(ids), _ptr(track_conf), N,
                                            _ptr(w6), _ptr(b6), w6.shape[0], _ptr(w7), _ptr(b7), w7.shape[0],
                                            _ptr(wc), _ptr(bc), K, _ptr(wr), _ptr(br), KR,
@@ -1755,27 +1650,6 @@ class FrameArgs(object):
         self._III.pack_into(self._buf, self._CARRY_INT0, *carry)
         self._FFF.pack_into(self._buf, self._FLT0, *thresholds)
         return self._addr
-
-
-def track_frame(args, dev, addr=None, feat_type=0):
-    """``smot_track_frame_fwd``: head [+ box-head refinement] + solver + masked template extraction of ONE tracking frame
-    (the stages ``args.stages`` selects) enqueued by one call.  ``args``: a filled ``FrameArgs``, packed here unless the
-    caller packed / poked it already and passes the block's address.  ``feat_type``: the element type of the maps
-    ``args.feats`` names (``FEAT_TYPES``).  Launch only."""
-    lib = _lib or load_library()
-    cur = torch.cuda.current_device()
-    if cur != dev.index:
-        torch.cuda.set_device(dev.index)
-    try:
-        if feat_type == 0:
-            rc = lib.smot_track_frame_fwd(args.pack() if addr is None else addr, _stream(dev))
-        else:
-            rc = lib.smot_track_frame_typed_fwd(args.pack() if addr is None else addr, feat_type, _stream(dev))
-    finally:
-        if cur != dev.index:
-            torch.cuda.set_device(cur)
-    if rc:
-        _check(rc, "track_frame")
 
 
 def track_frame_addr(lib, addr, dev, stream, feat_type=0):

@@ -264,9 +264,12 @@ def test_result_wire_format_matches_the_reference_contract():
 
 
 def test_wait_host_record_polls_then_falls_back_to_the_event():
-    """The tracking loop's one synchronisation (ops.wait_host_record): returns as soon as the record's completion
-    word is non-zero, falls back to the event behind the launch when it is not, and raises when even the event's
-    completion leaves the record incomplete (a faulted kernel must not read as an empty frame)."""
+    """The tracking loop's one synchronisation, ``ops.HostRecordRing.wait`` (track_head.py calls nothing else), and the one
+    function behind it, ``ops.wait_host_record(record view, fallback, spins)``: returns as soon as the record's completion
+    word is non-zero, falls back to a synchronisation behind the launch when it is not — the ring's event, or with
+    ``event=False`` its stream drain — and raises when even that leaves the record incomplete (a faulted kernel must not
+    read as an empty frame).  The ring is built here without its pinned buffers and its event: ``wait`` reads ``bufs``,
+    ``views``, ``in_flight``, ``event`` and ``_drain`` only."""
     import torch
     from siammot_amd import ops
 
@@ -281,15 +284,39 @@ def test_wait_host_record_polls_then_falls_back_to_the_event():
     done = torch.zeros(16, dtype=torch.int32)
     done[3] = 7
     ev = Ev()
-    ops.wait_host_record(done, ev)
+    ops.wait_host_record(done.numpy(), ev.synchronize)
     assert ev.calls == 0                                   # polled: the event was never touched
     late = torch.zeros(16, dtype=torch.int32)
     ev = Ev(late, 3)
-    ops.wait_host_record(late, ev, spins=50)
+    ops.wait_host_record(late.numpy(), ev.synchronize, spins=50)
     assert ev.calls == 1 and int(late[3]) == 3
     never = torch.zeros(16, dtype=torch.int32)
     with pytest.raises(RuntimeError):
-        ops.wait_host_record(never, Ev(never, 0), spins=50)
+        ops.wait_host_record(never.numpy(), Ev(never, 0).synchronize, spins=50)
+
+    # the same three through the ring's own wait, in both of its modes
+    def ring(event, drain):
+        r = ops.HostRecordRing.__new__(ops.HostRecordRing)
+        r.bufs = [torch.zeros(16, dtype=torch.int32) for _ in range(2)]
+        r.views = [b.numpy() for b in r.bufs]
+        r.in_flight, r.event, r._drain = [True, True], event, drain.synchronize
+        return r
+    for use_event in (True, False):
+        ev, drain = Ev(), Ev()
+        used, other = (ev, drain) if use_event else (drain, ev)
+        r = ring(ev, drain)
+        r.views[1][3] = 7
+        r.wait(r.bufs[1], event=use_event)
+        assert ev.calls == 0 and drain.calls == 0 and r.in_flight == [True, False]
+        r = ring(ev, drain)
+        used.rec, used.value = r.bufs[0], 3
+        r.wait(r.bufs[0], event=use_event)
+        assert used.calls == 1 and other.calls == 0 and int(r.bufs[0][3]) == 3 and r.in_flight == [False, True]
+        r = ring(ev, drain)
+        used.rec, used.value = r.bufs[0], 0
+        with pytest.raises(RuntimeError):
+            r.wait(r.bufs[0], event=use_event)
+        assert r.in_flight == [True, True]                 # an incomplete record stays in flight: drained before it is reused
 
 
 def test_order_hint_is_bound_to_the_tensors_it_was_made_from():
