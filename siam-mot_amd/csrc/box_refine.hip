@@ -197,18 +197,7 @@ extern "C" int smot_box_refine_post_fwd(const float* head_out, int ld, int num_c
 // ---- the whole refinement of the propagated tracks behind ONE call ------------------------------------------------------
 // HIP 7x7 pooler -> fc6 + ReLU -> fc7 + ReLU -> cls_score | bbox_pred -> post-processing: eight launches enqueued by one
 // C-ABI crossing (the Python layer paid one ctypes call + one tensor allocation per stage).
-#include "roi_common.h"
-namespace smot {
-int launch_roi_pool_separable(const LevelParams& P, int C, const float* rois, const float* level_boxes, int R,
-                              int out_size, float* out, int32_t* levels_out, hipStream_t st);          // sr_xcorr.hip
-int launch_linear_rows(const float* x, int M, int K, const float* W, const float* bias, int N, int relu, float* ws,
-                       float* y, int ldy, hipStream_t st);                                              // linear_rows.hip
-int launch_linear_rows2(const float* x, int M, int K, const float* W, const float* bias, int N1, const float* W2,
-                        const float* bias2, int N2, int relu, float* ws, float* y, int ldy, hipStream_t st);
-void linear_rows_layout(int M, int K, int N, int* S, int* nblk, int* rows_pad);
-int launch_linear_rows_chain(const float* x, int M, int K, const float* WA, const float* bA, int NA, int reluA, float* ws_a,
-                             const float* WB, int N1, const float* WB2, int N2, float* ws_b, hipStream_t st, int* rc);
-}
+#include "pool_launch.h"
 extern "C" long long smot_linear_rows_ws_floats(int M, int K, int N);
 
 static inline size_t br_align4(size_t n) { return (n + 3) & ~(size_t)3; }
@@ -260,7 +249,7 @@ extern "C" int smot_box_refine_fwd(const float* const* feats, const int* heights
     const long long g7 = smot_linear_rows_ws_floats(N, dim6, dim7);
     if (g7 > g67) g67 = g7;
     float* gh = gw + br_align4((size_t)g67);                                                  // the head's K-slice sums
-    rc = launch_roi_pool_separable(P, C, boxes, boxes, N, pooled, x0, nullptr, st);          // Pooler: level of the roi itself
+    rc = launch_roi_pool_separable(P, C, boxes, boxes, N, pooled, x0, nullptr, st, nullptr); // Pooler: level of the roi itself
     if (rc) return rc;
     if ((rc = launch_linear_rows(x0, N, K0, fc6_w, fc6_b, dim6, 1, gw, h6, dim6, st))) return rc;
     // cls_score | bbox_pred side by side in one launch; their K-slice sums are added by the post-processing kernel while

@@ -4,52 +4,8 @@
 //
 //   smot_emm_track_fwd         == the inference branch of EMM.forward          (reference EMM/track_core.py:28-79)
 //   smot_emm_extract_cache_fwd == EMM.extract_cache                             (reference EMM/track_core.py:81-98)
-#include "smot_common.h"
-#include "roi_common.h"
-#include "logit_src.h"
+#include "pool_launch.h"
 #include "knobs.h"
-
-namespace smot {
-int predictor_impl(const float* resp, int N, int C, int Ho, const float* cls_tower_w, const float* cls_gn_w,
-                   const float* cls_gn_b, const float* reg_tower_w, const float* reg_gn_w, const float* reg_gn_b,
-                   const float* cls_w, const float* cls_b, const float* center_w, const float* center_b,
-                   const float* reg_w, const float* reg_b, int gn_groups, float gn_eps,
-                   const float* tower_packed, float* tower_ws, float* logits, smot_stream_t stream, int* tiles_out,
-                   unsigned* zero_words, bool* zeroed, const float* plane_max);
-int decode_impl(LogitSrc L, const float* sr, const float* boxes, const float* hann, int N, int Ho, int up, int rx,
-                int rz, float pad_pixels, float one_minus_sigma, float sigma, int use_centerness, float clip_w,
-                float clip_h, float* cand_ws, float* bb, float* conf, int64_t* idx, bool tickets_zeroed,
-                hipStream_t st, const int* poison);
-unsigned* decode_tickets(float* cand_ws, int N, int Ho);
-int launch_extract_cache(const float* const* feats, const int* heights, const int* widths, const float* scales,
-                         int num_levels, int C, const float* boxes, int N, int rz, float pad_pixels, float half_e,
-                         float two_e, float min_wh, float* templates, float* sr, const int* n_valid, float* order_hint,
-                         hipStream_t st, int hint_extra_rows);
-int sr_xcorr_fused_impl(const float* const* feats, const int* heights, const int* widths, const int* pad_cells,
-                        const float* scales, int num_levels, int C, const float* boxes, const float* sr,
-                        const float* templates, int N, float* resp, float* x_debug, const float* order_hint,
-                        hipStream_t st, const int** hint_status, float* plane_max);
-int sr_xcorr_gather_impl(const float* const* feats, const int* heights, const int* widths, const int* pad_cells,
-                         const float* scales, int num_levels, int C, const float* boxes, const float* sr,
-                         const float* templates, int N, int rx, int rz, int sampling_ratio, float* resp, hipStream_t st,
-                         float* plane_max);
-// batched forms (smot_emm_*_batched_fwd)
-int launch_extract_cache_batched(const float* const* feats, const int* heights, const int* widths, const float* scales,
-                                 int num_levels, int C, const float* boxes, int N, int rz, float pad_pixels, float half_e,
-                                 float two_e, float min_wh, float* templates, float* sr, float* order_hint, hipStream_t st,
-                                 const ImageRows& I);
-int sr_xcorr_fused_batched_impl(const float* const* feats, const int* heights, const int* widths, const int* pad_cells,
-                                const float* scales, int num_levels, int C, const float* boxes, const float* sr,
-                                const float* templates, int N, float* resp, const float* order_hint, hipStream_t st,
-                                const int** hint_status, float* plane_max, const ImageRows& I);
-int sr_xcorr_gather_batched_impl(const float* const* feats, const int* heights, const int* widths, const int* pad_cells,
-                                 const float* scales, int num_levels, int C, const float* boxes, const float* sr,
-                                 const float* templates, int N, float* resp, hipStream_t st, float* plane_max,
-                                 const ImageRows& I);
-int roi_align_levels_batched(const float* const* feats, const int* heights, const int* widths, const int* pad_cells,
-                             const float* scales, int num_levels, int C, const float* rois, const float* level_boxes, int R,
-                             int out_hw, int sampling_ratio, float* out, hipStream_t st, const ImageRows& I);
-}  // namespace smot
 
 static inline bool p12_form3(int N, int C, int ho) { return smot_emm_tower_form(N, C, ho) == 3; }
 
@@ -91,26 +47,20 @@ static int emm_track_impl(const float* const* feats, const int* heights, const i
         // pooling feeds the correlation inside one kernel: the search-region tensor never reaches HBM
         // (a hint the kernel honours is VERIFIED against `boxes` / `sr` by it; `poison` = the list's status word)
         float* pm = (C <= 7 * ho * ho && p12_form3(N, C, ho)) ? logits : nullptr;
-        rc = I ? sr_xcorr_fused_batched_impl(feats, heights, widths, pad_cells, scales, num_levels, C, boxes, sr, templates, N,
-                                             resp, order_hint, (hipStream_t)stream, &poison, pm, *I)
-               : sr_xcorr_fused_impl(feats, heights, widths, pad_cells, scales, num_levels, C, boxes, sr, templates, N, resp,
-                                     nullptr, order_hint, (hipStream_t)stream, &poison, pm);
+        rc = sr_xcorr_fused_impl(feats, heights, widths, pad_cells, scales, num_levels, C, boxes, sr, templates, N, resp, nullptr,
+                                 order_hint, (hipStream_t)stream, &poison, pm, I);
         if (rc) return rc;
         plane_max = pm;
     } else if (rx == 35 && rz == 7 && sampling_ratio == 2 && !no_fuse) {
         // the second yaml family's shape: gathers + correlation in one kernel (sr_xcorr_small.hip), same arithmetic
         float* pm = (C <= 7 * ho * ho && p12_form3(N, C, ho)) ? logits : nullptr;
-        rc = I ? sr_xcorr_gather_batched_impl(feats, heights, widths, pad_cells, scales, num_levels, C, boxes, sr, templates, N,
-                                              resp, (hipStream_t)stream, pm, *I)
-               : sr_xcorr_gather_impl(feats, heights, widths, pad_cells, scales, num_levels, C, boxes, sr, templates, N, rx, rz,
-                                      sampling_ratio, resp, (hipStream_t)stream, pm);
+        rc = sr_xcorr_gather_impl(feats, heights, widths, pad_cells, scales, num_levels, C, boxes, sr, templates, N, resp,
+                                  (hipStream_t)stream, pm, I);
         if (rc) return rc;
         plane_max = pm;
     } else {
-        rc = I ? roi_align_levels_batched(feats, heights, widths, pad_cells, scales, num_levels, C, sr, boxes, N, rx,
-                                          sampling_ratio, x, (hipStream_t)stream, *I)
-               : smot_roi_align_levels_fwd(feats, heights, widths, pad_cells, scales, num_levels, C, sr, boxes, N, rx, rx,
-                                           sampling_ratio, x, nullptr, stream);
+        rc = roi_align_levels_impl(feats, heights, widths, pad_cells, scales, num_levels, C, sr, boxes, N, rx, rx, sampling_ratio,
+                                   x, nullptr, (hipStream_t)stream, I, I ? "roi_align_batched" : "roi_align");
         if (rc) return rc;
         rc = smot_xcorr_dw_fwd(x, templates, resp, N, C, rx, rz, stream);
         if (rc) return rc;
@@ -173,29 +123,48 @@ extern "C" int smot_emm_track_batched_fwd(const float* const* feats, const int* 
                           use_centerness, clip_w, clip_h, ws, bb, conf, idx, order_hint, stream, &I);
 }
 
+// EMM.extract_cache behind all of its entry points: one image (I == nullptr) or the rows of a batch; n_valid != nullptr = the
+// masked form (N is a capacity, the count is on the device; hint_extra_rows: SrOut::hint_extra).  `who` names the entry point.
+static int emm_extract_cache_impl(const float* const* feats, const int* heights, const int* widths, const float* scales,
+                                  int num_levels, int C, const float* boxes, int N, int rz, int sampling_ratio,
+                                  float pad_pixels, float search_expansion, float min_search_wh, float* templates, float* sr,
+                                  float* order_hint, smot_stream_t stream, const smot::ImageRows* I, const int* n_valid,
+                                  int hint_extra_rows, const char* who) {
+    using namespace smot;
+    SMOT_REQUIRE(N >= 0 && num_levels >= 1 && num_levels <= SMOT_MAX_LEVELS, "%s: bad sizes", who);
+    if (N == 0) return SMOT_OK;
+    const bool separable = (rz == 15 || rz == 7) && sampling_ratio == 2;
+    if (separable && (n_valid != nullptr || !knobs().roi_generic)) {
+        // one launch: separable template pooling, with the search regions written by the same kernel
+        // (the reference forms e/2 and e*2 in Python double before they meet the fp32 tensors)
+        const float half_e = (float)((double)search_expansion / 2.0);
+        const float two_e = (float)((double)search_expansion * 2.0);
+        return launch_extract_cache(feats, heights, widths, scales, num_levels, C, boxes, N, rz, pad_pixels, half_e, two_e,
+                                    min_search_wh, templates, sr, n_valid, order_hint, (hipStream_t)stream, hint_extra_rows, I);
+    }
+    if (n_valid != nullptr) {
+        set_error("%s: the masked extraction needs Rz=15 or 7, sampling_ratio=2 (got %d, %d); use smot_emm_extract_cache_fwd "
+                  "with the count on the host", who, rz, sampling_ratio);
+        return SMOT_ERR_UNSUPPORTED;
+    }
+    const int rc = roi_align_levels_impl(feats, heights, widths, nullptr, scales, num_levels, C, boxes, boxes, N, rz, rz,
+                                         sampling_ratio, templates, nullptr, (hipStream_t)stream, I,
+                                         I ? "roi_align_batched" : "roi_align");
+    if (rc) return rc;
+    return smot_search_region_fwd(boxes, N, pad_pixels, search_expansion, min_search_wh, sr, stream);
+}
+
 extern "C" int smot_emm_extract_cache_fwd(const float* const* feats, const int* heights, const int* widths,
                                           const float* scales, int num_levels, int C, const float* boxes, int N,
                                           int rz, int sampling_ratio, float pad_pixels, float search_expansion,
                                           float min_search_wh, float* templates, float* sr, float* order_hint,
                                           smot_stream_t stream) {
-    using namespace smot;
-    SMOT_REQUIRE(N >= 0 && num_levels >= 1 && num_levels <= SMOT_MAX_LEVELS, "emm_extract_cache: bad sizes");
-    if (N == 0) return SMOT_OK;
-    if ((rz == 15 || rz == 7) && sampling_ratio == 2 && !knobs().roi_generic) {
-        // one launch: separable template pooling, with the search regions written by the same kernel
-        const float half_e = (float)((double)search_expansion / 2.0);
-        const float two_e = (float)((double)search_expansion * 2.0);
-        return launch_extract_cache(feats, heights, widths, scales, num_levels, C, boxes, N, rz, pad_pixels, half_e,
-                                    two_e, min_search_wh, templates, sr, nullptr, order_hint, (hipStream_t)stream, 0);
-    }
-    int zero_pad[SMOT_MAX_LEVELS] = {0};
-    int rc = smot_roi_align_levels_fwd(feats, heights, widths, zero_pad, scales, num_levels, C, boxes, boxes, N, rz, rz,
-                                       sampling_ratio, templates, nullptr, stream);
-    if (rc) return rc;
-    return smot_search_region_fwd(boxes, N, pad_pixels, search_expansion, min_search_wh, sr, stream);
+    return emm_extract_cache_impl(feats, heights, widths, scales, num_levels, C, boxes, N, rz, sampling_ratio, pad_pixels,
+                                  search_expansion, min_search_wh, templates, sr, order_hint, stream, nullptr, nullptr, 0,
+                                  "emm_extract_cache");
 }
 
-// EMM.extract_cache over a batch of images (include/smot_emm.h): same routing as smot_emm_extract_cache_fwd.
+// EMM.extract_cache over a batch of images (include/smot_emm.h): the row ranges are checked before anything is launched.
 extern "C" int smot_emm_extract_cache_batched_fwd(const float* const* feats, const int* heights, const int* widths,
                                                   const float* scales, int num_levels, int C, const float* boxes, int N,
                                                   int rz, int sampling_ratio, float pad_pixels, float search_expansion,
@@ -204,19 +173,11 @@ extern "C" int smot_emm_extract_cache_batched_fwd(const float* const* feats, con
     using namespace smot;
     SMOT_REQUIRE(N >= 0 && num_levels >= 1 && num_levels <= SMOT_MAX_LEVELS, "emm_extract_cache_batched: bad sizes");
     ImageRows I;
-    int rc = fill_image_rows(&I, num_images, row_start, N, "emm_extract_cache_batched");
+    const int rc = fill_image_rows(&I, num_images, row_start, N, "emm_extract_cache_batched");
     if (rc) return rc;
-    if (N == 0) return SMOT_OK;
-    if ((rz == 15 || rz == 7) && sampling_ratio == 2 && !knobs().roi_generic) {
-        const float half_e = (float)((double)search_expansion / 2.0);
-        const float two_e = (float)((double)search_expansion * 2.0);
-        return launch_extract_cache_batched(feats, heights, widths, scales, num_levels, C, boxes, N, rz, pad_pixels, half_e,
-                                            two_e, min_search_wh, templates, sr, order_hint, (hipStream_t)stream, I);
-    }
-    rc = roi_align_levels_batched(feats, heights, widths, nullptr, scales, num_levels, C, boxes, boxes, N, rz, sampling_ratio,
-                                  templates, (hipStream_t)stream, I);
-    if (rc) return rc;
-    return smot_search_region_fwd(boxes, N, pad_pixels, search_expansion, min_search_wh, sr, stream);
+    return emm_extract_cache_impl(feats, heights, widths, scales, num_levels, C, boxes, N, rz, sampling_ratio, pad_pixels,
+                                  search_expansion, min_search_wh, templates, sr, order_hint, stream, &I, nullptr, 0,
+                                  "emm_extract_cache_batched");
 }
 
 // EMM.extract_cache over a CAPACITY of boxes of which only the first *n_valid (a device-resident count, e.g. word 1
@@ -232,16 +193,9 @@ extern "C" int smot_emm_extract_cache_masked_fwd(const float* const* feats, cons
     using namespace smot;
     SMOT_REQUIRE(capacity >= 0 && num_levels >= 1 && num_levels <= SMOT_MAX_LEVELS, "emm_extract_cache_masked: bad sizes");
     SMOT_REQUIRE(n_valid != nullptr, "emm_extract_cache_masked: null count pointer");
-    if (capacity == 0) return SMOT_OK;
-    if (!((rz == 15 || rz == 7) && sampling_ratio == 2)) {
-        set_error("emm_extract_cache_masked: only Rz=15 or 7, sampling_ratio=2 (got %d, %d); use smot_emm_extract_cache_fwd "
-                  "with the count on the host", rz, sampling_ratio);
-        return SMOT_ERR_UNSUPPORTED;
-    }
-    const float half_e = (float)((double)search_expansion / 2.0);
-    const float two_e = (float)((double)search_expansion * 2.0);
-    return launch_extract_cache(feats, heights, widths, scales, num_levels, C, boxes, capacity, rz, pad_pixels, half_e,
-                                two_e, min_search_wh, templates, sr, n_valid, order_hint, (hipStream_t)stream, 0);
+    return emm_extract_cache_impl(feats, heights, widths, scales, num_levels, C, boxes, capacity, rz, sampling_ratio, pad_pixels,
+                                  search_expansion, min_search_wh, templates, sr, order_hint, stream, nullptr, n_valid, 0,
+                                  "emm_extract_cache_masked");
 }
 
 
@@ -308,17 +262,10 @@ extern "C" int smot_track_frame_fwd(const smot_frame_args* a, smot_stream_t stre
     // = smot_emm_extract_cache_masked_fwd, whose order hint also ranks the dormant rows the solver's launch has just put
     // behind the active ones (SMOT_STAGE_CARRY: their boxes stand in act_boxes behind the count): a memory with dormant
     // tracks — most frames of a MOT sequence — keeps its hint
-    SMOT_REQUIRE(a->n_det + a->n_trk >= 0 && a->num_levels >= 1 && a->num_levels <= SMOT_MAX_LEVELS, "track_frame: bad sizes");
-    if (a->n_det + a->n_trk == 0) return SMOT_OK;
-    if (!((a->rz == 15 || a->rz == 7) && a->sampling_ratio == 2)) {
-        set_error("track_frame: the masked extraction needs Rz=15 or 7, sampling_ratio=2 (got %d, %d)", a->rz, a->sampling_ratio);
-        return SMOT_ERR_UNSUPPORTED;
-    }
-    return launch_extract_cache(a->feats, a->heights, a->widths, a->scales, a->num_levels, a->C, a->act_boxes,
-                                a->n_det + a->n_trk, a->rz, a->pad_pixels, (float)((double)a->search_expansion / 2.0),
-                                (float)((double)a->search_expansion * 2.0), a->min_search_wh, a->next_templates, a->next_sr,
-                                a->pool_state + 4, a->next_order_hint, (hipStream_t)stream,
-                                (stages & SMOT_STAGE_CARRY) ? a->carry_rows : 0);
+    return emm_extract_cache_impl(a->feats, a->heights, a->widths, a->scales, a->num_levels, a->C, a->act_boxes,
+                                  a->n_det + a->n_trk, a->rz, a->sampling_ratio, a->pad_pixels, a->search_expansion,
+                                  a->min_search_wh, a->next_templates, a->next_sr, a->next_order_hint, stream, nullptr,
+                                  a->pool_state + 4, (stages & SMOT_STAGE_CARRY) ? a->carry_rows : 0, "track_frame");
 }
 
 

@@ -16,8 +16,9 @@
 // Lanes walk the flattened (ph,pw) bin index (tables of one bin in registers, channels inner), so
 // stores are fully coalesced.  Windows that exceed the LDS budget
 // (degenerate aspect ratios) fall back to direct gathers from the map, same arithmetic.
-#include "roi_common.h"
+#include "pool_launch.h"
 #include "knobs.h"
+#include <type_traits>
 
 namespace smot {
 
@@ -86,39 +87,44 @@ roi_align_levels_nhwc_kernel(LevelParams P, int C, const float* __restrict__ roi
 #include "roi_align_body.h"
 }
 
-template <typename FT, int G, bool B>
-static int launch_roi_align_nhwc_one(dim3 grid, size_t smem, hipStream_t st, const LevelParams& P, int C, const float* rois,
-                                     const float* level_boxes, int PH, int PW, float* out, int32_t* levels_out,
-                                     int num_images, const ImageRows& I) {
-    const int rco = ensure_lds_optin((const void*)roi_align_levels_nhwc_kernel<FT, G, B>, 96 * 1024, "roi_align");
-    if (rco) return rco;
-    hipLaunchKernelGGL((roi_align_levels_nhwc_kernel<FT, G, B>), grid, dim3(256), smem, st, P, C, rois, level_boxes, PH, PW,
-                       RA_CH, out, levels_out, num_images, I);
-    return SMOT_OK;
-}
-// the channels-last launch of a typed call in progress (channels_last()): I = the batch's row ranges, or nullptr
-static int launch_roi_align_nhwc(int sampling_ratio, dim3 grid, size_t smem, hipStream_t st, const LevelParams& P, int C,
-                                 const float* rois, const float* level_boxes, int PH, int PW, float* out,
-                                 int32_t* levels_out, int num_images, const ImageRows* I) {
-    ImageRows none;
-    none.num_images = 1;
-    for (int b = 0; b <= SMOT_MAX_IMAGES; ++b) none.row_start[b] = 0;
-#define SMOT_RA_NHWC(FT_, G_)                                                                                          \
-    (I != nullptr ? launch_roi_align_nhwc_one<FT_, G_, true>(grid, smem, st, P, C, rois, level_boxes, PH, PW, out,      \
-                                                             levels_out, num_images, *I)                              \
-                  : launch_roi_align_nhwc_one<FT_, G_, false>(grid, smem, st, P, C, rois, level_boxes, PH, PW, out,     \
-                                                              levels_out, num_images, none))
-#define SMOT_RA_NHWC_G(G_)                                                                                             \
-    (feat_type() == SMOT_FEAT_F32 ? SMOT_RA_NHWC(float, G_)                                                            \
-                                  : (feat_type() == SMOT_FEAT_F16 ? SMOT_RA_NHWC(f16_t, G_) : SMOT_RA_NHWC(bf16_t, G_)))
+// The generic kernel's ONE launch site: grid, LDS size and opt-in, and the wrapper by (channels_last(), feat_type(), I,
+// samples per bin).  rois = [R,4] with level_boxes (the levels form), or [R,5] with num_images > 0 (smot_roi_align_fwd).
+static int launch_roi_align(const LevelParams& P, int C, const float* rois, const float* level_boxes, int R, int PH, int PW,
+                            int sampling_ratio, float* out, int32_t* levels_out, int num_images, hipStream_t st,
+                            const ImageRows* I, const char* who) {
+    const dim3 grid(R, (C + RA_CH - 1) / RA_CH);
+    const size_t smem = (size_t)(PH + PW) * sampling_ratio * 16 + (size_t)RA_CH * RA_WIN_FLOATS * sizeof(float);
+    SMOT_REQUIRE(smem <= 96 * 1024, "%s: pooled size %dx%d needs too much LDS", who, PH, PW);
+    // (the batched wrappers and the channels-last ones take row ranges behind the single-image wrappers' arguments)
+    auto launch = [&](auto kernel, const auto&... rows) {
+        const int rco = ensure_lds_optin((const void*)kernel, 96 * 1024, "roi_align");
+        if (rco) return rco;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), smem, st, P, C, rois, level_boxes, PH, PW, RA_CH, out, levels_out,
+                           num_images, rows...);
+        return check_launch(who);
+    };
+    auto by_samples = [&](auto g) {
+        constexpr int G = decltype(g)::value;
+        return with_feat_type([&](auto ft) {
+            using FT = decltype(ft);
+            if (channels_last()) {
+                if (I) return launch(roi_align_levels_nhwc_kernel<FT, G, true>, *I);
+                return launch(roi_align_levels_nhwc_kernel<FT, G, false>, one_image_rows(R));      // (not read)
+            } else if constexpr (sizeof(FT) == 4) {
+                if (I) return launch(roi_align_levels_batched_kernel<G>, *I);
+                return launch(roi_align_levels_kernel<G>);
+            } else {
+                if (I) return launch(roi_align_levels_half_batched_kernel<FT, G>, *I);
+                return launch(roi_align_levels_half_kernel<FT, G>);
+            }
+        });
+    };
     switch (sampling_ratio) {
-        case 1: return SMOT_RA_NHWC_G(1);
-        case 2: return SMOT_RA_NHWC_G(2);
-        case 3: return SMOT_RA_NHWC_G(3);
-        default: return SMOT_RA_NHWC_G(4);
+        case 1: return by_samples(std::integral_constant<int, 1>());
+        case 2: return by_samples(std::integral_constant<int, 2>());
+        case 3: return by_samples(std::integral_constant<int, 3>());
+        default: return by_samples(std::integral_constant<int, 4>());
     }
-#undef SMOT_RA_NHWC_G
-#undef SMOT_RA_NHWC
 }
 
 __global__ void search_region_kernel(const float* __restrict__ boxes, int N, float pad, float half_e,
@@ -137,63 +143,28 @@ __global__ void search_region_kernel(const float* __restrict__ boxes, int N, flo
     sr[n * 4 + 3] = add_rn(y2, h_ext);
 }
 
-}  // namespace smot
-
-namespace smot {
-int launch_roi_pool_separable(const LevelParams& P, int C, const float* rois, const float* level_boxes, int R,
-                              int out_size, float* out, int32_t* levels_out, hipStream_t st);   // sr_xcorr.hip
-}
-
-namespace smot {
-int launch_roi_pool_separable_batched(const LevelParams& P, int C, const float* rois, const float* level_boxes, int R,
-                                      int out_size, float* out, hipStream_t st, const ImageRows& I);   // sr_xcorr.hip
-
-// smot_roi_align_levels_fwd over a batch (the generic branches of smot_emm_*_batched_fwd): same routing, same kernels'
-// batched forms; the rows of image b are [I.row_start[b], I.row_start[b+1]) of rois / level_boxes / out
-int roi_align_levels_batched(const float* const* feats, const int* heights, const int* widths, const int* pad_cells,
-                             const float* scales, int num_levels, int C, const float* rois, const float* level_boxes, int R,
-                             int out_hw, int sampling_ratio, float* out, hipStream_t st, const ImageRows& I) {
-    SMOT_REQUIRE(C > 0 && out_hw > 0 && R >= 0, "roi_align_batched: bad sizes C=%d out=%d R=%d", C, out_hw, R);
+// smot_roi_align_levels_fwd's host code for one image (I == nullptr) or the rows of a batch (the generic branches of
+// smot_emm_*_batched_fwd: the rows of image b are [I->row_start[b], I->row_start[b+1]) of rois / level_boxes / out).
+int roi_align_levels_impl(const float* const* feats, const int* heights, const int* widths, const int* pad_cells,
+                          const float* scales, int num_levels, int C, const float* rois, const float* level_boxes, int R,
+                          int out_h, int out_w, int sampling_ratio, float* out, int32_t* levels_out, hipStream_t st,
+                          const ImageRows* I, const char* who) {
+    SMOT_REQUIRE(C > 0 && out_h > 0 && out_w > 0 && R >= 0, "%s: bad sizes C=%d out=%dx%d R=%d", who, C, out_h, out_w, R);
     if (sampling_ratio <= 0 || sampling_ratio > 4) {
-        set_error("roi_align_batched: sampling_ratio=%d unsupported (need 1..4)", sampling_ratio);
+        set_error("%s: sampling_ratio=%d unsupported (need 1..4; adaptive grid not implemented)", who, sampling_ratio);
         return SMOT_ERR_UNSUPPORTED;
     }
     if (R == 0) return SMOT_OK;
+    SMOT_REQUIRE(rois && out, "%s: null rois/out", who);
+    SMOT_REQUIRE(num_levels == 1 || level_boxes, "%s: level_boxes required for num_levels>1", who);
     LevelParams P;
-    const int rc = fill_level_params(&P, feats, heights, widths, pad_cells, scales, num_levels, "roi_align_batched", C);
+    const int rc = fill_level_params(&P, feats, heights, widths, pad_cells, scales, num_levels, who, C);
     if (rc) return rc;
-    if ((out_hw == 7 || out_hw == 15 || out_hw == 30) && sampling_ratio == 2 && !knobs().roi_generic)
-        return launch_roi_pool_separable_batched(P, C, rois, num_levels > 1 ? level_boxes : rois, R, out_hw, out, st, I);
-    dim3 grid(R, (C + RA_CH - 1) / RA_CH);
-    const size_t smem = (size_t)(2 * out_hw) * sampling_ratio * 16 + (size_t)RA_CH * RA_WIN_FLOATS * sizeof(float);
-    SMOT_REQUIRE(smem <= 96 * 1024, "roi_align_batched: pooled size %d needs too much LDS", out_hw);
-#define LAUNCH(G)                                                                                                  \
-    if (feat_type() != SMOT_FEAT_F32) {                                                                            \
-        SMOT_HALF_TYPES(                                                                                           \
-            const int rco = ensure_lds_optin((const void*)roi_align_levels_half_batched_kernel<FT, G>, 96 * 1024,  \
-                                             "roi_align");                                                         \
-            if (rco) return rco;                                                                                   \
-            hipLaunchKernelGGL((roi_align_levels_half_batched_kernel<FT, G>), grid, dim3(256), smem, st, P, C,      \
-                               rois, level_boxes, out_hw, out_hw, RA_CH, out, (int32_t*)nullptr, 0, I))            \
-    } else {                                                                                                       \
-        const int rco = ensure_lds_optin((const void*)roi_align_levels_batched_kernel<G>, 96 * 1024, "roi_align");  \
-        if (rco) return rco;                                                                                       \
-        hipLaunchKernelGGL(roi_align_levels_batched_kernel<G>, grid, dim3(256), smem, st, P, C, rois, level_boxes,  \
-                           out_hw, out_hw, RA_CH, out, (int32_t*)nullptr, 0, I);                                  \
-    }
-    if (channels_last()) {
-        const int rcn = launch_roi_align_nhwc(sampling_ratio, grid, smem, st, P, C, rois, level_boxes, out_hw, out_hw, out,
-                                              nullptr, 0, &I);
-        return rcn ? rcn : check_launch("roi_align_batched");
-    }
-    switch (sampling_ratio) {
-        case 1: LAUNCH(1); break;
-        case 2: LAUNCH(2); break;
-        case 3: LAUNCH(3); break;
-        default: LAUNCH(4); break;
-    }
-#undef LAUNCH
-    return check_launch("roi_align_batched");
+    // the EMM pooler shapes (15x15 templates, 30x30 search regions) and the box head's 7x7, 2x2 samples, take the separable
+    // wave-per-two-planes kernel of sr_xcorr.hip; everything else the generic kernel above
+    if (out_h == out_w && (out_h == 7 || out_h == 15 || out_h == 30) && sampling_ratio == 2 && !knobs().roi_generic)
+        return launch_roi_pool_separable(P, C, rois, num_levels > 1 ? level_boxes : rois, R, out_h, out, levels_out, st, I);
+    return launch_roi_align(P, C, rois, level_boxes, R, out_h, out_w, sampling_ratio, out, levels_out, 0, st, I, who);
 }
 }  // namespace smot
 
@@ -203,59 +174,8 @@ extern "C" int smot_roi_align_levels_fwd(const float* const* feats, const int* h
                                          const float* rois, const float* level_boxes, int R,
                                          int out_h, int out_w, int sampling_ratio, float* out,
                                          int32_t* levels_out, smot_stream_t stream) {
-    using namespace smot;
-    SMOT_REQUIRE(C > 0 && out_h > 0 && out_w > 0 && R >= 0, "roi_align: bad sizes C=%d out=%dx%d R=%d", C,
-                 out_h, out_w, R);
-    if (sampling_ratio <= 0 || sampling_ratio > 4) {
-        set_error("roi_align: sampling_ratio=%d unsupported (need 1..4; adaptive grid not implemented)",
-                  sampling_ratio);
-        return SMOT_ERR_UNSUPPORTED;
-    }
-    if (R == 0) return SMOT_OK;
-    SMOT_REQUIRE(rois && out, "roi_align: null rois/out");
-    SMOT_REQUIRE(num_levels == 1 || level_boxes, "roi_align: level_boxes required for num_levels>1");
-    LevelParams P;
-    {
-        const int rc = fill_level_params(&P, feats, heights, widths, pad_cells, scales, num_levels, "roi_align", C);
-        if (rc) return rc;
-    }
-
-    // the EMM pooler shapes (15x15 templates, 30x30 search regions) and the box head's 7x7, 2x2 samples, take the separable
-    // wave-per-two-planes kernel of sr_xcorr.hip; everything else the generic kernel below
-    if (out_h == out_w && (out_h == 7 || out_h == 15 || out_h == 30) && sampling_ratio == 2 && !knobs().roi_generic)
-        return launch_roi_pool_separable(P, C, rois, num_levels > 1 ? level_boxes : rois, R, out_h, out, levels_out,
-                                         (hipStream_t)stream);
-    const int ch_per_block = RA_CH;
-    dim3 grid(R, (C + ch_per_block - 1) / ch_per_block);
-    const size_t smem = (size_t)(out_h + out_w) * sampling_ratio * 16 + (size_t)RA_CH * RA_WIN_FLOATS * sizeof(float);
-    hipStream_t st = (hipStream_t)stream;
-#define LAUNCH(G)                                                                                        \
-    if (feat_type() != SMOT_FEAT_F32) {                                                                  \
-        SMOT_HALF_TYPES(                                                                                 \
-            const int rco = ensure_lds_optin((const void*)roi_align_levels_half_kernel<FT, G>, 96 * 1024, "roi_align"); \
-            if (rco) return rco;                                                                         \
-            hipLaunchKernelGGL((roi_align_levels_half_kernel<FT, G>), grid, dim3(256), smem, st, P, C, rois, \
-                               level_boxes, out_h, out_w, ch_per_block, out, levels_out, 0))             \
-    } else {                                                                                             \
-        const int rco = ensure_lds_optin((const void*)roi_align_levels_kernel<G>, 96 * 1024, "roi_align");   \
-        if (rco) return rco;                                                                             \
-        hipLaunchKernelGGL(roi_align_levels_kernel<G>, grid, dim3(256), smem, st, P, C, rois, level_boxes, \
-                           out_h, out_w, ch_per_block, out, levels_out, 0);                              \
-    }
-    SMOT_REQUIRE(smem <= 96 * 1024, "roi_align: pooled size %dx%d needs too much LDS", out_h, out_w);
-    if (channels_last()) {
-        const int rcn = launch_roi_align_nhwc(sampling_ratio, grid, smem, st, P, C, rois, level_boxes, out_h, out_w, out,
-                                              levels_out, 0, nullptr);
-        return rcn ? rcn : check_launch("roi_align");
-    }
-    switch (sampling_ratio) {
-        case 1: LAUNCH(1); break;
-        case 2: LAUNCH(2); break;
-        case 3: LAUNCH(3); break;
-        default: LAUNCH(4); break;
-    }
-#undef LAUNCH
-    return check_launch("roi_align");
+    return smot::roi_align_levels_impl(feats, heights, widths, pad_cells, scales, num_levels, C, rois, level_boxes, R, out_h,
+                                       out_w, sampling_ratio, out, levels_out, (hipStream_t)stream, nullptr, "roi_align");
 }
 
 extern "C" int smot_roi_align_fwd(const float* input, int num_images, int C, int H, int W, int pad_cells,
@@ -274,40 +194,10 @@ extern "C" int smot_roi_align_fwd(const float* input, int num_images, int C, int
     if (R == 0) return SMOT_OK;
     SMOT_REQUIRE(input && rois5 && out, "roi_align: null pointer");
     LevelParams P;
-    {
-        const int rc = fill_level_params(&P, &input, &H, &W, &pad_cells, &spatial_scale, 1, "roi_align", C);
-        if (rc) return rc;
-    }
-    dim3 grid(R, (C + RA_CH - 1) / RA_CH);
-    const size_t smem = (size_t)(pooled_h + pooled_w) * sampling_ratio * 16 + (size_t)RA_CH * RA_WIN_FLOATS * sizeof(float);
-    SMOT_REQUIRE(smem <= 96 * 1024, "roi_align: pooled size %dx%d needs too much LDS", pooled_h, pooled_w);
-    hipStream_t st = (hipStream_t)stream;
-#define LAUNCH(G)                                                                                        \
-    if (feat_type() != SMOT_FEAT_F32) {                                                                  \
-        SMOT_HALF_TYPES(                                                                                 \
-            const int rco = ensure_lds_optin((const void*)roi_align_levels_half_kernel<FT, G>, 96 * 1024, "roi_align"); \
-            if (rco) return rco;                                                                         \
-            hipLaunchKernelGGL((roi_align_levels_half_kernel<FT, G>), grid, dim3(256), smem, st, P, C, rois5, \
-                               (const float*)nullptr, pooled_h, pooled_w, RA_CH, out, (int32_t*)nullptr, num_images)) \
-    } else {                                                                                             \
-        const int rco = ensure_lds_optin((const void*)roi_align_levels_kernel<G>, 96 * 1024, "roi_align");   \
-        if (rco) return rco;                                                                             \
-        hipLaunchKernelGGL(roi_align_levels_kernel<G>, grid, dim3(256), smem, st, P, C, rois5,           \
-                           (const float*)nullptr, pooled_h, pooled_w, RA_CH, out, (int32_t*)nullptr, num_images); \
-    }
-    if (channels_last()) {
-        const int rcn = launch_roi_align_nhwc(sampling_ratio, grid, smem, st, P, C, rois5, nullptr, pooled_h, pooled_w, out,
-                                              nullptr, num_images, nullptr);
-        return rcn ? rcn : check_launch("roi_align");
-    }
-    switch (sampling_ratio) {
-        case 1: LAUNCH(1); break;
-        case 2: LAUNCH(2); break;
-        case 3: LAUNCH(3); break;
-        default: LAUNCH(4); break;
-    }
-#undef LAUNCH
-    return check_launch("roi_align");
+    const int rc = fill_level_params(&P, &input, &H, &W, &pad_cells, &spatial_scale, 1, "roi_align", C);
+    if (rc) return rc;
+    return launch_roi_align(P, C, rois5, nullptr, R, pooled_h, pooled_w, sampling_ratio, out, nullptr, num_images,
+                            (hipStream_t)stream, nullptr, "roi_align");
 }
 
 extern "C" int smot_search_region_fwd(const float* boxes, int N, float pad_pixels, float search_expansion,

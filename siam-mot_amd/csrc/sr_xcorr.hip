@@ -20,13 +20,12 @@
 //      xcorr_patch2_compute: responses are bit-identical to smot_xcorr_dw_fwd on the pooled planes.
 // Windows wider than 64 columns (search regions far larger than their FPN level suggests: degenerate
 // aspect ratios) take a workgroup-uniform slow path: per-bin gathers, same arithmetic as roi_align.hip.
-#include "roi_common.h"
+#include "pool_launch.h"
 #include "xcorr_patch2.h"
 #include "xcorr_patch1.h"
 #include "xcorr_f16x2.h"
 #include "knobs.h"
 #include <type_traits>
-namespace smot { int launch_plane_absmax(const float* resp, int planes, int hw, float* pm, hipStream_t st); }   // tower_wino.hip
 
 namespace smot {
 
@@ -556,129 +555,94 @@ static inline bool order_hint_rois(int N, bool consumer) {
     if (knobs().fused_gen == 2 || knobs().no_hint >= (consumer ? 1 : 2)) return false;      // (constant false: product)
     return N >= 2 && N <= 256 && fused_order() == 1;
 }
-// fp16 / bf16 maps (a typed call in progress: feat_type()): the kernel the fp32 call takes, in its *_half_* form; I = the
-// batch's row ranges or nullptr
-template <int RX, bool XCORR, int MM>
-static void launch_fused_half(dim3 grid, hipStream_t st, const LevelParams& P, int C, const float* rois, const float* boxes,
-                              const float* z, float* resp, float* out, int32_t* levels_out, const SrOut& S,
-                              const ImageRows* I) {
-    SMOT_HALF_TYPES(
-        if (I != nullptr) {
-            SMOT_LAUNCH((sr_xcorr_fused9_half_batched_kernel<FT, RX, 15, 2, XCORR, MM>), grid, dim3(512), 0, st, P, C, rois,
-                        boxes, z, resp, out, levels_out, S, *I);
-        } else {
-            SMOT_LAUNCH((sr_xcorr_fused9_half_kernel<FT, RX, 15, 2, XCORR, MM>), grid, dim3(512), 0, st, P, C, rois, boxes, z,
-                        resp, out, levels_out, S);
-        })
-}
 static inline bool half_maps() { return feat_type() != SMOT_FEAT_F32; }
 
-// channels-last maps (a typed call with SMOT_FEAT_CHANNELS_LAST in progress: channels_last()): the form the NCHW call takes,
-// in its channels-last kernel, by the maps' element type; I = the batch's row ranges, or nullptr for one image of R rois
-template <int RX, bool XCORR, int MM>
-static void launch_fused_nhwc(dim3 grid, hipStream_t st, const LevelParams& P, int C, const float* rois, const float* boxes,
-                              const float* z, float* resp, float* out, int32_t* levels_out, const SrOut& S,
-                              const ImageRows* I) {
-    ImageRows one;
-    if (I == nullptr) {
-        one.num_images = 1;
-        one.row_start[0] = 0;
-        for (int b = 1; b <= SMOT_MAX_IMAGES; ++b) one.row_start[b] = (int)grid.x;
-        I = &one;
-    }
-    if (feat_type() == SMOT_FEAT_F32) {
-        SMOT_LAUNCH((sr_xcorr_fused9_nhwc_kernel<float, RX, 15, 2, XCORR, MM>), grid, dim3(512), 0, st, P, C, rois, boxes, z,
-                    resp, out, levels_out, S, *I);
-    } else {
-        SMOT_HALF_TYPES(SMOT_LAUNCH((sr_xcorr_fused9_nhwc_kernel<FT, RX, 15, 2, XCORR, MM>), grid, dim3(512), 0, st, P, C,
-                                    rois, boxes, z, resp, out, levels_out, S, *I))
-    }
-}
-// (the pool-only forms by pooled size: 7, 15 or 30)
-static void launch_pool_nhwc(int out_size, dim3 grid, hipStream_t st, const LevelParams& P, int C, const float* rois,
-                             const float* boxes, float* out, int32_t* levels_out, const SrOut& S, const ImageRows* I) {
-    if (out_size == 30) launch_fused_nhwc<30, false, 0>(grid, st, P, C, rois, boxes, nullptr, nullptr, out, levels_out, S, I);
-    else if (out_size == 7) launch_fused_nhwc<7, false, 0>(grid, st, P, C, rois, boxes, nullptr, nullptr, out, levels_out, S, I);
-    else launch_fused_nhwc<15, false, 0>(grid, st, P, C, rois, boxes, nullptr, nullptr, out, levels_out, S, I);
-}
-
+// The ONE launch site of the kernel: pooling alone (XCORR = false: RX = 7, 15 or 30 bins) or feeding the correlation
+// (XCORR = true: RX = 30, on the matrix pipe — MM = 1).  The wrapper by (channels_last(), feat_type(), I): I = the row ranges
+// of a batch, or nullptr for one image of grid.x rois (the channels-last kernels then take it as a batch of one).
 template <int RX, bool XCORR>
 static void launch_fused(dim3 grid, hipStream_t st, const LevelParams& P, int C, const float* rois, const float* boxes,
-                         const float* z, float* resp, float* out, int32_t* levels_out, const SrOut& S) {
+                         const float* z, float* resp, float* out, int32_t* levels_out, const SrOut& S, const ImageRows* I) {
+    constexpr int MM = (RX == 30 && XCORR) ? 1 : 0;
+    // (the batched wrappers and the channels-last ones take row ranges behind the single-image wrappers' arguments)
+    auto launch = [&](auto kernel, size_t smem, const auto&... rows) {
+        SMOT_LAUNCH(kernel, grid, dim3(512), smem, st, P, C, rois, boxes, z, resp, out, levels_out, S, rows...);
+    };
     if (channels_last()) {
-        launch_fused_nhwc<RX, XCORR, (RX == 30 && XCORR) ? 1 : 0>(grid, st, P, C, rois, boxes, z, resp, out, levels_out, S, nullptr);
+        with_feat_type([&](auto ft) {
+            launch(sr_xcorr_fused9_nhwc_kernel<decltype(ft), RX, 15, 2, XCORR, MM>, 0, I ? *I : one_image_rows((int)grid.x));
+        });
         return;
     }
     if (half_maps()) {
-        launch_fused_half<RX, XCORR, (RX == 30 && XCORR) ? 1 : 0>(grid, st, P, C, rois, boxes, z, resp, out, levels_out, S, nullptr);
+        SMOT_HALF_TYPES(if (I) launch(sr_xcorr_fused9_half_batched_kernel<FT, RX, 15, 2, XCORR, MM>, 0, *I);
+                        else launch(sr_xcorr_fused9_half_kernel<FT, RX, 15, 2, XCORR, MM>, 0))
+        return;
+    }
+    if (I) {
+        launch(sr_xcorr_fused9_batched_kernel<RX, 15, 2, XCORR, FX_CH, MM>, 0, *I);
         return;
     }
 #ifdef SMOT_DEBUG
-    if (knobs().fused_gen == 2 && S.n_valid == nullptr) {      // (generation 2 has no masked form)
-        hipLaunchKernelGGL((sr_xcorr_fused8_kernel<RX, 15, 2, XCORR>), grid, dim3(512), 0, st, P, C, rois, boxes, z, resp,
-                           out, levels_out, S);
-        return;
-    }
-#endif
-    if constexpr (RX == 30 && XCORR) {
-#ifdef SMOT_DEBUG
-        if (knobs().fused_abl == 8 || knobs().fused_abl == 9) {
-            // A/B (measurement library, SMOT_FUSED_ABL=8): the fp32 FMA correlation of rounds 2-5; 9: the same with 26 KB of
-            // unused dynamic LDS, i.e. at TWO workgroups per CU like the matrix form (what the third workgroup is worth)
-            SMOT_LAUNCH((sr_xcorr_fused9_kernel<RX, 15, 2, XCORR>), grid, dim3(512), knobs().fused_abl == 9 ? 26000 : 0, st, P, C, rois,
-                        boxes, z, resp, out, levels_out, S);
+    // A/B switches of the measurement library: fp32 NCHW maps of one image only
+    if constexpr (RX != 7) {
+        if (knobs().fused_gen == 2 && S.n_valid == nullptr) {      // (generation 2 has no masked form)
+            hipLaunchKernelGGL((sr_xcorr_fused8_kernel<RX, 15, 2, XCORR>), grid, dim3(512), 0, st, P, C, rois, boxes, z, resp,
+                               out, levels_out, S);
             return;
         }
-#endif
-#ifdef SMOT_DEBUG
+    }
+    if constexpr (MM == 1) {
+        if (knobs().fused_abl == 8 || knobs().fused_abl == 9) {
+            // SMOT_FUSED_ABL=8: the fp32 FMA correlation of rounds 2-5; 9: the same with 26 KB of unused dynamic LDS, i.e. at
+            // TWO workgroups per CU like the matrix form (what the third workgroup is worth)
+            launch(sr_xcorr_fused9_kernel<RX, 15, 2, XCORR>, knobs().fused_abl == 9 ? 26000 : 0);
+            return;
+        }
         if (knobs().fused_abl == 10) {
-            // A/B (SMOT_FUSED_ABL=10): the matrix form's LEAN layout (5,760 B per plane, three workgroups per CU).  Measured,
+            // SMOT_FUSED_ABL=10: the matrix form's LEAN layout (5,760 B per plane, three workgroups per CU).  Measured,
             // same session, hinted: 15.66 vs 15.35 us at 30 tracks, 38.8 vs 39.65 at 100 — the third workgroup buys back what
             // the extra reads and funnel shifts cost (correlation phase 7.5 k vs 5.8 k cycles per workgroup) and no more.
-            SMOT_LAUNCH((sr_xcorr_fused9_kernel<RX, 15, 2, XCORR, FX_CH, false, 2>), grid, dim3(512), 0, st, P, C, rois, boxes, z,
-                        resp, out, levels_out, S);
+            launch(sr_xcorr_fused9_kernel<RX, 15, 2, XCORR, FX_CH, false, 2>, 0);
             return;
         }
-#endif
-        SMOT_LAUNCH((sr_xcorr_fused9_kernel<RX, 15, 2, XCORR, FX_CH, false, 1>), grid, dim3(512), 0, st, P, C, rois, boxes, z,
-                    resp, out, levels_out, S);
-    } else {
-        SMOT_LAUNCH((sr_xcorr_fused9_kernel<RX, 15, 2, XCORR>), grid, dim3(512), 0, st, P, C, rois, boxes, z, resp, out,
-                    levels_out, S);
     }
+#endif
+    launch(sr_xcorr_fused9_kernel<RX, 15, 2, XCORR, FX_CH, false, MM>, 0);
+}
+// (the pool-only forms by pooled size: 7, 15 or 30)
+static void launch_pool(int out_size, dim3 grid, hipStream_t st, const LevelParams& P, int C, const float* rois,
+                        const float* boxes, float* out, int32_t* levels_out, const SrOut& S, const ImageRows* I) {
+    if (out_size == 30) launch_fused<30, false>(grid, st, P, C, rois, boxes, nullptr, nullptr, out, levels_out, S, I);
+    else if (out_size == 7) launch_fused<7, false>(grid, st, P, C, rois, boxes, nullptr, nullptr, out, levels_out, S, I);
+    else launch_fused<15, false>(grid, st, P, C, rois, boxes, nullptr, nullptr, out, levels_out, S, I);
 }
 
-// Separable stand-alone pooling for the two EMM pooler shapes (called by smot_roi_align_levels_fwd).
+// Separable stand-alone pooling for the EMM pooler shapes and the box head's 7x7 (box_head.py:46, roi_heads.py:60-84): what
+// roi_align_levels_impl routes here, and box_refine.hip's pooler.
 int launch_roi_pool_separable(const LevelParams& P, int C, const float* rois, const float* level_boxes, int R,
-                              int out_size, float* out, int32_t* levels_out, hipStream_t st) {
+                              int out_size, float* out, int32_t* levels_out, hipStream_t st, const ImageRows* I) {
     dim3 grid(R, (C + FX_CH - 1) / FX_CH);
     SrOut none = {nullptr, 0.f, 0.f, 0.f, 0.f, g_trace, 0, nullptr, fused_order(), nullptr, nullptr, 0};
-    if (channels_last()) {
-        launch_pool_nhwc(out_size, grid, st, P, C, rois, level_boxes, out, levels_out, none, nullptr);
-    } else if (out_size == 30) {
-        launch_fused<30, false>(grid, st, P, C, rois, level_boxes, nullptr, nullptr, out, levels_out, none);
-    } else if (out_size == 7 && half_maps()) {
-        launch_fused_half<7, false, 0>(grid, st, P, C, rois, level_boxes, nullptr, nullptr, out, levels_out, none, nullptr);
-    } else if (out_size == 7) {        // the box head's 7x7 pooler (box_head.py:46, roi_heads.py:60-84): same kernel
-        SMOT_LAUNCH((sr_xcorr_fused9_kernel<7, 15, 2, false>), grid, dim3(512), 0, st, P, C, rois, level_boxes,
-                    (const float*)nullptr, (float*)nullptr, out, levels_out, none);
-    } else {
-        launch_fused<15, false>(grid, st, P, C, rois, level_boxes, nullptr, nullptr, out, levels_out, none);
-    }
-    return check_launch("roi_pool_separable");
+    launch_pool(out_size, grid, st, P, C, rois, level_boxes, out, levels_out, none, I);
+    return check_launch(I ? "roi_pool_separable_batched" : "roi_pool_separable");
 }
 
+// EMM.extract_cache in one launch: the templates (rz = 15, or 7: the second yaml family's, DLA_34_FPN_EMM_AOT.yaml:52-63) and
+// the next frame's search regions, of one image or a batch.  n_valid: the masked form (one image: rows >= *n_valid return at
+// once).  The hint writer row is the same for a batch (it reads only boxes).
 int launch_extract_cache(const float* const* feats, const int* heights, const int* widths, const float* scales,
                          int num_levels, int C, const float* boxes, int N, int rz, float pad_pixels, float half_e,
                          float two_e, float min_wh, float* templates, float* sr, const int* n_valid, float* order_hint,
-                         hipStream_t st, int hint_extra_rows) {
+                         hipStream_t st, int hint_extra_rows, const ImageRows* I) {
+    const char* who = I ? "emm_extract_cache_batched" : "emm_extract_cache";
     LevelParams P;
-    const int rc = fill_level_params(&P, feats, heights, widths, nullptr, scales, num_levels, "emm_extract_cache", C);
+    const int rc = fill_level_params(&P, feats, heights, widths, nullptr, scales, num_levels, who, C);
     if (rc) return rc;
-    SMOT_REQUIRE(boxes && templates && sr, "emm_extract_cache: null pointer");
+    SMOT_REQUIRE(boxes && templates && sr, "%s: null pointer", who);
     if (!order_hint_rois(N, false) || rz != 15) order_hint = nullptr;     // (the hint's consumer is the 30/15 head)
     SMOT_REQUIRE(order_hint == nullptr || ((((uintptr_t)order_hint) & 31) == 0 && (((uintptr_t)boxes) & 15) == 0),
-                 "emm_extract_cache: the order hint must be 32-byte aligned (and the boxes 16-byte aligned)");
+                 "%s: the order hint must be 32-byte aligned (and the boxes 16-byte aligned)", who);
     // with a hint to write: one extra row of workgroups in front, of which the first ranks the rois (fx_write_hint)
     dim3 grid(N, (C + FX_CH - 1) / FX_CH + (order_hint != nullptr ? 1 : 0));
     SrOut S = {sr, pad_pixels, half_e, two_e, min_wh, g_trace, 0, n_valid, fused_order(), order_hint, nullptr,
@@ -686,101 +650,8 @@ int launch_extract_cache(const float* const* feats, const int* heights, const in
     // the next frame's search-region pooling runs on maps zero-padded by int(pad_pixels / stride) cells per level
     // (track_utils.py:94-96); the hint's finished tables are built against exactly that
     for (int l = 0; l < num_levels && l < SMOT_MAX_LEVELS; ++l) S.plan_pad[l] = (int)(pad_pixels * scales[l]);
-    if (channels_last()) {
-        launch_pool_nhwc(rz, grid, st, P, C, boxes, boxes, templates, nullptr, S, nullptr);
-    } else if (rz == 7 && half_maps()) {
-        launch_fused_half<7, false, 0>(grid, st, P, C, boxes, boxes, nullptr, nullptr, templates, nullptr, S, nullptr);
-    } else if (rz == 7) {          // the second yaml family's template (DLA_34_FPN_EMM_AOT.yaml:52-63): same kernel, 7x7 bins
-        SMOT_LAUNCH((sr_xcorr_fused9_kernel<7, 15, 2, false>), grid, dim3(512), 0, st, P, C, boxes, boxes, (const float*)nullptr,
-                    (float*)nullptr, templates, (int32_t*)nullptr, S);
-    } else {
-        launch_fused<15, false>(grid, st, P, C, boxes, boxes, nullptr, nullptr, templates, nullptr, S);
-    }
-    return check_launch("emm_extract_cache");
-}
-
-// ---- batched launches (smot_emm_*_batched_fwd): the product's kernels (generation 3, default order), no A/B switches --------
-// Separable stand-alone pooling of a batch (the generic branch of the batched head / extraction, smot_roi_align_levels_fwd's
-// routing for the EMM pooler shapes).
-int launch_roi_pool_separable_batched(const LevelParams& P, int C, const float* rois, const float* level_boxes, int R,
-                                      int out_size, float* out, hipStream_t st, const ImageRows& I) {
-    dim3 grid(R, (C + FX_CH - 1) / FX_CH);
-    SrOut none = {nullptr, 0.f, 0.f, 0.f, 0.f, g_trace, 0, nullptr, fused_order(), nullptr, nullptr, 0};
-    if (channels_last()) {
-        launch_pool_nhwc(out_size, grid, st, P, C, rois, level_boxes, out, nullptr, none, &I);
-    } else if (half_maps()) {
-        if (out_size == 30) launch_fused_half<30, false, 0>(grid, st, P, C, rois, level_boxes, nullptr, nullptr, out, nullptr, none, &I);
-        else if (out_size == 7) launch_fused_half<7, false, 0>(grid, st, P, C, rois, level_boxes, nullptr, nullptr, out, nullptr, none, &I);
-        else launch_fused_half<15, false, 0>(grid, st, P, C, rois, level_boxes, nullptr, nullptr, out, nullptr, none, &I);
-    } else if (out_size == 30) {
-        SMOT_LAUNCH((sr_xcorr_fused9_batched_kernel<30, 15, 2, false>), grid, dim3(512), 0, st, P, C, rois, level_boxes,
-                    (const float*)nullptr, (float*)nullptr, out, (int32_t*)nullptr, none, I);
-    } else if (out_size == 7) {
-        SMOT_LAUNCH((sr_xcorr_fused9_batched_kernel<7, 15, 2, false>), grid, dim3(512), 0, st, P, C, rois, level_boxes,
-                    (const float*)nullptr, (float*)nullptr, out, (int32_t*)nullptr, none, I);
-    } else {
-        SMOT_LAUNCH((sr_xcorr_fused9_batched_kernel<15, 15, 2, false>), grid, dim3(512), 0, st, P, C, rois, level_boxes,
-                    (const float*)nullptr, (float*)nullptr, out, (int32_t*)nullptr, none, I);
-    }
-    return check_launch("roi_pool_separable_batched");
-}
-
-// launch_extract_cache over a batch (no masked form): the hint writer row is the single-image one (it reads only boxes)
-int launch_extract_cache_batched(const float* const* feats, const int* heights, const int* widths, const float* scales,
-                                 int num_levels, int C, const float* boxes, int N, int rz, float pad_pixels, float half_e,
-                                 float two_e, float min_wh, float* templates, float* sr, float* order_hint, hipStream_t st,
-                                 const ImageRows& I) {
-    LevelParams P;
-    const int rc = fill_level_params(&P, feats, heights, widths, nullptr, scales, num_levels, "emm_extract_cache_batched", C);
-    if (rc) return rc;
-    SMOT_REQUIRE(boxes && templates && sr, "emm_extract_cache_batched: null pointer");
-    if (!order_hint_rois(N, false) || rz != 15) order_hint = nullptr;
-    SMOT_REQUIRE(order_hint == nullptr || ((((uintptr_t)order_hint) & 31) == 0 && (((uintptr_t)boxes) & 15) == 0),
-                 "emm_extract_cache_batched: the order hint must be 32-byte aligned (and the boxes 16-byte aligned)");
-    dim3 grid(N, (C + FX_CH - 1) / FX_CH + (order_hint != nullptr ? 1 : 0));
-    SrOut S = {sr, pad_pixels, half_e, two_e, min_wh, g_trace, 0, nullptr, fused_order(), order_hint, nullptr, 0};
-    for (int l = 0; l < num_levels && l < SMOT_MAX_LEVELS; ++l) S.plan_pad[l] = (int)(pad_pixels * scales[l]);
-    if (channels_last()) {
-        launch_pool_nhwc(rz, grid, st, P, C, boxes, boxes, templates, nullptr, S, &I);
-    } else if (half_maps()) {
-        if (rz == 7) launch_fused_half<7, false, 0>(grid, st, P, C, boxes, boxes, nullptr, nullptr, templates, nullptr, S, &I);
-        else launch_fused_half<15, false, 0>(grid, st, P, C, boxes, boxes, nullptr, nullptr, templates, nullptr, S, &I);
-    } else if (rz == 7) {
-        SMOT_LAUNCH((sr_xcorr_fused9_batched_kernel<7, 15, 2, false>), grid, dim3(512), 0, st, P, C, boxes, boxes,
-                    (const float*)nullptr, (float*)nullptr, templates, (int32_t*)nullptr, S, I);
-    } else {
-        SMOT_LAUNCH((sr_xcorr_fused9_batched_kernel<15, 15, 2, false>), grid, dim3(512), 0, st, P, C, boxes, boxes,
-                    (const float*)nullptr, (float*)nullptr, templates, (int32_t*)nullptr, S, I);
-    }
-    return check_launch("emm_extract_cache_batched");
-}
-
-// sr_xcorr_fused_impl over a batch: the matrix-pipe kernel of the product, with the hint honoured and verified as there
-int sr_xcorr_fused_batched_impl(const float* const* feats, const int* heights, const int* widths, const int* pad_cells,
-                                const float* scales, int num_levels, int C, const float* boxes, const float* sr,
-                                const float* templates, int N, float* resp, const float* order_hint, hipStream_t st,
-                                const int** hint_status, float* plane_max, const ImageRows& I) {
-    LevelParams P;
-    const int rc = fill_level_params(&P, feats, heights, widths, pad_cells, scales, num_levels, "sr_xcorr_fused_batched", C);
-    if (rc) return rc;
-    if (!order_hint_rois(N, true)) order_hint = nullptr;
-    if (hint_status != nullptr)
-        *hint_status = order_hint != nullptr ? reinterpret_cast<const int*>(order_hint) + HINT_STATUS : nullptr;
-    SMOT_REQUIRE(order_hint == nullptr || (((uintptr_t)order_hint) & 31) == 0,
-                 "sr_xcorr_fused_batched: the order hint must be 32-byte aligned");
-    dim3 grid(N, (C + FX_CH - 1) / FX_CH);
-    SrOut none = {nullptr, 0.f, 0.f, 0.f, 0.f, g_trace, 0, nullptr, fused_order(), nullptr, order_hint, 0};
-    none.plane_max = plane_max;
-    timer_mark(0, 0, st);
-    if (channels_last())
-        launch_fused_nhwc<30, true, 1>(grid, st, P, C, sr, boxes, templates, resp, nullptr, nullptr, none, &I);
-    else if (half_maps())
-        launch_fused_half<30, true, 1>(grid, st, P, C, sr, boxes, templates, resp, nullptr, nullptr, none, &I);
-    else
-        SMOT_LAUNCH((sr_xcorr_fused9_batched_kernel<30, 15, 2, true, FX_CH, 1>), grid, dim3(512), 0, st, P, C, sr, boxes,
-                    templates, resp, (float*)nullptr, (int32_t*)nullptr, none, I);
-    timer_mark(0, 1, st);
-    return check_launch("sr_xcorr_fused_batched");
+    launch_pool(rz, grid, st, P, C, boxes, boxes, templates, nullptr, S, I);
+    return check_launch(who);
 }
 
 #ifdef SMOT_DEBUG
@@ -791,24 +662,24 @@ int launch_fused10(const LevelParams& P, int C, const float* plans, const float*
 int fused10_plan_floats();
 #endif
 
-// Pooling + correlation with an optional order hint for its rois (smot_emm_track_fwd; the stand-alone operator
-// smot_sr_xcorr_fused_fwd passes none).
+// Pooling + correlation of one image or a batch, with an optional order hint for its rois (smot_emm_track_fwd and its batched
+// twin; the stand-alone operator smot_sr_xcorr_fused_fwd passes none), honoured and verified by the kernel.
 int sr_xcorr_fused_impl(const float* const* feats, const int* heights, const int* widths, const int* pad_cells,
                         const float* scales, int num_levels, int C, const float* boxes, const float* sr,
                         const float* templates, int N, float* resp, float* x_debug, const float* order_hint,
-                        hipStream_t st, const int** hint_status, float* plane_max) {
+                        hipStream_t st, const int** hint_status, float* plane_max, const ImageRows* I) {
+    const char* who = I ? "sr_xcorr_fused_batched" : "sr_xcorr_fused";
     LevelParams P;
-    const int rc = fill_level_params(&P, feats, heights, widths, pad_cells, scales, num_levels, "sr_xcorr_fused", C);
+    const int rc = fill_level_params(&P, feats, heights, widths, pad_cells, scales, num_levels, who, C);
     if (rc) return rc;
     if (!order_hint_rois(N, true)) order_hint = nullptr;
     // the status word of a hint this launch honours (and verifies: fx_verify_hint) — for the head's decode kernel
     if (hint_status != nullptr)
         *hint_status = order_hint != nullptr ? reinterpret_cast<const int*>(order_hint) + HINT_STATUS : nullptr;
-    SMOT_REQUIRE(order_hint == nullptr || (((uintptr_t)order_hint) & 31) == 0,
-                 "sr_xcorr_fused: the order hint must be 32-byte aligned");
+    SMOT_REQUIRE(order_hint == nullptr || (((uintptr_t)order_hint) & 31) == 0, "%s: the order hint must be 32-byte aligned", who);
     dim3 grid(N, (C + FX_CH - 1) / FX_CH);
 #ifdef SMOT_DEBUG
-    if (knobs().fused_gen == 10 && !channels_last()) {             // stage 1 (measurement library): generation 4 with a stand-alone plan launch
+    if (I == nullptr && knobs().fused_gen == 10 && !channels_last()) {   // stage 1 (measurement library): generation 4 with a stand-alone plan launch
         static float* plans = nullptr;
         if (plans == nullptr && hipMalloc(&plans, (size_t)4096 * fused10_plan_floats() * 4) != hipSuccess) return SMOT_ERR_BAD_ARG;
         SMOT_REQUIRE(N <= 4096, "fused10 debug: at most 4096 rois");
@@ -822,12 +693,13 @@ int sr_xcorr_fused_impl(const float* const* feats, const int* heights, const int
     }
 #endif
     timer_mark(0, 0, st);
-    SrOut none = {nullptr, 0.f, 0.f, 0.f, 0.f, g_trace, knobs().fused_abl, nullptr, fused_order(), nullptr, order_hint, 0};
+    // (the timing ablations of the measurement library: one image only)
+    SrOut none = {nullptr, 0.f, 0.f, 0.f, 0.f, g_trace, I ? 0 : knobs().fused_abl, nullptr, fused_order(), nullptr, order_hint, 0};
     none.plane_max = plane_max;
 #ifdef SMOT_DEBUG
-    if (plane_max != nullptr && (knobs().fused_gen == 2 || knobs().fused_abl == 5)) {      // kernels that do not write them
+    if (I == nullptr && plane_max != nullptr && (knobs().fused_gen == 2 || knobs().fused_abl == 5)) {      // kernels that do not write them
         none.plane_max = nullptr;
-        launch_fused<30, true>(grid, st, P, C, sr, boxes, templates, resp, x_debug, nullptr, none);
+        launch_fused<30, true>(grid, st, P, C, sr, boxes, templates, resp, x_debug, nullptr, none, nullptr);
         timer_mark(0, 1, st);
         const int rcl = check_launch("sr_xcorr_fused");
         return rcl ? rcl : launch_plane_absmax(resp, N * C, 256, plane_max, st);
@@ -835,7 +707,7 @@ int sr_xcorr_fused_impl(const float* const* feats, const int* heights, const int
     // A/B (measurement library, SMOT_FUSED_ABL=4): four channels per workgroup, twice the workgroups (960 of four waves at
     // 30 tracks: finer balance, twice the table builds).  Bit-identical; 17.7 vs 17.7 us at 30 tracks, 39.0 vs 39.7 at 100
     // (measure/fused_ab.py): not worth a second configuration.
-    if (knobs().fused_abl == 5) {       // A/B: the correlation on plane pairs with 4x2 patches (half the LDS read volume)
+    if (I == nullptr && knobs().fused_abl == 5) {       // A/B: the correlation on plane pairs with 4x2 patches (half the LDS read volume)
         hipEvent_t e0_, e1_;
         if (timer_take(&e0_, &e1_)) {
             hipExtLaunchKernelGGL((sr_xcorr_fused9_kernel<30, 15, 2, true, 8, true>), grid, dim3(512), 0, st, e0_, e1_, 0, P, C, sr, boxes,
@@ -847,16 +719,16 @@ int sr_xcorr_fused_impl(const float* const* feats, const int* heights, const int
         timer_mark(0, 1, st);
         return check_launch("sr_xcorr_fused");
     }
-    if (knobs().fused_abl == 4) {
+    if (I == nullptr && knobs().fused_abl == 4) {
         hipLaunchKernelGGL((sr_xcorr_fused9_kernel<30, 15, 2, true, 4>), dim3(N, (C + 3) / 4), dim3(256), 0, st, P, C, sr, boxes,
                            templates, resp, x_debug, (int32_t*)nullptr, none);
         timer_mark(0, 1, st);
         return check_launch("sr_xcorr_fused");
     }
 #endif
-    launch_fused<30, true>(grid, st, P, C, sr, boxes, templates, resp, x_debug, nullptr, none);
+    launch_fused<30, true>(grid, st, P, C, sr, boxes, templates, resp, x_debug, nullptr, none, I);
     timer_mark(0, 1, st);
-    return check_launch("sr_xcorr_fused");
+    return check_launch(who);
 }
 }  // namespace smot
 
@@ -868,7 +740,7 @@ extern "C" int smot_debug_sr_xcorr_fused_hint_fwd(const float* const* feats, con
                                                   const float* boxes, const float* sr, const float* templates, int N,
                                                   float* resp, const float* order_hint, smot_stream_t stream) {
     return smot::sr_xcorr_fused_impl(feats, heights, widths, pad_cells, scales, num_levels, C, boxes, sr, templates, N,
-                                     resp, nullptr, order_hint, (hipStream_t)stream, nullptr, nullptr);
+                                     resp, nullptr, order_hint, (hipStream_t)stream, nullptr, nullptr, nullptr);
 }
 #endif
 
@@ -905,7 +777,7 @@ extern "C" int smot_sr_xcorr_fused_fwd(const float* const* feats, const int* hei
     if (N == 0) return SMOT_OK;
     SMOT_REQUIRE(boxes && sr && templates && resp, "sr_xcorr_fused: null pointer");
     return sr_xcorr_fused_impl(feats, heights, widths, pad_cells, scales, num_levels, C, boxes, sr, templates, N, resp,
-                               x_debug, nullptr, (hipStream_t)stream, nullptr, nullptr);
+                               x_debug, nullptr, (hipStream_t)stream, nullptr, nullptr, nullptr);
 }
 
 // fp16 / bf16 maps (include/smot_emm.h, "fp16 / bf16 FEATURE MAPS")

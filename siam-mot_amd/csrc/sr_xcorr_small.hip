@@ -19,7 +19,7 @@
 //              rows padded to 40 floats (the correlation's row segments are read as float4);
 //     xcorr    thread = (response row, group of four response columns): the template's 49 taps in registers, per window row
 //              one 10-float segment feeds 28 FMAs; plane after plane.
-#include "roi_common.h"
+#include "pool_launch.h"
 #include "knobs.h"
 #include "tower_common.h"      // plane_max_wave
 
@@ -78,53 +78,31 @@ sr_xcorr_gather_half_batched_kernel(LevelParams P, int C, const float* __restric
 #include "sr_xcorr_gather_body.h"
 }
 
-// (35, 7, sampling ratio 2) only; returns SMOT_ERR_UNSUPPORTED for anything else (the caller runs the two-kernel form).
-int launch_sr_xcorr_gather(const LevelParams& P, int C, const float* sr, const float* boxes, const float* templates, int N,
-                           int rx, int rz, int sampling_ratio, float* resp, hipStream_t st, float* plane_max) {
-    if (!(rx == 35 && rz == 7 && sampling_ratio == 2)) return SMOT_ERR_UNSUPPORTED;
-    if (N == 0) return SMOT_OK;
-    dim3 grid(N, (C + SX_CH - 1) / SX_CH);
-    timer_mark(0, 0, st);
-    if (feat_type() != SMOT_FEAT_F32) {
-        SMOT_HALF_TYPES(SMOT_LAUNCH((sr_xcorr_gather_half_kernel<FT, 35, 7, 2>), grid, dim3(256), 0, st, P, C, sr, boxes,
-                                    templates, resp, plane_max))
-    } else {
-        SMOT_LAUNCH((sr_xcorr_gather_kernel<35, 7, 2>), grid, dim3(256), 0, st, P, C, sr, boxes, templates, resp, plane_max);
-    }
-    timer_mark(0, 1, st);
-    return check_launch("sr_xcorr_gather");
-}
-
+// The (35, 7, sampling ratio 2) head's pooling + correlation — the only shape the kernel has; its callers check it.  One image
+// (I == nullptr) or the rows of a batch: the wrapper by I and the maps' element type, everything else once.
 int sr_xcorr_gather_impl(const float* const* feats, const int* heights, const int* widths, const int* pad_cells,
                          const float* scales, int num_levels, int C, const float* boxes, const float* sr,
-                         const float* templates, int N, int rx, int rz, int sampling_ratio, float* resp, hipStream_t st,
-                         float* plane_max) {
+                         const float* templates, int N, float* resp, hipStream_t st, float* plane_max, const ImageRows* I) {
+    const char* who = I ? "sr_xcorr_gather_batched" : "sr_xcorr_gather";
     LevelParams P;
-    const int rc = fill_level_params(&P, feats, heights, widths, pad_cells, scales, num_levels, "sr_xcorr_gather");
-    if (rc) return rc;
-    return launch_sr_xcorr_gather(P, C, sr, boxes, templates, N, rx, rz, sampling_ratio, resp, st, plane_max);
-}
-
-// sr_xcorr_gather_impl over a batch (smot_emm_track_batched_fwd): the rows of image b are [I.row_start[b], I.row_start[b+1])
-int sr_xcorr_gather_batched_impl(const float* const* feats, const int* heights, const int* widths, const int* pad_cells,
-                                 const float* scales, int num_levels, int C, const float* boxes, const float* sr,
-                                 const float* templates, int N, float* resp, hipStream_t st, float* plane_max,
-                                 const ImageRows& I) {
-    LevelParams P;
-    const int rc = fill_level_params(&P, feats, heights, widths, pad_cells, scales, num_levels, "sr_xcorr_gather_batched");
+    const int rc = fill_level_params(&P, feats, heights, widths, pad_cells, scales, num_levels, who);
     if (rc) return rc;
     if (N == 0) return SMOT_OK;
-    dim3 grid(N, (C + SX_CH - 1) / SX_CH);
+    const dim3 grid(N, (C + SX_CH - 1) / SX_CH);
+    // (the batched wrappers take the row ranges behind the single-image wrappers' arguments)
+    auto launch = [&](auto kernel, auto... rows) {
+        SMOT_LAUNCH(kernel, grid, dim3(256), 0, st, P, C, sr, boxes, templates, resp, plane_max, rows...);
+    };
     timer_mark(0, 0, st);
-    if (feat_type() != SMOT_FEAT_F32) {
-        SMOT_HALF_TYPES(SMOT_LAUNCH((sr_xcorr_gather_half_batched_kernel<FT, 35, 7, 2>), grid, dim3(256), 0, st, P, C, sr,
-                                    boxes, templates, resp, plane_max, I))
+    if (feat_type() == SMOT_FEAT_F32) {
+        if (I) launch(sr_xcorr_gather_batched_kernel<35, 7, 2>, *I);
+        else launch(sr_xcorr_gather_kernel<35, 7, 2>);
     } else {
-        SMOT_LAUNCH((sr_xcorr_gather_batched_kernel<35, 7, 2>), grid, dim3(256), 0, st, P, C, sr, boxes, templates, resp,
-                    plane_max, I);
+        SMOT_HALF_TYPES(if (I) launch(sr_xcorr_gather_half_batched_kernel<FT, 35, 7, 2>, *I);
+                        else launch(sr_xcorr_gather_half_kernel<FT, 35, 7, 2>))
     }
     timer_mark(0, 1, st);
-    return check_launch("sr_xcorr_gather_batched");
+    return check_launch(who);
 }
 
 }  // namespace smot
@@ -143,8 +121,8 @@ extern "C" int smot_sr_xcorr_gather_fwd(const float* const* feats, const int* he
     }
     if (N == 0) return SMOT_OK;
     SMOT_REQUIRE(boxes && sr && templates && resp, "sr_xcorr_gather: null pointer");
-    return sr_xcorr_gather_impl(feats, heights, widths, pad_cells, scales, num_levels, C, boxes, sr, templates, N, rx, rz,
-                                sampling_ratio, resp, (hipStream_t)stream, nullptr);
+    return sr_xcorr_gather_impl(feats, heights, widths, pad_cells, scales, num_levels, C, boxes, sr, templates, N, resp,
+                                (hipStream_t)stream, nullptr, nullptr);
 }
 
 // fp16 / bf16 maps (include/smot_emm.h, "fp16 / bf16 FEATURE MAPS")

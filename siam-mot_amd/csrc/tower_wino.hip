@@ -990,7 +990,7 @@ static int tower_tiles_per_workgroup(int N, int C) {
     // everywhere (kernel durations by start / stop events at C = 128, measure/debug/tower_forms_by_tracks.py,
     // profiles/r06_tower_forms_by_tracks.jsonl: 1 track 17.3 vs 18.5 us for the one-tile fp32 form, 16 tracks 18.9 vs 20.1,
     // 30: 20.0 vs 29.5, 64: 36.7 vs 55.5, 100: 68.0 vs 92.9), and one form means that a track's logits no longer depend on how
-    // many other tracks the frame has (rounds 4-5: fp32 up to 16 tracks, three-part bf16 above).
+    // many other tracks the frame has (rounds 4-5: fp32 up to 16 tracks, the split form above).
     // SMOT_TOWER_OCT = 1 / 2 forces a form, SMOT_TOWER_BF3 = 0 the fp32 form of two tiles, in the measurement library.
     (void)N;
     (void)C;
@@ -999,77 +999,72 @@ static int tower_tiles_per_workgroup(int N, int C) {
     return oct;
 }
 
+// A form of the kernel with its workgroup size and dynamic LDS: picked once per launch, for the LDS opt-in and the launch.
+typedef void (*tower_wino_fn)(const float*, const float*, TowerParams, int, int, int, float, float*, unsigned*, long long*,
+                              const float*);
+struct TowerForm {
+    tower_wino_fn fn;
+    int threads;
+    size_t smem;
+    bool split;          // the two-part fp16 form of the GEMMs (template parameter BF3): needs the response's plane maxima
+};
+constexpr size_t W_SPLIT_SMEM = (size_t)(W_RING * W_BUF + W_A_FLOATS) * sizeof(float);
+
+// The form of the 16 x 16 towers at `oct` tiles per workgroup.  The product library has one: two tiles, two-part fp16 operands
+// (knobs() is a constant there and tower_tiles_per_workgroup returns 2); the fp32 forms and the timing ablations (WRONG
+// results) exist in the measurement library, where the knobs that select them do.
+static TowerForm tower_form(int oct) {
+#ifdef SMOT_DEBUG
+#define W_FORM(A, O) TowerForm{tower_wino_kernel<A, O>, 256 * O, (size_t)w_smem_floats(O) * sizeof(float), false}
+#define WS_FORM(A) TowerForm{tower_wino_kernel<A, 2, 0, true>, 512, W_SPLIT_SMEM, true}
+    if (oct == 1) {
+        switch (knobs().wino_abl) {
+            case 1: return W_FORM(1, 1);
+            case 2: return W_FORM(2, 1);
+            case 3: return W_FORM(3, 1);
+            case 4: return W_FORM(4, 1);
+            case 5: return W_FORM(5, 1);
+            case 6: return W_FORM(6, 1);
+            default: return W_FORM(0, 1);
+        }
+    }
+    if (knobs().tower_bf3 == 0) {
+        switch (knobs().wino_abl) {
+            case 3: return W_FORM(3, 2);
+            case 4: return W_FORM(4, 2);
+            case 6: return W_FORM(6, 2);
+            default: return W_FORM(0, 2);
+        }
+    }
+    switch (knobs().wino_abl) {
+        case 7: return WS_FORM(7);          // no matrix instructions
+        case 9: return WS_FORM(9);
+        case 10: return WS_FORM(10);
+        case 12: return WS_FORM(12);        // every stage fetches A block 0 (L2-hot)
+        case 15: return WS_FORM(15);        // one stage's timeline per wave (trace layout [workgroup][wave][8])
+        default: break;
+    }
+#undef W_FORM
+#undef WS_FORM
+#endif
+    (void)oct;
+    return TowerForm{tower_wino_kernel<0, 2, 0, true>, 512, W_SPLIT_SMEM, true};
+}
+
 int launch_tower_wino(const float* resp, const float* packed, const TowerParams& P, int N, int C, int cpg, float eps,
                       float* part, unsigned* zero_words, hipStream_t st, const float* plane_max) {
     const int tiles = 2 * (C / 16);
     const int oct = tower_tiles_per_workgroup(N, C);
-    const bool bf3 = oct == 2 && knobs().tower_bf3 != 0;
-    const size_t smem = (size_t)(bf3 ? W_RING * W_BUF + W_A_FLOATS : w_smem_floats(oct)) * sizeof(float);
+    const TowerForm f = tower_form(oct);
     const int grid = ((N + 7) / 8) * 8 * (tiles / oct);
     if (oct == 2) {                            // 115 KB of dynamic LDS
-        const void* fn = bf3 ? reinterpret_cast<const void*>(&tower_wino_kernel<0, 2, 0, true>)
-                             : reinterpret_cast<const void*>(&tower_wino_kernel<0, 2>);
-#ifdef SMOT_DEBUG
-        if (bf3 && knobs().wino_abl == 7) fn = reinterpret_cast<const void*>(&tower_wino_kernel<7, 2, 0, true>);
-        if (bf3 && knobs().wino_abl == 9) fn = reinterpret_cast<const void*>(&tower_wino_kernel<9, 2, 0, true>);
-        if (bf3 && knobs().wino_abl == 10) fn = reinterpret_cast<const void*>(&tower_wino_kernel<10, 2, 0, true>);
-        if (bf3 && knobs().wino_abl == 12) fn = reinterpret_cast<const void*>(&tower_wino_kernel<12, 2, 0, true>);
-        if (bf3 && knobs().wino_abl == 15) fn = reinterpret_cast<const void*>(&tower_wino_kernel<15, 2, 0, true>);
-#endif
-        const int rco = ensure_lds_optin(fn, smem, "predictor towers (winograd)");
+        const int rco = ensure_lds_optin(reinterpret_cast<const void*>(f.fn), f.smem, "predictor towers (winograd)");
         if (rco) return rco;
     }
-    if (bf3) {
-        SMOT_REQUIRE(plane_max != nullptr, "predictor towers: the split form needs the response's plane maxima");
-#define WB_LAUNCH(A)                                                                                              \
-    SMOT_LAUNCH((tower_wino_kernel<A, 2, 0, true>), dim3(grid), dim3(512), smem, st, resp, packed, P, N, C, cpg, eps, part, \
-                zero_words, g_trace, plane_max)
-#ifdef SMOT_DEBUG
-        switch (knobs().wino_abl) {
-            case 7: WB_LAUNCH(7); break;        // no matrix instructions (timing, WRONG results)
-            case 9: WB_LAUNCH(9); break;
-            case 10: WB_LAUNCH(10); break;
-            case 12: WB_LAUNCH(12); break;      // every stage fetches A block 0 (L2-hot; timing, WRONG results)
-            case 15: WB_LAUNCH(15); break;      // one stage's timeline per wave (trace layout [workgroup][wave][8])
-            default: WB_LAUNCH(0); break;
-        }
-#else
-        WB_LAUNCH(0);
-#endif
-#undef WB_LAUNCH
-        return check_launch("predictor towers (winograd, fp16 x 2)");
-    }
-#define W_LAUNCH(A, O)                                                                                            \
-    SMOT_LAUNCH((tower_wino_kernel<A, O>), dim3(grid), dim3(256 * O), smem, st, resp, packed, P, N, C, cpg, eps, part, \
-                zero_words, g_trace, plane_max)
-#ifdef SMOT_DEBUG
-    if (oct == 1) {
-        switch (knobs().wino_abl) {          // timing ablations (wrong results): measurement library only
-            case 1: W_LAUNCH(1, 1); break;
-            case 2: W_LAUNCH(2, 1); break;
-            case 3: W_LAUNCH(3, 1); break;
-            case 4: W_LAUNCH(4, 1); break;
-            case 5: W_LAUNCH(5, 1); break;
-            case 6: W_LAUNCH(6, 1); break;
-            default: W_LAUNCH(0, 1); break;
-        }
-    } else {
-        switch (knobs().wino_abl) {
-            case 3: W_LAUNCH(3, 2); break;
-            case 4: W_LAUNCH(4, 2); break;
-            case 6: W_LAUNCH(6, 2); break;
-            default: W_LAUNCH(0, 2); break;
-        }
-    }
-#else
-    if (oct == 2) {
-        W_LAUNCH(0, 2);
-    } else {
-        W_LAUNCH(0, 1);
-    }
-#endif
-#undef W_LAUNCH
-    return check_launch("predictor towers (winograd)");
+    SMOT_REQUIRE(!f.split || plane_max != nullptr, "predictor towers: the split form needs the response's plane maxima");
+    SMOT_LAUNCH(f.fn, dim3(grid), dim3(f.threads), f.smem, st, resp, packed, P, N, C, cpg, eps, part, zero_words, g_trace,
+                plane_max);
+    return check_launch(f.split ? "predictor towers (winograd, fp16 x 2)" : "predictor towers (winograd)");
 }
 
 // 16-channel tiles per workgroup of the blocked 29 x 29 convolution for N tracks (1 or 2)
@@ -1077,7 +1072,8 @@ static int tower_blocks_tiles_per_workgroup(int N, int C) {
     const int tiles = 2 * (C / 16);
     const int np8 = ((N + 7) / 8) * 8 * 4;                 // block tracks: tracks padded to the XCD count, four blocks each
     // same dispatch-round arithmetic as tower_tiles_per_workgroup, on four block tracks per track (the two-tile form on
-    // three-part bf16 operands: 108.7 -> 97.0 us at 30 tracks, measure/debug/tower_blocked_bf3.py: 0.9 of the fp32 rounds)
+    // split operands — two-part fp16 since round 6: 108.7 -> 97.0 us at 30 tracks with the three-part bf16 form it replaced,
+    // measure/debug/tower_blocked_bf3.py: 0.9 of the fp32 rounds)
     const int w1 = np8 * tiles, w2 = np8 * (tiles / 2);
     const float c1 = (w1 <= 256) ? 20.0f
                                  : 27.0f * (float)(w1 / 512) + ((w1 % 512) == 0 ? 0.0f : ((w1 % 512) <= 256 ? 15.0f : 27.0f));
@@ -1093,26 +1089,22 @@ int launch_tower_wino_blocks(const float* resp, const float* packed, const Tower
     const int tiles = 2 * (C / 16);
     const int np8 = ((N + 7) / 8) * 8 * 4;
     const int oct = tower_blocks_tiles_per_workgroup(N, C);
-    const size_t smem = (size_t)w_smem_floats(oct) * sizeof(float);
     const int grid = np8 * (tiles / oct);
-    if (oct == 2 && knobs().tower_bf3 != 0) {      // the three-part bf16 form of the main loop (BF3 above)
-        const size_t smem3 = (size_t)(W_RING * W_BUF + W_A_FLOATS) * sizeof(float);
-        const int rco = ensure_lds_optin(reinterpret_cast<const void*>(&tower_wino_kernel<0, 2, 29, true>), smem3,
-                                         "predictor towers (winograd, 29x29 in blocks, fp16 x 2)");
+    // one tile per workgroup: fp32; two: the two-part fp16 form of the main loop (BF3 above)
+    TowerForm f = {tower_wino_kernel<0, 1, 29>, 256, (size_t)w_smem_floats(1) * sizeof(float), false};
+    if (oct == 2) {
+        f = TowerForm{tower_wino_kernel<0, 2, 29, true>, 512, W_SPLIT_SMEM, true};
+#ifdef SMOT_DEBUG
+        if (knobs().tower_bf3 == 0) f = TowerForm{tower_wino_kernel<0, 2, 29>, 512, (size_t)w_smem_floats(2) * sizeof(float), false};
+#endif
+        const int rco = ensure_lds_optin(reinterpret_cast<const void*>(f.fn), f.smem,
+                                         f.split ? "predictor towers (winograd, 29x29 in blocks, fp16 x 2)"
+                                                 : "predictor towers (winograd, 29x29 in blocks)");
         if (rco) return rco;
-        SMOT_REQUIRE(plane_max != nullptr, "predictor towers: the split form needs the response's plane maxima");
-        SMOT_LAUNCH((tower_wino_kernel<0, 2, 29, true>), dim3(grid), dim3(512), smem3, st, resp, packed, P, N, C, cpg, 0.0f, conv,
-                    zero_words, (long long*)nullptr, plane_max);
-    } else if (oct == 2) {
-        const int rco = ensure_lds_optin(reinterpret_cast<const void*>(&tower_wino_kernel<0, 2, 29>), smem,
-                                         "predictor towers (winograd, 29x29 in blocks)");
-        if (rco) return rco;
-        SMOT_LAUNCH((tower_wino_kernel<0, 2, 29>), dim3(grid), dim3(512), smem, st, resp, packed, P, N, C, cpg, 0.0f, conv,
-                    zero_words, (long long*)nullptr, plane_max);
-    } else {
-        SMOT_LAUNCH((tower_wino_kernel<0, 1, 29>), dim3(grid), dim3(256), smem, st, resp, packed, P, N, C, cpg, 0.0f, conv,
-                    zero_words, (long long*)nullptr, plane_max);
     }
+    SMOT_REQUIRE(!f.split || plane_max != nullptr, "predictor towers: the split form needs the response's plane maxima");
+    SMOT_LAUNCH(f.fn, dim3(grid), dim3(f.threads), f.smem, st, resp, packed, P, N, C, cpg, 0.0f, conv, zero_words,
+                (long long*)nullptr, plane_max);
     return check_launch("predictor towers (winograd, 29x29 in blocks)");
 }
 

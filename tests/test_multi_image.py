@@ -353,3 +353,45 @@ def test_module_loop_of_four_streams_equals_four_single_stream_loops(ops):
                 assert torch.equal(res[b].get_field("ids"), dets[b].get_field("ids"))
                 n0 += counts[b]
             dets = res
+
+
+# ---- the generic poolers of a batch (pooled sizes / sampling ratios that neither separable kernel takes) -----------------
+GENERIC_WH, GENERIC_ROWS = (256, 128), [2, 0, 3]          # four levels, 64 x 32 down to 8 x 4; the second image has no rows
+FAMILIES["20/9"] = (20, 9, 512, 1.0, 0, 0.4, True)        # (20, 10) is refused by the decode kernel's check (odd rz only)
+
+
+def _generic_maps(seed, dtype, layout):
+    f = tuple(m.to(dtype) for m in _maps(len(GENERIC_ROWS), 32, GENERIC_WH, seed))
+    return tuple(m.to(memory_format=torch.channels_last) for m in f) if layout == "channels-last" else f
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("layout", ["NCHW", "channels-last"])
+def test_generic_poolers_of_a_batch_equal_one_image_calls(ops, layout, dtype):
+    """rz = 9 at sampling ratios 1..4: the generic ROIAlign kernel's batched forms (and, for the search regions, the
+    stand-alone kernel) against the single-image forms on each image's maps, bit for bit."""
+    fa = _generic_maps(61, dtype, layout)
+    boxes = _boxes(sum(GENERIC_ROWS), GENERIC_WH, 62)
+    for ratio in (1, 2, 3, 4):
+        z, sr = ops.emm_extract_cache_batched(fa, boxes, GENERIC_ROWS, 9, SCALES, ratio, 512, 1.0, 0)
+        assert z.shape == (sum(GENERIC_ROWS), 32, 9, 9) and sr.shape == (sum(GENERIC_ROWS), 4)
+        n0 = 0
+        for b, r in enumerate(GENERIC_ROWS):
+            z1, sr1 = ops.emm_extract_cache(_img(fa, b), boxes[n0:n0 + r], 9, SCALES, ratio, 512, 1.0, 0)
+            assert z1.shape == (r, 32, 9, 9) and sr1.shape == (r, 4)
+            assert torch.equal(z[n0:n0 + r], z1), "templates: ratio %d, image %d" % (ratio, b)
+            assert torch.equal(sr[n0:n0 + r], sr1), "search regions: ratio %d, image %d" % (ratio, b)
+            n0 += r
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16])
+def test_generic_head_of_a_batch_equals_one_image_calls(ops, dtype):
+    """(rx, rz) = (20, 9) takes neither fused kernel: generic pooler + smot_xcorr_dw_fwd, batched against image by image."""
+    fa, fb = _generic_maps(71, dtype, "NCHW"), _generic_maps(72, dtype, "NCHW")
+    boxes = _boxes(sum(GENERIC_ROWS), GENERIC_WH, 73)
+    P = Pair(ops, "20/9", 32, GENERIC_WH, _params(32, boxes, 74))
+    got, _ = P.run(fa, fb, boxes, GENERIC_ROWS)
+    assert got["bb"].shape == (sum(GENERIC_ROWS), 4) and torch.isfinite(got["bb"]).all() and torch.isfinite(got["conf"]).all()
+    _per_image_check(ops, P, fa, fb, boxes, GENERIC_ROWS, got, "20/9")
