@@ -46,9 +46,9 @@ marks = []
 waits = []
 
 
-def timed_emu(lib, addr, dev, stream):
+def timed_emu(lib, addr, dev, stream, feat_type=0):
     t0 = time.perf_counter()
-    r = emu(lib, addr, dev, stream)
+    r = emu(lib, addr, dev, stream, feat_type)
     t1 = time.perf_counter()
     marks.append((t0, t1))
     return r

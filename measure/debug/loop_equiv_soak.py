@@ -33,9 +33,6 @@ with torch.no_grad():
 for lp in loops[1:]:
     lp.track.tracker.load_state_dict(loops[0].track.tracker.state_dict())
 loops[1].native_frame = False
-for lp in loops:
-    lp.lazy_memory = os.environ.get("NO_LAZY") is None
-    lp.solver.track_pool.mirror_skip = os.environ.get("NO_SKIP") is None
 if not refine:
     loops[2]._lean_ok = lambda d: False
 shapes = gi.feature_shapes((1280, 704), 32)

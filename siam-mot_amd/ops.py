@@ -1339,7 +1339,7 @@ class HostRecordRing(object):
     before that buffer is handed out again, so a late store of the old kernel cannot complete a newer record."""
 
     def __init__(self, dev, pool_capacity):
-        n = 8 + 4 * track_solve_max_boxes() + 3 * pool_capacity
+        n = FrameBuffers.record_words(track_solve_max_boxes(), pool_capacity)
         self.dev = dev
         self.bufs = [torch.zeros((n,), dtype=torch.int32).pin_memory() for _ in range(2)]
         self.views = [b.numpy() for b in self.bufs]          # the same memory as numpy arrays (cheap element access)
@@ -1378,15 +1378,96 @@ class HostRecordRing(object):
         torch.cuda.current_stream(self.dev).synchronize()
 
 
+class FrameBuffers(object):
+    """What the solver's launch and the masked extraction behind it write for a frame of M input rows (include/smot_emm.h,
+    smot_track_solve_fwd), and the ONE owner of where — nothing outside this class spells an offset into them:
+
+        fbuf      fp32   out_boxes [4M] | act_boxes [4M] | out_scores [M] | act_scores [M] | (to 8 floats) order hint [M, HINT_FLOATS]
+        ibuf      int64  out_ids [M] | out_labels [M] | act_ids [M] | act_labels [M]
+        templates [M, C, rz, rz], sr_rows [M, 4]    the extraction's rows of act_boxes (the next frame's memory)
+        record    int32  K, A, max id, frame index, active ids, dormant ids, flags, M | kept input rows [M] | kept ids [M] |
+                         active ids [M] | active table, dormant table, its frames [3 x capacity] | input ids [M]
+    The first K rows of the out_* and the first A of the act_* fields are valid.  The order hint is kept as an OFFSET
+    (``hint_off`` floats into ``fbuf``, 0: none) and addresses are read off the tensors on every call: a deep copy / pickle
+    copies the buffers, and the hint with them."""
+    __slots__ = ("fbuf", "ibuf", "templates", "sr_rows", "M", "hint_off")
+
+    def __init__(self, fbuf, ibuf, M, templates=None, sr_rows=None, hint_off=0):
+        self.fbuf, self.ibuf, self.M, self.templates, self.sr_rows, self.hint_off = fbuf, ibuf, M, templates, sr_rows, hint_off
+
+    @staticmethod
+    def allocate(M, dev, row_shape=None, hint=False):
+        """For M rows; ``row_shape`` (C, rz, rz): with the extraction's outputs; ``hint``: with its order hint (2 .. 256 rows)."""
+        n = max(M, 1)
+        hint_off = ((10 * n + 7) & ~7) if (hint and 2 <= M <= 256) else 0          # (a 32-byte boundary)
+        b = FrameBuffers(torch.empty((hint_off + HINT_FLOATS * M if hint_off else 10 * n,), dtype=_F32, device=dev),
+                         torch.empty((4 * n,), dtype=torch.int64, device=dev), M, hint_off=hint_off)
+        if row_shape is not None:
+            b.templates = torch.empty((M,) + tuple(row_shape), dtype=_F32, device=dev)
+            b.sr_rows = torch.empty((M, 4), dtype=_F32, device=dev)
+        return b
+
+    def solver_pointers(self):
+        """(out_boxes, out_scores, out_ids, out_labels, act_boxes, act_ids, act_labels, act_scores)."""
+        fp, ip, M = self.fbuf.data_ptr(), self.ibuf.data_ptr(), self.M
+        return fp, fp + 32 * M, ip, ip + 8 * M, fp + 16 * M, ip + 16 * M, ip + 24 * M, fp + 36 * M
+
+    @property
+    def hint_ptr(self):
+        return self.fbuf.data_ptr() + 4 * self.hint_off if self.hint_off else 0
+
+    def pointers(self):
+        """(template boxes, search regions, templates, ids, labels, order hint or 0) of the act rows: the next head's inputs."""
+        fp, ip, M = self.fbuf.data_ptr(), self.ibuf.data_ptr(), self.M
+        return (fp + 16 * M, self.sr_rows.data_ptr(), self.templates.data_ptr(), ip + 16 * M, ip + 24 * M,
+                fp + 4 * self.hint_off if self.hint_off else 0)
+
+    def carry_pointers(self):
+        """(templates, boxes, search regions, ids, labels, scores) of the act rows: ``memory_carry``'s order."""
+        fp, ip, M = self.fbuf.data_ptr(), self.ibuf.data_ptr(), self.M
+        return self.templates.data_ptr(), fp + 16 * M, self.sr_rows.data_ptr(), ip + 16 * M, ip + 24 * M, fp + 36 * M
+
+    def kept(self, K):
+        """(boxes [K,4], ids, scores, labels) of the frame's output rows."""
+        st, f, i, M = torch.as_strided, self.fbuf, self.ibuf, self.M
+        return st(f, (K, 4), (4, 1), 0), st(i, (K,), (1,), 0), st(f, (K,), (1,), 8 * M), st(i, (K,), (1,), M)
+
+    def active(self, A):
+        """(boxes [A,4], ids, scores, labels) of the rows the solver leaves active (and what was carried behind them)."""
+        st, f, i, M = torch.as_strided, self.fbuf, self.ibuf, self.M
+        return st(f, (A, 4), (4, 1), 4 * M), st(i, (A,), (1,), 2 * M), st(f, (A,), (1,), 9 * M), st(i, (A,), (1,), 3 * M)
+
+    def hint_status(self):
+        """Status word of the order hint (0 = fine / no hint).  Synchronises: error paths and tests only."""
+        return order_hint_status(self.fbuf[self.hint_off:]) if self.hint_off else 0
+
+    def clear_hint_status(self):
+        """Zero the hint's status word on the current stream (a head launched on a wrong guess fails its verification)."""
+        if self.hint_off:
+            w = self.hint_off + HINT_STATUS_WORD
+            self.fbuf[w:w + 1].zero_()
+
+    # ---- the record (a numpy array, on the host): its size in words and its slices ---------------------------------------
+    record_words = staticmethod(lambda M, capacity: 8 + 4 * M + 3 * capacity)
+    kept_rows = staticmethod(lambda rec, M, K: rec[8:8 + K])
+    kept_ids = staticmethod(lambda rec, M, K: rec[8 + M:8 + M + K])
+    active_ids = staticmethod(lambda rec, M, A: rec[8 + 2 * M:8 + 2 * M + A])
+    input_ids = staticmethod(lambda rec, M, capacity: rec[8 + 3 * M + 3 * capacity:8 + 4 * M + 3 * capacity])
+
+    @staticmethod
+    def tables(rec, M, capacity):
+        """(active ids, dormant ids, the frames they were last active in): the snapshot of the pool's tables."""
+        na, nd, base = int(rec[4]), int(rec[5]), 8 + 3 * M
+        return rec[base:base + na], rec[base + capacity:base + capacity + nd], rec[base + 2 * capacity:base + 2 * capacity + nd]
+
+
 def track_solve(det, trk, trk_score_bias, thresholds, nms_thresh, max_dormant_frames, pool_state, pool_capacity,
                 host_record=False, carry=None):
     """``smot_track_solve_fwd``: one launch for TrackSolver.forward + the pool transitions + the active-row filter.
 
     det / trk: ``(boxes [n,4] xyxy, scores [n], ids [n] int64, labels [n] int64 or None)`` device tensors or ``None``
-    for an empty segment.  Launch only (no synchronisation).  Returns ``(fbuf, ibuf, rec, M)``: ``fbuf`` fp32
-    ``[10*M]`` = out_boxes | act_boxes | out_scores | act_scores, ``ibuf`` int64 ``[4*M]`` = out_ids | out_labels |
-    act_ids | act_labels (capacity M rows each; the first K / A are valid) and ``rec``, the record on the DEVICE
-    (``rec[0]`` = K, ``rec[1]`` = A, ...: include/smot_emm.h); ``track_solve_record(rec)`` brings it to the host.
+    for an empty segment.  Launch only (no synchronisation).  Returns ``(fbuf, ibuf, rec, M)``: the two output buffers
+    and ``rec``, the record on the DEVICE, as ``FrameBuffers`` lays them out; ``track_solve_record(rec)`` brings it to the host.
     ``host_record=ring`` (a ``HostRecordRing``): the kernel writes the record straight into the ring's next pinned
     host buffer (``rec`` is then that host tensor; ``ring.record_event()`` behind this launch, ``ring.wait(rec)`` to
     read it — no copy command; the count of active rows for device-side consumers is ``pool_state[4:5]``).
@@ -1394,47 +1475,28 @@ def track_solve(det, trk, trk_score_bias, thresholds, nms_thresh, max_dormant_fr
     first destination row, next_templates address, next_sr address, row_floats): ``smot_track_solve_carry_fwd`` — the
     dormant rows of the track memory go behind the active rows in this launch."""
     lib = _lib or load_library()
-    segs = []
     dev = pool_state.device
-    for seg in (det, trk):
-        if seg is None or seg[0].shape[0] == 0:
-            segs.append((0, 0, 0, 0, 0))
-            continue
-        b, s_, i_, l_ = seg
-        _check_segment(b, s_, i_, l_, dev)
-        segs.append((b.data_ptr(), s_.data_ptr(), i_.data_ptr(), l_.data_ptr() if l_ is not None else 0, b.shape[0]))
+    segs = [segment_pointers(seg, dev) for seg in (det, trk)]
     M = segs[0][4] + segs[1][4]
-    nrec = 8 + 4 * M + 3 * pool_capacity
-    fbuf = torch.empty((10 * max(M, 1),), dtype=_F32, device=dev)
-    ibuf = torch.empty((4 * max(M, 1),), dtype=torch.int64, device=dev)
-    rec = host_record.next() if host_record else torch.empty((nrec,), dtype=torch.int32, device=dev)
-    fp, ip = fbuf.data_ptr(), ibuf.data_ptr()
+    buf = FrameBuffers.allocate(M, dev)
+    rec = host_record.next() if host_record else torch.empty((buf.record_words(M, pool_capacity),), dtype=torch.int32, device=dev)
     cur = torch.cuda.current_device()
     if cur != dev.index:
         torch.cuda.set_device(dev.index)
+    args = segs[0] + segs[1] + (trk_score_bias, thresholds[0], thresholds[1], thresholds[2], nms_thresh, max_dormant_frames,
+                                pool_state.data_ptr(), pool_capacity) + buf.solver_pointers() + (rec.data_ptr(),)
     try:
         if carry is None:
-            rc = lib.smot_track_solve_fwd(segs[0][0], segs[0][1], segs[0][2], segs[0][3], segs[0][4],
-                                          segs[1][0], segs[1][1], segs[1][2], segs[1][3], segs[1][4], trk_score_bias,
-                                          thresholds[0], thresholds[1], thresholds[2], nms_thresh, max_dormant_frames,
-                                          pool_state.data_ptr(), pool_capacity,
-                                          fp, fp + 32 * M, ip, ip + 8 * M, fp + 16 * M, ip + 16 * M, ip + 24 * M, fp + 36 * M,
-                                          rec.data_ptr(), _stream(dev))
+            rc = lib.smot_track_solve_fwd(*args, _stream(dev))
         else:
             src, row0, rows, dst0, nz, nsr, row_floats = carry
-            rc = lib.smot_track_solve_carry_fwd(segs[0][0], segs[0][1], segs[0][2], segs[0][3], segs[0][4],
-                                                segs[1][0], segs[1][1], segs[1][2], segs[1][3], segs[1][4], trk_score_bias,
-                                                thresholds[0], thresholds[1], thresholds[2], nms_thresh, max_dormant_frames,
-                                                pool_state.data_ptr(), pool_capacity,
-                                                fp, fp + 32 * M, ip, ip + 8 * M, fp + 16 * M, ip + 16 * M, ip + 24 * M,
-                                                fp + 36 * M, rec.data_ptr(), src[0], src[1], src[2], src[3], src[4], src[5],
-                                                int(row0), int(rows), int(dst0), nz, nsr, int(row_floats), _stream(dev))
+            rc = lib.smot_track_solve_carry_fwd(*args, *src, int(row0), int(rows), int(dst0), nz, nsr, int(row_floats), _stream(dev))
     finally:
         if cur != dev.index:
             torch.cuda.set_device(cur)
     if rc:
         _check(rc, "track_solve")
-    return fbuf, ibuf, rec, M
+    return buf.fbuf, buf.ibuf, rec, M
 
 
 def track_solve_record(rec):
@@ -1698,6 +1760,15 @@ def memory_carry(src, src_rows_total, dst, dst_capacity, rows, dst_row0, row_flo
     if rc:
         _check(rc, "memory_carry")
     MEMORY_CARRY["launched"] += 1
+
+
+def segment_pointers(seg, dev):
+    """(boxes, scores, ids, labels or 0, rows) of one checked segment as the solver's entry points take them; None: empty."""
+    if seg is None or seg[0].shape[0] == 0:
+        return 0, 0, 0, 0, 0
+    b, s_, i_, l_ = seg
+    _check_segment(b, s_, i_, l_, dev)
+    return b.data_ptr(), s_.data_ptr(), i_.data_ptr(), l_.data_ptr() if l_ is not None else 0, b.shape[0]
 
 
 def _check_segment(b, s_, i_, l_, dev):

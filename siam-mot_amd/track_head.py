@@ -24,6 +24,7 @@ import torch
 
 from . import ops
 from .emm import OrderHint
+from .solver import rows_boxlist
 from .structures import BoxList, cat_boxlist
 
 
@@ -114,68 +115,33 @@ class TrackHead(torch.nn.Module):
         return target[torch.tensor(rows, dtype=torch.int64, device=ids.device)]
 
 
-class _LazyMemory(object):
+class _LazyMemory(ops.FrameBuffers):
     """The track memory ``(templates, [search-region BoxList], [template-box BoxList])`` as the tracking loop leaves it for
     the next frame — rows 0 .. n_act-1 the frame's active rows (the solver's and the masked extraction's own outputs), rows
-    n_act .. A-1 the dormant tracks' rows, copied behind them on the device (``TrackingLoop._carry_dormant``) —: the tuple's
-    six view tensors and two BoxLists are built on first access.  The next frame's head only needs five POINTERS into the
-    solver's output buffers and the extraction's outputs (``pointers``) — building the views costs ~8 us of host time on the
-    frame's serial chain and, frame after frame, nobody looks at them.  Indexing / iterating / ``len`` behave like the
-    tuple."""
-    __slots__ = ("_val", "fbuf", "ibuf", "templates", "sr_rows", "M", "A", "size", "sr_size", "host_ids", "cls", "hint_off",
-                 "n_act", "dormant")
+    n_act .. A-1 the dormant tracks' rows, copied behind them on the device (``TrackingLoop._carry_dormant``) —: the frame's
+    buffers (``ops.FrameBuffers`` knows where the rows are) and the row counts; the tuple's six view tensors and two BoxLists
+    are built on first access.  The next frame's head only needs five POINTERS into them (``pointers``) — building the views
+    costs ~8 us of host time on the frame's serial chain and, frame after frame, nobody looks at them.  Indexing / iterating
+    / ``len`` behave like the tuple.  The order hint (``hint_off``) is the one the masked extraction wrote for exactly rows
+    0 .. A-1, or 0: none; the head VERIFIES it against the rows it is given (csrc/sr_xcorr.hip, fx_verify_hint), so a stale
+    one is reported, not used."""
+    __slots__ = ("_val", "A", "size", "sr_size", "host_ids", "cls", "n_act", "dormant")
 
-    def __init__(self, fbuf, ibuf, templates, sr_rows, M, A, size, sr_size, host_ids, cls, hint_off=0, n_act=None, dormant=()):
+    def __init__(self, buf, A, size, sr_size, host_ids, cls, hinted=True, n_act=None, dormant=()):
         self._val = None
-        self.fbuf, self.ibuf, self.templates, self.sr_rows = fbuf, ibuf, templates, sr_rows
-        self.M, self.A, self.size, self.sr_size, self.host_ids, self.cls = M, A, size, sr_size, host_ids, cls
+        self.fbuf, self.ibuf, self.templates, self.sr_rows, self.M = buf.fbuf, buf.ibuf, buf.templates, buf.sr_rows, buf.M
+        self.hint_off = buf.hint_off if hinted else 0
+        self.A, self.size, self.sr_size, self.host_ids, self.cls = A, size, sr_size, host_ids, cls
         self.n_act = A if n_act is None else n_act          # rows 0 .. n_act-1 are active tracks, the rest dormant ones
         self.dormant = dormant                              # ids of rows n_act .. A-1, in row order
-        # where in `fbuf` (in floats, behind the frame's float outputs) the order hint lives that the masked extraction wrote
-        # for exactly rows 0 .. A-1, or 0: none.  An OFFSET, not an address (ADVICE r4): a deep copy / pickle of the loop
-        # mid-video copies `fbuf` and the hint with it.  It needs no host object — and the head VERIFIES the list against the
-        # rows it is given with (csrc/sr_xcorr.hip, fx_verify_hint), so a stale one is reported, not used.
-        self.hint_off = hint_off
-
-    @property
-    def hint_ptr(self):
-        return self.fbuf.data_ptr() + 4 * self.hint_off if self.hint_off else 0
-
-    def hint_status(self):
-        """Status word of this memory's order hint (0 = fine / no hint).  Synchronises: error paths and tests only."""
-        if not self.hint_off:
-            return 0
-        w = self.hint_off + ops.HINT_STATUS_WORD
-        return int(self.fbuf[w:w + 1].view(torch.int32).item())
-
-    def clear_hint_status(self):
-        """Zero the hint's status word on the current stream (after a speculative head that was launched on a guessed row
-        count and discarded: its verification failed by construction)."""
-        if self.hint_off:
-            w = self.hint_off + ops.HINT_STATUS_WORD
-            self.fbuf[w:w + 1].zero_()
-
-    def pointers(self):
-        """(template boxes, search regions, templates, ids, labels, order hint or 0) of rows 0 .. A-1 as device addresses."""
-        fp, ip, M = self.fbuf.data_ptr(), self.ibuf.data_ptr(), self.M
-        return (fp + 16 * M, self.sr_rows.data_ptr(), self.templates.data_ptr(), ip + 16 * M, ip + 24 * M,
-                fp + 4 * self.hint_off if self.hint_off else 0)
-
-    def carry_pointers(self):
-        """(templates, boxes, search regions, ids, labels, scores) as device addresses: ``ops.memory_carry``'s order."""
-        fp, ip, M = self.fbuf.data_ptr(), self.ibuf.data_ptr(), self.M
-        return self.templates.data_ptr(), fp + 16 * M, self.sr_rows.data_ptr(), ip + 16 * M, ip + 24 * M, fp + 36 * M
 
     def _materialise(self):
         v = self._val
         if v is None:
-            st, M, A = torch.as_strided, self.M, self.A
-            fbuf, ibuf = self.fbuf, self.ibuf
-            fields = {"ids": st(ibuf, (A,), (1,), 2 * M), "scores": st(fbuf, (A,), (1,), 9 * M),
-                      "labels": st(ibuf, (A,), (1,), 3 * M)}
-            act = BoxList._wrap(st(fbuf, (A, 4), (4, 1), 4 * M), self.size, "xyxy", fields)
+            A = self.A
+            act = rows_boxlist(BoxList, self.size, self.active(A))
             act.host_ids = self.host_ids.tolist()
-            sr = BoxList._wrap(self.sr_rows.narrow(0, 0, A), self.sr_size, "xyxy", dict(fields))
+            sr = BoxList._wrap(self.sr_rows.narrow(0, 0, A), self.sr_size, "xyxy", dict(act.extra_fields))
             v = self._val = (self.templates.narrow(0, 0, A), [sr], [act])
         return v
 
@@ -189,27 +155,33 @@ class _LazyMemory(object):
         return 3
 
 
-def _memory_rows(mem):
-    """Number of rows of a track memory (0 for None / an empty memory) without building a lazy one."""
-    if mem is None:
-        return 0
-    if type(mem) is _LazyMemory:
-        return mem.A
-    return len(mem[2][0]) if mem[0].numel() > 0 else 0
-
-
 class _FramePlan(object):
     """What ``TrackingLoop._frame_plan`` keeps between frames (see there)."""
     __slots__ = ("dev", "emm", "solver", "pool", "refine", "g", "scales", "params", "hann", "rz", "rx", "C", "amodal",
                  "ws_need", "lib", "args", "box_params", "box_ptrs", "box_amodal", "image_wh", "a_pp", "state", "ft")
 
 
-def _frame_call(P, addr, dev, stream):
-    """The frame entry point on plan ``P``'s block: fp32 maps as ever, fp16 / bf16 maps (``P.ft``) through its typed twin."""
-    if P.ft:
-        ops.track_frame_addr(P.lib, addr, dev, stream, P.ft)
-    else:
-        ops.track_frame_addr(P.lib, addr, dev, stream)
+class _Verdicts(object):
+    """What ``TrackingLoop._lean_ok`` / ``_native_ok`` decide once per model: the static facts, what the box head can do for
+    a row count (``rows_ok[n]`` = (device-only form, whole chain in one call): it follows from its layer shapes, asked once
+    per count while ``state_key`` stands) and whether head and box head share levels and clip rule (``geometry_ok``)."""
+    __slots__ = ("emm", "solver", "has_raw", "has_device_path", "max_boxes", "refine", "rows_ok", "state_key", "geometry_ok")
+
+
+class _GuessedHead(object):
+    """A head for the NEXT frame that ``_step_native`` launched (next features shown) or — ``early`` — prepared for launch on
+    the next call's first line, on a guess: that ``memory`` stays the unbuilt memory it is, with ``rows`` rows, the maps
+    ``features`` and the parameter block ``params`` (its ``a_pp``).  It writes ``out`` only (laid out for ``out_rows`` rows):
+    a guess that did not hold costs a launch, never a result.  ``hint``: the order-hint address it was given (0: none).  An
+    early launch also names the ``plan`` whose block holds its arguments, the ``stream`` it was prepared for, and ``alive``:
+    what that block points at and ops' caches may drop before the launch — the parameter block, its host array of weight
+    pointers and packed filters (a refresh replaces them: the objects are held, not just their owner), the workspace.
+    Without these the early launch read a freed pointer array, "predictor: null pointer" once in a full test session."""
+    __slots__ = ("memory", "rows", "features", "params", "out", "out_rows", "hint", "early", "plan", "stream", "alive")
+
+    def __init__(self, rows, features, params, out, out_rows, hint, early, plan=None, stream=None, alive=None):
+        self.rows, self.features, self.params, self.out, self.out_rows, self.hint = rows, features, params, out, out_rows, hint
+        self.memory, self.early, self.plan, self.stream, self.alive = None, early, plan, stream, alive    # (memory: after the record)
 
 
 def _GLOBAL_HOOKS():
@@ -233,6 +205,22 @@ class TrackingLoop(torch.nn.Module):
     def _refined_output_enqueued(self, boxes, scores, ids, labels):  # pragma: no cover - subclasses only
         raise NotImplementedError
 
+    # ---- switches (set on an instance: bench.py's A/B legs, tests) ------------------------------------------------------
+    native_frame = True         # the frame entry point (_step_native); False: the Python-composed form (_step_lean)
+    device_carry = True         # dormant rows copied on the device; False: concatenated on the host, as the reference does
+    loop_order_hint = True      # the masked extraction ranks the next frame's rois for the next head (2 .. 256 rows)
+    early_head = True           # the next call's head launch is prepared a call early and enqueued on that call's first line
+
+    # ---- everything the loop keeps from one call to the next beside `track_memory`: rebuilt on demand — a copy or a pickle
+    # of the loop carries none of it, and none survives a new head, solver or box head
+    _CALL_STATE = ("_plan",               # _FramePlan: the packed argument block and what it was built from
+                   "_verdicts",           # _Verdicts
+                   "_own_memory",         # the memory this loop built itself: its tensors are taken without re-checking
+                   "_spec_head", "_early_head",     # _GuessedHead: launched for the next call / to be launched on its first line
+                   "_prev_n_trk", "_prev_K",        # the last frame's propagated tracks / output rows: what the guesses go by
+                   "_hint_extra",         # dormant rows behind the active ones that this frame's order hint ranks as well
+                   "_carry_ahead_kept")   # the dormant rows copied before the record was read were the right ones
+
     def __init__(self, track_head, solver, refine_tracks=None):
         super(TrackingLoop, self).__init__()
         self.track = track_head
@@ -245,63 +233,66 @@ class TrackingLoop(torch.nn.Module):
         self.track.reset_track_pool()
 
     def __getstate__(self):
-        # per-frame caches (ctypes blocks, library handles, the trusted-memory marker) are rebuilt on demand: a copy or a
-        # pickle of the loop carries none of them
-        d = self.__dict__.copy()
-        for k in ("_plan", "_lean_static", "_own_memory", "_spec_head", "_prev_n_trk", "_early_head", "_prev_K", "_hint_extra"):
-            d.pop(k, None)
-        return d
+        return {k: v for k, v in self.__dict__.items() if k not in self._CALL_STATE}
 
     def __setattr__(self, name, value):
-        if name in ("track", "solver", "refine_tracks"):                 # what the per-frame caches below were built from
-            self.__dict__.pop("_lean_static", None)
-            self.__dict__.pop("_plan", None)
+        if name in ("track", "solver", "refine_tracks"):                 # what the call-to-call state was built from
+            for k in self._CALL_STATE:
+                self.__dict__.pop(k, None)
         super(TrackingLoop, self).__setattr__(name, value)
+
+    def _model_verdicts(self):
+        """A new ``_Verdicts`` of this loop's modules (submodule lookups go through nn.Module.__getattr__: once)."""
+        st = self.__dict__["_verdicts"] = _Verdicts()
+        st.emm, st.solver, st.refine = self.track.tracker, self.solver, self.refine_tracks
+        st.has_raw = hasattr(st.emm, "track_raw")
+        st.has_device_path = getattr(st.solver, "_device_path", None) is not None
+        st.max_boxes, st.rows_ok, st.state_key, st.geometry_ok = ops.track_solve_max_boxes(), {}, None, None
+        return st
+
+    @staticmethod
+    def _refine_verdict(st, n):
+        """(``refine_raw`` applies, the whole chain fits ``smot_box_refine_fwd``) for ``n`` propagated rows."""
+        refine = st.refine
+        # the verdict rests on mutable state (the post-processor's score threshold, where the weights live): re-read the
+        # cheap key every frame and drop the cached verdicts when it moved
+        cur = getattr(refine, "raw_state_key", None)
+        cur = cur() if cur is not None else None
+        if st.state_key != cur:
+            st.rows_ok.clear()
+            st.state_key = cur
+        r = st.rows_ok.get(n)
+        if r is None:
+            ok = getattr(refine, "raw_ok", None)
+            one = getattr(getattr(refine, "box", None), "one_call_ok", None)
+            r = st.rows_ok[n] = (ok is not None and bool(ok(n)), one is not None and bool(one(n)))
+        return r
+
+    def _memory_rows(self):
+        """Rows of the track memory (0: none / empty), without building a lazy one."""
+        mem = self.track_memory
+        return (mem.A if type(mem) is _LazyMemory else len(mem[2][0])) if mem is not None else 0
 
     def _lean_ok(self, detections):
         """The per-frame fast path applies: this repository's EMM head, no box-head refinement or one with a
         device-only form (``refine_raw``), the one-launch solver, device tensors."""
-        st = self.__dict__.get("_lean_static")
-        if st is None:                    # (submodule lookups go through nn.Module.__getattr__: once)
-            emm, solver = self.track.tracker, self.solver
-            st = self.__dict__["_lean_static"] = (emm, solver, hasattr(emm, "track_raw"),
-                                                  getattr(solver, "_device_path", None) is not None,
-                                                  ops.track_solve_max_boxes(), self.refine_tracks, {})
-        emm, solver, has_raw, has_device_path, max_boxes, refine, refine_ok = st
-        if not (has_raw and has_device_path):
+        st = self.__dict__.get("_verdicts") or self._model_verdicts()
+        if not (st.has_raw and st.has_device_path):
             return False
-        mem = self.track_memory
-        n_mem = (mem.A if type(mem) is _LazyMemory else len(mem[2][0])) if mem is not None else 0
+        refine, n_mem = st.refine, self._memory_rows()
         if refine is not None and n_mem > 0:
-            # (what a box head can do for n rows follows from its layer shapes: asked once per row count)
-            r = refine_ok.get(n_mem)
-            if r is None:
-                ok = getattr(refine, "raw_ok", None)
-                one = getattr(getattr(refine, "box", None), "one_call_ok", None)
-                r = refine_ok[n_mem] = (ok is not None and bool(ok(n_mem)), one is not None and bool(one(n_mem)))
-            # the verdict rests on mutable state (the post-processor's score threshold, where the weights live): re-read
-            # the two cheap predicates every frame and drop the cached verdicts when they moved
-            key = refine_ok.get("key")
-            cur = getattr(refine, "raw_state_key", None)
-            cur = cur() if cur is not None else None
-            if key != cur:
-                refine_ok.clear()
-                refine_ok["key"] = cur
-                ok = getattr(refine, "raw_ok", None)
-                one = getattr(getattr(refine, "box", None), "one_call_ok", None)
-                r = refine_ok[n_mem] = (ok is not None and bool(ok(n_mem)), one is not None and bool(one(n_mem)))
-            if not r[0]:
+            if not self._refine_verdict(st, n_mem)[0]:
                 return False
         elif refine is not None and getattr(refine, "raw_ok", None) is None:
             return False
-        if not detections.bbox.is_cuda or emm.rz not in (15, 7) or detections.mode != "xyxy":     # (the masked extraction's shapes)
+        if not detections.bbox.is_cuda or st.emm.rz not in (15, 7) or detections.mode != "xyxy":     # (the masked extraction's shapes)
             return False
-        kernel_fields = solver._KERNEL_FIELDS
+        kernel_fields = st.solver._KERNEL_FIELDS
         for f in detections.fields():
             if f not in kernel_fields:
                 return False                 # extra fields: the general path keeps them
         n = len(detections) + n_mem
-        return solver.nms_mask_fn is ops.nms_keep_mask and 0 < n <= max_boxes
+        return st.solver.nms_mask_fn is ops.nms_keep_mask and 0 < n <= st.max_boxes
 
     def _step_lean(self, features, detections):
         """One frame with the minimum of host work between the launches: raw tensors into ``ops.emm_track``, the
@@ -332,41 +323,41 @@ class TrackingLoop(torch.nn.Module):
             (float(solver.track_thresh), float(solver.start_thresh), float(solver.resume_track_thresh)),
             float(solver.NMS_THRESH), int(pool._max_dormant_frames), state, pool.DEVICE_CAPACITY, host_record=ring)
         ring.record_event()                 # behind the solver: its record lands in pinned host memory, no copy command
-        ob, ab, osc, asc = fbuf.split((4 * M, 4 * M, M, M))
-        act_boxes = ab.view(M, 4)
-        pre = emm.extract_cache_rows(features, act_boxes, state[4:5])              # runs while the host wakes up
-        ahead = None
-        if pre is not None and len(pre) == 2:
-            ahead = self._carry_ahead(mem, fbuf, ibuf, pre[0], pre[1], M, state, dev, ops._stream(dev))
+        buf = ops.FrameBuffers(fbuf, ibuf, M)
+        pre = emm.extract_cache_rows(features, buf.active(M)[0], state[4:5])       # runs while the host wakes up
+        ahead = hint = None
+        if pre is not None:
+            buf.templates, buf.sr_rows = pre[0], pre[1]
+            if len(pre) == 2:
+                ahead = self._carry_ahead(mem, buf, state, dev, ops._stream(dev))
+            else:
+                hint = pre[2]
         ring.wait(rec_host)                                                        # the frame's one synchronisation
-        return self._finish_frame(features, detections, rec_host, fbuf, ibuf, M, pre, carried_ahead=ahead)
+        return self._finish_frame(features, detections, rec_host, buf, hint, carried_ahead=ahead)
 
-    def _carry_ahead(self, mem, fbuf, ibuf, templates, sr_rows, M, state, dev, stream, lib=None):
+    def _carry_ahead(self, mem, buf, state, dev, stream, lib=None):
         """Before the frame's record is read: the dormant rows of the memory this frame's head ran on, copied behind the
         rows the solver is leaving active — the first destination row read from the solver's count on the device — on the
-        guess that the dormant tracks stay the ones they were (the usual frame).  ``_carry_dormant`` checks the guess
-        against the record and copies again when it did not hold; the copy launch is off the frame's serial chain
-        (record -> next head) either way.  Returns (source rows, guessed first destination row) or None."""
-        if not (type(mem) is _LazyMemory and mem.A > mem.n_act and self.__dict__.get("device_carry", True)):
+        guess that the dormant tracks stay the ones they were (the usual frame).  ``_carry_dormant`` checks the guess against
+        the record and copies again when it did not hold.  Returns (source rows, guessed first destination row) or None."""
+        if not (type(mem) is _LazyMemory and mem.A > mem.n_act and self.device_carry):
             return None
         rows = list(range(mem.n_act, mem.A))
-        fp, ip = fbuf.data_ptr(), ibuf.data_ptr()
-        ops.memory_carry(mem.carry_pointers(), mem.A, (templates.data_ptr(), fp + 16 * M, sr_rows.data_ptr(), ip + 16 * M,
-                                                       ip + 24 * M, fp + 36 * M), M, rows, mem.n_act, templates[0].numel(),
+        ops.memory_carry(mem.carry_pointers(), mem.A, buf.carry_pointers(), buf.M, rows, mem.n_act, buf.templates[0].numel(),
                          dev, stream, dst_row0_dev=state.data_ptr() + 16, lib=lib)
         return rows, mem.n_act
 
-    def _carry_dormant(self, prev, pool, fbuf, ibuf, templates, sr_rows, M, A, ahead=None):
+    def _carry_dormant(self, prev, pool, buf, A, ahead=None):
         """The dormant tracks' rows of the next memory, copied on the device from the memory this frame's head ran on
         (``prev``) to rows A .. of the frame's output buffers: one launch instead of the reference's ``torch.cat`` +
         two ``cat_boxlist`` per frame (track_head.py:77-97; ``TrackHead._update_memory_with_dormant_track`` is the general
         form).  Which rows: the reference appends ``cache[id]`` for every id of ``get_dormant_ids()`` — in that set's
         iteration order — that has a cache entry; an entry never changes while its track is dormant, and ``prev`` holds
         it: as an active row when the track went dormant in this frame (``TrackPool._mirror`` made exactly that row its
-        entry), as a carried row otherwise.  Returns (ids, source rows, copied ahead) or None: the general form applies
-        (no previous memory this code can address, an entry that is not a row of it, more rows than one launch takes).
-        ``ahead`` = (source rows, first destination row) of a copy that was enqueued before the record was read."""
-        if prev is None or not self.__dict__.get("device_carry", True):
+        entry), as a carried row otherwise.  ``ahead``: what ``_carry_ahead`` returned.  Returns (ids, source rows, copied
+        ahead) or None: the general form applies (no previous memory this code can address, an entry that is not a row of
+        it, more rows than one launch takes)."""
+        if prev is None or not self.device_carry:
             return None
         order = list(pool.get_dormant_ids())                    # a fresh set of the dict's keys, as track_head.py:83 iterates
         lazy = type(prev) is _LazyMemory
@@ -397,13 +388,14 @@ class TrackingLoop(torch.nn.Module):
         D = len(rows)
         if D == 0:
             return ids, rows, False
-        if D > ops.MEMORY_CARRY_MAX_ROWS or A + D > M:
+        if D > ops.MEMORY_CARRY_MAX_ROWS or A + D > buf.M:
             return None
         if ahead is not None and ahead[0] == rows and ahead[1] == A:
             ops.MEMORY_CARRY["ahead_kept"] += 1
             return ids, rows, True
         if ahead is not None:
             ops.MEMORY_CARRY["ahead_redone"] += 1
+        row_floats, dev = buf.templates[0].numel(), buf.fbuf.device
         if lazy:
             src, n_prev = prev.carry_pointers(), prev.A
         else:
@@ -414,123 +406,96 @@ class TrackingLoop(torch.nn.Module):
             t = (z, tb0.bbox, sr0.bbox, tb0.get_field("ids"), tb0.get_field("labels"), tb0.get_field("scores"))
             want = (torch.float32, torch.float32, torch.float32, torch.int64, torch.int64, torch.float32)
             for x, dt in zip(t, want):
-                if not (x.is_cuda and x.device == fbuf.device and x.dtype is dt and x.is_contiguous() and x.shape[0] == n_prev):
+                if not (x.is_cuda and x.device == dev and x.dtype is dt and x.is_contiguous() and x.shape[0] == n_prev):
                     return None
-            if z[0].numel() != templates[0].numel() or tb0.bbox.shape[1] != 4 or sr0.bbox.shape[1] != 4:
+            if z[0].numel() != row_floats or tb0.bbox.shape[1] != 4 or sr0.bbox.shape[1] != 4:
                 return None
             src = tuple(x.data_ptr() for x in t)
-        fp, ip = fbuf.data_ptr(), ibuf.data_ptr()
-        dev = fbuf.device
-        ops.memory_carry(src, n_prev, (templates.data_ptr(), fp + 16 * M, sr_rows.data_ptr(), ip + 16 * M, ip + 24 * M,
-                                       fp + 36 * M), M, rows, A, templates[0].numel(), dev, ops._stream(dev))
+        ops.memory_carry(src, n_prev, buf.carry_pointers(), buf.M, rows, A, row_floats, dev, ops._stream(dev))
         return ids, rows, False
 
-    def _finish_frame(self, features, detections, rec_host, fbuf, ibuf, M, pre, P=None, hint_off=0, carried_ahead=None,
-                      pre_out=None):
+    def _finish_frame(self, features, detections, rec_host, buf, hint=None, P=None, carried_ahead=None, pre_out=None):
         """After the record arrived: mirror the pool, slice the outputs, build the next track memory.  This is host work on
-        the frame's serial chain: ten strided views straight off the two output buffers (no intermediate splits), the
-        record through the ring's numpy view, BoxLists of this package's own class without re-validation."""
+        the frame's serial chain: strided views straight off the frame's buffers (``buf``: no intermediate splits), the
+        record through the ring's numpy view, BoxLists of this package's own class without re-validation.  ``hint``: the
+        order hint as a tensor of its own, when the extraction returned one (the Python-composed form)."""
         if P is not None:
             emm, pool = P.emm, P.pool
         else:
             emm, pool = self.track.tracker, self.solver.track_pool
+        M = buf.M
         ring = pool._ring
         view = ring.view(rec_host) if ring is not None and (rec_host is ring.bufs[0] or rec_host is ring.bufs[1]) else rec_host.numpy()
         if (pre_out is not None and view[6] == 4 and view[7] == M and view[0] == pre_out[0] and view[1] >= 1 and not pool._dormant_ids
-                and not self.__dict__.get("_hint_extra") and pool._last_tables is not None and self.__dict__.get("lazy_memory", True)
-                and pool.__dict__.get("mirror_skip", True)):
-            # The steady frame, in as few bytecodes as it takes (this is the serial chain: the GPU waits for the next head):
-            # the kernel says the id tables stand (record word 6 == 4: no overflow, no NaN score, nothing started /
-            # suspended / resumed / expired), there are no dormant tracks, the output has the row count its views were
-            # built for.  Same state as the general code below leaves: pool counters, output, the unbuilt next memory.
+                and not self.__dict__.get("_hint_extra") and pool._last_tables is not None):
+            # The steady frame, in as few bytecodes as it takes (the serial chain: the GPU waits for the next head): the
+            # kernel says the id tables stand (record word 6 == 4: no overflow, no NaN score, nothing started / suspended /
+            # resumed / expired), no dormant tracks, the output has the row count its views were built for.  Same state
+            # as the general code below leaves: pool counters, output, the unbuilt next memory.
             K, A = pre_out[0], int(view[1])
             pool._max_id, pool._frame_idx = int(view[2]), int(view[3])
             out = pre_out[1]
-            out.host_ids = view[8 + M:8 + M + K].copy()
-            host_ids = view[8 + 2 * M:8 + 2 * M + A].copy()
+            out.host_ids = buf.kept_ids(view, M, K).copy()
+            host_ids = buf.active_ids(view, M, A).copy()
             size = detections.size
             pad2 = emm.track_utils.pad_pixels * 2
-            memory = _LazyMemory(fbuf, ibuf, pre[0], pre[1], M, A, size, [int(size[0] + pad2), int(size[1] + pad2)], host_ids,
-                                 BoxList, hint_off if A >= 2 else 0, A, [])
+            memory = _LazyMemory(buf, A, size, [int(size[0] + pad2), int(size[1] + pad2)], host_ids, BoxList, A >= 2, A, [])
             pool._pending = (memory, host_ids)                      # = pool.note_memory
             d = self.__dict__
             d["_carry_ahead_kept"] = False
             d["track_memory"] = d["_own_memory"] = memory
             return out
-        rec = view[:8 + 4 * M + 3 * pool.DEVICE_CAPACITY].copy()
+        rec = view[:buf.record_words(M, pool.DEVICE_CAPACITY)].copy()
         K, A = int(rec[0]), int(rec[1])
         if int(rec[7]) != M:
             # the record's layout is sized by the row count the KERNEL saw: a mismatch means the argument block named another
             # count than this call allocated and parsed for (ADVICE r5) — never parse such a record
             raise RuntimeError("siammot_amd: the solver ran on %d rows, this frame was laid out for %d" % (int(rec[7]), M))
         if rec[6] & 2:
-            # a propagated track came in with a NaN score: what a head writes whose order hint failed the kernel's
-            # verification (include/smot_emm.h, order_hint) — ask the hint; NaN features give NaN scores too and pass
+            # a propagated track with a NaN score: what a head writes whose order hint failed the kernel's verification
+            # (include/smot_emm.h, order_hint) — ask the hint; NaN features give NaN scores too and pass
             self._raise_on_bad_hint(self.__dict__.get("track_memory"))
         pool._mirror(rec, M)
-        cls, size = detections.__class__, detections.size
-        st = torch.as_strided
-        # fbuf = out_boxes [4M] | act_boxes [4M] | out_scores [M] | act_scores [M]; ibuf = out_ids | out_labels | act_ids | act_labels
-        own = cls is BoxList
-        if not (pre_out is not None and pre_out[0] == K):
-            ob, oi, osc, ol = (st(fbuf, (K, 4), (4, 1), 0), st(ibuf, (K,), (1,), 0), st(fbuf, (K,), (1,), 8 * M),
-                               st(ibuf, (K,), (1,), M))
+        cls, size, own = detections.__class__, detections.size, detections.__class__ is BoxList
         if pre_out is not None and pre_out[0] == K:
             out = pre_out[1]              # the output's views were built before the record arrived, on the right row count
-        elif own:
-            out = BoxList._wrap(ob, size, "xyxy", {"ids": oi, "scores": osc, "labels": ol})
         else:
-            out = cls(ob, size, mode="xyxy")
-            out.add_field("ids", oi)
-            out.add_field("scores", osc)
-            out.add_field("labels", ol)
-        out.host_ids = rec[8 + M:8 + M + K]
-        hint = pre[2] if pre is not None and len(pre) > 2 else None
+            out = rows_boxlist(cls, size, buf.kept(K))
+        out.host_ids = buf.kept_ids(rec, M, K)
+        extracted = buf.templates is not None     # (None: no masked kernel for this pooler shape)
         self.__dict__["_carry_ahead_kept"] = False
-        if own and A > 0 and pre is not None and hint is None and self.__dict__.get("lazy_memory", True):
+        if own and A > 0 and extracted and hint is None:
             # the usual frame: the active rows — with the dormant tracks' rows copied behind them on the device — ARE the next
-            # memory, left unbuilt (see _LazyMemory); `out.active_rows` (read by the general path's
-            # TrackHead._get_track_targets only) is not needed either
+            # memory, left unbuilt (_LazyMemory); `out.active_rows` (for TrackHead._get_track_targets only) is not needed
             carried = ((), (), False)
             if pool._dormant_ids:
-                carried = self._carry_dormant(self.__dict__.get("track_memory"), pool, fbuf, ibuf, pre[0], pre[1], M, A,
-                                              carried_ahead)
+                carried = self._carry_dormant(self.__dict__.get("track_memory"), pool, buf, A, carried_ahead)
             if carried is not None:
                 dormant, D = carried[0], len(carried[0])
-                host_ids = rec[8 + 2 * M:8 + 2 * M + A]
+                host_ids = buf.active_ids(rec, M, A)
                 if D:
                     host_ids = np.concatenate([host_ids, np.asarray(dormant, dtype=host_ids.dtype)])
                     self.__dict__["_carry_ahead_kept"] = carried[2]
                 pad2 = emm.track_utils.pad_pixels * 2
-                # the extraction's order hint describes the memory's rows when it ranked exactly them: the active rows plus
-                # the dormant rows that were in place behind them when it ran (carried inside the solver's launch, and the
-                # guess about them held: `carried[2]`) — `_hint_extra` is how many such rows it was told about
+                # the extraction's order hint describes the memory's rows when it ranked exactly them: the active rows plus the
+                # `_hint_extra` dormant rows in place behind them when it ran (carried in the solver's launch, the guess held)
                 hint_ok = A + D >= 2 and self.__dict__.get("_hint_extra", 0) == D and (D == 0 or carried[2])
-                memory = _LazyMemory(fbuf, ibuf, pre[0], pre[1], M, A + D, size, [int(size[0] + pad2), int(size[1] + pad2)],
-                                     host_ids, cls, hint_off if hint_ok else 0, A, list(dormant))
+                memory = _LazyMemory(buf, A + D, size, [int(size[0] + pad2), int(size[1] + pad2)], host_ids, cls, hint_ok, A,
+                                     list(dormant))
                 pool.note_memory(memory, memory.host_ids)
-                self.__dict__["track_memory"] = memory
-                self.__dict__["_own_memory"] = memory
+                self.__dict__["track_memory"] = self.__dict__["_own_memory"] = memory
                 return out
             ops.FALLBACKS["dormant_rows_on_the_host"] += 1
-        ab, ai, asc, al = (st(fbuf, (A, 4), (4, 1), 4 * M), st(ibuf, (A,), (1,), 2 * M), st(fbuf, (A,), (1,), 9 * M),
-                           st(ibuf, (A,), (1,), 3 * M))
-        if own:
-            act = BoxList._wrap(ab, size, "xyxy", {"ids": ai, "scores": asc, "labels": al})
-        else:
-            act = cls(ab, size, mode="xyxy")
-            act.add_field("ids", ai)
-            act.add_field("scores", asc)
-            act.add_field("labels", al)
-        act.host_ids = rec[8 + 2 * M:8 + 2 * M + A].tolist()
+        act = rows_boxlist(cls, size, buf.active(A))
+        act.host_ids = buf.active_ids(rec, M, A).tolist()
         out.active_rows = act
-        if A == 0 or pre is None:
+        if A == 0 or not extracted:
             # no active row (the reference's empty memory) or no masked kernel for this pooler shape: general code
             self.track_memory = self.track.get_track_memory(features, [out])
             return out
         # (the extraction ranked exactly the rows of `act` — the first A of act_boxes — for the next frame's head)
         hint = hint.narrow(0, 0, A) if hint is not None else None
-        zv, srv = pre[0].narrow(0, 0, A), pre[1].narrow(0, 0, A)
+        zv, srv = buf.templates.narrow(0, 0, A), buf.sr_rows.narrow(0, 0, A)
         if own and hint is None:
             pad2 = emm.track_utils.pad_pixels * 2                                  # = EMM.wrap_cache
             sr = BoxList._wrap(srv, [int(size[0] + pad2), int(size[1] + pad2)], "xyxy", dict(act.extra_fields))
@@ -564,46 +529,40 @@ class TrackingLoop(torch.nn.Module):
     def _native_ok(self, detections):
         """``smot_track_frame_fwd`` applies: the one-launch path's conditions, the 15x15 template pooler's masked kernel
         and — with refinement — a box head whose whole chain fits ``smot_box_refine_fwd``."""
-        if not self.__dict__.get("native_frame", True):
+        if not self.native_frame:
             return False              # (``loop.native_frame = False``: the Python-composed form, _step_lean)
-        P = self.__dict__.get("_plan")
-        if P is None:
+        if self.__dict__.get("_plan") is None:
             emm = self.track.tracker
             fz = emm.feature_extractor.pooler_z
             if not (emm.rz in (15, 7) and fz.sampling_ratio == 2):
                 return False
-        st = self.__dict__.get("_lean_static")
-        if st is not None and st[5] is not None:                         # with refinement: the box head's whole chain must
-            geom = st[6].get("geom")                                     # fit smot_box_refine_fwd (asked by _lean_ok)
+        st = self.__dict__.get("_verdicts") or self._model_verdicts()
+        if st.refine is not None:                          # with refinement: the box head's whole chain must fit
+            geom = st.geometry_ok                          # smot_box_refine_fwd
             if geom is None:
-                # smot_frame_args carries ONE level geometry (scales, level count) and ONE clip pair for the head and the
-                # refinement: the frame entry point applies only when the box head's pooler sits on the search pooler's
-                # levels (the reference keeps MODEL.ROI_BOX_HEAD.POOLER_SCALES and MODEL.TRACK_HEAD.POOLER_SCALES apart) and
-                # both stages clip alike (INPUT.AMODAL in the reference's cfg; RefineTracks accepts any box head).  Otherwise
-                # the Python-composed form, which handles the two independently.
-                emm, box = self.track.tracker, st[5].box
+                # smot_frame_args carries ONE level geometry and ONE clip pair for the head and the refinement: the entry point
+                # applies only when the box head's pooler sits on the search pooler's levels (the reference keeps
+                # MODEL.ROI_BOX_HEAD.POOLER_SCALES and MODEL.TRACK_HEAD.POOLER_SCALES apart) and both stages clip alike
+                # (INPUT.AMODAL; RefineTracks accepts any box head).  Otherwise the Python-composed form: it handles them apart.
+                emm, box = st.emm, st.refine.box
                 bx = getattr(getattr(box, "feature_extractor", None), "pooler", None)
                 pp_ = getattr(box, "post_processor", None)
-                geom = st[6]["geom"] = bool(
+                geom = st.geometry_ok = bool(
                     bx is not None and pp_ is not None
                     and tuple(float(v) for v in bx.scales) == tuple(float(v) for v in emm.feature_extractor.pooler_x.scales)
                     and bool(pp_.amodal_inference) == bool(emm.amodal))
             if not geom:
                 return False
-            mem = self.track_memory
-            n_mem = _memory_rows(mem)
-            if n_mem > 0:
-                r = st[6].get(n_mem)
-                if r is None or not r[1]:
-                    return False
-        elif st is None and self.refine_tracks is not None:
-            return False
+            n_mem = self._memory_rows()
+            # (the verdict `_lean_ok` has just asked for, when it ran; asked here when it was overridden)
+            if n_mem > 0 and not (st.rows_ok.get(n_mem) or self._refine_verdict(st, n_mem))[1]:
+                return False
         return True
 
     def _frame_plan(self, dev, features):
         """Everything of a frame's argument block that stands while the video's geometry and the model stand: packed once
         (``ops.FrameArgs``), re-packed when a feature shape or dtype, a weight pointer or the device changes.  The maps'
-        element type (fp32 / fp16 / bf16) is not a field of the block: ``P.ft`` goes to the frame call beside it (``_frame_call``)."""
+        element type (fp32 / fp16 / bf16) is not a field of the block: ``P.ft`` goes to the frame call beside it."""
         P = self.__dict__.get("_plan")
         if P is not None and P.dev == dev and ops._geometry_refresh(P.g, features, dev):
             return P
@@ -644,11 +603,126 @@ class TrackingLoop(torch.nn.Module):
             a.box_wx, a.box_wy, a.box_ww, a.box_wh = bc.weights
             a.box_xform_clip = bc.bbox_xform_clip
             P.box_amodal = bool(pp_.amodal_inference)
-        P.image_wh = None
-        P.a_pp = None
-        P.state = None
+        P.image_wh = P.a_pp = P.state = None
         self.__dict__["_plan"] = P
         return P
+
+    @staticmethod
+    def _ws_need(P, n):
+        """(head, box-head refinement) workspace floats for ``n`` propagated rows: asked of the library once per count."""
+        need = P.ws_need.get(n)
+        if need is None:
+            a = P.args
+            need = P.ws_need[n] = (
+                int(P.lib.smot_emm_track_ws_floats(n, P.C, P.rx, P.rz)),
+                int(P.lib.smot_box_refine_ws_floats(n, P.C, a.box_pooled, a.dim6, a.dim7, a.num_classes, a.reg_classes))
+                if a.refine else 0)
+        return need
+
+    @staticmethod
+    def _plan_current(P, blk, size, dev):
+        """Keep plan ``P``'s block current: packed again when the parameter block, the image size's clip pair, a box-head weight
+        pointer or the pool's state tensor (``P.state``) is not what was packed (a dozen reads).  Returns whether it was."""
+        a = P.args
+        repack = False
+        if blk.a_pp != P.a_pp:
+            a.predictor_params, P.a_pp, repack = blk.a_pp, blk.a_pp, True
+        if size != P.image_wh:
+            P.image_wh = size
+            cw, ch = (0.0, 0.0) if P.amodal else (float(size[0]), float(size[1]))
+            if P.box_params is not None and P.box_amodal:
+                cw = ch = 0.0                   # (head and box head share the flag in the reference's cfg: INPUT.AMODAL)
+            a.clip_w, a.clip_h, repack = cw, ch, True
+        if P.box_params is not None:
+            ptrs = tuple([p_.data_ptr() for p_ in P.box_params])
+            if ptrs != P.box_ptrs:
+                P.box_ptrs = ptrs
+                a.fc6_w, a.fc6_b, a.fc7_w, a.fc7_b, a.cls_w, a.cls_b, a.reg_w, a.reg_b = ptrs
+                repack = True
+        state = P.pool.device_state(dev)
+        if state is not P.state:
+            P.state, a.pool_state, repack = state, state.data_ptr(), True
+        if repack:
+            a.pack()
+        return repack
+
+    def _built_memory_pointers(self, P, mem, dev):
+        """(rows, the head's pointers — ``_LazyMemory.pointers``' order) of a memory that exists as tensors: one somebody has
+        looked at, or one this loop did not build itself — that one with the full checks."""
+        z, sr, tb = mem
+        tb0, sr0 = tb[0], sr[0]
+        tbb, srb = tb0.bbox, sr0.bbox
+        n_trk = tbb.shape[0]
+        ids_t, lab_t = tb0.get_field("ids"), tb0.get_field("labels")
+        if mem is not self.__dict__.get("_own_memory"):
+            tbb, srb = ops._chk(tbb, "template boxes", (n_trk, 4)), ops._chk(srb, "sr", (n_trk, 4))
+            z = ops._chk(z, "template_features", (n_trk, P.C, P.rz, P.rz))
+            if not (ids_t.is_contiguous() and lab_t.is_contiguous() and ids_t.dtype is torch.int64 and lab_t.dtype is torch.int64):
+                ids_t, lab_t = ids_t.to(torch.int64).contiguous(), lab_t.to(torch.int64).contiguous()
+            ops._same_device(dev, ("template boxes", tbb), ("sr", srb), ("template_features", z), ("ids", ids_t),
+                             ("labels", lab_t))
+        hint = OrderHint.lookup(sr0, tb0.bbox, sr0.bbox, P.scales) if "order_hint" in sr0.__dict__ else None
+        return n_trk, (tbb.data_ptr(), srb.data_ptr(), z.data_ptr(), ids_t.data_ptr(), lab_t.data_ptr(),
+                       hint.data_ptr() if hint is not None else 0)
+
+    @staticmethod
+    def _guess_held(head, mem, n_trk, head_ptrs, repack, features, blk):
+        """Accept or discard the head launched for this frame on a guess (``_GuessedHead``).  Usable only while the memory is
+        the unbuilt lazy one: tensors somebody has looked at may have been edited in place since that head read them."""
+        held = (head_ptrs is not None and not repack and head.memory is mem and head.rows == n_trk
+                and type(mem) is _LazyMemory and mem._val is None and head.features is features and head.params == blk.a_pp)
+        if held:
+            ops.SPECULATION["early_used" if head.early else "used"] += 1
+        else:
+            if head.hint and head.memory is mem:
+                mem.clear_hint_status()       # it VERIFIED the hint against rows that were not the frame's: see _step_native
+            ops.SPECULATION["early_discarded" if head.early else "discarded"] += 1
+        return held
+
+    def _poke_head(self, P, ptrs, rows, n_poked, dev, stream):
+        """A head launch's argument range in ``P``'s block: an output buffer for ``rows`` rows (boxes [4 rows] | scores [rows] |
+        refined boxes [4 rows] | refined scores [rows]), the workspace for that many, the memory's pointers ``ptrs``
+        (``_LazyMemory.pointers``' order), the row count ``n_poked``.  Returns (output buffer, workspace, block address)."""
+        p_tbb, p_sr, p_z, p_ids, p_lab, p_hint = ptrs
+        out = torch.empty((10 * rows,), dtype=torch.float32, device=dev)
+        p = out.data_ptr()
+        ws = ops._workspace(dev, self._ws_need(P, rows)[0], stream.value)
+        return out, ws, P.args.poke_head((ws.data_ptr(), p_tbb, p_sr, p_z, p_hint, p_ids, p_lab, p, p + 16 * rows), n_poked,
+                                         ops.STAGE_HEAD)
+
+    def _launch_rest(self, P, mem, detections, n_trk, tf, tf_cap, ring, dev, stream):
+        """While the head runs: detections, the frame's buffers, the second call — refinement, solver (with the dormant rows'
+        carry), masked extraction.  Returns (buffers, record buffer, the refinement's ids | labels or None, ``_carry_ahead``'s result)."""
+        a, solver = P.args, P.solver
+        det = ops.segment_pointers(solver._segment(detections), dev)
+        n_det = det[4]
+        # (with room for the order hint the masked extraction ranks the NEXT frame's rois into — one wave of one extra workgroup
+        # of that launch — handed to the next head as a bare address when the memory stays the extraction's own output)
+        buf = ops.FrameBuffers.allocate(n_det + n_trk, dev, (P.C, P.rz, P.rz), self.loop_order_hint)
+        rec_host = ring.next()
+        ti, refined = None, (0, 0, 0, 0, 0)           # workspace, then boxes and scores (in the head's output buffer), ids, labels
+        stages = ops.STAGE_SOLVE | ops.STAGE_EXTRACT
+        if n_trk > 0 and a.refine:
+            ti = torch.empty((2 * n_trk,), dtype=torch.int64, device=dev)
+            p, pi = tf.data_ptr(), ti.data_ptr()
+            refined = (ops._workspace(dev, self._ws_need(P, n_trk)[1], ("refine", stream.value)).data_ptr(),
+                       p + 20 * tf_cap, p + 36 * tf_cap, pi, pi + 8 * n_trk)
+            stages |= ops.STAGE_REFINE
+        # the dormant rows go behind the rows the solver leaves active in the solver's own launch (extra workgroups beside its
+        # one: no launch, no time on the chain) — _carry_ahead's guess, and that the active count stays what it was
+        carried_ahead, carry_src, carry = None, (0,) * 6, (0, 0, 0)
+        if type(mem) is _LazyMemory and mem.A > mem.n_act and self.device_carry and (P.C * P.rz * P.rz) % 4 == 0:
+            carry_src = mem.carry_pointers()
+            carry = (mem.n_act, mem.A - mem.n_act, mem.n_act)
+            carried_ahead = (list(range(mem.n_act, mem.A)), mem.n_act)
+            stages |= ops.STAGE_CARRY
+            ops.MEMORY_CARRY["in_the_solver_launch"] += 1
+        self.__dict__["_hint_extra"] = carry[1]   # (they stand in act_boxes when the extraction runs: its hint ranks them too)
+        addr = a.poke_rest(refined + det[:4] + buf.solver_pointers()
+                           + (rec_host.data_ptr(), buf.templates.data_ptr(), buf.sr_rows.data_ptr(), buf.hint_ptr) + carry_src,
+                           stages, n_det, (solver.track_thresh, solver.start_thresh, solver.resume_track_thresh), carry, n_trk)
+        ops.track_frame_addr(P.lib, addr, dev, stream, P.ft)
+        return buf, rec_host, ti, carried_ahead
 
     def _step_native(self, features, detections, next_features=None):
         """``_step_lean`` through ``smot_track_frame_fwd``: same kernels, same arguments, same single synchronisation, two
@@ -665,241 +739,101 @@ class TrackingLoop(torch.nn.Module):
         path (~30 us of Python) then runs while the GPU works on that head instead of leaving it idle.  The next call
         takes the head's output as it is when the guess held (same memory, same row count, same feature tensors, same
         parameters) and launches the head again when it did not — the speculative launch only ever wrote its own buffers,
-        so results are the synchronous path's bit for bit either way."""
+        so results are the synchronous path's bit for bit either way.  (Without them: the early head, below.)"""
         dev = detections.bbox.device
         P = self._frame_plan(dev, features)
-        a, emm, solver, pool = P.args, P.emm, P.solver, P.pool
+        a, pool = P.args, P.pool
         blk = ops._param_block(P.params)           # revalidated per frame (a dozen attribute reads): load_state_dict / .to()
         mem = self.track_memory
         if mem is None:
             pool.reset()                                                           # track_head.py:39-40
-        size = detections.size
-        repack = False
-        if blk.a_pp != P.a_pp:
-            a.predictor_params, P.a_pp, repack = blk.a_pp, blk.a_pp, True
-        if size != P.image_wh:
-            P.image_wh = size
-            cw, ch = (0.0, 0.0) if P.amodal else (float(size[0]), float(size[1]))
-            if P.box_params is not None and P.box_amodal:
-                cw = ch = 0.0                   # (head and box head share the flag in the reference's cfg: INPUT.AMODAL)
-            a.clip_w, a.clip_h, repack = cw, ch, True
-        if P.box_params is not None:
-            ptrs = tuple([p_.data_ptr() for p_ in P.box_params])
-            if ptrs != P.box_ptrs:
-                P.box_ptrs = ptrs
-                a.fc6_w, a.fc6_b, a.fc7_w, a.fc7_b, a.cls_w, a.cls_b, a.reg_w, a.reg_b = ptrs
-                repack = True
-        state = pool.device_state(dev)
-        if state is not P.state:
-            P.state, a.pool_state, repack = state, state.data_ptr(), True
-        if repack:
-            a.pack()
-        n_trk = 0
-        tf = ti = None
+        repack = self._plan_current(P, blk, detections.size, dev)
         stream = ops._stream(dev)
-        head_ptrs = None
+        n_trk, head_ptrs = 0, None
         if type(mem) is _LazyMemory and mem._val is None:
-            # the memory this loop left behind, untouched since: five addresses, no tensor is built
-            n_trk = mem.A
-            head_ptrs = mem.pointers()
+            n_trk, head_ptrs = mem.A, mem.pointers()      # the memory this loop left behind, untouched since: no tensor is built
         elif mem is not None and mem[0].numel() > 0:
-            z, sr, tb = mem
-            tb0, sr0 = tb[0], sr[0]
-            tbb, srb = tb0.bbox, sr0.bbox
-            n_trk = tbb.shape[0]
-            ids_t, lab_t = tb0.get_field("ids"), tb0.get_field("labels")
-            if mem is not self.__dict__.get("_own_memory"):      # a memory this loop did not build itself: full checks
-                tbb, srb = ops._chk(tbb, "template boxes", (n_trk, 4)), ops._chk(srb, "sr", (n_trk, 4))
-                z = ops._chk(z, "template_features", (n_trk, P.C, P.rz, P.rz))
-                if not (ids_t.is_contiguous() and lab_t.is_contiguous() and ids_t.dtype is torch.int64 and lab_t.dtype is torch.int64):
-                    ids_t, lab_t = ids_t.to(torch.int64).contiguous(), lab_t.to(torch.int64).contiguous()
-                ops._same_device(dev, ("template boxes", tbb), ("sr", srb), ("template_features", z), ("ids", ids_t),
-                                 ("labels", lab_t))
-            hint = OrderHint.lookup(sr0, tb0.bbox, sr0.bbox, P.scales) if "order_hint" in sr0.__dict__ else None
-            head_ptrs = (tbb.data_ptr(), srb.data_ptr(), z.data_ptr(), ids_t.data_ptr(), lab_t.data_ptr(),
-                         hint.data_ptr() if hint is not None else 0)
-        spec = self.__dict__.pop("_spec_head", None)
-        # (usable only while the memory is the unbuilt lazy one: once somebody has looked at its tensors they may have been
-        # edited in place, and the speculative head read what was there before)
-        if spec is not None and not (head_ptrs is not None and not repack and spec[0] is mem and spec[1] == n_trk
-                                     and type(mem) is _LazyMemory and mem._val is None
-                                     and spec[2] is features and spec[3] == blk.a_pp):
-            if spec[5] and spec[0] is mem:
-                mem.clear_hint_status()                   # (see the other discard below)
-            ops.SPECULATION["early_discarded" if spec[7] else "discarded"] += 1
-            spec = None                                   # the guess did not hold: the head runs again, below
-        tf_cap = n_trk                    # rows the head's output buffer `tf` is laid out for: boxes | scores | refined boxes | refined scores
-        if spec is not None:
-            tf, tf_cap = spec[4], spec[6]                 # the head of this frame has been running since the last call /
-            need = P.ws_need.get(n_trk)                   # since this call's first line (early head: TrackingLoop.forward)
-            if need is None:
-                need = P.ws_need[n_trk] = (
-                    int(P.lib.smot_emm_track_ws_floats(n_trk, P.C, P.rx, P.rz)),
-                    int(P.lib.smot_box_refine_ws_floats(n_trk, P.C, a.box_pooled, a.dim6, a.dim7, a.num_classes, a.reg_classes))
-                    if a.refine else 0)
-            ops.SPECULATION["early_used" if spec[7] else "used"] += 1
-        elif head_ptrs is not None:
-            p_tbb, p_sr, p_z, p_ids, p_lab, p_hint = head_ptrs
-            need = P.ws_need.get(n_trk)
-            if need is None:
-                need = P.ws_need[n_trk] = (
-                    int(P.lib.smot_emm_track_ws_floats(n_trk, P.C, P.rx, P.rz)),
-                    int(P.lib.smot_box_refine_ws_floats(n_trk, P.C, a.box_pooled, a.dim6, a.dim7, a.num_classes, a.reg_classes))
-                    if a.refine else 0)
-            tf = torch.empty((10 * n_trk,), dtype=torch.float32, device=dev)
-            p = tf.data_ptr()
-            if p_hint == 0 and 2 <= n_trk <= 256 and P.rz == 15:
+            n_trk, head_ptrs = self._built_memory_pointers(P, mem, dev)
+        head = self.__dict__.pop("_spec_head", None)
+        if head is not None and not self._guess_held(head, mem, n_trk, head_ptrs, repack, features, blk):
+            head = None                                   # the guess did not hold: the head runs again, below
+        tf, tf_cap = None, n_trk          # the head's output buffer and the rows it is laid out for (_poke_head)
+        if head is not None:
+            tf, tf_cap = head.out, head.out_rows          # the head of this frame has been running since the last call /
+        elif head_ptrs is not None:                       # since this call's first line (early head: _forward)
+            if head_ptrs[5] == 0 and 2 <= n_trk <= 256 and P.rz == 15:
                 ops.FALLBACKS["unhinted_head"] += 1
-            addr = a.poke_head((ops._workspace(dev, need[0], stream.value).data_ptr(), p_tbb, p_sr, p_z, p_hint, p_ids,
-                                p_lab, p, p + 16 * n_trk), n_trk, ops.STAGE_HEAD)
-            _frame_call(P, addr, dev, stream)                         # the head is running from here on
+            tf, _, addr = self._poke_head(P, head_ptrs, n_trk, n_trk, dev, stream)
+            ops.track_frame_addr(P.lib, addr, dev, stream, P.ft)                  # the head is running from here on
         if self._probed and n_trk > 0:              # (a test-only subclass: tests/sequence_replay.ProbedTrackingLoop)
             self._head_output_enqueued(tf[:4 * n_trk].view(n_trk, 4), tf[4 * tf_cap:4 * tf_cap + n_trk])
         # ---- while the head runs: detections, output buffers, the remaining stages --------------------------------------
-        seg = solver._segment(detections)
-        n_det = 0
-        d0 = d1 = d2 = d3 = 0
-        if seg is not None:
-            db, dsc, did, dlab = seg
-            ops._check_segment(db, dsc, did, dlab, dev)
-            n_det = db.shape[0]
-            d0, d1, d2, d3 = db.data_ptr(), dsc.data_ptr(), did.data_ptr(), (dlab.data_ptr() if dlab is not None else 0)
-        M = n_det + n_trk
         ring = pool.host_record_ring(dev)
-        # float outputs [10 M] and, behind them at a 32-byte boundary, the order hint [M, HINT_FLOATS] the masked extraction ranks
-        # the NEXT frame's rois into (one wave of one extra workgroup of that launch; 2..256 rows) — handed to the next
-        # head as a bare address when the memory stays the extraction's own output (_LazyMemory)
-        hint_off = ((10 * M + 7) & ~7) if (2 <= M <= 256 and self.__dict__.get("loop_order_hint", True)) else 0
-        fbuf = torch.empty((hint_off + ops.HINT_FLOATS * M,) if hint_off else (10 * M,), dtype=torch.float32, device=dev)
-        ibuf = torch.empty((4 * M,), dtype=torch.int64, device=dev)
-        templates = torch.empty((M, P.C, P.rz, P.rz), dtype=torch.float32, device=dev)
-        sr_next = torch.empty((M, 4), dtype=torch.float32, device=dev)
-        rec_host = ring.next()
-        fp, ip = fbuf.data_ptr(), ibuf.data_ptr()
-        rw = r0 = r1 = r2 = r3 = 0
-        stages = ops.STAGE_SOLVE | ops.STAGE_EXTRACT
-        if n_trk > 0:
-            if a.refine:
-                ti = torch.empty((2 * n_trk,), dtype=torch.int64, device=dev)
-                p = tf.data_ptr()
-                rw = ops._workspace(dev, need[1], ("refine", stream.value)).data_ptr()
-                r0, r1, r2, r3 = p + 20 * tf_cap, p + 36 * tf_cap, ti.data_ptr(), ti.data_ptr() + 8 * n_trk
-                stages |= ops.STAGE_REFINE
-        # the dormant rows of the memory this frame's head ran on go behind the rows the solver leaves active, in the solver's
-        # own launch (extra workgroups beside its one: no launch, no time on the chain) — on the guess that the dormant
-        # tracks stay the ones they were and the active count what it was (the usual frame); _carry_dormant checks both
-        # against the record and copies again, with the stand-alone kernel, when the guess did not hold
-        carried_ahead = None
-        cz = cb = cs = ci = cl = cc = 0
-        carry = (0, 0, 0)
-        if (type(mem) is _LazyMemory and mem.A > mem.n_act and self.__dict__.get("device_carry", True)
-                and (P.C * P.rz * P.rz) % 4 == 0 and self.__dict__.get("carry_in_solver", True)):
-            cz, cb, cs, ci, cl, cc = mem.carry_pointers()
-            carry = (mem.n_act, mem.A - mem.n_act, mem.n_act)
-            carried_ahead = (list(range(mem.n_act, mem.A)), mem.n_act)
-            stages |= ops.STAGE_CARRY
-            ops.MEMORY_CARRY["in_the_solver_launch"] += 1
-        # rows behind the active ones that the extraction's order hint ranks as well (smot_track_frame_fwd: the rows carried
-        # in the solver's launch stand in act_boxes when the extraction runs)
-        self.__dict__["_hint_extra"] = carry[1] if (stages & ops.STAGE_CARRY) else 0
-        addr = a.poke_rest((rw, r0, r1, r2, r3, d0, d1, d2, d3,
-                            fp, fp + 32 * M, ip, ip + 8 * M,                       # out_boxes, out_scores, out_ids, out_labels
-                            fp + 16 * M, ip + 16 * M, ip + 24 * M, fp + 36 * M,    # act_boxes, act_ids, act_labels, act_scores
-                            rec_host.data_ptr(), templates.data_ptr(), sr_next.data_ptr(), (fp + 4 * hint_off) if hint_off else 0,
-                            cz, cb, cs, ci, cl, cc),
-                           stages, n_det, (solver.track_thresh, solver.start_thresh, solver.resume_track_thresh), carry, n_trk)
-        _frame_call(P, addr, dev, stream)
+        buf, rec_host, ti, carried_ahead = self._launch_rest(P, mem, detections, n_trk, tf, tf_cap, ring, dev, stream)
         if self._probed and n_trk > 0 and a.refine:
             self._refined_output_enqueued(tf[5 * tf_cap:5 * tf_cap + 4 * n_trk].view(n_trk, 4), tf[9 * tf_cap:9 * tf_cap + n_trk],
                                           ti[:n_trk], ti[n_trk:])
-        hint_ptr = (fp + 4 * hint_off) if hint_off else 0
-        spec_tf = None
+        in_solver = carried_ahead is not None         # (the dormant rows went with the solver's launch)
         if carried_ahead is None:
-            carried_ahead = self._carry_ahead(mem, fbuf, ibuf, templates, sr_next, M, state, dev, stream, P.lib)
-        # (a wrong guess costs the GPU a whole head: the guess is made only while the count has been holding — this frame
-        # had as many tracks as the frame before)
+            carried_ahead = self._carry_ahead(mem, buf, P.state, dev, stream, P.lib)
+        # ---- beside the GPU: one guess about the next frame's head, one about this frame's output -------------------------
+        # (a wrong guess costs the GPU a whole head: the speculative one is made only while the track count has been holding)
         steady = self.__dict__.get("_prev_n_trk") == n_trk
         self.__dict__["_prev_n_trk"] = n_trk
-        if (next_features is not None and steady and n_trk >= 1 and type(mem) is _LazyMemory and detections.__class__ is BoxList
-                and self.__dict__.get("lazy_memory", True) and ops._geometry_refresh(P.g, next_features, dev)):
-            # the next frame's head on this frame's outputs, guessing that n_trk rows stay active (the steady state: the
-            # memory of this frame was the previous frame's active rows, untouched): rows 0 .. n_trk-1 of act_boxes / ids /
-            # labels, of the extraction's search regions and templates, and its order hint
-            need = P.ws_need[n_trk]
-            # (... and that the dormant tracks stay the ones they were: their rows went behind the active rows just above)
-            spec_tf = torch.empty((10 * n_trk,), dtype=torch.float32, device=dev)
-            p = spec_tf.data_ptr()
-            spec_hint = hint_ptr if (n_trk >= 2 and (carried_ahead is None or (stages & ops.STAGE_CARRY))) else 0
-            addr = a.poke_head((ops._workspace(dev, need[0], stream.value).data_ptr(), fp + 16 * M, sr_next.data_ptr(),
-                                templates.data_ptr(), spec_hint, ip + 16 * M,
-                                ip + 24 * M, p, p + 16 * n_trk), n_trk, ops.STAGE_HEAD)
-            _frame_call(P, addr, dev, stream)
+        own, spec, early = detections.__class__ is BoxList, None, None
+        if (next_features is not None and steady and n_trk >= 1 and type(mem) is _LazyMemory and own
+                and ops._geometry_refresh(P.g, next_features, dev)):
+            # the next frame's head on rows 0 .. n_trk-1 of this frame's buffers and the extraction's order hint, guessing
+            # that n_trk rows stay active and the dormant tracks the ones they were (their rows went behind them just above)
+            ptrs = buf.pointers()
+            hint = ptrs[5] if (n_trk >= 2 and (carried_ahead is None or in_solver)) else 0
+            out, _, addr = self._poke_head(P, ptrs[:5] + (hint,), n_trk, n_trk, dev, stream)
+            ops.track_frame_addr(P.lib, addr, dev, stream, P.ft)
             ops.SPECULATION["launched"] += 1
             ops._geometry_refresh(P.g, features, dev)     # the plan's pointer array names THIS frame's maps again (ADVICE r4)
-        early = None
-        if (spec_tf is None and M >= 1 and detections.__class__ is BoxList and self.__dict__.get("early_head", True)
-                and self.__dict__.get("lazy_memory", True)):
-            # No speculative head: the NEXT call's head launch is prepared NOW, while the GPU works on this frame — its
-            # output buffer, workspace and the nine pointers of the head's argument range (all of them addresses inside THIS
-            # frame's output buffers: the next memory, if it stays the unbuilt lazy one) — so that the next call can enqueue
-            # its head on its FIRST line (TrackingLoop.forward) and validate afterwards: what used to be ~12 us of host work
-            # between the record and the first launch of the next frame — the GPU idle — runs beside the GPU here.  The row
-            # count is this frame's, corrected after the record.
-            nm = P.ws_need.get(M)
-            if nm is None:
-                nm = P.ws_need[M] = (
-                    int(P.lib.smot_emm_track_ws_floats(M, P.C, P.rx, P.rz)),
-                    int(P.lib.smot_box_refine_ws_floats(M, P.C, a.box_pooled, a.dim6, a.dim7, a.num_classes, a.reg_classes))
-                    if a.refine else 0)
-            e_tf = torch.empty((10 * M,), dtype=torch.float32, device=dev)
-            p = e_tf.data_ptr()
-            e_ws = ops._workspace(dev, nm[0], stream.value)
-            a.poke_head((e_ws.data_ptr(), fp + 16 * M, sr_next.data_ptr(),
-                         templates.data_ptr(), hint_ptr, ip + 16 * M, ip + 24 * M, p, p + 16 * M), max(n_trk, 1), ops.STAGE_HEAD)
-            # (the launch happens in the NEXT call: everything its argument block names must stay alive until then — the
-            # parameter block `blk` owns the host array of weight pointers the block's `predictor_params` points at, and
-            # ops' caches may drop both it and the workspace tensor when other modules / loops come and go in between:
-            # without these references the early launch read a freed pointer array, "predictor: null pointer" once in a
-            # full test session)
-            early = (e_tf, stream.value, blk.a_pp, (blk, getattr(blk, "pp", None), getattr(blk, "packed", None), tuple(getattr(blk, "tensors", ()))), e_ws)   # (a refresh of `blk`
-            # replaces its pointer array and packed filters: the objects themselves are held, not just their owner)
+            spec = _GuessedHead(n_trk, next_features, P.a_pp, out, n_trk, hint, False)
+        elif buf.M >= 1 and own and self.early_head:
+            # no speculative head: the NEXT call's head launch is prepared NOW, while the GPU works on this frame — output
+            # buffer, workspace, the pointers into THIS frame's buffers (the next memory, if it stays the unbuilt lazy one) —
+            # so that the next call enqueues its head on its FIRST line (_forward) and validates afterwards: ~12 us of host
+            # work between the record and the next frame's first launch run beside the GPU.  The row count is this frame's,
+            # corrected after the record
+            ptrs = buf.pointers()
+            out, ws, _ = self._poke_head(P, ptrs, buf.M, max(n_trk, 1), dev, stream)
+            early = _GuessedHead(max(n_trk, 1), None, blk.a_pp, out, buf.M, ptrs[5], True, P, stream.value,
+                                 (blk, getattr(blk, "pp", None), getattr(blk, "packed", None), tuple(getattr(blk, "tensors", ())), ws))
         # the frame's output BoxList, built NOW on the guess that it has as many rows as the last frame's (four strided views:
         # ~6 us that would otherwise sit between the record and the return)
         pre_out = None
         Kg = self.__dict__.get("_prev_K")
-        if Kg is not None and Kg <= M and detections.__class__ is BoxList:
-            st = torch.as_strided
-            pre_out = (Kg, BoxList._wrap(st(fbuf, (Kg, 4), (4, 1), 0), detections.size, "xyxy",
-                                         {"ids": st(ibuf, (Kg,), (1,), 0), "scores": st(fbuf, (Kg,), (1,), 8 * M),
-                                          "labels": st(ibuf, (Kg,), (1,), M)}))
+        if Kg is not None and Kg <= buf.M and own:
+            pre_out = (Kg, rows_boxlist(BoxList, detections.size, buf.kept(Kg)))
         ring.wait(rec_host, event=False)                                           # the frame's one synchronisation
-        out = self._finish_frame(features, detections, rec_host, fbuf, ibuf, M, (templates, sr_next), P, hint_off=hint_off,
-                                 carried_ahead=carried_ahead, pre_out=pre_out)
-        self.__dict__["_prev_K"] = len(out.bbox)
-        if spec_tf is not None:
-            # valid for exactly the memory _finish_frame just built, if it is the lazy one over these buffers with n_trk rows
-            # — and its dormant rows, if any, are the ones that were copied before that head was enqueued
-            m2 = self.__dict__.get("track_memory")
-            if (type(m2) is _LazyMemory and m2.fbuf is fbuf and m2.A == n_trk
-                    and (m2.A == m2.n_act or self.__dict__.get("_carry_ahead_kept"))
-                    and (not spec_hint or m2.hint_off)):      # (a hint that turned out not to describe the rows: that head's output is NaN)
-                self.__dict__["_spec_head"] = (m2, n_trk, next_features, P.a_pp, spec_tf, spec_hint, n_trk, False)
+        out = self._finish_frame(features, detections, rec_host, buf, None, P, carried_ahead, pre_out)
+        # ---- after the record: both guesses are settled against the memory _finish_frame just built ------------------------
+        d = self.__dict__
+        d["_prev_K"] = len(out.bbox)
+        m2 = d.get("track_memory")
+        ours = type(m2) is _LazyMemory and m2.fbuf is buf.fbuf         # the lazy memory over this frame's buffers
+        if spec is not None:
+            # valid for exactly that memory with n_trk rows, its dormant rows, if any, the ones copied before that head
+            if (ours and m2.A == n_trk and (m2.A == m2.n_act or d.get("_carry_ahead_kept"))
+                    and (not spec.hint or m2.hint_off)):      # (a hint that turned out not to describe the rows: that head's output is NaN)
+                spec.memory = m2
+                d["_spec_head"] = spec
             else:
                 ops.SPECULATION["discarded"] += 1        # the row count changed, or the dormant rows are not the ones copied ahead
-                # the discarded head VERIFIED the extraction's hint against a row count that was not the frame's and raised
-                # its status word: the head that runs again on the true rows must find it clear
-                if spec_hint and type(m2) is _LazyMemory and m2.fbuf is fbuf:
+                # (it VERIFIED the hint against a row count that was not the frame's: the head that runs again finds it clear)
+                if spec.hint and ours:
                     m2.clear_hint_status()
-        self.__dict__["_early_head"] = None
-        if early is not None:
-            m2 = self.__dict__.get("track_memory")
-            if type(m2) is _LazyMemory and m2.fbuf is fbuf and m2.A >= 1:
-                # the head's argument range stands as poked above; the record brought the row count (and whether the
-                # extraction's hint describes all rows: not when dormant rows were carried behind them)
-                use_hint = hint_ptr if m2.hint_off else 0
-                if m2.A != max(n_trk, 1) or use_hint != hint_ptr:
-                    a.fix_head(m2.A, use_hint)
-                self.__dict__["_early_head"] = (m2, m2.A, early[0], early[1], early[2], use_hint, M, P, early[3], early[4])
+        d["_early_head"] = None
+        if early is not None and ours and m2.A >= 1:
+            # the record brought the row count and whether the hint describes all rows (not with rows carried behind them)
+            hint = early.hint if m2.hint_off else 0
+            if m2.A != early.rows or hint != early.hint:
+                a.fix_head(m2.A, hint)
+            early.memory, early.rows, early.hint = m2, m2.A, hint
+            d["_early_head"] = early
         return out
 
     def __call__(self, features, detections, next_features=None):
@@ -922,19 +856,18 @@ class TrackingLoop(torch.nn.Module):
     def _forward(self, features, detections, next_features=None):
         eh = self.__dict__.get("_early_head")
         if eh is not None:
-            # the head of THIS frame, prepared by the last call while the GPU was busy (see _step_native): enqueued before
-            # anything else — the checks that it is the right launch follow while it runs (the memory object untouched, the
-            # same stream and device, the maps' geometry here; parameters and packing in _step_native, which launches the
-            # head again when any of them moved: the early launch wrote its own output buffer only)
+            # the head of THIS frame, prepared by the last call (see _step_native): enqueued before anything else — what
+            # decides whether it is the right launch is checked while it runs (the memory untouched, stream, device and
+            # geometry here; parameters and packing in _step_native, which launches the head again when one of them moved)
             self.__dict__["_early_head"] = None
-            mem = self.__dict__.get("track_memory")
-            P = eh[7]
+            mem, P = self.__dict__.get("track_memory"), eh.plan
             stream = ops._stream(P.dev)
-            if (eh[0] is mem and mem._val is None and P is self.__dict__.get("_plan")
-                    and stream.value == eh[3] and ops._geometry_refresh(P.g, features, P.dev)):
-                _frame_call(P, P.args._addr, P.dev, stream)
+            if (eh.memory is mem and mem._val is None and P is self.__dict__.get("_plan")
+                    and stream.value == eh.stream and ops._geometry_refresh(P.g, features, P.dev)):
+                ops.track_frame_addr(P.lib, P.args._addr, P.dev, stream, P.ft)
                 ops.SPECULATION["early_launched"] += 1
-                self.__dict__["_spec_head"] = (mem, eh[1], features, eh[4], eh[2], eh[5], eh[6], True)
+                eh.features = features
+                self.__dict__["_spec_head"] = eh
         if self._lean_ok(detections):
             if self._native_ok(detections):
                 if next_features is None:

@@ -187,7 +187,7 @@ def test_closed_loop_with_the_hip_head_equals_the_reference(name, lean):
         ops_a.SPECULATION.clear()
     if lean:
         which = "_step_lean" if lean == "python" else "_step_native"
-        loop.native_frame = lean != "python"            # (the one-call frame is opt-in)
+        loop.native_frame = lean != "python"            # (_step_native is the default; False: the Python-composed form)
         step = getattr(loop, which)
 
         def counted(*a, **k):
@@ -331,28 +331,8 @@ def test_frame_entry_point_hands_the_order_hint_to_the_next_head():
     Steady tracks, no dormant ids: every head launch from the third frame on carries a hint, and the frames' outputs are
     bit-identical to a loop that never passes one."""
     import siammot_amd.ops as ops_
-    from siammot_amd.structures import BoxList
-    inp, emm, loop = _gpu_loop("plain", True)
-    loop.native_frame = True
-    dev = "cuda:0"
-    feats = [tuple(torch.from_numpy(f).to(dev) for f in inp.features(t)) for t in range(2)]
-    rs = np.random.RandomState(5)
     n = 9
-    # a head that HOLDS its tracks (bench.py's construction): zeroed head convolutions -> the arg-max is the cosine window's
-    # centre cell; a regression bias that encodes the (uniform) box size and compensates the half-cell offset of the
-    # reference's location grid (track_core.py:184-225) -> the decoded box lands on the box it came from
-    mw, mh = 64.0, 128.0
-    wh = np.tile(np.array([[mw, mh]], np.float32), (n, 1))
-    xy = np.stack([(np.arange(n) % 3) * 420.0 + 20.0, (np.arange(n) // 3) * 230.0 + 5.0], 1).astype(np.float32)
-    boxes = torch.from_numpy(np.concatenate([xy, xy + wh], 1)).to(dev)
-    with torch.no_grad():
-        pr = emm.predictor
-        for name in ("cls", "center", "reg"):
-            getattr(pr, name).weight.zero_()
-            getattr(pr, name).bias.zero_()
-        dx, dy = (2.0 * mw + 1.0) / 958.0, (2.0 * mh + 1.0) / 958.0
-        pr.reg.bias.copy_(torch.tensor([0.5 * mw + dx, 0.5 * mh + dy, 0.5 * mw - dx, 0.5 * mh - dy]))
-    loop.solver.track_thresh = 0.0
+    inp, loop, feats, dets = _holding_loop(n)
 
     def run(hint, ahead=False):
         loop.reset()
@@ -365,10 +345,7 @@ def test_frame_entry_point_hands_the_order_hint_to_the_next_head():
         ops_.FrameArgs.poke_head = counting_poke
         try:
             for t in range(8):
-                d = BoxList(boxes + 0.25 * (t & 1), inp.case["image_wh"], mode="xyxy")
-                d.add_field("ids", torch.full((n,), -1, dtype=torch.int64, device=dev))
-                d.add_field("labels", torch.ones(n, dtype=torch.int64, device=dev))
-                d.add_field("scores", torch.full((n,), 0.97, device=dev))
+                d = dets(t)
                 out = loop(feats[t & 1], d, next_features=feats[(t + 1) & 1]) if ahead else loop(feats[t & 1], d)
                 outs.append((out.bbox.clone(), out.get_field("scores").clone(), out.get_field("ids").clone()))
         finally:
@@ -392,12 +369,14 @@ def test_frame_entry_point_hands_the_order_hint_to_the_next_head():
     assert int((out_h[-1][2] >= 0).sum()) >= n - 1
 
 
-def _holding_loop(n=9):
-    """A loop whose head HOLDS its tracks (the construction of test_frame_entry_point_hands_the_order_hint_to_the_next_head):
-    returns (inp, loop, feats of two alternating frames, detections(t))."""
+def _holding_loop(n=9, native=True):
+    """A loop whose head HOLDS its tracks (bench.py's construction): zeroed head convolutions -> the arg-max is the cosine
+    window's centre cell; a regression bias that encodes the (uniform) box size and compensates the half-cell offset of the
+    reference's location grid (track_core.py:184-225) -> the decoded box lands on the box it came from.  Returns (inp, loop,
+    feats of two alternating frames, detections(t[, scores]))."""
     from siammot_amd.structures import BoxList
-    inp, emm, loop = _gpu_loop("plain", True)
-    loop.native_frame = True
+    inp, emm, loop = _gpu_loop("plain", True if native else "python")
+    loop.native_frame = native
     dev = "cuda:0"
     feats = [tuple(torch.from_numpy(f).to(dev) for f in inp.features(t)) for t in range(2)]
     mw, mh = 64.0, 128.0
@@ -413,11 +392,11 @@ def _holding_loop(n=9):
         pr.reg.bias.copy_(torch.tensor([0.5 * mw + dx, 0.5 * mh + dy, 0.5 * mw - dx, 0.5 * mh - dy]))
     loop.solver.track_thresh = 0.0
 
-    def dets(t):
+    def dets(t, scores=None):
         d = BoxList(boxes + 0.25 * (t & 1), inp.case["image_wh"], mode="xyxy")
         d.add_field("ids", torch.full((n,), -1, dtype=torch.int64, device=dev))
         d.add_field("labels", torch.ones(n, dtype=torch.int64, device=dev))
-        d.add_field("scores", torch.full((n,), 0.97, device=dev))
+        d.add_field("scores", torch.full((n,), 0.97, device=dev) if scores is None else scores)
         return d
     return inp, loop, feats, dets
 
@@ -539,24 +518,10 @@ def test_dormant_rows_carried_on_the_device_equal_the_concatenated_memory(native
     BEFORE the record is read, on the guess that nothing changes — give identical outputs in every frame and identical
     final memories (templates, boxes, search regions, ids, labels, scores, row order)."""
     import siammot_amd.ops as ops_
-    from siammot_amd.structures import BoxList
     from siammot_amd.track_head import _LazyMemory
-    inp, emm, loop = _gpu_loop("plain", True if native else "python")
-    loop.native_frame = native
-    dev = "cuda:0"
-    feats = [tuple(torch.from_numpy(f).to(dev) for f in inp.features(t)) for t in range(2)]
     n, k = 9, 2
-    mw, mh = 64.0, 128.0
-    wh = np.tile(np.array([[mw, mh]], np.float32), (n, 1))
-    xy = np.stack([(np.arange(n) % 3) * 420.0 + 20.0, (np.arange(n) // 3) * 230.0 + 5.0], 1).astype(np.float32)
-    boxes = torch.from_numpy(np.concatenate([xy, xy + wh], 1)).to(dev)
-    with torch.no_grad():                       # a head that holds its tracks (see the test above)
-        pr = emm.predictor
-        for name in ("cls", "center", "reg"):
-            getattr(pr, name).weight.zero_()
-            getattr(pr, name).bias.zero_()
-        dx, dy = (2.0 * mw + 1.0) / 958.0, (2.0 * mh + 1.0) / 958.0
-        pr.reg.bias.copy_(torch.tensor([0.5 * mw + dx, 0.5 * mh + dy, 0.5 * mw - dx, 0.5 * mh - dy]))
+    inp, loop, feats, dets = _holding_loop(n, native)
+    dev = "cuda:0"
     thresholds = (loop.solver.track_thresh, loop.solver.start_thresh, loop.solver.resume_track_thresh)
     frames = 10
 
@@ -567,13 +532,10 @@ def test_dormant_rows_carried_on_the_device_equal_the_concatenated_memory(native
         loop.device_carry = carry
         outs, rows = [], []
         for t in range(frames):
-            d = BoxList(boxes + 0.25 * (t & 1), inp.case["image_wh"], mode="xyxy")
-            d.add_field("ids", torch.full((n,), -1, dtype=torch.int64, device=dev))
-            d.add_field("labels", torch.ones(n, dtype=torch.int64, device=dev))
             sc = torch.full((n,), 0.97, device=dev)
             if t == 1:
                 sc[n - k:] = 3.5               # above every propagated row's band: tracks n-k .. n-1 lose their rows in the NMS
-            d.add_field("scores", sc)
+            d = dets(t, sc)
             if native and ahead:
                 out = loop(feats[t & 1], d, next_features=feats[(t + 1) & 1])
             else:

@@ -402,7 +402,7 @@ class _FrameEntryEmulation(object):
         import ctypes
         return self._arr(ptr, n, ctypes.c_int64, np.int64)
 
-    def __call__(self, lib, addr, dev, stream):
+    def __call__(self, lib, addr, dev, stream, feat_type=0):
         import ctypes
         ops_ = self.ops
         fmt = ops_.FrameArgs._FMT
@@ -578,9 +578,29 @@ def test_frame_entry_point_bookkeeping_with_speculation_and_carried_rows_on_cpu(
     sp = {k: ops_.SPECULATION[k] - sp0.get(k, 0) for k in ("launched", "used", "discarded", "early_launched", "early_used",
                                                            "early_discarded")}
     mc = {k: ops_.MEMORY_CARRY[k] - mc0.get(k, 0) for k in ("in_the_solver_launch", "ahead_kept", "ahead_redone", "launched")}
+    def a_copy_tracks_on():
+        # a copy of the loop carries none of the call-to-call state (``TrackingLoop._CALL_STATE``: dropped by construction, not by
+        # a hand-kept list) and tracks the next frame as the original would: like the general path, as in every frame above
+        import copy
+        step = (lambda lp, f: lp(feats, traffic(rs[0], f))) if mode == "early" else (
+            lambda lp, f: lp._step_native(feats, traffic(rs[0], f), next_features=feats))
+        a, b = step(loops[0], 200), loops[1](feats, traffic(rs[1], 200))     # (one more frame: its memory is left unbuilt)
+        assert torch.equal(a.bbox, b.bbox) and torch.equal(a.get_field("ids"), b.get_field("ids"))
+        held = set(TrackingLoop._CALL_STATE) & set(loops[0].__dict__)
+        assert {"_plan", "_own_memory", "_prev_n_trk", "_prev_K", "_hint_extra", "_carry_ahead_kept"} <= held, held
+        assert not set(TrackingLoop._CALL_STATE) & set(loops[0].__getstate__()) and "track_memory" in loops[0].__getstate__()
+        twin = copy.copy(loops[0])
+        assert not set(TrackingLoop._CALL_STATE) & set(twin.__dict__) and twin.track_memory is loops[0].track_memory
+        assert type(twin.track_memory) is _LazyMemory and twin.track_memory._val is None
+        a, b = step(twin, 201), loops[1](feats, traffic(rs[1], 201))
+        assert torch.equal(a.bbox, b.bbox) and torch.equal(a.get_field("ids"), b.get_field("ids"))
+        assert torch.equal(a.get_field("scores"), b.get_field("scores")) and torch.equal(a.get_field("labels"), b.get_field("labels"))
+        assert pa.get_active_ids() == pb.get_active_ids() and list(pa._dormant_ids.items()) == list(pb._dormant_ids.items())
+        ma, mb = twin.track_memory, loops[1].track_memory
+        assert torch.equal(ma[0], mb[0]) and torch.equal(ma[1][0].bbox, mb[1][0].bbox) and torch.equal(ma[2][0].bbox, mb[2][0].bbox)
     if no_track:
         assert emu.no_head_frames >= 3, emu.no_head_frames      # calls without a head behind frames with rows did occur
-        return
+        return a_copy_tracks_on()
     if mode == "early":
         # every frame whose memory was left unbuilt (two of three: the comparison builds the third) started with the head
         # that the call before had prepared, whatever happened to the row count in between; none was launched twice
@@ -592,6 +612,7 @@ def test_frame_entry_point_bookkeeping_with_speculation_and_carried_rows_on_cpu(
     assert mc["in_the_solver_launch"] >= 60 and mc["ahead_kept"] >= 20 and mc["ahead_redone"] >= 20, mc
     assert emu.carried == mc["in_the_solver_launch"] and compared >= 60
     assert ops_.FALLBACKS["dormant_rows_on_the_host"] == fb0 and pa._kill_ids and pa._max_id > 25
+    a_copy_tracks_on()
 
 
 @pytest.mark.gpu
