@@ -7,6 +7,7 @@ import siammot_amd.ops as ops
 dev = torch.device("cuda:0")
 lib = ops.load_library()
 scales = (0.25, 0.125, 0.0625, 0.03125)
+_vp = lambda a: ctypes.cast(a, ctypes.c_void_p)
 for n in [int(a) for a in sys.argv[1:]] or [30]:
     boxes = bench.synthetic_boxes(n, (1280, 704)).to(dev)
     feats = bench.synthetic_features(1, dev)
@@ -14,14 +15,14 @@ for n in [int(a) for a in sys.argv[1:]] or [30]:
     z = ops.roi_align_levels(feats, boxes, boxes, 15, scales, 2)
     lv = ops.roi_align_levels(feats, boxes, boxes, 15, scales, 2, return_levels=True)[1].cpu().numpy()
     _, sr_h, hint = ops.emm_extract_cache(feats, boxes, 15, scales, 2, 512, 1.0, 0, hint=True)
-    fl, fp, hs, ws_, sc = ops._level_arrays(feats, scales)
+    fl, fp, hs, ws_, sc = ops._level_arrays(feats, scales)[:5]
     pc = (ctypes.c_int * 4)(128, 64, 32, 16)
     resp_h = torch.empty((n, 128, 16, 16), device=dev)
 
     def hinted():
         with ops.debug_library() as dbg:
             dbg.smot_debug_trace(ops._ptr(tr) if tracing else None)
-            rc = dbg.smot_debug_sr_xcorr_fused_hint_fwd(ops._cast(fp), ops._cast(hs), ops._cast(ws_), ops._cast(pc), ops._cast(sc), 4, 128,
+            rc = dbg.smot_debug_sr_xcorr_fused_hint_fwd(_vp(fp), _vp(hs), _vp(ws_), _vp(pc), _vp(sc), 4, 128,
                                                         ops._ptr(boxes), ops._ptr(sr_h), ops._ptr(z), n, ops._ptr(resp_h), ops._ptr(hint),
                                                         ops._stream(dev))
             dbg.smot_debug_trace(None)

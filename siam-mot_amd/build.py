@@ -32,10 +32,24 @@ ARCH = "gfx950"
 # 1 ulp ~ 1e-5 in the output).  FMAs are written explicitly (fmaf) where they are wanted.
 # (tower_wino.hip without -fno-slp-vectorize was measured: the packed adds hipcc then forms in the operand transform make
 # both forms of the kernel slower — fp32 main loop 40.6 k -> 42.4 k cycles, bf16 x 3 32.7 k -> 37.9 k)
-# (-mllvm -amdgpu-kernarg-preload-count=16 — leading scalar / pointer kernel arguments delivered in SGPRs with the wave
-# instead of through an s_load — was measured in round 6: the tower kernels get 4-10 dwords preloaded, kernels whose first
-# argument is a struct none; interleaved A/B of two library builds: 52.95 vs 52.75 us per frame pair WITH the flag. Not used.)
-FLAGS = ["-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "-ffp-contract=off", "--offload-arch=" + ARCH]
+# -mllvm -amdgpu-kernarg-preload-count=16: leading scalar / pointer kernel arguments are delivered in user SGPRs with the
+# wave instead of through an s_load from the kernel-argument segment (gfx950 takes 14 dwords beside the segment pointer; a
+# by-value struct ends the preloaded run, so the four frame-pair kernels lead with plain arguments — see the "Argument order"
+# comments at sr_xcorr_fused9_kernel, tower_wino_kernel and decode_kernel).  Their first data loads then need no scalar
+# round trip in front of them.  check_preload() below reads the result back from the built libraries.
+FLAGS = ["-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "-ffp-contract=off", "--offload-arch=" + ARCH,
+         "-mllvm", "-amdgpu-kernarg-preload-count=16"]
+
+# The frame pair's kernels, every instantiation of which must have its leading arguments preloaded, and what a workgroup of
+# the product's hot forms may use without losing its workgroups per CU: (substring of the mangled name, LDS bytes, VGPRs).
+PRELOAD_FAMILIES = ("sr_xcorr_fused9_kernel", "sr_xcorr_fused9_batched_kernel", "sr_xcorr_fused9_half_kernel",
+                    "sr_xcorr_fused9_half_batched_kernel", "sr_xcorr_fused9_nhwc_kernel", "tower_wino_kernel", "decode_kernel")
+HOT_FORMS = (
+    ("22sr_xcorr_fused9_kernelILi30ELi15ELi2ELb1ELi8ELb0ELi1EE", 76176, 128),     # two workgroups of eight waves per CU
+    ("22sr_xcorr_fused9_kernelILi15ELi15ELi2ELb0ELi8ELb0ELi0EE", 51728, 80),      # three (launch bound: 6 waves per SIMD)
+    ("17tower_wino_kernelILi0ELi2ELi0ELb1EE", 0, 256),                            # one of 512 threads (dynamic LDS: 122,880 B)
+    ("13decode_kernelILi2EE", 5072, 64),                                          # eight waves per SIMD
+)
 
 
 def _hipcc():
@@ -90,6 +104,78 @@ def _build_one(lib, sources, extra_flags, objdir, verbose):
     return lib
 
 
+def code_objects(lib):
+    """The gfx950 code objects (ELF images) inside a built library: one per source file, in its offload bundles."""
+    data = open(lib, "rb").read()
+    magic = b"__CLANG_OFFLOAD_BUNDLE__"
+    out, pos = [], data.find(magic)
+    while pos >= 0:
+        n = int.from_bytes(data[pos + 24:pos + 32], "little")
+        q = pos + 32
+        for _ in range(n):
+            off, size, tl = (int.from_bytes(data[q + 8 * k:q + 8 * k + 8], "little") for k in range(3))
+            triple = data[q + 24:q + 24 + tl].decode()
+            q += 24 + tl
+            if triple.startswith("hip") and ARCH in triple and size:
+                out.append(data[pos + off:pos + off + size])
+        pos = data.find(magic, pos + 1)
+    return out
+
+
+def kernel_descriptors(lib):
+    """{mangled kernel name: {"preload", "lds", "scratch", "vgprs"}} from the kernel descriptors (the 64-byte `<name>.kd`
+    objects, LLVM AMDGPUUsage "Kernel Descriptor") of every gfx950 code object in ``lib``."""
+    import struct
+    out = {}
+    for elf in code_objects(lib):
+        assert elf[:4] == b"\x7fELF" and elf[4] == 2 and elf[5] == 1, "code object: not a little-endian ELF64"
+        shoff, = struct.unpack_from("<Q", elf, 0x28)
+        shentsize, shnum = struct.unpack_from("<HH", elf, 0x3A)
+        secs = [struct.unpack_from("<IIQQQQIIQQ", elf, shoff + i * shentsize) for i in range(shnum)]
+        symtabs = [sec for sec in secs if sec[1] == 2] or [sec for sec in secs if sec[1] == 11]
+        for sec in symtabs:
+            stroff = secs[sec[6]][4]
+            for i in range(sec[5] // 24):
+                name_i, _, _, shndx, value, size = struct.unpack_from("<IBBHQQ", elf, sec[4] + 24 * i)
+                name = elf[stroff + name_i:elf.index(b"\0", stroff + name_i)].decode()
+                if not name.endswith(".kd") or size != 64 or not 0 < shndx < shnum:
+                    continue
+                kd = elf[secs[shndx][4] + value - secs[shndx][3]:][:64]
+                lds, scratch = struct.unpack_from("<II", kd, 0)
+                rsrc1, = struct.unpack_from("<I", kd, 48)
+                preload, = struct.unpack_from("<H", kd, 58)          # KERNARG_PRELOAD_SPEC_LENGTH: bits 470:464
+                out[name[:-3]] = {"preload": preload & 0x7F, "lds": lds, "scratch": scratch, "vgprs": ((rsrc1 & 0x3F) + 1) * 8}
+    return out
+
+
+def check_preload(lib, verbose=True):
+    """State the preload length the compiler gave each of the frame pair's kernels in ``lib``; raise if one got none, or
+    if a hot form's static LDS, scratch or register allocation left the budget of its workgroups per CU."""
+    kds = kernel_descriptors(lib)
+    fam = {k: v for k, v in kds.items() if any("%d%sI" % (len(f), f) in k for f in PRELOAD_FAMILIES)}
+    if not fam:
+        raise RuntimeError("%s: no kernel descriptor of the frame pair's kernels found" % lib)
+    lengths = sorted(set(v["preload"] for v in fam.values()))
+    if verbose:
+        print("%s: %d frame-pair kernel instantiations, preloaded kernel-argument dwords: %s" % (
+            os.path.basename(lib), len(fam), ", ".join(str(n) for n in lengths)), flush=True)
+    none = sorted(k for k, v in fam.items() if v["preload"] == 0)
+    if none:
+        raise RuntimeError("%s: no kernel arguments preloaded for %s" % (lib, ", ".join(none)))
+    for key, lds, vgprs in HOT_FORMS:
+        hits = [(k, v) for k, v in fam.items() if key in k]
+        if not hits:
+            raise RuntimeError("%s: hot kernel form %s not found" % (lib, key))
+        for k, v in hits:
+            if verbose:
+                print("  %s: preload %d dwords, LDS %d B, scratch %d B, %d VGPRs allocated" % (
+                    k, v["preload"], v["lds"], v["scratch"], v["vgprs"]), flush=True)
+            if v["lds"] != lds or v["scratch"] != 0 or v["vgprs"] > vgprs:
+                raise RuntimeError("%s: %s left its occupancy budget (LDS %d B, %d VGPRs, no scratch): %r" % (
+                    lib, k, lds, vgprs, v))
+    return fam
+
+
 def build(force=False, verbose=True, debug=True):
     """Compile every HIP source for gfx950 and link the product library (and, with ``debug``, the measurement
     library next to it).  Returns the product library's path."""
@@ -99,8 +185,10 @@ def build(force=False, verbose=True, debug=True):
                 os.remove(lib)
     if force or _stale(LIB, SOURCES):
         _build_one(LIB, SOURCES, [], os.path.join(CSRC, "obj"), verbose)
+        check_preload(LIB, verbose)
     if debug and (force or _stale(LIB_DEBUG, SOURCES + DEBUG_ONLY_SOURCES)):
         _build_one(LIB_DEBUG, SOURCES + DEBUG_ONLY_SOURCES, ["-DSMOT_DEBUG"], os.path.join(CSRC, "obj_debug"), verbose)
+        check_preload(LIB_DEBUG, verbose)
     return LIB
 
 

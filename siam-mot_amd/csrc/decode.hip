@@ -220,20 +220,57 @@ struct FinalizeArgs {
     float* conf;
     long long* idx_out;
     unsigned* ticket;       // [N], zero at launch
-    long long* trace;       // phase trace (smot_debug_trace) or nullptr: 8 stamps per workgroup
     int rx, rz;
     float pad, clip_w, clip_h;
+    int nband;              // bands per track = Ho + 1 = the launch's gridDim.y
     const int* poison;      // status word of the order hint this head's pooling + correlation kernel verified (sr_xcorr.hip,
                             // fx_verify_hint) or nullptr: non-zero = the hint did not describe the rois, the responses are
                             // not the rois' -> every row's box and score are written as NaN (reported, never silently used)
 };
 
+// What the band kernel takes behind its leading arguments (see decode_kernel).
+// (Neither this struct nor FinalizeArgs has padding or a member the kernel does not read: the segment loads' dead dwords are
+// registers hipcc re-uses at once, and the write then waits for the whole segment.)
+struct DecodeTail {
+    const float* cls_b;
+    const float* center_b;
+    const float* reg_b;
+    float one_minus_sigma, sigma;
+};
+
 // SPLIT: workgroups of 256*SPLIT threads; the band's output rows are divided among the SPLIT thread groups
 // (SPLIT = 2 halves the serial row walk of a lane at the price of a duplicated horizontal pass).
+//
+// Argument order.  The leading pointers and scalars arrive in user SGPRs with the wave (kernel-argument preload, build.py:
+// 14 dwords fit beside the segment pointer), everything behind them through the kernel-argument segment as before.  Ordered by
+// first use: `part` / `logits` (the source branch and the first vector loads), `boxes` and `hann` (requested beside them),
+// `trace` (the phase tracer's null test is the kernel's first branch: behind the segment it would hold back every load), then
+// tpt, Ho (addresses of the first loads), up, G (the band's rows: hann's address).  inv_up, use_centerness, F.nband and the
+// three bias pointers do not fit: they are first used behind the first loads' issue (the biases' loads then wait for the segment, beside
+// the partial sums' round trip, and are consumed behind it).
+// F.nband = Ho + 1 = gridDim.y and 256 * SPLIT = blockDim.x: both were reads through the implicit-argument pointer, one more
+// dependent scalar load in front of the first data load.
 template <int SPLIT>
 __global__ void __launch_bounds__(256 * SPLIT)
-decode_kernel(LogitSrc L, const float* __restrict__ boxes, const float* __restrict__ hann, DecodeParams D,
-              unsigned long long* __restrict__ cand, FinalizeArgs F) {
+decode_kernel(const float* __restrict__ part_in, const float* __restrict__ logits_in, const float* __restrict__ boxes,
+              const float* __restrict__ hann, long long* __restrict__ trace, int tpt, int Ho_in, int up_in, int G_in,
+              float inv_up, int use_centerness, DecodeTail T, unsigned long long* __restrict__ cand, FinalizeArgs F) {
+    LogitSrc L;
+    L.logits = logits_in;
+    L.part = part_in;
+    L.tpt = tpt;
+    L.cls_b = T.cls_b;
+    L.center_b = T.center_b;
+    L.reg_b = T.reg_b;
+    L.logits_out = nullptr;
+    DecodeParams D;
+    D.Ho = Ho_in;
+    D.up = up_in;
+    D.G = G_in;
+    D.inv_up = inv_up;
+    D.one_minus_sigma = T.one_minus_sigma;
+    D.sigma = T.sigma;
+    D.use_centerness = use_centerness;
     extern __shared__ __attribute__((aligned(16))) float lg[];   // [7][Ho][Ho]
     __shared__ unsigned long long wbest[4 * SPLIT];
     __shared__ unsigned nom[DEC_NOM];     // flat indices of the cells nominated for exact re-scoring
@@ -247,15 +284,27 @@ decode_kernel(LogitSrc L, const float* __restrict__ boxes, const float* __restri
     const int n = blockIdx.x;
     const int f = (int)blockIdx.y - 1;                 // bicubic source row of this band
     const int Ho = D.Ho, up = D.up, G = D.G;
-    const int nband = gridDim.y;
+    const int nband = F.nband;                         // (= Ho + 1; the tracer's first stamp below spells it from the preloaded Ho)
 #define DC_TRACE(SLOT)                                                                                          \
-    if (F.trace && threadIdx.x == 0)                                                                            \
-        F.trace[((size_t)blockIdx.x * gridDim.y + blockIdx.y) * 8 + (SLOT)] = (long long)__builtin_amdgcn_s_memtime();
+    if (trace && threadIdx.x == 0)                                                                              \
+        trace[((size_t)blockIdx.x * (Ho + 1) + blockIdx.y) * 8 + (SLOT)] = (long long)__builtin_amdgcn_s_memtime();
     DC_TRACE(0)
+    const int y_begin = max(0, up * f + up / 2);
+    const int y_end = min(G, up * f + up / 2 + up);
+    // the window's row factors and the track's box are requested in front of the source loads (their addresses need nothing
+    // but preloaded arguments; vector loads return in order, so the source values' wait is not held back by them) and used
+    // where they were: behind the source values / behind the first barrier
+    float hy_early = 0.0f, box_early[4];
+    auto request_early = [&]() {
+        if ((int)threadIdx.x < y_end - y_begin) hy_early = hann[y_begin + threadIdx.x];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) box_early[k] = boxes[n * 4 + k];
+    };
+    request_early();
     if (L.logits != nullptr) {
         // a band only touches its four source rows f-1..f+2 (clamped) of the seven planes: 28 * Ho logits, not 7 * Ho^2
         // (at Ho = 29 the whole image was 23.5 KB per workgroup, 900 workgroups: 21 MB of loads for 2.9 MB of need)
-        for (int e = threadIdx.x; e < 28 * Ho; e += blockDim.x) {          // (ch, k, col)
+        for (int e = threadIdx.x; e < 28 * Ho; e += 256 * SPLIT) {          // (ch, k, col)
             const int ch = e / (4 * Ho), r = e - ch * 4 * Ho;
             const int k = r / Ho, col = r - k * Ho;
             const int row = clampi(f - 1 + k, 0, Ho - 1);
@@ -279,8 +328,6 @@ decode_kernel(LogitSrc L, const float* __restrict__ boxes, const float* __restri
             if (e < 448) lg[ch * 256 + row * 16 + (e & 15)] = c2[j];   // clamped duplicates write equal values
         }
     }
-    const int y_begin = max(0, up * f + up / 2);
-    const int y_end = min(G, up * f + up / 2 + up);
     if ((int)threadIdx.x < y_end - y_begin) {      // row coefficients are lane-independent: once per band
         int by;
         float ty, w4[4];
@@ -290,12 +337,12 @@ decode_kernel(LogitSrc L, const float* __restrict__ boxes, const float* __restri
         wy_tab[threadIdx.x][1] = w4[1];
         wy_tab[threadIdx.x][2] = w4[2];
         wy_tab[threadIdx.x][3] = w4[3];
-        hy_tab[threadIdx.x] = hann[y_begin + threadIdx.x];
+        hy_tab[threadIdx.x] = hy_early;
     }
     __syncthreads();
 
-    const float box_w = sub_rn(boxes[n * 4 + 2], boxes[n * 4 + 0]);
-    const float box_h = sub_rn(boxes[n * 4 + 3], boxes[n * 4 + 1]);
+    const float box_w = sub_rn(box_early[2], box_early[0]);
+    const float box_h = sub_rn(box_early[3], box_early[1]);
     const float inv_bw = div_rn(1.0f, box_w), inv_bh = div_rn(1.0f, box_h);
     int rows[4];
 #pragma unroll
@@ -493,7 +540,7 @@ decode_kernel(LogitSrc L, const float* __restrict__ boxes, const float* __restri
     unsigned old = 0u;
     if (lane == 0) old = __hip_atomic_fetch_add((gu32_t*)(F.ticket + n), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     old = (unsigned)__builtin_amdgcn_readfirstlane((int)old);
-    if (F.trace && lane == 0) F.trace[((size_t)blockIdx.x * gridDim.y + blockIdx.y) * 8 + 6] = (long long)__builtin_amdgcn_s_memtime();
+    if (trace && lane == 0) trace[((size_t)blockIdx.x * nband + blockIdx.y) * 8 + 6] = (long long)__builtin_amdgcn_s_memtime();
     if (old != (unsigned)(nband - 1)) return;
 
     // ---- last workgroup of the track: arg-max over the bands' exact winners, box, confidence --------------------
@@ -554,7 +601,7 @@ decode_kernel(LogitSrc L, const float* __restrict__ boxes, const float* __restri
     const float e0 = expf(sub_rn(v[0], m)), e1 = expf(sub_rn(v[1], m));
     F.conf[n] = (poisoned != 0) ? qnan : div_rn(e1, add_rn(e0, e1));
     if (F.idx_out != nullptr) F.idx_out[n] = (long long)idx;
-    if (F.trace) F.trace[((size_t)blockIdx.x * gridDim.y + blockIdx.y) * 8 + 7] = (long long)__builtin_amdgcn_s_memtime();
+    if (trace) trace[((size_t)blockIdx.x * nband + blockIdx.y) * 8 + 7] = (long long)__builtin_amdgcn_s_memtime();
 #undef DC_TRACE
 }
 
@@ -643,8 +690,9 @@ int decode_impl(LogitSrc L, const float* sr, const float* boxes, const float* ha
     F.pad = pad_pixels;
     F.clip_w = clip_w;
     F.clip_h = clip_h;
-    F.trace = g_trace;
+    F.nband = Ho + 1;
     F.poison = poison;
+    const DecodeTail T = {L.cls_b, L.center_b, L.reg_b, one_minus_sigma, sigma};
     if (!tickets_zeroed) {
         hipError_t e = hipMemsetAsync(F.ticket, 0, (size_t)N * sizeof(unsigned), st);
         if (e != hipSuccess) {
@@ -653,11 +701,14 @@ int decode_impl(LogitSrc L, const float* sr, const float* boxes, const float* ha
         }
     }
     if (split == 4) {
-        SMOT_LAUNCH(decode_kernel<4>, dim3(N, Ho + 1), dim3(1024), smem, st, L, boxes, hann, D, cand, F);
+        SMOT_LAUNCH(decode_kernel<4>, dim3(N, Ho + 1), dim3(1024), smem, st, L.part, L.logits, boxes, hann, g_trace, L.tpt, Ho, up, (int)G,
+                    D.inv_up, use_centerness, T, cand, F);
     } else if (split == 2) {
-        SMOT_LAUNCH(decode_kernel<2>, dim3(N, Ho + 1), dim3(512), smem, st, L, boxes, hann, D, cand, F);
+        SMOT_LAUNCH(decode_kernel<2>, dim3(N, Ho + 1), dim3(512), smem, st, L.part, L.logits, boxes, hann, g_trace, L.tpt, Ho, up, (int)G,
+                    D.inv_up, use_centerness, T, cand, F);
     } else {
-        SMOT_LAUNCH(decode_kernel<1>, dim3(N, Ho + 1), dim3(256), smem, st, L, boxes, hann, D, cand, F);
+        SMOT_LAUNCH(decode_kernel<1>, dim3(N, Ho + 1), dim3(256), smem, st, L.part, L.logits, boxes, hann, g_trace, L.tpt, Ho, up, (int)G,
+                    D.inv_up, use_centerness, T, cand, F);
     }
     return check_launch("decode");
 }

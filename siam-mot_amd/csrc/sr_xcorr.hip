@@ -179,9 +179,9 @@ __device__ __forceinline__ float4 search_region_of(float b0, float b1, float b2,
 // sequence), against the pad cells the next frame's pooling uses.
 template <int RXN, int G>
 __device__ __forceinline__ void fx_write_hint(const LevelParams& P, const float* __restrict__ boxes, const SrOut& S,
-                                              int NT, int x, int wave, int lane) {
+                                              const int* n_valid, float* hint_out, int NT, int x, int wave, int lane) {
     if (NT > 256 || wave >= 2) return;                         // (the consumer keeps grid order beyond 256 rois)
-    const int nv = (S.n_valid != nullptr) ? min(*S.n_valid + S.hint_extra, NT) : NT;
+    const int nv = (n_valid != nullptr) ? min(*n_valid + S.hint_extra, NT) : NT;
     if (x >= nv) return;
     unsigned long long mask[4][3];
     int cnt[3] = {0, 0, 0};
@@ -231,7 +231,7 @@ __device__ __forceinline__ void fx_write_hint(const LevelParams& P, const float*
     const float x2 = mul_rn(roi.z, scale), y2 = mul_rn(roi.w, scale);
     const float bin_h = div_rn(fmaxf(sub_rn(y2, y1), 1.0f), (float)RXN);
     const float bin_w = div_rn(fmaxf(sub_rn(x2, x1), 1.0f), (float)RXN);
-    int* ent = reinterpret_cast<int*>(S.hint_out) + (size_t)rank * HINT_FLOATS;
+    int* ent = reinterpret_cast<int*>(hint_out) + (size_t)rank * HINT_FLOATS;
     int lo = 0, hi = 0;
     float wl = 0.0f, wh = 0.0f;
     if (lane < RXN * G) {
@@ -271,7 +271,7 @@ __device__ __forceinline__ void fx_write_hint(const LevelParams& P, const float*
             ent[HINT_GEOM + 2] = W;
             ent[HINT_GEOM + 3] = __float_as_int(scale);           // (the tables were built with this scale: part of the stamp)
             // the by-roi record of roi x, in entry x (not entry `rank`): what the consumer verifies against its own tensors
-            int* rec = reinterpret_cast<int*>(S.hint_out) + (size_t)x * HINT_FLOATS + HINT_BYROI;
+            int* rec = reinterpret_cast<int*>(hint_out) + (size_t)x * HINT_FLOATS + HINT_BYROI;
             float4* r4 = reinterpret_cast<float4*>(rec);
             r4[0] = roi;
             rec[4] = lvl;
@@ -327,11 +327,10 @@ __device__ __forceinline__ void fx_verify_hint(const LevelParams& P, const float
 // workgroup's own roi loads — a second dependent memory round trip — are then not needed).
 __device__ __forceinline__ bool fx_assign(const LevelParams& P, const float* __restrict__ sr,
                                           const float* __restrict__ boxes, const int* __restrict__ n_valid, int order,
-                                          int by, int ny, const float* __restrict__ hint, int lane, int* n_out,
+                                          int by, int ny, const float* __restrict__ hint, int NT, int lane, int* n_out,
                                           int* cg_out, float4* roi_out, int* lvl_out, int* k_out) {
     // (by, ny): the workgroup's row and the number of rows of the (roi, channel group) grid — blockIdx.y / gridDim.y
-    // less the hint row of an extraction launch
-    const int NT = gridDim.x;
+    // less the hint row of an extraction launch; NT = gridDim.x (a kernel argument: see FX_LEAD_PARAMS)
     int n = blockIdx.x, cg = by;
     *n_out = n;
     *cg_out = cg;
@@ -467,11 +466,28 @@ __device__ __forceinline__ bool fx_assign(const LevelParams& P, const float* __r
 // MM == 2: the LEAN layout of the same (xl_*: 5,760 B per plane) — three workgroups per CU again.
 // The kernel's body is in sr_xcorr_fused9_body.h (shared with the batched form below).
 
+// Argument order, for every form of the kernel.  The leading 14 dwords arrive in user SGPRs with the wave (kernel-argument
+// preload, build.py), everything behind them through the kernel-argument segment; ordered by first use:
+//   hint     the order hint: the list this launch honours (XCORR: SrOut::hint_in) or writes (pool-only: SrOut::hint_out) — the
+//            consumer's entry, tables and by-roi record are its first loads, the writer's row its first branch;
+//   n_valid  the masked form's count (a scalar load and the first early return);
+//   sr, boxes  the rois (fx_assign / fx_verify_hint, the extraction's own roi);
+//   trace    the phase tracer's null test is the kernel's first instruction;
+//   order, grid_nx, grid_ny  the assignment; grid_nx / grid_ny = gridDim.x / gridDim.y, which were reads through the
+//            implicit-argument pointer (behind the segment, in front of the hint entry's address);
+//   C        the channel tail.
+// The template pointer, the outputs (search regions and templates of the extraction role: SrOut::sr, x_debug) and the structs
+// do not fit the user SGPRs: their first use is behind the assignment's round trip.  SrOut keeps its members of the same
+// names for the host code and the generation-2 kernel; the kernels here read the leading arguments.
+#define FX_LEAD_PARAMS                                                                                                  \
+    float *hint, const int *n_valid, const float *__restrict__ sr, const float *__restrict__ boxes,                     \
+        long long *__restrict__ trace, int order, int grid_nx, int grid_ny, int C
+#define FX_TAIL_PARAMS                                                                                                  \
+    const float *__restrict__ z, float *__restrict__ resp, float *__restrict__ x_debug, int32_t *__restrict__ levels_out, \
+        LevelParams P, SrOut S
 template <int RX, int RZ, int G, bool XCORR, int NCH = FX_CH, bool P2 = false, int MM = 0>
 __global__ void __launch_bounds__(64 * NCH, (P2 || MM == 1) ? 4 : 6) // <= 80 VGPRs: THREE workgroups (24 waves) per CU (LDS allows three)
-sr_xcorr_fused9_kernel(LevelParams P, int C, const float* __restrict__ sr, const float* __restrict__ boxes,
-                       const float* __restrict__ z, float* __restrict__ resp, float* __restrict__ x_debug,
-                       int32_t* __restrict__ levels_out, SrOut S) {
+sr_xcorr_fused9_kernel(FX_LEAD_PARAMS, FX_TAIL_PARAMS) {
     constexpr bool BATCHED = false;
     constexpr NoImages I{};
     using FT = float;
@@ -483,9 +499,7 @@ sr_xcorr_fused9_kernel(LevelParams P, int C, const float* __restrict__ sr, const
 // adds its roi's image (I.row_start) to the level's 64-bit base address.
 template <int RX, int RZ, int G, bool XCORR, int NCH = FX_CH, int MM = 0>
 __global__ void __launch_bounds__(64 * NCH, MM == 1 ? 4 : 6)
-sr_xcorr_fused9_batched_kernel(LevelParams P, int C, const float* __restrict__ sr, const float* __restrict__ boxes,
-                               const float* __restrict__ z, float* __restrict__ resp, float* __restrict__ x_debug,
-                               int32_t* __restrict__ levels_out, SrOut S, ImageRows I) {
+sr_xcorr_fused9_batched_kernel(FX_LEAD_PARAMS, FX_TAIL_PARAMS, ImageRows I) {
     constexpr bool BATCHED = true;
     constexpr bool P2 = false;
     using FT = float;
@@ -497,9 +511,7 @@ sr_xcorr_fused9_batched_kernel(LevelParams P, int C, const float* __restrict__ s
 // image offset of the batched form is in elements of FT.  Only the product's forms exist (no A/B variants).
 template <typename FT, int RX, int RZ, int G, bool XCORR, int MM = 0>
 __global__ void __launch_bounds__(64 * FX_CH, MM == 1 ? 4 : 6)
-sr_xcorr_fused9_half_kernel(LevelParams P, int C, const float* __restrict__ sr, const float* __restrict__ boxes,
-                            const float* __restrict__ z, float* __restrict__ resp, float* __restrict__ x_debug,
-                            int32_t* __restrict__ levels_out, SrOut S) {
+sr_xcorr_fused9_half_kernel(FX_LEAD_PARAMS, FX_TAIL_PARAMS) {
     static_assert(sizeof(FT) == 2, "fp16 / bf16 maps");
     constexpr bool BATCHED = false;
     constexpr NoImages I{};
@@ -510,9 +522,7 @@ sr_xcorr_fused9_half_kernel(LevelParams P, int C, const float* __restrict__ sr, 
 }
 template <typename FT, int RX, int RZ, int G, bool XCORR, int MM = 0>
 __global__ void __launch_bounds__(64 * FX_CH, MM == 1 ? 4 : 6)
-sr_xcorr_fused9_half_batched_kernel(LevelParams P, int C, const float* __restrict__ sr, const float* __restrict__ boxes,
-                                    const float* __restrict__ z, float* __restrict__ resp, float* __restrict__ x_debug,
-                                    int32_t* __restrict__ levels_out, SrOut S, ImageRows I) {
+sr_xcorr_fused9_half_batched_kernel(FX_LEAD_PARAMS, FX_TAIL_PARAMS, ImageRows I) {
     static_assert(sizeof(FT) == 2, "fp16 / bf16 maps");
     constexpr bool BATCHED = true;
     constexpr int NCH = FX_CH;
@@ -528,9 +538,7 @@ sr_xcorr_fused9_half_batched_kernel(LevelParams P, int C, const float* __restric
 // registers: 128 VGPRs, two workgroups of eight waves per CU, for every form.)
 template <typename FT, int RX, int RZ, int G, bool XCORR, int MM = 0>
 __global__ void __launch_bounds__(64 * FX_CH, 4)
-sr_xcorr_fused9_nhwc_kernel(LevelParams P, int C, const float* __restrict__ sr, const float* __restrict__ boxes,
-                            const float* __restrict__ z, float* __restrict__ resp, float* __restrict__ x_debug,
-                            int32_t* __restrict__ levels_out, SrOut S, ImageRows I) {
+sr_xcorr_fused9_nhwc_kernel(FX_LEAD_PARAMS, FX_TAIL_PARAMS, ImageRows I) {
     constexpr bool BATCHED = true;
     constexpr int NCH = FX_CH;
     constexpr bool P2 = false;
@@ -565,8 +573,10 @@ static void launch_fused(dim3 grid, hipStream_t st, const LevelParams& P, int C,
                          const float* z, float* resp, float* out, int32_t* levels_out, const SrOut& S, const ImageRows* I) {
     constexpr int MM = (RX == 30 && XCORR) ? 1 : 0;
     // (the batched wrappers and the channels-last ones take row ranges behind the single-image wrappers' arguments)
+    float* const hint = XCORR ? const_cast<float*>(S.hint_in) : S.hint_out;      // (the kernels' leading arguments: FX_LEAD_PARAMS)
     auto launch = [&](auto kernel, size_t smem, const auto&... rows) {
-        SMOT_LAUNCH(kernel, grid, dim3(512), smem, st, P, C, rois, boxes, z, resp, out, levels_out, S, rows...);
+        SMOT_LAUNCH(kernel, grid, dim3(512), smem, st, hint, S.n_valid, rois, boxes, S.trace, S.order, (int)grid.x, (int)grid.y,
+                    C, z, resp, out, levels_out, P, S, rows...);
     };
     if (channels_last()) {
         with_feat_type([&](auto ft) {
@@ -710,18 +720,21 @@ int sr_xcorr_fused_impl(const float* const* feats, const int* heights, const int
     if (I == nullptr && knobs().fused_abl == 5) {       // A/B: the correlation on plane pairs with 4x2 patches (half the LDS read volume)
         hipEvent_t e0_, e1_;
         if (timer_take(&e0_, &e1_)) {
-            hipExtLaunchKernelGGL((sr_xcorr_fused9_kernel<30, 15, 2, true, 8, true>), grid, dim3(512), 0, st, e0_, e1_, 0, P, C, sr, boxes,
-                                  templates, resp, x_debug, (int32_t*)nullptr, none);
+            hipExtLaunchKernelGGL((sr_xcorr_fused9_kernel<30, 15, 2, true, 8, true>), grid, dim3(512), 0, st, e0_, e1_, 0,
+                                  const_cast<float*>(none.hint_in), none.n_valid, sr, boxes, none.trace, none.order, (int)grid.x,
+                                  (int)grid.y, C, templates, resp, x_debug, (int32_t*)nullptr, P, none);
         } else {
-            hipLaunchKernelGGL((sr_xcorr_fused9_kernel<30, 15, 2, true, 8, true>), grid, dim3(512), 0, st, P, C, sr, boxes,
-                               templates, resp, x_debug, (int32_t*)nullptr, none);
+            hipLaunchKernelGGL((sr_xcorr_fused9_kernel<30, 15, 2, true, 8, true>), grid, dim3(512), 0, st,
+                               const_cast<float*>(none.hint_in), none.n_valid, sr, boxes, none.trace, none.order, (int)grid.x,
+                               (int)grid.y, C, templates, resp, x_debug, (int32_t*)nullptr, P, none);
         }
         timer_mark(0, 1, st);
         return check_launch("sr_xcorr_fused");
     }
     if (I == nullptr && knobs().fused_abl == 4) {
-        hipLaunchKernelGGL((sr_xcorr_fused9_kernel<30, 15, 2, true, 4>), dim3(N, (C + 3) / 4), dim3(256), 0, st, P, C, sr, boxes,
-                           templates, resp, x_debug, (int32_t*)nullptr, none);
+        hipLaunchKernelGGL((sr_xcorr_fused9_kernel<30, 15, 2, true, 4>), dim3(N, (C + 3) / 4), dim3(256), 0, st,
+                           const_cast<float*>(none.hint_in), none.n_valid, sr, boxes, none.trace, none.order, N, (C + 3) / 4, C,
+                           templates, resp, x_debug, (int32_t*)nullptr, P, none);
         timer_mark(0, 1, st);
         return check_launch("sr_xcorr_fused");
     }

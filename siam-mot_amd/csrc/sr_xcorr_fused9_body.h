@@ -26,7 +26,17 @@
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // 0..7
-    const long long t_start = S.trace ? (long long)__builtin_amdgcn_s_memtime() : 0ll;
+    // (the leading kernel arguments — FX_LEAD_PARAMS in sr_xcorr.hip — under the names the text below uses)
+    const float* const hint_in = XCORR ? hint : nullptr;
+    float* const hint_out = XCORR ? nullptr : hint;
+    const long long t_start = trace ? (long long)__builtin_amdgcn_s_memtime() : 0ll;
+    // pooled sizes <= 15 keep grid order (fx_assign: n = blockIdx.x): the workgroup's roi is requested now, beside the masked
+    // form's count, and used where the loads stood
+    float roi_early[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if constexpr (RX <= 15) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) roi_early[k] = sr[(size_t)blockIdx.x * 4 + k];
+    }
     // The level's map size, padding, scale and base pointer are read from the kernel-argument segment with a DYNAMIC index
     // once the level is known: scalar loads that DEPEND on the workgroup's first memory round trip and — at a kernel's start,
     // with the scalar cache and the XCD's L2 freshly invalidated — may miss all the way to memory.  Their three 64-byte lines
@@ -48,7 +58,7 @@
     // Measured: 17.0 us at no delay, 17.05-17.2 us for delays of 2 k .. 8 k cycles, 18.0 at 16 k — the late workgroup
     // catches up exactly: a CU's time is the SUM of its workgroups' instruction issue (1,500 vector instructions per
     // wave, 900 of them the correlation's FMAs), not a chain of latencies that a phase shift could overlap.
-    if (S.abl >= 100 && (int)(blockIdx.y * gridDim.x + blockIdx.x) >= 256) {
+    if (S.abl >= 100 && (int)(blockIdx.y * grid_nx + blockIdx.x) >= 256) {
         for (int d = 0; d < S.abl - 100; ++d) __builtin_amdgcn_s_sleep(8);
     }
 #endif
@@ -65,11 +75,11 @@
     // Also measured and dropped for the 33..64-column windows that set the makespan: three 10-row blocks per plane with
     // the next block's row loads issued before the current block's gathers (96 VGPRs, two workgroups per CU):
     // bit-identical, 17.0 instead of 16.75 us at 30 rois, 12.9 instead of 12.3 at 16 (profiles/r02_fused_pipelined_wide.jsonl).
-    int grid_row = blockIdx.y, grid_rows = gridDim.y;
+    int grid_row = blockIdx.y, grid_rows = grid_ny;
     if constexpr (!XCORR) {
-        if (S.hint_out != nullptr) {                 // extraction launch with one extra row in front: the hint writer
+        if (hint_out != nullptr) {                 // extraction launch with one extra row in front: the hint writer
             if (grid_row == 0) {
-                fx_write_hint<30, G>(P, boxes, S, gridDim.x, blockIdx.x, wave, lane);     // (the consumer's shape: 30x30 bins)
+                fx_write_hint<30, G>(P, boxes, S, n_valid, hint_out, grid_nx, blockIdx.x, wave, lane);     // (the consumer's shape: 30x30 bins)
                 return;
             }
             grid_row -= 1;
@@ -83,9 +93,9 @@
     typedef int v8h_t __attribute__((ext_vector_type(8)));
     v8h_t g8 = {0, 0, 0, 0, -1, -1, -1, 0};
     if constexpr (XCORR && RX == 30) {
-        if (S.hint_in != nullptr && S.order == 1 && S.n_valid == nullptr && gridDim.x >= 2 && gridDim.x <= 256) {
-            const int k0 = (int)(blockIdx.y * gridDim.x + blockIdx.x) / (int)gridDim.y;        // = fx_assign's rank k
-            const int* ent = reinterpret_cast<const int*>(S.hint_in) + (size_t)k0 * HINT_FLOATS;
+        if (hint_in != nullptr && order == 1 && n_valid == nullptr && grid_nx >= 2 && grid_nx <= 256) {
+            const int k0 = (int)(blockIdx.y * grid_nx + blockIdx.x) / grid_ny;        // = fx_assign's rank k
+            const int* ent = reinterpret_cast<const int*>(hint_in) + (size_t)k0 * HINT_FLOATS;
             g8 = *reinterpret_cast<const __attribute__((address_space(4))) v8h_t*>(
                 reinterpret_cast<unsigned long long>(ent) + 4ull * HINT_BOUNDS);
             if (wave < 2) tab_early = *reinterpret_cast<const int4*>(ent + (wave == 0 ? HINT_YTAB : HINT_XTAB) + 4 * lane);
@@ -102,17 +112,17 @@
         }
     }
     if constexpr (XCORR && RX == 30) {
-        if (S.hint_in != nullptr && S.order == 1 && S.n_valid == nullptr && gridDim.x >= 2 && gridDim.x <= 256 &&
+        if (hint_in != nullptr && order == 1 && n_valid == nullptr && grid_nx >= 2 && grid_nx <= 256 &&
             blockIdx.y == 0 && wave == 2
 #ifdef SMOT_DEBUG
             && S.abl != 6                 // A/B (measurement library, SMOT_FUSED_ABL=6): the round-4 kernel that trusted the hint
 #endif
         )
-            fx_verify_hint(P, sr, boxes, S.hint_in, blockIdx.x, gridDim.x, lane);
+            fx_verify_hint(P, sr, boxes, hint_in, blockIdx.x, grid_nx, lane);
     }
     int k_assigned = -1;
-    const bool have_roi = fx_assign(P, sr, boxes, S.n_valid, RX > 15 ? S.order : 0, grid_row, grid_rows,
-                                    XCORR ? S.hint_in : nullptr, lane, &n_assigned, &cg_assigned, &roi_assigned,
+    const bool have_roi = fx_assign(P, sr, boxes, n_valid, RX > 15 ? order : 0, grid_row, grid_rows,
+                                    XCORR ? hint_in : nullptr, grid_nx, lane, &n_assigned, &cg_assigned, &roi_assigned,
                                     &lvl_assigned, &k_assigned);
     SMOT_KA_USE();
 #undef SMOT_KA_USE
@@ -120,23 +130,30 @@
         asm volatile("" ::"s"(ka_i[0]), "s"(ka_i[1]), "s"(ka_i[2]), "s"(ka_i[3]), "s"(ka_i[4]), "s"(ka_i[5]));
     const int n = __builtin_amdgcn_readfirstlane(n_assigned);
     const int cgrp = __builtin_amdgcn_readfirstlane(cg_assigned);
-    if (S.n_valid != nullptr && n >= *S.n_valid) return;         // workgroup-uniform (scalar load)
+    if (n_valid != nullptr && n >= *n_valid) return;         // workgroup-uniform (scalar load)
     int img = 0;                                                 // the roi's image (batched form)
     if constexpr (BATCHED) img = image_of_row(I, n);
     // (trace rows are indexed by the item, not by the workgroup that happened to take it)
 #define FX_TRACE(SLOT)                                                                      \
-    if (S.trace && tid == 0)                                                                \
-        S.trace[((size_t)n * grid_rows + cgrp) * 8 + (SLOT)] = (long long)__builtin_amdgcn_s_memtime();
-    if (S.trace && tid == 0) S.trace[((size_t)n * grid_rows + cgrp) * 8 + 0] = t_start;
+    if (trace && tid == 0)                                                                  \
+        trace[((size_t)n * grid_rows + cgrp) * 8 + (SLOT)] = (long long)__builtin_amdgcn_s_memtime();
+    if (trace && tid == 0) trace[((size_t)n * grid_rows + cgrp) * 8 + 0] = t_start;
     FX_TRACE(5)                                   // after the assignment
 
     float roi0 = roi_assigned.x, roi1 = roi_assigned.y, roi2 = roi_assigned.z, roi3 = roi_assigned.w;
     int lvl = lvl_assigned;
     if (!have_roi) {                             // workgroup-uniform
-        roi0 = sr[(size_t)n * 4 + 0];
-        roi1 = sr[(size_t)n * 4 + 1];
-        roi2 = sr[(size_t)n * 4 + 2];
-        roi3 = sr[(size_t)n * 4 + 3];
+        if constexpr (RX <= 15) {                // (n == blockIdx.x)
+            roi0 = roi_early[0];
+            roi1 = roi_early[1];
+            roi2 = roi_early[2];
+            roi3 = roi_early[3];
+        } else {
+            roi0 = sr[(size_t)n * 4 + 0];
+            roi1 = sr[(size_t)n * 4 + 1];
+            roi2 = sr[(size_t)n * 4 + 2];
+            roi3 = sr[(size_t)n * 4 + 3];
+        }
         lvl = 0;
         if (P.num_levels > 1) lvl = map_level(boxes + (size_t)n * 4, P.k_min, P.k_max);
     }

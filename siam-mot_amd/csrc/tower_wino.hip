@@ -182,11 +182,17 @@ __device__ __forceinline__ void heads_group(const float (&hw)[9], const float (&
 // profiles/r04_ubench_bf16x3_rate.jsonl).  The transformed operands of a K = 32 block (four stages) are collected as
 // packed bf16 pairs in 96 registers, then one burst of 96 instructions consumes them against A parts fetched as needed.
 // OCT = 2 only (also in BLOCKED mode: the same loop over 18 x 18 windows).
+// Argument order.  The leading 14 dwords arrive in user SGPRs with the wave (kernel-argument preload, build.py), ordered by
+// first use: the response and the packed weight image (the first stage and A fetches), the plane maxima (requested beside
+// them), the ticket words and the tracer (the kernel's first branches), N and C (the workgroup's track and every offset);
+// cpg and eps fill the remaining two.  `part` and the GroupNorm / head parameters are first used in the epilogue and come
+// through the kernel-argument segment.  (Before: three dependent segment loads and waits — tracer, N / C, the pointers — in
+// front of the first fetch.)
 template <int ABL, int OCT, int BHO = 0, bool BF3 = false>
 __global__ void __launch_bounds__(256 * OCT, OCT == 1 ? 2 : 1)
-tower_wino_kernel(const float* __restrict__ resp, const float* __restrict__ packed, TowerParams P, int N, int C,
-                  int cpg, float eps, float* __restrict__ part, unsigned* __restrict__ zero_words,
-                  long long* __restrict__ trace, const float* __restrict__ plane_max) {
+tower_wino_kernel(const float* __restrict__ resp, const float* __restrict__ packed, const float* __restrict__ plane_max,
+                  unsigned* __restrict__ zero_words, long long* __restrict__ trace, int N, int C, int cpg, float eps,
+                  float* __restrict__ part, TowerParams P) {
     constexpr int NT = 256 * OCT;             // threads
     constexpr int NP = 2 / OCT;               // tile-row halves (pairs of N-tiles) per wave
     constexpr bool BLOCKED = BHO > 0;
@@ -1000,8 +1006,8 @@ static int tower_tiles_per_workgroup(int N, int C) {
 }
 
 // A form of the kernel with its workgroup size and dynamic LDS: picked once per launch, for the LDS opt-in and the launch.
-typedef void (*tower_wino_fn)(const float*, const float*, TowerParams, int, int, int, float, float*, unsigned*, long long*,
-                              const float*);
+typedef void (*tower_wino_fn)(const float*, const float*, const float*, unsigned*, long long*, int, int, int, float, float*,
+                              TowerParams);
 struct TowerForm {
     tower_wino_fn fn;
     int threads;
@@ -1062,8 +1068,8 @@ int launch_tower_wino(const float* resp, const float* packed, const TowerParams&
         if (rco) return rco;
     }
     SMOT_REQUIRE(!f.split || plane_max != nullptr, "predictor towers: the split form needs the response's plane maxima");
-    SMOT_LAUNCH(f.fn, dim3(grid), dim3(f.threads), f.smem, st, resp, packed, P, N, C, cpg, eps, part, zero_words, g_trace,
-                plane_max);
+    SMOT_LAUNCH(f.fn, dim3(grid), dim3(f.threads), f.smem, st, resp, packed, plane_max, zero_words, g_trace, N, C, cpg, eps,
+                part, P);
     return check_launch(f.split ? "predictor towers (winograd, fp16 x 2)" : "predictor towers (winograd)");
 }
 
@@ -1103,8 +1109,8 @@ int launch_tower_wino_blocks(const float* resp, const float* packed, const Tower
         if (rco) return rco;
     }
     SMOT_REQUIRE(!f.split || plane_max != nullptr, "predictor towers: the split form needs the response's plane maxima");
-    SMOT_LAUNCH(f.fn, dim3(grid), dim3(f.threads), f.smem, st, resp, packed, P, N, C, cpg, 0.0f, conv, zero_words,
-                (long long*)nullptr, plane_max);
+    SMOT_LAUNCH(f.fn, dim3(grid), dim3(f.threads), f.smem, st, resp, packed, plane_max, zero_words, (long long*)nullptr, N, C,
+                cpg, 0.0f, conv, P);
     return check_launch("predictor towers (winograd, 29x29 in blocks)");
 }
 
