@@ -847,6 +847,41 @@ int smot_rpn_proposals_fwd(const void* const* objectness, const void* const* reg
                            void* ws, float* out_boxes, float* out_objectness, int32_t* out_count,
                            smot_stream_t stream);
 
+/*
+ * BOX-HEAD POST-PROCESSING OF THE DETECTIONS (csrc/box_detect.hip): the half of the post-processor
+ * smot_box_refine_post_fwd leaves out — one image whose proposals are all detections (ids = -1: what the RPN hands over).
+ * Replaces: PostProcessor.forward + filter_results (reference siammot/modelling/box_head/inference.py:46-191) — per
+ * foreground class a nonzero, three mask gathers, `len(det) > 0`, an argsort, the NMS launch and its mask gather,
+ * `trk_idx.any()` and two cat_boxlist: ~25 launches and three to four host synchronisations per class — by FOUR launches
+ * and no memset (their number depends on neither M nor num_classes nor the count), without a host synchronisation and
+ * deterministic to the bit.
+ *
+ *   head_out       [M, ld] device, the columns of smot_box_refine_post_fwd: [0, K) logits, [K, K + 4 KR) deltas; KR =
+ *                  reg_classes = K, or 2 (class-agnostic regression: the last four columns are used)
+ *   boxes          [M, 4] device, xyxy proposals
+ *   count          DEVICE int32: rows >= *count do not exist and are never loaded (*count > M counts as M, < 0 as 0)
+ *   semantics      soft-max over the K logits; for every class j in [1, K): BoxCoder.decode of class j's deltas with
+ *                  weights (wx, wy, ww, wh), TO_REMOVE = 1, dw / dh clamped at xform_clip with NaN kept; the clamp to
+ *                  [0, clip_w - 1] x [0, clip_h - 1] unless clip_w == 0 (amodal); candidates: rows with p_j > score_thresh
+ *                  (a NaN score is none); greedy NMS (+1 IoU, suppressed when IoU > nms_thresh) in descending score
+ *                  order, ties to the lower row.  Output: classes ascending, inside a class ASCENDING PROPOSAL ROW.
+ *                  DETECTIONS_PER_IMG is not applied.
+ *   outputs        capacity M * (K - 1) rows: out_boxes [cap, 4], out_scores [cap], out_labels [cap] int64, out_rows [cap]
+ *                  int32 (the proposal row of the detection), out_count [K] int32 (word 0: total, words 1 .. K - 1: per
+ *                  class); rows beyond the total are zero.
+ *   capacities     1 <= M <= 2048, 2 <= num_classes <= 128 (SMOT_ERR_BAD_ARG beyond); SMOT_ERR_UNSUPPORTED for
+ *                  nms_thresh <= 0.
+ *   ws             smot_box_detect_post_ws_bytes(M, num_classes) bytes (-1 for shapes the call refuses), 16-byte aligned.
+ *                  Its largest part is the NMS bitmask, (K - 1) * M * ceil(M / 64) * 8 bytes (12 KB at 300 rows x 2
+ *                  classes; 67 MB at 2048 x 128).  All of it is scratch.
+ */
+long long smot_box_detect_post_ws_bytes(int M, int num_classes);
+int smot_box_detect_post_fwd(const float* head_out, int ld, int num_classes, int reg_classes, const float* boxes,
+                             const int32_t* count, int M, float wx, float wy, float ww, float wh, float xform_clip,
+                             float clip_w, float clip_h, float score_thresh, float nms_thresh, void* ws,
+                             float* out_boxes, float* out_scores, int64_t* out_labels, int32_t* out_rows,
+                             int32_t* out_count, smot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

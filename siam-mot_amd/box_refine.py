@@ -13,6 +13,11 @@ that they survive, clip, per-class threshold, NMS on detections only).  The pool
 (``poolers.Pooler``); the four ``Linear`` layers are library GEMMs (hipBLASLt through torch) — plain dense layers, not
 hand kernels, as the north star assigns them.  Parameter names are upstream's (``feature_extractor.fc6.weight`` ...), so
 the ``roi_heads.box.*`` entries of a reference checkpoint load with ``load_state_dict``.
+
+Two halves of the post-processor also exist as HIP kernels on raw device tensors, without a host synchronisation: rows that
+are all tracks (``refine_raw``, csrc/box_refine.hip) and rows that are all detections — proposals without ids, what the RPN
+hands over every frame (``detect_raw``, csrc/box_detect.hip; ``forward`` takes it for id-less device proposals and reads one
+number back, the detection count).  Mixed rows keep the ``BoxList`` path.
 """
 import math
 
@@ -179,8 +184,61 @@ class TrackBoxHead(nn.Module):
     def forward(self, features, proposals, targets=None):
         if self.training:
             raise NotImplementedError("siammot_amd.TrackBoxHead is an inference path (box_head.py:39-43,52-61)")
+        if len(proposals) == 1 and self.detect_ok(proposals[0]):
+            # proposals without ids (what the RPN hands over): pooler, three library GEMMs and four post-processing
+            # launches (csrc/box_detect.hip); the detection count is the call's one device-to-host copy
+            box = proposals[0]
+            n = len(box)
+            count = torch.full((1,), n, dtype=torch.int32, device=box.bbox.device)
+            boxes, scores, labels, _, out_count, x, _ = self.detect_raw(features, box.bbox, count, box.size)
+            return x, [self.wrap_detections(boxes, scores, labels, out_count, box.size)], {}
+        if len(proposals) == 1 and proposals[0].bbox.is_cuda and not proposals[0].has_field("ids"):
+            ops.FALLBACKS["box_detect_torch"] += 1
         x = self.feature_extractor(features, proposals)
         return x, self.post_processor(self.predictor(x), proposals), {}
+
+    # ---- proposals that are all detections on raw device tensors: no BoxList, no host synchronisation -----------------
+    def detect_shapes_ok(self, m):
+        """``detect_raw`` applies to ``m`` capacity rows: HIP pooler, the package's own NMS, shapes ``ops.box_detect_post``
+        takes (and a bitmask scratch the grow-only workspace may keep)."""
+        pp = self.post_processor
+        K = self.predictor.cls_score.out_features
+        return (isinstance(self.feature_extractor.pooler, Pooler) and pp.nms_fn is boxlist_nms and pp.nms > 0
+                and 1 <= m <= ops.BOX_DETECT_MAX_ROWS and 2 <= K <= ops.BOX_DETECT_MAX_CLASSES
+                and ops.box_detect_mask_bytes(m, K) <= ops.BOX_DETECT_MAX_MASK_BYTES
+                and self.predictor.cls_score.weight.is_cuda)
+
+    def detect_ok(self, box):
+        """``forward`` takes the device path for this BoxList: no ``ids`` field, on the device, xyxy, within capacity."""
+        return (not box.has_field("ids") and box.bbox.is_cuda and box.mode == "xyxy" and box.bbox.dtype is torch.float32
+                and self.detect_shapes_ok(len(box)))
+
+    @torch.no_grad()
+    def detect_raw(self, features, boxes, count_dev, image_wh):
+        """The box head on ``boxes [M, 4]`` of which the first ``count_dev[0]`` (a device int32 tensor) exist, every row a
+        detection: HIP pooler on all M capacity rows (rows beyond the count hold whatever the producer left; the RPN
+        leaves zeros), fc6 / fc7 / ``cls_score | bbox_pred`` as library GEMMs (the weight-streaming kernels for a handful
+        of rows), ``ops.box_detect_post``.  Returns ``(boxes [cap, 4], scores [cap], labels [cap], rows [cap], count [K],
+        x [M, dim], head_out [M, K + 4 KR])`` — ``PostProcessor``'s detections in its order with the proposal row of
+        each, ``count[0]`` of them — without reading anything back."""
+        fe, pp = self.feature_extractor, self.post_processor
+        pooler = fe.pooler
+        cs, bp = self.predictor.cls_score, self.predictor.bbox_pred
+        bc = pp.box_coder
+        x = ops.roi_align_levels(features, boxes, boxes, pooler.output_size[0], pooler.scales, pooler.sampling_ratio)
+        x = x.view(x.shape[0], -1)
+        h, out = self._mlp_rows(x)
+        res = ops.box_detect_post(out, cs.out_features, bp.out_features // 4, boxes, count_dev, bc.weights,
+                                  bc.bbox_xform_clip, None if pp.amodal_inference else image_wh, pp.score_thresh, pp.nms)
+        return res + (h, out)
+
+    @staticmethod
+    def wrap_detections(boxes, scores, labels, out_count, size):
+        """``detect_raw``'s padded outputs as the BoxList ``PostProcessor`` returns (fields ``scores``, ``ids`` = -1,
+        ``labels``): reads ``out_count[0]`` — one device-to-host copy."""
+        n = int(out_count[:1].cpu()[0])
+        ids = torch.full((n,), -1, dtype=torch.int64, device=boxes.device)
+        return BoxList._wrap(boxes[:n], size, "xyxy", {"scores": scores[:n], "ids": ids, "labels": labels[:n]})
 
     # ---- the propagated tracks on raw device tensors: no BoxList, no host synchronisation -----------------------------
     def _track_weights(self):
@@ -194,6 +252,26 @@ class TrackBoxHead(nn.Module):
                 hit = (stamp, torch.cat((cs.weight, bp.weight), 0).t().contiguous(), torch.cat((cs.bias, bp.bias), 0))
             self.__dict__["_track_w"] = hit
         return hit[1], hit[2]
+
+    def _mlp_rows(self, x):
+        """fc6 + ReLU, fc7 + ReLU and ``cls_score | bbox_pred`` on pooled rows ``x [M, C*P*P]`` -> ``(h [M, dim], head_out
+        [M, K + 4*KR])``: the weight-streaming kernels on all CUs for a handful of rows (csrc/linear_rows.hip; the two
+        predictor layers write the column blocks of one buffer), library GEMMs otherwise."""
+        fe = self.feature_extractor
+        cs, bp = self.predictor.cls_score, self.predictor.bbox_pred
+        if x.shape[0] <= ops.linear_rows_max_rows() and x.shape[1] % 4 == 0 and fe.fc6.out_features % 4 == 0 \
+                and fe.fc7.out_features % 4 == 0:
+            h = ops.linear_rows(x, fe.fc6.weight, fe.fc6.bias, relu=True)
+            h = ops.linear_rows(h, fe.fc7.weight, fe.fc7.bias, relu=True)
+            out = torch.empty((x.shape[0], cs.out_features + bp.out_features), dtype=torch.float32, device=x.device)
+            ops.linear_rows(h, cs.weight, cs.bias, out=out)
+            ops.linear_rows(h, bp.weight, bp.bias, out=out[:, cs.out_features:])
+        else:
+            h = _linear_relu(x, fe.fc6)
+            h = _linear_relu(h, fe.fc7)
+            w, b = self._track_weights()
+            out = torch.addmm(b, h, w)
+        return h, out
 
     def one_call_ok(self, n):
         """The whole refinement of ``n`` rows fits ``smot_box_refine_fwd`` (and so the one-call tracking frame)."""
@@ -241,20 +319,7 @@ class TrackBoxHead(nn.Module):
         x = x.view(x.shape[0], -1)
         if x.shape[0] > ops.linear_rows_max_rows():
             ops.FALLBACKS["refine_library_gemm"] += 1
-        if x.shape[0] <= ops.linear_rows_max_rows() and x.shape[1] % 4 == 0 and fe.fc6.out_features % 4 == 0 \
-                and fe.fc7.out_features % 4 == 0:
-            # a handful of rows: weight-streaming kernels on all CUs (csrc/linear_rows.hip); the two predictor layers
-            # write the column blocks of one buffer
-            h = ops.linear_rows(x, fe.fc6.weight, fe.fc6.bias, relu=True)
-            h = ops.linear_rows(h, fe.fc7.weight, fe.fc7.bias, relu=True)
-            out = torch.empty((x.shape[0], cs.out_features + bp.out_features), dtype=torch.float32, device=x.device)
-            ops.linear_rows(h, cs.weight, cs.bias, out=out)
-            ops.linear_rows(h, bp.weight, bp.bias, out=out[:, cs.out_features:])
-        else:
-            h = _linear_relu(x, fe.fc6)
-            h = _linear_relu(h, fe.fc7)
-            w, b = self._track_weights()
-            out = torch.addmm(b, h, w)
+        _, out = self._mlp_rows(x)
         K = self.predictor.cls_score.out_features
         KR = self.predictor.bbox_pred.out_features // 4
         res = ops.box_refine_post(out, K, KR, boxes, labels, ids, conf, bc.weights, bc.bbox_xform_clip,

@@ -1,0 +1,59 @@
+"""Anchors to detections with one device-to-host copy: the RPN's proposal selection and the box head behind one call.
+
+``RPNPostProcessor.forward`` (rpn.py) and ``TrackBoxHead.forward`` (box_refine.py) each read one count back: the number of
+proposals, then the number of detections.  ``DetectionHead`` hands the RPN's padded proposals and their device-resident
+count straight to the box head (``ops.rpn_proposals`` in raw form -> ``TrackBoxHead.detect_raw``), so only the detection
+count crosses to the host — and the result is the BoxList ``TrackingLoop.forward(features, detections)`` takes.
+
+One image per call (the box head's pooler routes one image's rois).  When either half is over its capacity or not on the
+device, the two modules' ``forward``s are composed as they are today.
+"""
+import torch
+
+from . import ops
+from .box_refine import TrackBoxHead
+from .rpn import make_rpn_postprocessor
+
+
+class DetectionHead(torch.nn.Module):
+    """``forward(anchors, objectness, box_regression, features) -> [BoxList]`` (fields ``scores``, ``ids`` = -1,
+    ``labels``): ``rpn_post`` is an ``rpn.RPNPostProcessor``, ``box_head`` a ``TrackBoxHead``."""
+
+    def __init__(self, rpn_post, box_head):
+        super(DetectionHead, self).__init__()
+        self.rpn_post = rpn_post
+        self.box_head = box_head
+
+    def raw_ok(self, anchors, objectness):
+        """Both halves take their device paths for this call."""
+        rpn, box = self.rpn_post, self.box_head
+        if len(anchors) != 1 or not all(t.is_cuda for t in objectness):
+            return False
+        if not (hasattr(rpn, "_within_capacity") and rpn._within_capacity(anchors, objectness)):
+            return False
+        cap = rpn.fpn_post_nms_top_n if len(objectness) > 1 else min(rpn.post_nms_top_n, rpn.pre_nms_top_n)
+        return hasattr(box, "detect_shapes_ok") and box.detect_shapes_ok(cap)
+
+    @torch.no_grad()
+    def forward(self, anchors, objectness, box_regression, features):
+        if self.training:
+            raise NotImplementedError("siammot_amd.detector.DetectionHead is an inference path")
+        rpn, box = self.rpn_post, self.box_head
+        if not self.raw_ok(anchors, objectness):
+            proposals = rpn(anchors, objectness, box_regression)
+            return box(features, proposals)[1]
+        size = anchors[0][0].size
+        boxes, _, count = ops.rpn_proposals(
+            objectness, box_regression, [[a.bbox for a in anchors[0]]], [size], rpn.pre_nms_top_n, rpn.post_nms_top_n,
+            rpn.fpn_post_nms_top_n, rpn.nms_thresh, rpn.min_size, amodal=rpn._amodal, weights=rpn.box_coder.weights,
+            xform_clip=rpn.box_coder.bbox_xform_clip)
+        det_boxes, scores, labels, _, out_count, _, _ = box.detect_raw(features, boxes[0], count[0:1], size)
+        return [box.wrap_detections(det_boxes, scores, labels, out_count, size)]       # the call's one device-to-host copy
+
+
+def build_detection_head(cfg, rpn_box_coder, in_channels, box_head=None):
+    """``DetectionHead`` from a config: the reference's RPN factory keys (``MODEL.RPN.*_TEST``) and the given box head or a
+    fresh ``TrackBoxHead``."""
+    if box_head is None:
+        box_head = TrackBoxHead(cfg, in_channels).eval()
+    return DetectionHead(make_rpn_postprocessor(cfg, rpn_box_coder, is_train=False).eval(), box_head).eval()

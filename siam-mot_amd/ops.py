@@ -121,6 +121,10 @@ _SIGNATURES = {
     "smot_rpn_proposals_ws_bytes": (ctypes.c_longlong, [_i, _i, _vp, _vp, _vp, _i, _i]),
     "smot_rpn_proposals_fwd": (ctypes.c_int, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _f, _f, _i,
                                               _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp]),
+    # box-head post-processing of the detections (proposals without ids): four launches, no host synchronisation
+    "smot_box_detect_post_ws_bytes": (ctypes.c_longlong, [_i, _i]),
+    "smot_box_detect_post_fwd": (ctypes.c_int, [_vp, _i, _i, _i, _vp, _vp, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _vp,
+                                                _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 _DEBUG_SIGNATURES = {
@@ -1089,6 +1093,7 @@ TIMER_XCORR, TIMER_TOWER = 0, 1
 #   unhinted_head        a pooling + correlation launch that ranked its rois itself although an order hint could exist
 #   general_frame        a tracking-loop frame that did not take the one-launch path at all
 #   rpn_torch            an RPN proposal selection on device tensors beyond ``rpn_proposals``' capacities (torch composition)
+#   box_detect_torch     a box-head call on id-less device proposals that ``box_detect_post`` does not take (torch composition)
 import collections as _collections
 FALLBACKS = _collections.Counter()
 # speculative next-frame heads of the tracking loop (TrackingLoop.forward(..., next_features=...)): launched / used as they
@@ -1558,6 +1563,61 @@ def box_refine_post(head_out, num_classes, reg_classes, boxes, labels, ids, trac
                                           _ptr(out_labels), ln.stream)
     _check(rc, "box_refine_post")
     return out_boxes, out_scores, out_ids, out_labels
+
+
+# capacities of ``box_detect_post`` (include/smot_emm.h): beyond them ``TrackBoxHead.forward`` keeps its torch composition
+BOX_DETECT_MAX_ROWS = 2048
+BOX_DETECT_MAX_CLASSES = 128
+BOX_DETECT_MAX_MASK_BYTES = 64 << 20   # NMS bitmask scratch the box head accepts (box_detect_mask_bytes); beyond: the torch path
+
+
+def box_detect_mask_bytes(rows, num_classes):
+    """Size of the largest part of ``box_detect_post``'s workspace, the NMS bitmasks: 8 bytes per (candidate row, 64-column
+    tile) of every foreground class — 12 KB at 300 rows x 2 classes, 67 MB at the capacities 2048 x 128."""
+    return (num_classes - 1) * rows * ((rows + 63) // 64) * 8
+
+
+def box_detect_post(head_out, num_classes, reg_classes, boxes, count, weights, xform_clip, clip_wh, score_thresh,
+                    nms_thresh):
+    """``smot_box_detect_post_fwd``: the box head's post-processing of M proposals that are all detections (no ids) —
+    soft-max, per-class decode, clip, threshold and per-class NMS in four launches, free of host synchronisation.
+    ``head_out`` ``[M, >= K + 4*KR]`` = class logits | box deltas; ``count``: a device int32 tensor whose first element is
+    the number of rows that exist (rows beyond it are never read).  Returns ``(boxes [cap,4], scores [cap], labels [cap]
+    int64, rows [cap] int32, count [K] int32)`` with ``cap = M * (K - 1)``: classes ascending, ascending proposal row
+    inside a class, rows beyond ``count[0]`` zero; ``count[1:]`` are the per-class counts.  Nothing is read back."""
+    lib = _lib or load_library()
+    head_out = _dev_f32(head_out, "head_out")
+    boxes = _dev_f32(boxes, "boxes")
+    M, dev = boxes.shape[0], boxes.device
+    K, KR = int(num_classes), int(reg_classes)
+    if boxes.dim() != 2 or boxes.shape[1] != 4:
+        raise RuntimeError("siammot_amd.box_detect_post: boxes must be [M, 4], got %s" % (tuple(boxes.shape),))
+    if head_out.dim() != 2 or head_out.shape[0] != M or head_out.shape[1] < K + 4 * KR:
+        raise RuntimeError("siammot_amd.box_detect_post: head_out %s does not hold %d logits + %d deltas for %d rows"
+                           % (tuple(head_out.shape), K, 4 * KR, M))
+    if not (isinstance(count, torch.Tensor) and count.is_cuda and count.dtype is torch.int32 and count.device == dev
+            and count.numel() >= 1 and count.is_contiguous()):
+        raise RuntimeError("siammot_amd.box_detect_post: count must be a contiguous int32 tensor on the boxes' device")
+    nbytes = lib.smot_box_detect_post_ws_bytes(M, K)
+    if nbytes < 0:
+        _check(-1, "box_detect_post")
+    stream = _stream(dev)
+    work = _workspace(dev, nbytes // 4, ("box_detect", stream.value))
+    cap = M * (K - 1)
+    out_boxes = torch.empty((cap, 4), dtype=_F32, device=dev)
+    out_scores = torch.empty((cap,), dtype=_F32, device=dev)
+    out_labels = torch.empty((cap,), dtype=torch.int64, device=dev)
+    out_rows = torch.empty((cap,), dtype=torch.int32, device=dev)
+    out_count = torch.empty((K,), dtype=torch.int32, device=dev)
+    cw, ch = (0.0, 0.0) if clip_wh is None else (float(clip_wh[0]), float(clip_wh[1]))
+    with _Launch(head_out, boxes, count) as ln:
+        rc = lib.smot_box_detect_post_fwd(_ptr(head_out), head_out.shape[1], K, KR, _ptr(boxes), _ptr(count), M,
+                                          float(weights[0]), float(weights[1]), float(weights[2]), float(weights[3]),
+                                          float(xform_clip), cw, ch, float(score_thresh), float(nms_thresh), _ptr(work),
+                                          _ptr(out_boxes), _ptr(out_scores), _ptr(out_labels), _ptr(out_rows),
+                                          _ptr(out_count), ln.stream)
+    _check(rc, "box_detect_post")
+    return out_boxes, out_scores, out_labels, out_rows, out_count
 
 
 def box_refine(features, scales, pooled, sampling_ratio, boxes, labels, ids, track_conf, layers, weights, xform_clip,
