@@ -52,6 +52,10 @@ typedef void* smot_stream_t; /* hipStream_t */
  *     smot_xcorr_dw_fwd's to rounding, not bit for bit).
  * 14: smot_emm_track_batched_fwd / smot_emm_extract_cache_batched_fwd and SMOT_MAX_IMAGES added (several images per
  *     call); existing entry points unchanged.
+ *     Added since without a new version (every existing symbol, struct and layout unchanged; a host layer asks for the
+ *     symbols it needs): the _typed_ entry points, smot_rpn_proposals_*, smot_box_detect_post_*, and the box head over
+ *     several images: smot_roi_align_levels_batched_typed_fwd, smot_box_detect_post_batched_ws_bytes,
+ *     smot_box_detect_post_batched_fwd.
  */
 #define SMOT_ABI_VERSION 14
 
@@ -755,6 +759,19 @@ int smot_roi_align_levels_typed_fwd(const void* const* feats, int feat_type, con
                                     int out_h, int out_w, int sampling_ratio,
                                     float* out, int32_t* levels_out, smot_stream_t stream);
 
+/* smot_roi_align_levels_typed_fwd over a BATCH of images (the box head's pooler for several cameras): feats[l] points at
+ * [num_images, C, H_l, W_l] maps (channels-last with the flag: [num_images, H_l, W_l, C]), the rois of image b are rows
+ * [row_start[b], row_start[b+1]) of rois / level_boxes / out / levels_out (R = row_start[num_images]); num_images and
+ * row_start (a HOST array) are checked as for smot_emm_*_batched_fwd, before any launch.  The rows of image b are bit for
+ * bit what the single-image call returns on that image's maps with those rows — the separable 7 / 15 / 30 kernel and the
+ * generic kernel alike.  Images without rois and R == 0 are legal. */
+int smot_roi_align_levels_batched_typed_fwd(const void* const* feats, int feat_type, const int* heights, const int* widths,
+                                            const int* pad_cells, const float* scales, int num_levels, int C,
+                                            const float* rois, const float* level_boxes, int R,
+                                            int out_h, int out_w, int sampling_ratio,
+                                            float* out, int32_t* levels_out, smot_stream_t stream,
+                                            int num_images, const int* row_start);
+
 int smot_roi_align_typed_fwd(const void* input, int feat_type, int num_images, int C, int H, int W, int pad_cells,
                              const float* rois5, int R, float spatial_scale, int pooled_h, int pooled_w,
                              int sampling_ratio, float* out, smot_stream_t stream);
@@ -881,6 +898,36 @@ int smot_box_detect_post_fwd(const float* head_out, int ld, int num_classes, int
                              float clip_w, float clip_h, float score_thresh, float nms_thresh, void* ws,
                              float* out_boxes, float* out_scores, int64_t* out_labels, int32_t* out_rows,
                              int32_t* out_count, smot_stream_t stream);
+
+/*
+ * The same over the images of a call (several cameras): still FOUR launches and no memset whatever num_images is — the
+ * image is one more grid dimension of the same four kernels — without a host synchronisation or a global atomic.
+ * Replaces: PostProcessor.forward over a list of images (inference.py:46-82 splits the rows per image and runs
+ * filter_results on each).
+ *
+ *   rows           the rows of all images concatenated: head_out [M, ld], boxes [M, 4]; image b owns rows [row_start[b],
+ *                  row_start[b+1]) — num_images and row_start (HOST array of num_images + 1 ints) as for
+ *                  smot_emm_*_batched_fwd: SMOT_ERR_BAD_ARG before any launch for num_images outside [1, SMOT_MAX_IMAGES],
+ *                  row_start[0] != 0, a decrease, or row_start[num_images] != M.  M_b = row_start[b+1] - row_start[b] may be
+ *                  0 and is at most 2048 per image.
+ *   count          DEVICE int32 [num_images]: image b has min(max(count[b], 0), M_b) rows that exist; the rest is never loaded
+ *   clip_w/clip_h  the one image size of the call
+ *   outputs        the detections of image b occupy rows [row_start[b] (K - 1), row_start[b+1] (K - 1)) of out_boxes /
+ *                  out_scores / out_labels / out_rows — classes ascending, ascending proposal row inside a class, out_rows
+ *                  RELATIVE to the image's first row, the tail of the segment zero; out_count [num_images, K]: per image
+ *                  the total, then the per-class counts.
+ *   contract       for every image every output equals BIT FOR BIT what smot_box_detect_post_fwd returns on that image's
+ *                  rows alone (the same device text, arithmetic and NaN rules).
+ *   ws             smot_box_detect_post_batched_ws_bytes(num_images, row_start, num_classes) bytes (-1 for a call the entry
+ *                  refuses), 16-byte aligned: one segment per image, each laid out as the single-image call's workspace of
+ *                  M_b rows (for one image the two byte counts are equal).  All of it is scratch.
+ */
+long long smot_box_detect_post_batched_ws_bytes(int num_images, const int* row_start, int num_classes);
+int smot_box_detect_post_batched_fwd(const float* head_out, int ld, int num_classes, int reg_classes, const float* boxes,
+                                     const int32_t* count, int M, float wx, float wy, float ww, float wh, float xform_clip,
+                                     float clip_w, float clip_h, float score_thresh, float nms_thresh, void* ws,
+                                     float* out_boxes, float* out_scores, int64_t* out_labels, int32_t* out_rows,
+                                     int32_t* out_count, smot_stream_t stream, int num_images, const int* row_start);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,8 @@ the ``roi_heads.box.*`` entries of a reference checkpoint load with ``load_state
 Two halves of the post-processor also exist as HIP kernels on raw device tensors, without a host synchronisation: rows that
 are all tracks (``refine_raw``, csrc/box_refine.hip) and rows that are all detections — proposals without ids, what the RPN
 hands over every frame (``detect_raw``, csrc/box_detect.hip; ``forward`` takes it for id-less device proposals and reads one
-number back, the detection count).  Mixed rows keep the ``BoxList`` path.
+number back, the detection count; several images of one size: ``detect_raw_batched``, the same launches for all of them and
+one copy of the B counts).  Mixed rows keep the ``BoxList`` path.
 """
 import math
 
@@ -184,6 +185,8 @@ class TrackBoxHead(nn.Module):
     def forward(self, features, proposals, targets=None):
         if self.training:
             raise NotImplementedError("siammot_amd.TrackBoxHead is an inference path (box_head.py:39-43,52-61)")
+        if len(proposals) > 1:
+            return self._forward_images(features, proposals)
         if len(proposals) == 1 and self.detect_ok(proposals[0]):
             # proposals without ids (what the RPN hands over): pooler, three library GEMMs and four post-processing
             # launches (csrc/box_detect.hip); the detection count is the call's one device-to-host copy
@@ -196,6 +199,34 @@ class TrackBoxHead(nn.Module):
             ops.FALLBACKS["box_detect_torch"] += 1
         x = self.feature_extractor(features, proposals)
         return x, self.post_processor(self.predictor(x), proposals), {}
+
+    def _forward_images(self, features, proposals):
+        """``forward`` on B > 1 images (``features[l]`` = ``[B, C, H_l, W_l]``): id-less device proposals of one image size
+        within the batched capacities go through ``detect_raw_batched`` — one set of launches and ONE device-to-host copy,
+        the B detection counts; anything else is today's ``forward`` image by image."""
+        if self.detect_batch_ok(proposals):
+            dev, size = proposals[0].bbox.device, proposals[0].size
+            rows = [len(p) for p in proposals]
+            boxes = torch.cat([p.bbox for p in proposals], 0)
+            # every row exists: any count >= M_b means "all M_b rows" (one fill, nothing copied to the device)
+            count = torch.full((len(rows),), ops.BOX_DETECT_MAX_ROWS, dtype=torch.int32, device=dev)
+            det, scores, labels, _, out_count, x, _ = self.detect_raw_batched(features, boxes, rows, count, size)
+            return x, self.wrap_detections_batched(det, scores, labels, out_count, rows, size), {}
+        xs, results = [], []
+        for b, p in enumerate(proposals):
+            if len(p) == 0:                                  # (nothing to pool or post-process: the empty result)
+                dev = p.bbox.device
+                if p.bbox.is_cuda and not p.has_field("ids"):
+                    ops.FALLBACKS["box_detect_torch"] += 1
+                x = torch.zeros((0, self.feature_extractor.out_channels), dtype=torch.float32, device=dev)
+                r = [BoxList._wrap(p.bbox.new_zeros((0, 4)), p.size, "xyxy",
+                                   {"scores": p.bbox.new_zeros((0,)), "ids": torch.zeros((0,), dtype=torch.int64, device=dev),
+                                    "labels": torch.zeros((0,), dtype=torch.int64, device=dev)})]
+            else:
+                x, r, _ = self.forward([f[b:b + 1] for f in features], [p])
+            xs.append(x)
+            results.append(r[0])
+        return torch.cat(xs, 0), results, {}
 
     # ---- proposals that are all detections on raw device tensors: no BoxList, no host synchronisation -----------------
     def detect_shapes_ok(self, m):
@@ -212,6 +243,65 @@ class TrackBoxHead(nn.Module):
         """``forward`` takes the device path for this BoxList: no ``ids`` field, on the device, xyxy, within capacity."""
         return (not box.has_field("ids") and box.bbox.is_cuda and box.mode == "xyxy" and box.bbox.dtype is torch.float32
                 and self.detect_shapes_ok(len(box)))
+
+    def detect_shapes_ok_batched(self, rows_per_image):
+        """``detect_raw_batched`` applies to images of these capacity rows (an image may have none): what
+        ``detect_shapes_ok`` asks, per image, with the bitmask scratch summed over the images."""
+        pp = self.post_processor
+        K = self.predictor.cls_score.out_features
+        return (isinstance(self.feature_extractor.pooler, Pooler) and pp.nms_fn is boxlist_nms and pp.nms > 0
+                and 1 <= len(rows_per_image) <= ops.MAX_IMAGES
+                and all(0 <= m <= ops.BOX_DETECT_MAX_ROWS for m in rows_per_image)
+                and 2 <= K <= ops.BOX_DETECT_MAX_CLASSES
+                and ops.box_detect_mask_bytes_batched(rows_per_image, K) <= ops.BOX_DETECT_MAX_MASK_BYTES
+                and self.predictor.cls_score.weight.is_cuda)
+
+    def detect_batch_ok(self, proposals):
+        """``forward`` takes the batched device path for these BoxLists: each without ``ids``, on one device, xyxy, fp32;
+        one image size; within the batched capacities."""
+        first = proposals[0]
+        return (all(not p.has_field("ids") and p.bbox.is_cuda and p.mode == "xyxy" and p.bbox.dtype is torch.float32
+                    and p.bbox.device == first.bbox.device and tuple(p.size) == tuple(first.size) for p in proposals)
+                and self.detect_shapes_ok_batched([len(p) for p in proposals]))
+
+    @torch.no_grad()
+    def detect_raw_batched(self, features, boxes, rows_per_image, count_dev, image_wh):
+        """``detect_raw`` on the B images of a call: ``features[l]`` = ``[B, C, H_l, W_l]``, ``boxes [M, 4]`` = the capacity
+        rows of all images (image b: the ``rows_per_image[b]`` rows after those of the images before it), of which the first
+        ``count_dev[b]`` (device int32 ``[B]``) exist; ``image_wh``: the one image size.  Batched pooler, the GEMMs on all M
+        rows, ``ops.box_detect_post_batched``.  Returns ``detect_raw``'s tuple with ``count [B, K]`` and the detections of
+        image b in the segment that starts at row ``(K - 1) * sum(rows_per_image[:b])`` — without reading anything back."""
+        fe, pp = self.feature_extractor, self.post_processor
+        pooler = fe.pooler
+        cs, bp = self.predictor.cls_score, self.predictor.bbox_pred
+        bc = pp.box_coder
+        if boxes.shape[0] == 0:                              # (no image has a row: nothing to pool, the counts are still written)
+            h = boxes.new_zeros((0, fe.out_channels))
+            out = boxes.new_zeros((0, cs.out_features + bp.out_features))
+        else:
+            x = ops.roi_align_levels_batched(features, boxes, boxes, rows_per_image, pooler.output_size[0], pooler.scales,
+                                             pooler.sampling_ratio)
+            h, out = self._mlp_rows(x.view(x.shape[0], fe.fc6.in_features))
+        res = ops.box_detect_post_batched(out, cs.out_features, bp.out_features // 4, boxes, rows_per_image, count_dev,
+                                          bc.weights, bc.bbox_xform_clip, None if pp.amodal_inference else image_wh,
+                                          pp.score_thresh, pp.nms)
+        return res + (h, out)
+
+    @staticmethod
+    def wrap_detections_batched(boxes, scores, labels, out_count, rows_per_image, size):
+        """``detect_raw_batched``'s padded outputs as one BoxList per image (fields ``scores``, ``ids`` = -1, ``labels``):
+        reads the B totals ``out_count[:, 0]`` — one device-to-host copy."""
+        totals = out_count.cpu()[:, 0].tolist()              # (the whole contiguous [B, K] table: no gather in front of the copy)
+        C = out_count.shape[1] - 1
+        ids = torch.full((sum(totals),), -1, dtype=torch.int64, device=boxes.device)
+        out, start, done = [], 0, 0
+        for m, n in zip(rows_per_image, totals):
+            out.append(BoxList._wrap(boxes[start:start + n], size, "xyxy",
+                                     {"scores": scores[start:start + n], "ids": ids[done:done + n],
+                                      "labels": labels[start:start + n]}))
+            start += m * C
+            done += n
+        return out
 
     @torch.no_grad()
     def detect_raw(self, features, boxes, count_dev, image_wh):

@@ -8,7 +8,9 @@
 //
 // Here: FOUR launches and no memset, whatever the number of rows M, of classes K and the device-resident row count; a
 // foreground class is a grid slice of the same launch (the structure of rpn_proposals.hip with classes for (image, level)
-// pairs).  No host synchronisation, no atomics on global memory: two runs give the same bits.
+// pairs).  No host synchronisation, no atomics on global memory: two runs give the same bits.  Several images of a call
+// (smot_box_detect_post_batched_fwd) are one more grid dimension of the same four kernels: the same four launches, every
+// image's outputs bit for bit the single-image call's on that image's rows.
 //
 //   1  box_detect_cand_kernel, one workgroup per class j in [1, K): soft-max of the row's K logits (box_refine.hip's op
 //      order), BoxCoder.decode of class j's deltas (class-agnostic: the last four columns), clip, candidates = rows with
@@ -26,6 +28,7 @@
 // candidate of no class; a NaN among a candidate's deltas gives the NaN coordinates box_refine.hip documents, and such a
 // box neither suppresses nor is suppressed (every comparison with its IoU is false).
 #include "nms_common.h"
+#include "roi_common.h"
 
 namespace smot {
 
@@ -64,12 +67,14 @@ __device__ __forceinline__ unsigned bd_key(float x) {
 
 __device__ __forceinline__ int bd_rows(const BoxDetectArgs& A) { return min(max(*A.count, 0), A.M); }
 
-__global__ void __launch_bounds__(BD_SORT_T) box_detect_cand_kernel(BoxDetectArgs A) {
+// ---- the four kernels' bodies: one text behind the single-image kernels (A = the call) and the batched ones (A = the view
+// of one image of the call, bd_image below); `c` = the foreground class's slot ---------------------------------------------
+__device__ __forceinline__ void bd_cand_body(const BoxDetectArgs& A, const int c) {
     __shared__ unsigned long long s_key[BD_MAX_ROWS];        // score key << 32 | ~row; 0: not a candidate
     __shared__ float4 s_box[BD_MAX_ROWS];                    // by row
     __shared__ float s_score[BD_MAX_ROWS];                   // by row
     __shared__ int s_cnt;
-    const int c = blockIdx.x, j = c + 1, t = threadIdx.x;
+    const int j = c + 1, t = threadIdx.x;
     const int n = bd_rows(A);
     int P = 2;
     while (P < n) P <<= 1;
@@ -158,11 +163,10 @@ __global__ void __launch_bounds__(BD_SORT_T) box_detect_cand_kernel(BoxDetectArg
     }
 }
 
-// nms_mask_kernel of nms.hip over the classes: blockIdx.y = class, blockIdx.x = (row tile, column tile)
-__global__ void __launch_bounds__(NMS_T) box_detect_mask_kernel(BoxDetectArgs A) {
-    const int c = blockIdx.y;
+// nms_mask_kernel of nms.hip over the classes: c = class, tile = (row tile, column tile) < nblk * nblk
+__device__ __forceinline__ void bd_mask_body(const BoxDetectArgs& A, const int c, const unsigned tile) {
     const int n = min(A.cand_count[c], A.M);
-    const int rb = blockIdx.x / A.nblk, cb = blockIdx.x - rb * A.nblk;
+    const int rb = tile / A.nblk, cb = tile - rb * A.nblk;
     if (rb * NMS_T >= n || cb * NMS_T >= n) return;
     const float* boxes = A.cand_box + (size_t)c * A.M * 4;
     unsigned long long* mask = A.mask + (size_t)c * A.M * A.nblk;
@@ -191,13 +195,12 @@ __global__ void __launch_bounds__(NMS_T) box_detect_mask_kernel(BoxDetectArgs A)
 
 // nms_scan_kernel of nms.hip per class (at most 2048 candidates: one `removed` word per lane of wave 0); the survivors
 // leave in ascending proposal-row order
-__global__ void __launch_bounds__(BD_T) box_detect_scan_kernel(BoxDetectArgs A) {
+__device__ __forceinline__ void bd_scan_body(const BoxDetectArgs& A, const int c) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long slab[];   // [64 rows][ne]
     __shared__ int s_kept[BD_MAX_ROWS];                        // ranks of the kept candidates, in score order
     __shared__ int s_rank[BD_MAX_ROWS];                        // by proposal row: rank + 1 of a kept candidate, else 0
     __shared__ int s_scan[BD_T];
     __shared__ int s_nkept;
-    const int c = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = min(A.cand_count[c], A.M);
     const int ne = (n + NMS_T - 1) / NMS_T;                    // <= 32 words per row in use
@@ -264,9 +267,9 @@ __global__ void __launch_bounds__(BD_T) box_detect_scan_kernel(BoxDetectArgs A) 
     if (tid == 0) A.keep_count[c] = total;
 }
 
-__global__ void __launch_bounds__(BD_T) box_detect_write_kernel(BoxDetectArgs A) {
+__device__ __forceinline__ void bd_write_body(const BoxDetectArgs& A, const int c) {
     __shared__ int s_cnt[BD_MAX_CLASSES];
-    const int c = blockIdx.x, t = threadIdx.x, C = A.K - 1;
+    const int t = threadIdx.x, C = A.K - 1;
     if (t < C) s_cnt[t] = min(max(A.keep_count[t], 0), A.M);
     __syncthreads();
     int base = 0, total = 0;
@@ -304,9 +307,9 @@ struct BoxDetectLayout {
     size_t cand_count, cand_row, cand_score, cand_box, mask, keep_count, keep_rank, end;
 };
 
-static inline size_t bd_al4(size_t w) { return (w + 3) & ~(size_t)3; }
+__host__ __device__ static inline size_t bd_al4(size_t w) { return (w + 3) & ~(size_t)3; }
 
-static BoxDetectLayout bd_layout(int M, int K) {
+__host__ __device__ static inline BoxDetectLayout bd_layout(int M, int K) {
     const size_t C = (size_t)K - 1, nblk = (size_t)(M + NMS_T - 1) / NMS_T;
     BoxDetectLayout o;
     size_t w = 0;
@@ -321,12 +324,102 @@ static BoxDetectLayout bd_layout(int M, int K) {
     return o;
 }
 
+// the workspace sections of one image (or of the single-image call) behind `ws`
+__host__ __device__ static inline void bd_set_workspace(BoxDetectArgs& A, void* ws) {
+    const BoxDetectLayout o = bd_layout(A.M, A.K);
+    int* wi = reinterpret_cast<int*>(ws);
+    float* wf = reinterpret_cast<float*>(ws);
+    A.cand_count = wi + o.cand_count;
+    A.cand_row = wi + o.cand_row;
+    A.cand_score = wf + o.cand_score;
+    A.cand_box = wf + o.cand_box;
+    A.mask = reinterpret_cast<unsigned long long*>(wi + o.mask);
+    A.keep_count = wi + o.keep_count;
+    A.keep_rank = wi + o.keep_rank;
+}
+
+// ---- one image -------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(BD_SORT_T) box_detect_cand_kernel(BoxDetectArgs A) { bd_cand_body(A, blockIdx.x); }
+// blockIdx.y = class, blockIdx.x = (row tile, column tile)
+__global__ void __launch_bounds__(NMS_T) box_detect_mask_kernel(BoxDetectArgs A) { bd_mask_body(A, blockIdx.y, blockIdx.x); }
+__global__ void __launch_bounds__(BD_T) box_detect_scan_kernel(BoxDetectArgs A) { bd_scan_body(A, blockIdx.x); }
+__global__ void __launch_bounds__(BD_T) box_detect_write_kernel(BoxDetectArgs A) { bd_write_body(A, blockIdx.x); }
+
+// ---- several images: the image is one more grid dimension of the same four kernels -----------------------------------------
+// A = the call (head / boxes / out_* at row 0 of image 0, count[0], out_count[0]; M, nblk and the workspace sections are
+// per image and filled by bd_image), I = the validated row ranges, ws_off[b] = where image b's workspace segment starts (in
+// 4-byte words; a multiple of 4).  A segment is laid out like the single-image call's workspace of M_b rows.
+struct BoxDetectBatch {
+    BoxDetectArgs A;
+    int* ws;
+    ImageRows I;
+    unsigned long long ws_off[SMOT_MAX_IMAGES];
+};
+
+// the call as image b alone sees it: what smot_box_detect_post_fwd is given for that image's rows (b is workgroup-uniform:
+// scalar loads from the kernel-argument segment)
+__device__ __forceinline__ BoxDetectArgs bd_image(const BoxDetectBatch& B, const int b) {
+    BoxDetectArgs A = B.A;
+    const int r0 = B.I.row_start[b], C = A.K - 1;
+    A.M = B.I.row_start[b + 1] - r0;
+    A.nblk = (A.M + NMS_T - 1) / NMS_T;
+    A.head += (size_t)r0 * A.ld;
+    A.boxes += (size_t)r0 * 4;
+    A.count += b;
+    bd_set_workspace(A, B.ws + B.ws_off[b]);
+    A.out_boxes += (size_t)r0 * C * 4;
+    A.out_scores += (size_t)r0 * C;
+    A.out_labels += (size_t)r0 * C;
+    A.out_rows += (size_t)r0 * C;
+    A.out_count += (size_t)b * A.K;
+    return A;
+}
+
+// blockIdx.x = class, blockIdx.y = image
+__global__ void __launch_bounds__(BD_SORT_T) box_detect_cand_batched_kernel(BoxDetectBatch B) {
+    bd_cand_body(bd_image(B, blockIdx.y), blockIdx.x);
+}
+// blockIdx.x = (row tile, column tile) of the LARGEST image of the call, blockIdx.y = class, blockIdx.z = image
+__global__ void __launch_bounds__(NMS_T) box_detect_mask_batched_kernel(BoxDetectBatch B) {
+    const BoxDetectArgs A = bd_image(B, blockIdx.z);
+    if ((int)blockIdx.x >= A.nblk * A.nblk) return;                  // (workgroup-uniform; an image without rows: nblk = 0)
+    bd_mask_body(A, blockIdx.y, blockIdx.x);
+}
+__global__ void __launch_bounds__(BD_T) box_detect_scan_batched_kernel(BoxDetectBatch B) {
+    bd_scan_body(bd_image(B, blockIdx.y), blockIdx.x);
+}
+__global__ void __launch_bounds__(BD_T) box_detect_write_batched_kernel(BoxDetectBatch B) {
+    bd_write_body(bd_image(B, blockIdx.y), blockIdx.x);
+}
+
 static int bd_check_shapes(int M, int K) {
     SMOT_REQUIRE(M >= 1 && M <= BD_MAX_ROWS, "box_detect_post: M=%d not in [1,%d]", M, BD_MAX_ROWS);
     SMOT_REQUIRE(K >= 2 && K <= BD_MAX_CLASSES, "box_detect_post: num_classes=%d not in [2,%d]", K, BD_MAX_CLASSES);
     return SMOT_OK;
 }
 
+// the row ranges and per-image shapes of a batched call, checked before anything else; ws_off / *total: the images' workspace
+// segments in 4-byte words
+static int bd_check_batch(ImageRows* I, int num_images, const int* row_start, int M, int K, unsigned long long* ws_off,
+                          unsigned long long* total, int* max_nblk) {
+    int rc = fill_image_rows(I, num_images, row_start, M, "box_detect_post_batched");
+    if (rc) return rc;
+    unsigned long long w = 0;
+    int nb = 0;
+    for (int b = 0; b < num_images; ++b) {
+        const int Mb = I->row_start[b + 1] - I->row_start[b];
+        rc = bd_check_shapes(Mb > 0 ? Mb : 1, K);                    // (an image without rows is legal)
+        if (rc) return rc;
+        if (ws_off) ws_off[b] = w;
+        w += bd_layout(Mb, K).end;
+        nb = max(nb, (Mb + NMS_T - 1) / NMS_T);
+    }
+    if (ws_off)
+        for (int b = num_images; b < SMOT_MAX_IMAGES; ++b) ws_off[b] = w;
+    *total = w;
+    *max_nblk = nb;
+    return SMOT_OK;
+}
 }  // namespace smot
 
 extern "C" long long smot_box_detect_post_ws_bytes(int M, int num_classes) {
@@ -352,9 +445,6 @@ extern "C" int smot_box_detect_post_fwd(const float* head_out, int ld, int num_c
     SMOT_REQUIRE(head_out && boxes && count && ws && out_boxes && out_scores && out_labels && out_rows && out_count,
                  "box_detect_post: null pointer");
     SMOT_REQUIRE(((uintptr_t)ws & 15) == 0, "box_detect_post: ws must be 16-byte aligned");
-    const BoxDetectLayout o = bd_layout(M, num_classes);
-    int* wi = reinterpret_cast<int*>(ws);
-    float* wf = reinterpret_cast<float*>(ws);
     BoxDetectArgs A;
     A.head = head_out;
     A.ld = ld;
@@ -373,13 +463,7 @@ extern "C" int smot_box_detect_post_fwd(const float* head_out, int ld, int num_c
     A.clip_h = clip_h;
     A.score_thresh = score_thresh;
     A.nms_thresh = nms_thresh;
-    A.cand_count = wi + o.cand_count;
-    A.cand_row = wi + o.cand_row;
-    A.cand_score = wf + o.cand_score;
-    A.cand_box = wf + o.cand_box;
-    A.mask = reinterpret_cast<unsigned long long*>(wi + o.mask);
-    A.keep_count = wi + o.keep_count;
-    A.keep_rank = wi + o.keep_rank;
+    bd_set_workspace(A, ws);
     A.out_boxes = out_boxes;
     A.out_scores = out_scores;
     A.out_labels = (long long*)out_labels;
@@ -392,4 +476,75 @@ extern "C" int smot_box_detect_post_fwd(const float* head_out, int ld, int num_c
     hipLaunchKernelGGL(box_detect_scan_kernel, dim3(C), dim3(BD_T), (size_t)NMS_T * A.nblk * 8, st, A);
     hipLaunchKernelGGL(box_detect_write_kernel, dim3(C), dim3(BD_T), 0, st, A);
     return check_launch("box_detect_post");
+}
+
+// ---- several images per call ---------------------------------------------------------------------------------------------
+extern "C" long long smot_box_detect_post_batched_ws_bytes(int num_images, const int* row_start, int num_classes) {
+    smot::ImageRows I;
+    unsigned long long words = 0;
+    int nb = 0;
+    if (num_images < 1 || num_images > SMOT_MAX_IMAGES || row_start == nullptr) return -1;
+    if (smot::bd_check_batch(&I, num_images, row_start, row_start[num_images], num_classes, nullptr, &words, &nb)) return -1;
+    return (long long)words * 4;
+}
+
+extern "C" int smot_box_detect_post_batched_fwd(const float* head_out, int ld, int num_classes, int reg_classes,
+                                                const float* boxes, const int32_t* count, int M, float wx, float wy, float ww,
+                                                float wh, float xform_clip, float clip_w, float clip_h, float score_thresh,
+                                                float nms_thresh, void* ws, float* out_boxes, float* out_scores,
+                                                int64_t* out_labels, int32_t* out_rows, int32_t* out_count,
+                                                smot_stream_t stream, int num_images, const int* row_start) {
+    using namespace smot;
+    BoxDetectBatch B;
+    unsigned long long words = 0;
+    int max_nblk = 0;
+    int rc = bd_check_batch(&B.I, num_images, row_start, M, num_classes, B.ws_off, &words, &max_nblk);
+    if (rc) return rc;
+    SMOT_REQUIRE((reg_classes == num_classes || reg_classes == 2) && ld >= num_classes + 4 * reg_classes,
+                 "box_detect_post_batched: bad head shape K=%d KR=%d ld=%d", num_classes, reg_classes, ld);
+    SMOT_REQUIRE(wx > 0.f && wy > 0.f && ww > 0.f && wh > 0.f,
+                 "box_detect_post_batched: regression weights must be positive");
+    if (!(nms_thresh > 0.0f)) {
+        set_error("box_detect_post_batched: nms_thresh=%g (the reference's NMS returns the class unsuppressed there)",
+                  nms_thresh);
+        return SMOT_ERR_UNSUPPORTED;
+    }
+    SMOT_REQUIRE(count && ws && out_count && (M == 0 || (head_out && boxes && out_boxes && out_scores && out_labels && out_rows)),
+                 "box_detect_post_batched: null pointer");
+    SMOT_REQUIRE(((uintptr_t)ws & 15) == 0, "box_detect_post_batched: ws must be 16-byte aligned");
+    BoxDetectArgs& A = B.A;
+    A.head = head_out;
+    A.ld = ld;
+    A.K = num_classes;
+    A.KR = reg_classes;
+    A.M = 0;                         // (per image: bd_image)
+    A.nblk = 0;
+    A.boxes = boxes;
+    A.count = count;
+    A.wx = wx;
+    A.wy = wy;
+    A.ww = ww;
+    A.wh = wh;
+    A.xform_clip = xform_clip;
+    A.clip_w = clip_w;
+    A.clip_h = clip_h;
+    A.score_thresh = score_thresh;
+    A.nms_thresh = nms_thresh;
+    A.cand_count = A.cand_row = A.keep_count = A.keep_rank = nullptr;
+    A.cand_score = A.cand_box = nullptr;
+    A.mask = nullptr;
+    A.out_boxes = out_boxes;
+    A.out_scores = out_scores;
+    A.out_labels = (long long*)out_labels;
+    A.out_rows = out_rows;
+    A.out_count = out_count;
+    B.ws = reinterpret_cast<int*>(ws);
+    hipStream_t st = (hipStream_t)stream;
+    const int C = num_classes - 1;
+    const int tiles = max_nblk > 0 ? max_nblk * max_nblk : 1;       // (a call without rows still writes its counts)
+    hipLaunchKernelGGL(box_detect_cand_batched_kernel, dim3(C, num_images), dim3(BD_SORT_T), 0, st, B);
+    hipLaunchKernelGGL(box_detect_mask_batched_kernel, dim3(tiles, C, num_images), dim3(NMS_T), 0, st, B);
+    hipLaunchKernelGGL(box_detect_scan_batched_kernel, dim3(C, num_images), dim3(BD_T), (size_t)NMS_T * max_nblk * 8, st, B);
+    hipLaunchKernelGGL(box_detect_write_batched_kernel, dim3(C, num_images), dim3(BD_T), 0, st, B);
+    return check_launch("box_detect_post_batched");
 }

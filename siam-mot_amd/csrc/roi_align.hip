@@ -227,6 +227,25 @@ extern "C" int smot_roi_align_levels_typed_fwd(const void* const* feats, int fea
                                      C, rois, level_boxes, R, out_h, out_w, sampling_ratio, out, levels_out, stream);
 }
 
+// several images per call: the maps are [num_images, C, H_l, W_l], the rows of image b are [row_start[b], row_start[b+1])
+extern "C" int smot_roi_align_levels_batched_typed_fwd(const void* const* feats, int feat_type, const int* heights,
+                                                       const int* widths, const int* pad_cells, const float* scales,
+                                                       int num_levels, int C, const float* rois, const float* level_boxes,
+                                                       int R, int out_h, int out_w, int sampling_ratio, float* out,
+                                                       int32_t* levels_out, smot_stream_t stream, int num_images,
+                                                       const int* row_start) {
+    using namespace smot;
+    const int rc = check_feat_type(feat_type, "roi_align_levels_batched_typed");
+    if (rc) return rc;
+    FeatTypeScope scope(feat_type);
+    ImageRows I;
+    const int rci = fill_image_rows(&I, num_images, row_start, R, "roi_align_levels_batched_typed");
+    if (rci) return rci;
+    return roi_align_levels_impl(reinterpret_cast<const float* const*>(feats), heights, widths, pad_cells, scales, num_levels,
+                                 C, rois, level_boxes, R, out_h, out_w, sampling_ratio, out, levels_out, (hipStream_t)stream,
+                                 &I, "roi_align_levels_batched_typed");
+}
+
 extern "C" int smot_roi_align_typed_fwd(const void* input, int feat_type, int num_images, int C, int H, int W, int pad_cells,
                                         const float* rois5, int R, float spatial_scale, int pooled_h, int pooled_w,
                                         int sampling_ratio, float* out, smot_stream_t stream) {

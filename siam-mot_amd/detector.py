@@ -5,8 +5,10 @@ proposals, then the number of detections.  ``DetectionHead`` hands the RPN's pad
 count straight to the box head (``ops.rpn_proposals`` in raw form -> ``TrackBoxHead.detect_raw``), so only the detection
 count crosses to the host — and the result is the BoxList ``TrackingLoop.forward(features, detections)`` takes.
 
-One image per call (the box head's pooler routes one image's rois).  When either half is over its capacity or not on the
-device, the two modules' ``forward``s are composed as they are today.
+Several images of one size per call (``features[l]`` = ``[N, C, H_l, W_l]``) take the same launches: the RPN's ``boxes [N,
+cap, 4]`` and ``count [N]`` go to ``TrackBoxHead.detect_raw_batched`` as they are and the N detection counts are the call's
+one copy.  When either half is over its capacity or not on the device, or the images differ in size, the two modules'
+``forward``s are composed as they are today.
 """
 import torch
 
@@ -16,7 +18,7 @@ from .rpn import make_rpn_postprocessor
 
 
 class DetectionHead(torch.nn.Module):
-    """``forward(anchors, objectness, box_regression, features) -> [BoxList]`` (fields ``scores``, ``ids`` = -1,
+    """``forward(anchors, objectness, box_regression, features) -> [BoxList]`` per image (fields ``scores``, ``ids`` = -1,
     ``labels``): ``rpn_post`` is an ``rpn.RPNPostProcessor``, ``box_head`` a ``TrackBoxHead``."""
 
     def __init__(self, rpn_post, box_head):
@@ -27,12 +29,17 @@ class DetectionHead(torch.nn.Module):
     def raw_ok(self, anchors, objectness):
         """Both halves take their device paths for this call."""
         rpn, box = self.rpn_post, self.box_head
-        if len(anchors) != 1 or not all(t.is_cuda for t in objectness):
+        N = len(anchors)
+        if N < 1 or not all(t.is_cuda for t in objectness):
             return False
         if not (hasattr(rpn, "_within_capacity") and rpn._within_capacity(anchors, objectness)):
             return False
         cap = rpn.fpn_post_nms_top_n if len(objectness) > 1 else min(rpn.post_nms_top_n, rpn.pre_nms_top_n)
-        return hasattr(box, "detect_shapes_ok") and box.detect_shapes_ok(cap)
+        if N == 1:
+            return hasattr(box, "detect_shapes_ok") and box.detect_shapes_ok(cap)
+        size = tuple(anchors[0][0].size)                       # (one clip for the box head's batched launches)
+        return (all(tuple(per_image[0].size) == size for per_image in anchors)
+                and hasattr(box, "detect_shapes_ok_batched") and box.detect_shapes_ok_batched([cap] * N))
 
     @torch.no_grad()
     def forward(self, anchors, objectness, box_regression, features):
@@ -42,13 +49,17 @@ class DetectionHead(torch.nn.Module):
         if not self.raw_ok(anchors, objectness):
             proposals = rpn(anchors, objectness, box_regression)
             return box(features, proposals)[1]
-        size = anchors[0][0].size
+        size, N = anchors[0][0].size, len(anchors)
         boxes, _, count = ops.rpn_proposals(
-            objectness, box_regression, [[a.bbox for a in anchors[0]]], [size], rpn.pre_nms_top_n, rpn.post_nms_top_n,
-            rpn.fpn_post_nms_top_n, rpn.nms_thresh, rpn.min_size, amodal=rpn._amodal, weights=rpn.box_coder.weights,
-            xform_clip=rpn.box_coder.bbox_xform_clip)
-        det_boxes, scores, labels, _, out_count, _, _ = box.detect_raw(features, boxes[0], count[0:1], size)
-        return [box.wrap_detections(det_boxes, scores, labels, out_count, size)]       # the call's one device-to-host copy
+            objectness, box_regression, [[a.bbox for a in per_image] for per_image in anchors], [size] * N,
+            rpn.pre_nms_top_n, rpn.post_nms_top_n, rpn.fpn_post_nms_top_n, rpn.nms_thresh, rpn.min_size, amodal=rpn._amodal,
+            weights=rpn.box_coder.weights, xform_clip=rpn.box_coder.bbox_xform_clip)
+        if N == 1:
+            det_boxes, scores, labels, _, out_count, _, _ = box.detect_raw(features, boxes[0], count[0:1], size)
+            return [box.wrap_detections(det_boxes, scores, labels, out_count, size)]   # the call's one device-to-host copy
+        rows = [boxes.shape[1]] * N
+        det_boxes, scores, labels, _, out_count, _, _ = box.detect_raw_batched(features, boxes.view(-1, 4), rows, count, size)
+        return box.wrap_detections_batched(det_boxes, scores, labels, out_count, rows, size)   # the one copy: N counts
 
 
 def build_detection_head(cfg, rpn_box_coder, in_channels, box_head=None):

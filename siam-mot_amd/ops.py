@@ -125,6 +125,12 @@ _SIGNATURES = {
     "smot_box_detect_post_ws_bytes": (ctypes.c_longlong, [_i, _i]),
     "smot_box_detect_post_fwd": (ctypes.c_int, [_vp, _i, _i, _i, _vp, _vp, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _vp,
                                                 _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the box head over several images: the twins' arguments + num_images, row_start (host int array)
+    "smot_roi_align_levels_batched_typed_fwd": (ctypes.c_int, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i,
+                                                               _vp, _vp, _vp, _i, _vp]),
+    "smot_box_detect_post_batched_ws_bytes": (ctypes.c_longlong, [_i, _vp, _i]),
+    "smot_box_detect_post_batched_fwd": (ctypes.c_int, [_vp, _i, _i, _i, _vp, _vp, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _vp,
+                                                        _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 _DEBUG_SIGNATURES = {
@@ -527,13 +533,18 @@ def emm_decode(logits, sr, boxes, rx, rz, pad_pixels, sigma=0.4, use_centerness=
 _cast = lambda a: ctypes.cast(a, ctypes.c_void_p)
 
 
-def _level_arrays(features, scales, nhwc=True, what=""):
+def _level_arrays(features, scales, nhwc=True, what="", batched=False):
     """The first ``len(scales)`` levels as the library takes them and their ctypes arrays -> (maps, pointers, heights, widths,
-    scales, ``feat_type``).  ``what``: the caller's name in the error text (".roi_align_levels")."""
+    scales, ``feat_type``).  ``what``: the caller's name in the error text (".roi_align_levels").  ``batched``: ``[B, C, H_l,
+    W_l]`` maps with one B and one C for every level instead of one image."""
     L = len(scales)
     feats, ft = _dev_feats(features, L, nhwc)      # (one dtype per call: raises otherwise)
     for f in feats:
-        if f.dim() != 4 or f.shape[0] != 1:
+        if batched:
+            if f.dim() != 4 or f.shape[:2] != feats[0].shape[:2]:
+                raise RuntimeError("siammot_amd%s: every level must be [B, C, H, W] with one B and one C, got feature shapes %s"
+                                   % (what, [tuple(g.shape) for g in feats]))
+        elif f.dim() != 4 or f.shape[0] != 1:
             raise RuntimeError("siammot_amd%s: one image per call, got feature shape %s" % (what, tuple(f.shape)))
     fp = (ctypes.c_void_p * L)(*[f.data_ptr() for f in feats])
     hs = (ctypes.c_int * L)(*[f.shape[2] for f in feats])
@@ -960,6 +971,37 @@ def emm_extract_cache_batched(features, boxes, rows_per_image, rz, scales, sampl
     in ``emm_track_batched``) -> (templates, sr) or, with ``hint=True``, (templates, sr, order hint or None)."""
     return _emm_extract_cache(True, features, boxes, rows_per_image, rz, scales, sampling_ratio, pad_pixels,
                               search_expansion, min_search_wh, None, hint)
+
+
+def roi_align_levels_batched(features, rois, level_boxes, rows_per_image, out_size, scales, sampling_ratio, pad_cells=None):
+    """``roi_align_levels`` over B images in one library call: ``features`` are ``[B, C, H_l, W_l]`` per level (fp32, fp16 or
+    bf16, NCHW or channels-last, as for one image), the rois of image b are the ``rows_per_image[b]`` consecutive rows after
+    those of images 0..b-1 (host ints; zero is fine).  Returns ``[R, C, out_size, out_size]``; the rows of image b are bit for
+    bit what ``roi_align_levels`` gives on ``features[l][b:b+1]`` with them."""
+    lib = load_library()
+    L = len(scales)
+    feats, fp, hs, ws, sc, ft = _level_arrays(features, scales, what=".roi_align_levels_batched", batched=True)
+    B, C = feats[0].shape[0], feats[0].shape[1]
+    rois = _dev_f32(rois, "rois")
+    level_boxes = rois if level_boxes is None else _dev_f32(level_boxes, "level_boxes")
+    if rois.dim() != 2 or rois.shape[1] != 4 or level_boxes.shape != rois.shape:
+        raise RuntimeError("siammot_amd.roi_align_levels_batched: rois and level_boxes must be [R, 4], got %s and %s"
+                           % (tuple(rois.shape), tuple(level_boxes.shape)))
+    R = rois.shape[0]
+    if B > MAX_IMAGES:
+        raise RuntimeError("siammot_amd.roi_align_levels_batched: %d images, at most %d per call" % (B, MAX_IMAGES))
+    starts = _row_starts(rows_per_image, B, R)
+    if pad_cells is None:
+        pad_cells = [0] * L
+    out = torch.empty((R, C, out_size, out_size), dtype=torch.float32, device=rois.device)
+    pc = (ctypes.c_int * L)(*[int(p) for p in pad_cells[:L]])
+    with _Launch(rois, level_boxes, *feats) as ln:
+        rc = lib.smot_roi_align_levels_batched_typed_fwd(_cast(fp), ft, _cast(hs), _cast(ws), _cast(pc), _cast(sc), L, C,
+                                                         _ptr(rois), _ptr(level_boxes), R, out_size, out_size,
+                                                         int(sampling_ratio), _ptr(out), _ptr(None), ln.stream, B,
+                                                         _cast(starts))
+    _check(rc, "roi_align_levels_batched")
+    return out
 
 
 try:
@@ -1588,10 +1630,10 @@ def box_detect_post(head_out, num_classes, reg_classes, boxes, count, weights, x
     lib = _lib or load_library()
     head_out = _dev_f32(head_out, "head_out")
     boxes = _dev_f32(boxes, "boxes")
-    M, dev = boxes.shape[0], boxes.device
-    K, KR = int(num_classes), int(reg_classes)
     if boxes.dim() != 2 or boxes.shape[1] != 4:
         raise RuntimeError("siammot_amd.box_detect_post: boxes must be [M, 4], got %s" % (tuple(boxes.shape),))
+    M, dev = boxes.shape[0], boxes.device
+    K, KR = int(num_classes), int(reg_classes)
     if head_out.dim() != 2 or head_out.shape[0] != M or head_out.shape[1] < K + 4 * KR:
         raise RuntimeError("siammot_amd.box_detect_post: head_out %s does not hold %d logits + %d deltas for %d rows"
                            % (tuple(head_out.shape), K, 4 * KR, M))
@@ -1617,6 +1659,61 @@ def box_detect_post(head_out, num_classes, reg_classes, boxes, count, weights, x
                                           _ptr(out_boxes), _ptr(out_scores), _ptr(out_labels), _ptr(out_rows),
                                           _ptr(out_count), ln.stream)
     _check(rc, "box_detect_post")
+    return out_boxes, out_scores, out_labels, out_rows, out_count
+
+
+def box_detect_mask_bytes_batched(rows_per_image, num_classes):
+    """``box_detect_mask_bytes`` of a batched call: the sum over its images (one workspace segment per image)."""
+    return sum(box_detect_mask_bytes(int(r), num_classes) for r in rows_per_image)
+
+
+def box_detect_post_batched(head_out, num_classes, reg_classes, boxes, rows_per_image, count, weights, xform_clip, clip_wh,
+                            score_thresh, nms_thresh):
+    """``smot_box_detect_post_batched_fwd``: ``box_detect_post`` over the B images of a call in the same four launches.
+    ``head_out`` ``[M, >= K + 4*KR]`` and ``boxes`` ``[M, 4]`` hold the rows of all images, image b the ``rows_per_image[b]``
+    (host ints, each at most ``BOX_DETECT_MAX_ROWS``, zero is fine) consecutive rows after those of images 0..b-1; ``count``:
+    a device int32 tensor of B elements, the rows of each image that exist; ``clip_wh``: the one image size.  Returns
+    ``(boxes [cap,4], scores [cap], labels [cap] int64, rows [cap] int32, count [B, K] int32)`` with ``cap = M * (K - 1)``:
+    the detections of image b start at row ``(K - 1) * sum(rows_per_image[:b])`` and are, with ``count[b]``, bit for bit what
+    ``box_detect_post`` returns on that image's rows alone (``rows`` are relative to the image).  Nothing is read back."""
+    lib = _lib or load_library()
+    head_out = _dev_f32(head_out, "head_out")
+    boxes = _dev_f32(boxes, "boxes")
+    if boxes.dim() != 2 or boxes.shape[1] != 4:
+        raise RuntimeError("siammot_amd.box_detect_post_batched: boxes must be [M, 4], got %s" % (tuple(boxes.shape),))
+    M, dev = boxes.shape[0], boxes.device
+    K, KR = int(num_classes), int(reg_classes)
+    rows = [int(r) for r in rows_per_image]
+    B = len(rows)
+    if head_out.dim() != 2 or head_out.shape[0] != M or head_out.shape[1] < K + 4 * KR:
+        raise RuntimeError("siammot_amd.box_detect_post_batched: head_out %s does not hold %d logits + %d deltas for %d rows"
+                           % (tuple(head_out.shape), K, 4 * KR, M))
+    if not 1 <= B <= MAX_IMAGES:
+        raise RuntimeError("siammot_amd.box_detect_post_batched: %d images, need 1..%d per call" % (B, MAX_IMAGES))
+    if not (isinstance(count, torch.Tensor) and count.is_cuda and count.dtype is torch.int32 and count.device == dev
+            and count.numel() == B and count.is_contiguous()):
+        raise RuntimeError("siammot_amd.box_detect_post_batched: count must be a contiguous int32 tensor of exactly one "
+                           "element per image (%d) on the boxes' device" % B)
+    starts = _row_starts(rows, B, M)
+    nbytes = lib.smot_box_detect_post_batched_ws_bytes(B, _cast(starts), K)
+    if nbytes < 0:
+        _check(-1, "box_detect_post_batched")
+    stream = _stream(dev)
+    work = _workspace(dev, nbytes // 4, ("box_detect", stream.value))
+    cap = M * (K - 1)
+    out_boxes = torch.empty((cap, 4), dtype=_F32, device=dev)
+    out_scores = torch.empty((cap,), dtype=_F32, device=dev)
+    out_labels = torch.empty((cap,), dtype=torch.int64, device=dev)
+    out_rows = torch.empty((cap,), dtype=torch.int32, device=dev)
+    out_count = torch.empty((B, K), dtype=torch.int32, device=dev)
+    cw, ch = (0.0, 0.0) if clip_wh is None else (float(clip_wh[0]), float(clip_wh[1]))
+    with _Launch(head_out, boxes, count) as ln:
+        rc = lib.smot_box_detect_post_batched_fwd(_ptr(head_out), head_out.shape[1], K, KR, _ptr(boxes), _ptr(count), M,
+                                                  float(weights[0]), float(weights[1]), float(weights[2]), float(weights[3]),
+                                                  float(xform_clip), cw, ch, float(score_thresh), float(nms_thresh),
+                                                  _ptr(work), _ptr(out_boxes), _ptr(out_scores), _ptr(out_labels),
+                                                  _ptr(out_rows), _ptr(out_count), ln.stream, B, _cast(starts))
+    _check(rc, "box_detect_post_batched")
     return out_boxes, out_scores, out_labels, out_rows, out_count
 
 

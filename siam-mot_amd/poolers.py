@@ -5,8 +5,10 @@ uses it: ``ROIBoxHead`` (siammot/modelling/box_head/box_head.py:17,46) pools ≤
 ``CombinedROIHeads._refine_tracks`` (siammot/modelling/roi_heads.py:60-84) pools the N track boxes again.
 Same contract: ``Pooler(output_size, scales, sampling_ratio)(x, boxes) -> Tensor[R, C, h, w]``; each roi is
 assigned a level by ``LevelMapper`` of ITS OWN box (k_min/k_max from the first/last scale), legacy
-(non-aligned) ROIAlign with ``sampling_ratio``² samples per bin.  One image per call, as everywhere on
-this path (reference EMM/track_core.py:75); no padding (the box head pools the raw maps).
+(non-aligned) ROIAlign with ``sampling_ratio``² samples per bin; no padding (the box head pools the raw maps).
+``boxes`` is upstream's list of images: one BoxList is the single-image call, several take the maps as ``[B, C, H_l,
+W_l]`` and pool all images' rois in one launch (``ops.roi_align_levels_batched``) — rows in image order, each image's
+rows bit for bit what the single-image call gives on ``x[l][b:b+1]``; an image without rois is fine.
 """
 from torch import nn
 
@@ -26,7 +28,10 @@ class Pooler(nn.Module):
         self.sampling_ratio = sampling_ratio
 
     def forward(self, x, boxes):
-        if len(boxes) != 1:
-            raise RuntimeError("Pooler: one image per call")
+        if len(boxes) < 1:
+            raise RuntimeError("Pooler: at least one image per call")
         rois = cat([b.bbox for b in boxes], dim=0)
-        return ops.roi_align_levels(x, rois, rois, self.output_size[0], self.scales, self.sampling_ratio)
+        if len(boxes) == 1:
+            return ops.roi_align_levels(x, rois, rois, self.output_size[0], self.scales, self.sampling_ratio)
+        return ops.roi_align_levels_batched(x, rois, rois, [len(b) for b in boxes], self.output_size[0], self.scales,
+                                            self.sampling_ratio)
