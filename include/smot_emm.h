@@ -55,7 +55,7 @@ typedef void* smot_stream_t; /* hipStream_t */
  *     Added since without a new version (every existing symbol, struct and layout unchanged; a host layer asks for the
  *     symbols it needs): the _typed_ entry points, smot_rpn_proposals_*, smot_box_detect_post_*, and the box head over
  *     several images: smot_roi_align_levels_batched_typed_fwd, smot_box_detect_post_batched_ws_bytes,
- *     smot_box_detect_post_batched_fwd.
+ *     smot_box_detect_post_batched_fwd; the frames of several cameras in one call: smot_preprocess_batch_fwd.
  */
 #define SMOT_ABI_VERSION 14
 
@@ -303,6 +303,36 @@ int smot_preprocess_fwd(const unsigned char* frame, int H, int W,
                         int OH, int OW, int max_tile_rows,
                         const float* mean3, const float* std3, int to_bgr255,
                         float* out, smot_stream_t stream);
+
+/*
+ * The frames of several cameras in one call: num_images uint8 RGB HWC frames, each of its own input size and anywhere on
+ * the device, -> one [num_images, 3, OH, OW] network input of ONE output size, in ceil(num_images / 16) launches (image =
+ * blockIdx.z; the per-image values travel in the kernel-argument block).  Resampling, ToTensor and Normalize are
+ * smot_preprocess_fwd's, operation for operation: with out_type SMOT_FEAT_F32, image b is bit for bit what that call
+ * gives on frame b.
+ *
+ *   frames, H, W, xbounds, xcoeffs, kx, ybounds, ycoeffs, ky, max_tile_rows
+ *                HOST arrays of length num_images; entry b describes image b as smot_preprocess_fwd's arguments of the
+ *                same names do (the tables are device memory, made for H[b] x W[b] -> OH x OW; images of one input size
+ *                may share theirs).
+ *   mean3, std3  HOST arrays, indexed by OUTPUT channel; to_bgr255 as in smot_preprocess_fwd; one set per call.
+ *   out_type     SMOT_FEAT_F32, SMOT_FEAT_F16 or SMOT_FEAT_BF16 (defined below), optionally OR'ed with
+ *                SMOT_FEAT_CHANNELS_LAST: the element type and the layout of `out`.  A half output is the fp32 result
+ *                followed by exactly one round-to-nearest-even conversion (bit for bit `fp32_result.to(dtype)`).
+ *   out          without the layout flag [num_images, 3, OH, OW] contiguous: out[((b*3+c)*OH+y)*OW+x]; with it the same
+ *                tensor in channels-last memory: out[((b*OH+y)*OW+x)*3+c].  Aligned to its element size.
+ *
+ * Before the first launch, and without touching the device: SMOT_ERR_BAD_ARG for num_images outside [1, SMOT_MAX_IMAGES],
+ * a null pointer (array or entry), a non-positive size, an out_type outside {0, 1, 2, 16, 17, 18} or a misaligned out;
+ * SMOT_ERR_UNSUPPORTED for an image whose max_tile_rows * 384 bytes exceed 64 KiB of LDS (the message names the image).
+ * Deterministic; no atomics, no workspace.
+ */
+int smot_preprocess_batch_fwd(int num_images, const unsigned char* const* frames, const int* H, const int* W,
+                              const int* const* xbounds, const int* const* xcoeffs, const int* kx,
+                              const int* const* ybounds, const int* const* ycoeffs, const int* ky,
+                              const int* max_tile_rows, int OH, int OW,
+                              const float* mean3, const float* std3, int to_bgr255,
+                              void* out, int out_type, smot_stream_t stream);
 
 /*
  * Instrumentation (bench.py roofline leg): between _begin and _end every smot_xcorr_dw_fwd and

@@ -56,6 +56,9 @@ _SIGNATURES = {
                                                _vp, _vp, _vp]),
     "smot_sr_xcorr_gather_fwd": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "smot_preprocess_fwd": (ctypes.c_int, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    # the frames of several cameras in one call: host arrays of per-image pointers / sizes, one output size and tensor
+    "smot_preprocess_batch_fwd": (ctypes.c_int, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i,
+                                                 _vp, _i, _vp]),
     "smot_nms_ws_bytes": (ctypes.c_longlong, [_i]),
     "smot_nms_fwd": (ctypes.c_int, [_vp, _i, _f, _vp, _vp, _vp]),
     "smot_xcorr_timer_begin": (ctypes.c_int, [_i]),
@@ -1965,4 +1968,63 @@ def preprocess_frame(frame, tables, out_hw, mean, std, to_bgr255):
         rc = lib.smot_preprocess_fwd(_ptr(frame), H, W, _ptr(xb), _ptr(xk), xk.shape[1], _ptr(yb), _ptr(yk), yk.shape[1],
                                      OH, OW, int(max_rows), _cast(m), _cast(s), int(bool(to_bgr255)), _ptr(out), ln.stream)
     _check(rc, "preprocess_frame")
+    return out
+
+
+def preprocess_frames(frames, tables, out_hw, mean, std, to_bgr255, dtype=torch.float32, channels_last=False, out=None):
+    """The frames of several cameras -> one network input ``[B, 3, OH, OW]`` of ``dtype`` (fp32, fp16 or bf16), contiguous or
+    (``channels_last``) in ``torch.channels_last`` memory, in one library call (``smot_preprocess_batch_fwd``: one launch
+    per 16 images).  ``frames``: uint8 RGB ``[H_b, W_b, 3]`` device tensors, each of its own size; ``tables``: per frame the
+    tuple ``preprocess_frame`` takes (frames of one size share theirs), all made for ``out_hw``.  A half result is bit for
+    bit ``fp32_result.to(dtype)``.  ``out``: a tensor of exactly that shape, dtype and layout on the frames' device, written
+    in place and returned (anything else raises before the launch)."""
+    lib = load_library()
+    frames, tables = list(frames), list(tables)
+    B = len(frames)
+    if not 1 <= B <= MAX_IMAGES:
+        raise RuntimeError("siammot_amd.preprocess_frames: %d frames, need 1..%d per call" % (B, MAX_IMAGES))
+    if len(tables) != B:
+        raise RuntimeError("siammot_amd.preprocess_frames: %d table tuples for %d frames" % (len(tables), B))
+    if dtype not in FEAT_TYPES:
+        raise RuntimeError("siammot_amd.preprocess_frames: dtype must be float32, float16 or bfloat16, got %s" % (dtype,))
+    OH, OW = int(out_hw[0]), int(out_hw[1])
+    keep = []
+    for b, f in enumerate(frames):
+        if not isinstance(f, torch.Tensor) or not f.is_cuda or f.dtype != torch.uint8:
+            raise RuntimeError("siammot_amd.preprocess_frames: frames[%d] must be a uint8 device (ROCm) tensor — no CPU path "
+                               "exists" % b)
+        if f.dim() != 3 or f.shape[2] != 3:
+            raise RuntimeError("siammot_amd.preprocess_frames: frames[%d] must be [H, W, 3], got %s" % (b, tuple(f.shape)))
+        xb, _, yb, _, _ = tables[b]
+        if xb.shape[0] != OW or yb.shape[0] != OH:
+            raise RuntimeError("siammot_amd.preprocess_frames: tables[%d] are for %dx%d, asked for %dx%d"
+                               % (b, yb.shape[0], xb.shape[0], OH, OW))
+        keep.append(f.contiguous())
+    dev = keep[0].device
+    fmt = _CL if channels_last else torch.contiguous_format
+    if out is None:
+        out = torch.empty((B, 3, OH, OW), dtype=dtype, device=dev, memory_format=fmt)
+    else:
+        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != dev:
+            raise RuntimeError("siammot_amd.preprocess_frames: out must be a tensor on the frames' device (%s)" % dev)
+        if tuple(out.shape) != (B, 3, OH, OW) or out.dtype != dtype:
+            raise RuntimeError("siammot_amd.preprocess_frames: out must be %s of %s, got %s of %s"
+                               % ((B, 3, OH, OW), dtype, tuple(out.shape), out.dtype))
+        want = (OH * OW * 3, 1, OW * 3, 3) if channels_last else (3 * OH * OW, OH * OW, OW, 1)
+        if tuple(out.stride())[B == 1:] != want[B == 1:]:           # (a dimension of size 1 has no stride to speak of)
+            raise RuntimeError("siammot_amd.preprocess_frames: out must be %s with strides %s, got strides %s"
+                               % ("channels-last" if channels_last else "contiguous", want, tuple(out.stride())))
+    I, P = ctypes.c_int * B, ctypes.c_void_p * B
+    tabs = [t for tb in tables for t in tb[:4]]
+    m = (ctypes.c_float * 3)(*[float(v) for v in mean])
+    s = (ctypes.c_float * 3)(*[float(v) for v in std])
+    with _Launch(out, *(keep + tabs)) as ln:
+        rc = lib.smot_preprocess_batch_fwd(
+            B, _cast(P(*[f.data_ptr() for f in keep])), _cast(I(*[f.shape[0] for f in keep])),
+            _cast(I(*[f.shape[1] for f in keep])), _cast(P(*[tb[0].data_ptr() for tb in tables])),
+            _cast(P(*[tb[1].data_ptr() for tb in tables])), _cast(I(*[tb[1].shape[1] for tb in tables])),
+            _cast(P(*[tb[2].data_ptr() for tb in tables])), _cast(P(*[tb[3].data_ptr() for tb in tables])),
+            _cast(I(*[tb[3].shape[1] for tb in tables])), _cast(I(*[int(tb[4]) for tb in tables])), OH, OW, _cast(m), _cast(s),
+            int(bool(to_bgr255)), _ptr(out), FEAT_TYPES[dtype] | (FEAT_CHANNELS_LAST if channels_last else 0), ln.stream)
+    _check(rc, "preprocess_frames")
     return out

@@ -78,9 +78,27 @@ def max_tile_rows(ybounds, tile=TILE_ROWS):
     return int((last[ends] - first[starts]).max())
 
 
+def staging_plan(shapes, align=256):
+    """Where the uint8 frames of ``shapes`` (``(H, W, 3)`` each) sit in ONE staging buffer -> (offsets, total_bytes): frame b
+    occupies ``[offsets[b], offsets[b] + H*W*3)``, every offset a multiple of ``align``, in the order given.  A pure function
+    of the shapes."""
+    align = int(align)
+    if align <= 0:
+        raise ValueError("staging_plan: align must be positive, got %d" % align)
+    offsets, pos = [], 0
+    for shape in shapes:
+        n = 1
+        for d in shape:
+            n *= int(d)
+        offsets.append(pos)
+        pos = (pos + n + align - 1) // align * align
+    return offsets, pos
+
+
 class FramePreprocessor(object):
     """uint8 RGB frame ``[H,W,3]`` -> fp32 ``[3,oh,ow]`` on ``device``; drop-in for the reference's
-    ``transform(PIL image)`` at test time (no augmentation)."""
+    ``transform(PIL image)`` at test time (no augmentation).  ``batch`` takes the frames of several cameras in one call
+    (one staging copy, one library call) and returns ``[B,3,oh,ow]`` in the backbone's dtype and layout."""
 
     def __init__(self, min_size, max_size, size_divisibility=32, pixel_mean=(0.485, 0.456, 0.406),
                  pixel_std=(0.229, 0.224, 0.225), to_bgr255=False, device="cuda"):
@@ -93,6 +111,9 @@ class FramePreprocessor(object):
         self.device = torch.device(device)
         self._tables = {}
         self._staging = None
+        self._staging_many = None          # upload_many's pinned buffer, its device twin and the event guarding reuse
+        self._device_many = None
+        self._staged_many_event = None
 
     @classmethod
     def from_cfg(cfg_cls, cfg, device="cuda"):
@@ -141,3 +162,65 @@ class FramePreprocessor(object):
         out_hw = self.get_size((w, h))
         return ops.preprocess_frame(frame, self.tables((h, w), out_hw), out_hw, self.pixel_mean, self.pixel_std,
                                     self.to_bgr255)
+
+    def upload_many(self, frames):
+        """The frames of one call -> device tensors.  Host frames (numpy / CPU uint8) are packed into ONE pinned buffer at
+        ``staging_plan``'s offsets, cross in one asynchronous copy on the current stream and come back as views of one
+        device buffer; frames already on the device pass through untouched.  Both buffers grow, never shrink, are separate
+        from ``upload``'s and are reused by the next call: the pinned one only after the copy out of it has run (an event),
+        the device one in stream order — the views are valid until the next ``upload_many`` that has host frames (which
+        overwrites them: do not pass them back in together with new host frames)."""
+        frames = [torch.from_numpy(np.ascontiguousarray(f)) if isinstance(f, np.ndarray) else f for f in frames]
+        host = [b for b, f in enumerate(frames) if not f.is_cuda]
+        for b in host:
+            if frames[b].dtype != torch.uint8:
+                raise RuntimeError("siammot_amd.preprocess: frames must be uint8 RGB, got %s (frame %d)" % (frames[b].dtype, b))
+        if not host:
+            return frames
+        offsets, total = staging_plan([tuple(frames[b].shape) for b in host])
+        if self._staging_many is None or self._staging_many.numel() < total:
+            if self._staged_many_event is not None:
+                self._staged_many_event.synchronize()
+            self._staging_many = torch.empty(total, dtype=torch.uint8).pin_memory()
+            self._device_many = torch.empty(total, dtype=torch.uint8, device=self.device)
+            self._staged_many_event = None
+        if self._staged_many_event is not None:
+            self._staged_many_event.synchronize()
+        for off, b in zip(offsets, host):
+            f = frames[b]
+            self._staging_many[off:off + f.numel()].view(f.shape).copy_(f)
+        self._device_many[:total].copy_(self._staging_many[:total], non_blocking=True)
+        self._staged_many_event = torch.cuda.Event()
+        self._staged_many_event.record()
+        for off, b in zip(offsets, host):
+            f = frames[b]
+            frames[b] = self._device_many[off:off + f.numel()].view(f.shape)
+        return frames
+
+    @staticmethod
+    def image_sizes(frames):
+        """The original ``(w, h)`` of every frame, for mapping results back to the cameras' pixels."""
+        return [(int(f.shape[1]), int(f.shape[0])) for f in frames]
+
+    def batch(self, frames, dtype=torch.float32, channels_last=False, out=None):
+        """The frames of B cameras ``[H_b,W_b,3]`` (any mix of input sizes, host or device) -> ``[B,3,oh,ow]`` of ``dtype``,
+        contiguous or channels-last, optionally into the caller's ``out``.  Every frame's network size comes from
+        ``get_size``; they must all agree (as everywhere downstream: all images of a call share one size)."""
+        frames = list(frames)
+        if not 1 <= len(frames) <= ops.MAX_IMAGES:
+            raise RuntimeError("siammot_amd.preprocess: %d frames, need 1..%d per call" % (len(frames), ops.MAX_IMAGES))
+        for b, f in enumerate(frames):
+            if not isinstance(f, (np.ndarray, torch.Tensor)) or f.ndim != 3 or f.shape[2] != 3:
+                raise RuntimeError("siammot_amd.preprocess: frame %d must be [H, W, 3], got %s"
+                                   % (b, tuple(getattr(f, "shape", ())) or type(f).__name__))
+            if f.dtype != (np.uint8 if isinstance(f, np.ndarray) else torch.uint8):
+                raise RuntimeError("siammot_amd.preprocess: frames must be uint8 RGB, got %s (frame %d)" % (f.dtype, b))
+        sizes = [self.get_size(wh) for wh in self.image_sizes(frames)]
+        if any(sz != sizes[0] for sz in sizes):
+            raise RuntimeError("siammot_amd.preprocess: the frames of one call must share one network size, got %s for inputs %s"
+                               % (sizes, [(int(f.shape[0]), int(f.shape[1])) for f in frames]))
+        frames = self.upload_many(frames)
+        out_hw = sizes[0]
+        tables = [self.tables((int(f.shape[0]), int(f.shape[1])), out_hw) for f in frames]
+        return ops.preprocess_frames(frames, tables, out_hw, self.pixel_mean, self.pixel_std, self.to_bgr255, dtype=dtype,
+                                     channels_last=channels_last, out=out)
