@@ -34,7 +34,7 @@ typedef void* smot_stream_t; /* hipStream_t */
 #define SMOT_ERR_UNSUPPORTED (-2)  /* legal in the reference but not implemented here (documented per call) */
 
 #define SMOT_MAX_LEVELS 8
-#define SMOT_MAX_IMAGES 64          /* images per call of the batched head (smot_emm_*_batched_fwd) */
+#define SMOT_MAX_IMAGES 64          /* images per call of the batched head (smot_emm_*_batched_fwd) and solver */
 /* ABI history.
  * 10: the image of smot_emm_tower_pack grew (fp32 image + three-part bf16 image: ask smot_emm_tower_pack_floats), an image
  *     packed by a version-9 library is too short for this one; smot_emm_tower_form added.  (9: order-hint entries of 528 floats)
@@ -55,7 +55,8 @@ typedef void* smot_stream_t; /* hipStream_t */
  *     Added since without a new version (every existing symbol, struct and layout unchanged; a host layer asks for the
  *     symbols it needs): the _typed_ entry points, smot_rpn_proposals_*, smot_box_detect_post_*, and the box head over
  *     several images: smot_roi_align_levels_batched_typed_fwd, smot_box_detect_post_batched_ws_bytes,
- *     smot_box_detect_post_batched_fwd; the frames of several cameras in one call: smot_preprocess_batch_fwd.
+ *     smot_box_detect_post_batched_fwd; the frames of several cameras in one call: smot_preprocess_batch_fwd; the track
+ *     solver over several images: smot_track_solve_batched_fwd.
  */
 #define SMOT_ABI_VERSION 14
 
@@ -619,6 +620,47 @@ int smot_track_solve_carry_fwd(const float* det_boxes, float* det_scores, const 
                                const int64_t* carry_ids, const int64_t* carry_labels, const float* carry_scores,
                                int carry_src_row0, int carry_rows, int carry_dst_row0,
                                float* next_templates, float* next_sr, int row_floats, smot_stream_t stream);
+
+/*
+ * The track solver for the images (cameras) of a call: smot_track_solve_fwd on num_images independent frames, each with its
+ * own pool, in ONE launch per 16 images that have rows (ABI 14, additive).
+ *
+ * Replaces num_images calls of smot_track_solve_fwd — num_images single-workgroup launches that run one after the other on
+ * one compute unit each — for callers that run the batched head (smot_emm_track_batched_fwd) over several video streams.
+ * Every image gets one workgroup of the same solver; image b's results are bit for bit those of smot_track_solve_fwd on
+ * image b's arguments.  Workgroups share nothing.
+ *
+ *   layout    every argument of smot_track_solve_fwd as a HOST array of num_images entries, in that entry's order: entry b
+ *             of each array is image b's argument (det_labels[b] / trk_labels[b] may be NULL: 1).  Thresholds, nms_thresh
+ *             and max_dormant_frames are per image: cameras may be configured differently.  The arrays are read during the
+ *             call only — the per-image arguments travel in the launches' kernel arguments, nothing is kept.
+ *   empty     an image with n_det[b] + n_trk[b] == 0 gets no workgroup: its pool_state, outputs and record are neither read
+ *             nor written (its pointers may be NULL), as a caller of the single entry skips such a frame (the reference
+ *             does neither expire_tracks nor increment_frame for it).  A call in which no image has rows returns 0 and
+ *             launches nothing.
+ *   record    record[b]: int32 [8 + 4*M_b + 3*pool_capacity[b]] as smot_track_solve_fwd writes it, word 3 last behind a
+ *             system-scope fence; the segments may lie back to back in one allocation (one host copy for all images).
+ *   limits    1 <= num_images <= SMOT_MAX_IMAGES.  No dormant-row carry in this form (smot_track_solve_carry_fwd is
+ *             single-image).  The images' buffers must not overlap; the call checks what would make two workgroups race.
+ *
+ * Before the first launch and before any per-image pointer is dereferenced, with a message that names the image:
+ * SMOT_ERR_BAD_ARG for num_images outside [1, SMOT_MAX_IMAGES], a null array, a negative count, and — for an image with rows
+ * — the null-pointer and 16-byte alignment conditions of smot_track_solve_fwd, or the same pool_state or the same record as
+ * an earlier image with rows; SMOT_ERR_UNSUPPORTED for an image with more than smot_track_solve_max_boxes() rows or a
+ * larger pool_capacity.  A call that returns an error has launched nothing.
+ */
+int smot_track_solve_batched_fwd(int num_images,
+                                 const float* const* det_boxes, float* const* det_scores, const int64_t* const* det_ids,
+                                 const int64_t* const* det_labels, const int* n_det,
+                                 const float* const* trk_boxes, float* const* trk_scores, const int64_t* const* trk_ids,
+                                 const int64_t* const* trk_labels, const int* n_trk, const float* trk_score_bias,
+                                 const float* track_thresh, const float* start_thresh, const float* resume_thresh,
+                                 const float* nms_thresh, const int* max_dormant_frames,
+                                 int* const* pool_state, const int* pool_capacity,
+                                 float* const* out_boxes, float* const* out_scores, int64_t* const* out_ids,
+                                 int64_t* const* out_labels, float* const* act_boxes, int64_t* const* act_ids,
+                                 int64_t* const* act_labels, float* const* act_scores,
+                                 int* const* record, smot_stream_t stream);
 
 /*
  * One tracking frame behind ONE call (or two): the launches of smot_emm_track_fwd (3) [+ smot_box_refine_fwd (8)] +

@@ -12,6 +12,7 @@ Operator ↔ reference map (reference paths relative to amazon-science/siam-mot)
     emm_predictor      EMMPredictor.forward        EMM/feature_extractor.py:62-69
     emm_decode         3x F.interpolate + get_locations + decode_response   EMM/track_core.py:69-77
 """
+import array as _array
 import contextlib
 import ctypes
 import struct
@@ -134,6 +135,8 @@ _SIGNATURES = {
     "smot_box_detect_post_batched_ws_bytes": (ctypes.c_longlong, [_i, _vp, _i]),
     "smot_box_detect_post_batched_fwd": (ctypes.c_int, [_vp, _i, _i, _i, _vp, _vp, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _vp,
                                                         _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    # the track solver over several images: num_images, smot_track_solve_fwd's 27 arguments as host arrays, stream
+    "smot_track_solve_batched_fwd": (ctypes.c_int, [_i] + [_vp] * 27 + [_vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 _DEBUG_SIGNATURES = {
@@ -1137,6 +1140,7 @@ TIMER_XCORR, TIMER_TOWER = 0, 1
 #   host_solver          a frame beyond the one-launch solver's capacity (or with fields it does not carry): host path
 #   unhinted_head        a pooling + correlation launch that ranked its rois itself although an order hint could exist
 #   general_frame        a tracking-loop frame that did not take the one-launch path at all
+#   multi_camera_per_camera  a ``solver.solve_batched`` call that ran camera by camera (an image failed ``_device_path``)
 #   rpn_torch            an RPN proposal selection on device tensors beyond ``rpn_proposals``' capacities (torch composition)
 #   box_detect_torch     a box-head call on id-less device proposals that ``box_detect_post`` does not take (torch composition)
 import collections as _collections
@@ -1562,6 +1566,84 @@ def track_solve_record(rec):
     host.copy_(rec, non_blocking=True)
     torch.cuda.current_stream(dev).synchronize()
     return host.numpy().copy()
+
+
+TRACK_SOLVE_CHUNK = 16               # images per launch of the batched solver (csrc/track_solver.hip: TS_BATCH)
+
+
+def track_solve_batched(per_image):
+    """``smot_track_solve_batched_fwd``: ``track_solve`` for the B images (cameras) of a call, one workgroup per image in
+    ONE launch per ``TRACK_SOLVE_CHUNK`` images that have rows.  No synchronisation.
+
+    ``per_image``: B tuples ``(det, trk, trk_score_bias, thresholds, nms_thresh, max_dormant_frames, pool_state,
+    pool_capacity)``, each as ``track_solve`` takes them; every image has its own ``pool_state``.  Returns ``(bufs, rec,
+    offsets)``: ``bufs[b]`` the image's ``FrameBuffers`` (None for an image without rows: nothing is launched for it and its
+    pool state stands), ``rec`` ONE device int32 tensor with the images' records back to back and ``offsets`` (B + 1 words
+    into it; an image without rows has an empty segment).  ``track_solve_records(rec, offsets)`` brings them to the host."""
+    lib = _lib or load_library()
+    B = len(per_image)
+    if not 1 <= B <= MAX_IMAGES:
+        raise RuntimeError("siammot_amd.track_solve_batched: %d images, need 1..%d per call" % (B, MAX_IMAGES))
+    dev = per_image[0][6].device
+    # the 27 host arrays of the call, in the entry's order: 18 of pointers, 4 of ints, 5 of floats — three flat arrays, one
+    # row of B entries per argument (plain Python lists into array.array: cheaper than element-wise numpy at these sizes)
+    ptr = [[] for _ in range(18)]       # det (boxes, scores, ids, labels), trk (the same), pool state, 8 outputs, record
+    ints = [[] for _ in range(4)]       # n_det, n_trk, max dormant frames, pool capacity
+    flt = [[] for _ in range(5)]        # score bias, track / start / resume thresholds, NMS threshold
+    bufs, offsets = [], [0]
+    none8 = (0,) * 8
+    for b, (det, trk, bias, thresholds, nms_thresh, max_dormant, state, cap) in enumerate(per_image):
+        if state.device != dev:
+            raise RuntimeError("siammot_amd.track_solve_batched: image %d's pool state lives on %s, image 0's on %s"
+                               % (b, state.device, dev))
+        s0, s1 = segment_pointers(det, dev), segment_pointers(trk, dev)
+        M = s0[4] + s1[4]
+        buf = FrameBuffers.allocate(M, dev) if M else None
+        bufs.append(buf)
+        offsets.append(offsets[-1] + (FrameBuffers.record_words(M, cap) if M else 0))
+        for k, v in enumerate(s0[:4] + s1[:4] + (state.data_ptr(),) + (buf.solver_pointers() if M else none8)):
+            ptr[k].append(v)
+        for k, v in enumerate((s0[4], s1[4], max_dormant, cap)):
+            ints[k].append(v)
+        for k, v in enumerate((bias, thresholds[0], thresholds[1], thresholds[2], nms_thresh)):
+            flt[k].append(v)
+    rec = torch.empty((offsets[-1],), dtype=torch.int32, device=dev)
+    rp = rec.data_ptr()
+    ptr[17] = [rp + 4 * o for o in offsets[:-1]]
+    ptr, ints, flt = (_array.array(code, [v for row in rows for v in row])
+                      for code, rows in (("Q", ptr), ("i", ints), ("f", flt)))
+    P0, I0, F0 = ptr.buffer_info()[0], ints.buffer_info()[0], flt.buffer_info()[0]
+    P, I, F = (lambda k: P0 + 8 * B * k), (lambda k: I0 + 4 * B * k), (lambda k: F0 + 4 * B * k)
+    cur = torch.cuda.current_device()
+    if cur != dev.index:
+        torch.cuda.set_device(dev.index)
+    try:
+        rc = lib.smot_track_solve_batched_fwd(B, P(0), P(1), P(2), P(3), I(0), P(4), P(5), P(6), P(7), I(1), F(0), F(1), F(2),
+                                              F(3), F(4), I(2), P(8), I(3), P(9), P(10), P(11), P(12), P(13), P(14), P(15),
+                                              P(16), P(17), _stream(dev))
+    finally:
+        if cur != dev.index:
+            torch.cuda.set_device(cur)
+    if rc:
+        _check(rc, "track_solve_batched")
+    return bufs, rec, offsets
+
+
+_recs_pinned = {}
+
+
+def track_solve_records(rec, offsets):
+    """The records of ``track_solve_batched`` on the host, one numpy array per image (empty for an image without rows): ONE
+    copy of the concatenated tensor through a pinned buffer + ONE stream synchronisation, whatever the number of images —
+    ``track_solve_record`` for a call's worth of records.  The pinned buffer is kept per device and grown, never per size."""
+    dev, n = rec.device, rec.shape[0]
+    host = _recs_pinned.get(dev)
+    if host is None or host.shape[0] < n:
+        host = _recs_pinned[dev] = torch.empty((max(2 * n, 4096),), dtype=torch.int32).pin_memory()
+    host[:n].copy_(rec, non_blocking=True)
+    torch.cuda.current_stream(dev).synchronize()
+    whole = host.numpy()[:n].copy()
+    return [whole[offsets[b]:offsets[b + 1]] for b in range(len(offsets) - 1)]
 
 
 def wait_host_record(flag, fallback, spins=20000):
