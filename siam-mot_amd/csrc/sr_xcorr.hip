@@ -14,7 +14,9 @@
 //      loads the (up to) four feature rows of the two y-samples — contiguous row segments, coalesced,
 //      no LDS window — forms the two column values, and lane pw gathers its four column values with
 //      ds_bpermute (cross-lane, no LDS storage).  Terms are added in the reference's (iy, ix) order; only
-//      the factorisation (hy*hx)*v -> hx*(hy*v) differs (fp32 rounding level, tested to 1e-5).
+//      the factorisation (hy*hx)*v -> hx*(hy*v) differs: fp32 rounding level, held to (2 e32 + 2^-22) * sum w|v| of an
+//      fp64 evaluation on the reference's own fp32 sample tables (e32: the fp32 reference's own error in that case,
+//      <= 2^-21; measured here <= 2.4e-7 * sum w|v|: tests/test_roi_pool_edges.py).
 //   3. The pooled 30x30 planes land in the same LDS image the xcorr kernel stages from HBM
 //      (xcorr_patch2.h), the templates are staged next to them, and the FMA phase is the shared
 //      xcorr_patch2_compute: responses are bit-identical to smot_xcorr_dw_fwd on the pooled planes.
