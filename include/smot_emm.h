@@ -79,6 +79,12 @@ int smot_debug_sr_xcorr_fused_hint_fwd(const float* const* feats, const int* hei
                                        const int* pad_cells, const float* scales, int num_levels, int C,
                                        const float* boxes, const float* sr, const float* templates, int N,
                                        float* resp, const float* order_hint, smot_stream_t stream);
+/* Measurement library only: smot_linear_rows_fwd's layer on up to smot_box_refine_batched_max_rows() rows, in the form
+ * smot_box_refine_batched_typed_fwd runs it (row blocks of 128 in the same two launches) — for the test that row r equals,
+ * bit for bit, what smot_linear_rows_fwd gives for it in any call of at most 128 rows.  K % 4 == 0. */
+long long smot_debug_linear_rows_blocks_ws_floats(int M, int K, int N);
+int smot_debug_linear_rows_blocks_fwd(const float* x, int M, int K, const float* W, const float* bias, int N, int relu,
+                                      float* ws, float* y, int ldy, smot_stream_t stream);
 #endif
 
 /* Message describing the last non-zero return on the calling thread ("" if none). */
@@ -1000,6 +1006,54 @@ int smot_box_detect_post_batched_fwd(const float* head_out, int ld, int num_clas
                                      float clip_w, float clip_h, float score_thresh, float nms_thresh, void* ws,
                                      float* out_boxes, float* out_scores, int64_t* out_labels, int32_t* out_rows,
                                      int32_t* out_count, smot_stream_t stream, int num_images, const int* row_start);
+
+/*
+ * BOX-HEAD REFINEMENT OF THE PROPAGATED TRACKS OF SEVERAL IMAGES (csrc/box_refine.hip): smot_box_refine_post_fwd and
+ * smot_box_refine_typed_fwd over the cameras of a call.
+ * Replaces: CombinedROIHeads._refine_tracks (reference siammot/modelling/roi_heads.py:60-84) called once per image.
+ *
+ *   rows           the rows of all images concatenated (head_out / boxes / labels / ids / track_conf and every output); image
+ *                  b owns rows [row_start[b], row_start[b+1]) — num_images and row_start (HOST array of num_images + 1 ints)
+ *                  as for smot_emm_*_batched_fwd.  Before any launch: SMOT_ERR_BAD_ARG for num_images outside
+ *                  [1, SMOT_MAX_IMAGES], a null row_start, row_start[0] != 0, a decrease (the image is named in
+ *                  smot_last_error()), row_start[num_images] != N, null pointers, a misaligned ws.  An image may have no rows;
+ *                  a call in which none has returns 0 and launches nothing.
+ *   feats          [num_images, C, H_l, W_l] per level, of element type and layout feat_type (SMOT_FEAT_*, as for
+ *                  smot_box_refine_typed_fwd); one image size, one clip pair and one tracktor flag per call.
+ *   outputs        image b's rows in ITS segment [row_start[b], row_start[b+1]): grouped by label inside the segment, input
+ *                  order inside a label; the box-head score of OUTPUT row p of the segment is averaged with the matching
+ *                  score of INPUT row p of the segment (roi_heads.py:66,70, per image).
+ *   contract       for every image every output equals BIT FOR BIT what the single-image entry (smot_box_refine_post_fwd /
+ *                  smot_box_refine_typed_fwd) returns on that image's maps and rows alone: the layers run
+ *                  smot_linear_rows_fwd's kernels with one more grid dimension (row blocks of 128), and a row's sums do not
+ *                  depend on the rows that share its launch.
+ *   launches       smot_box_refine_post_batched_fwd: one (a workgroup per image).  smot_box_refine_batched_typed_fwd: eight
+ *                  whatever num_images is (batched pooler, a partial-sum and a reduction launch per layer, post-processing),
+ *                  no host synchronisation.
+ *   limits         smot_box_refine_post_batched_fwd: smot_box_refine_post_max_rows() rows per image (SMOT_ERR_BAD_ARG).
+ *                  smot_box_refine_batched_typed_fwd: SMOT_ERR_UNSUPPORTED for an image of more than 128 rows (named in the
+ *                  message; alone it would not take the one-call path), for N > smot_box_refine_batched_max_rows() (1024)
+ *                  and for the pooler shapes / layer widths smot_box_refine_fwd refuses.
+ *   ws             device fp32 [smot_box_refine_batched_ws_floats(N, ...)] (N = all rows; 0 for a call the entry refuses),
+ *                  16-byte aligned, all of it scratch: the pooled rows, the three layers' outputs and the largest layer's
+ *                  K-slice sums — at the yaml head (C 128, 7x7, 1024-1024) 0.2 MB per row + 33 MB per 128 rows.
+ */
+int smot_box_refine_batched_max_rows(void);
+long long smot_box_refine_batched_ws_floats(int N, int C, int pooled, int dim6, int dim7, int num_classes, int reg_classes);
+int smot_box_refine_post_batched_fwd(const float* head_out, int ld, int num_classes, int reg_classes, const float* boxes,
+                                     const int64_t* labels, const int64_t* ids, const float* track_conf, int N, float wx,
+                                     float wy, float ww, float wh, float xform_clip, float clip_w, float clip_h, int tracktor,
+                                     float* out_boxes, float* out_scores, int64_t* out_ids, int64_t* out_labels,
+                                     smot_stream_t stream, int num_images, const int* row_start);
+int smot_box_refine_batched_typed_fwd(const void* const* feats, int feat_type, const int* heights, const int* widths,
+                                      const float* scales, int num_levels, int C, int pooled, int sampling_ratio,
+                                      const float* boxes, const int64_t* labels, const int64_t* ids, const float* track_conf,
+                                      int N, const float* fc6_w, const float* fc6_b, int dim6, const float* fc7_w,
+                                      const float* fc7_b, int dim7, const float* cls_w, const float* cls_b, int num_classes,
+                                      const float* reg_w, const float* reg_b, int reg_classes, float wx, float wy, float ww,
+                                      float wh, float xform_clip, float clip_w, float clip_h, int tracktor, float* ws,
+                                      float* out_boxes, float* out_scores, int64_t* out_ids, int64_t* out_labels,
+                                      smot_stream_t stream, int num_images, const int* row_start);
 
 #ifdef __cplusplus
 }

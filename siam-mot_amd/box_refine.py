@@ -18,7 +18,10 @@ Two halves of the post-processor also exist as HIP kernels on raw device tensors
 are all tracks (``refine_raw``, csrc/box_refine.hip) and rows that are all detections — proposals without ids, what the RPN
 hands over every frame (``detect_raw``, csrc/box_detect.hip; ``forward`` takes it for id-less device proposals and reads one
 number back, the detection count; several images of one size: ``detect_raw_batched``, the same launches for all of them and
-one copy of the B counts).  Mixed rows keep the ``BoxList`` path.
+one copy of the B counts).  Mixed rows keep the ``BoxList`` path.  The track half has a form for several images as
+well: ``refine_raw_batched`` — the propagated tracks of the B cameras of a call in one library call, every image's rows bit
+for bit those of ``refine_raw`` on it alone — which ``RefineTracks`` takes when it is given several BoxLists
+(INTEGRATION.md §3j).
 """
 import math
 
@@ -417,6 +420,38 @@ class TrackBoxHead(nn.Module):
         return res
 
 
+    # ---- the propagated tracks of several images (cameras) in one library call -------------------------------------------
+    def refine_batch_offered(self):
+        """This box head has the batched device form at all (whatever the row counts): what ``raw_ok`` asks beside them."""
+        return (isinstance(self.feature_extractor.pooler, Pooler) and self.post_processor.score_thresh < 1.0
+                and self.predictor.cls_score.weight.is_cuda)
+
+    def refine_batch_ok(self, rows_per_image):
+        """``refine_raw_batched`` applies to images of these row counts (an image may have none): ``one_call_ok`` for every
+        image that has rows — so that each is bit for bit what ``refine_raw`` gives on it alone — and the call's caps."""
+        rows = [int(n) for n in rows_per_image]
+        total = sum(rows)
+        return (1 <= len(rows) <= ops.MAX_IMAGES and total > 0 and all(n >= 0 for n in rows)
+                and all(n <= ops.BOX_REFINE_IMAGE_ROWS and self.one_call_ok(n) for n in rows if n)
+                and total <= ops.box_refine_batched_max_rows())
+
+    @torch.no_grad()
+    def refine_raw_batched(self, features, boxes, conf, ids, labels, rows_per_image, image_wh, tracktor=False):
+        """``refine_raw`` on the B images of a call: ``features[l]`` = ``[B, C, H_l, W_l]``, ``boxes [N, 4]`` / ``conf`` /
+        ``ids`` / ``labels`` = the rows of all images (image b: the ``rows_per_image[b]`` rows after those of the images before
+        it; host ints), ``image_wh`` the one image size.  One library call, eight launches whatever B is, nothing read back.
+        Returns ``(boxes, scores, ids, labels)`` with image b's rows in its input segment, in the box head's output order
+        inside it — bit for bit ``refine_raw`` on ``features[l][b:b+1]`` and the image's rows (``refine_batch_ok``)."""
+        fe, pp = self.feature_extractor, self.post_processor
+        pooler = fe.pooler
+        cs, bp = self.predictor.cls_score, self.predictor.bbox_pred
+        bc = pp.box_coder
+        return ops.box_refine_batched(features, pooler.scales, pooler.output_size[0], pooler.sampling_ratio, boxes, labels, ids,
+                                      conf, rows_per_image, (fe.fc6.weight, fe.fc6.bias, fe.fc7.weight, fe.fc7.bias, cs.weight,
+                                                             cs.bias, bp.weight, bp.bias), bc.weights, bc.bbox_xform_clip,
+                                      None if pp.amodal_inference else image_wh, tracktor)
+
+
 class RefineTracks(object):
     """roi_heads.py:60-84 as a callable: ``refine(features, [tracks]) -> [tracks]``.
 
@@ -441,7 +476,59 @@ class RefineTracks(object):
     def refine_raw(self, features, boxes, conf, ids, labels, image_wh):
         return self.box.refine_raw(features, boxes, conf, ids, labels, image_wh, self.tracktor)
 
+    def offers_batched(self):
+        """The box head has a batched device form (``MultiCameraTrackingLoop`` then makes one call per step)."""
+        offered = getattr(self.box, "refine_batch_offered", None)
+        return offered is not None and bool(offered())
+
+    def refine_batch_ok(self, rows_per_image):
+        """The batched device form applies to images of these row counts (``TrackBoxHead.refine_batch_ok``)."""
+        ok = getattr(self.box, "refine_batch_ok", None)
+        return ok is not None and ok(rows_per_image)
+
+    def refine_raw_batched(self, features, boxes, conf, ids, labels, rows_per_image, image_wh):
+        return self.box.refine_raw_batched(features, boxes, conf, ids, labels, rows_per_image, image_wh, self.tracktor)
+
+    def batch_ok(self, tracks):
+        """``__call__`` takes the batched device path for these BoxLists: device fp32 xyxy boxes on one device, one image
+        size, ``scores`` / ``ids`` / ``labels`` on every list that has rows, row counts within ``refine_batch_ok``."""
+        live = [t for t in tracks if len(t)]
+        if not live:
+            return False
+        first = live[0]
+        return (all(t.bbox.is_cuda and t.bbox.dtype is torch.float32 and t.mode == "xyxy" and t.bbox.device == first.bbox.device
+                    and tuple(t.size) == tuple(first.size) and t.has_field("scores") and t.has_field("ids")
+                    and t.has_field("labels") for t in live)
+                and self.refine_batch_ok([len(t) for t in tracks]))
+
+    def _call_images(self, features, tracks):
+        """``__call__`` on B > 1 images (``features[l]`` = ``[B, C, H_l, W_l]``): one ``refine_raw_batched`` call when
+        ``batch_ok`` holds, otherwise image by image on ``f[b:b+1]``.  Empty lists come back untouched."""
+        if self.batch_ok(tracks):
+            live = [t for t in tracks if len(t)]
+            cat = (lambda ts: ts[0] if len(ts) == 1 else torch.cat(ts))
+            boxes, scores, ids, labels = self.refine_raw_batched(
+                features, cat([t.bbox for t in live]), cat([t.get_field("scores") for t in live]),
+                cat([t.get_field("ids") for t in live]), cat([t.get_field("labels") for t in live]),
+                [len(t) for t in tracks], live[0].size)
+            out, n0 = [], 0
+            for t in tracks:
+                if len(t) == 0:
+                    out.append(t)
+                    continue
+                n1 = n0 + len(t)
+                r = t.__class__(boxes[n0:n1], t.size, mode="xyxy")
+                r.add_field("scores", scores[n0:n1])
+                r.add_field("ids", ids[n0:n1])
+                r.add_field("labels", labels[n0:n1])
+                out.append(r)
+                n0 = n1
+            return out
+        return [t if len(t) == 0 else self(tuple(f[b:b + 1] for f in features), [t])[0] for b, t in enumerate(tracks)]
+
     def __call__(self, features, tracks):
+        if len(tracks) > 1:
+            return self._call_images(features, tracks)
         if len(tracks[0]) == 0:
             return tracks
         track_scores = tracks[0].get_field("scores") + 1.0

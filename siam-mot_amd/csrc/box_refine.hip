@@ -24,7 +24,13 @@
 // deltas gives NaN in exactly the coordinates where BoxCoder.decode followed by torch.clamp gives NaN (dx, dw: x1 and
 // x2; dy, dh: y1 and y2), clipped or not: the clamps of dw / dh and of clip_to_image keep a NaN (min_nan, clamp_nan).
 // No other row is affected (tests/test_box_refine_edges.py).
+//
+// Several images per call (box_refine_post_batched_kernel): one workgroup per image on its rows [row_start[b],
+// row_start[b+1]) — the same body on pointers moved to the image's first row, so ranks, the LDS tables, the output rows and
+// the output-row / input-row pairing of the scores are the image's own, and image b's rows are bit for bit what the single
+// launch gives on them alone.  The row ranges travel in the kernel arguments (ImageRows); an image without rows returns.
 #include "smot_common.h"
+#include "pool_launch.h"
 
 namespace smot {
 
@@ -54,8 +60,9 @@ struct BoxRefineArgs {
 };
 constexpr int BR_PART_ROWS = 128, BR_PART_COLS = 64;
 
+// The workgroup's work on N rows that start at the pointers of A (both kernels below)
 template <bool PART>
-__global__ void __launch_bounds__(BR_MAXN) box_refine_post_kernel(BoxRefineArgs A, int N) {
+__device__ __forceinline__ void box_refine_post_rows(const BoxRefineArgs& A, int N) {
     __shared__ int slab[BR_MAXN];
     __shared__ float sdet[BR_MAXN];
     __shared__ float head[PART ? BR_PART_ROWS * BR_PART_COLS : 1];
@@ -147,24 +154,32 @@ __global__ void __launch_bounds__(BR_MAXN) box_refine_post_kernel(BoxRefineArgs 
     }
 }
 
-}  // namespace smot
+template <bool PART>
+__global__ void __launch_bounds__(BR_MAXN) box_refine_post_kernel(BoxRefineArgs A, int N) {
+    box_refine_post_rows<PART>(A, N);
+}
 
-extern "C" int smot_box_refine_post_max_rows(void) { return smot::BR_MAXN; }
+// image = blockIdx.x (the head's output as finished logits: A.logits)
+__global__ void __launch_bounds__(BR_MAXN) box_refine_post_batched_kernel(BoxRefineArgs A, ImageRows I) {
+    const int r0 = I.row_start[blockIdx.x], n = I.row_start[blockIdx.x + 1] - r0;
+    if (n <= 0) return;
+    A.logits += (size_t)r0 * A.ldo;
+    A.boxes += (size_t)r0 * 4;
+    A.labels += r0;
+    A.ids += r0;
+    A.track_conf += r0;
+    A.out_boxes += (size_t)r0 * 4;
+    A.out_scores += r0;
+    A.out_ids += r0;
+    A.out_labels += r0;
+    box_refine_post_rows<false>(A, n);
+}
 
-extern "C" int smot_box_refine_post_fwd(const float* head_out, int ld, int num_classes, int reg_classes,
-                                        const float* boxes, const int64_t* labels, const int64_t* ids,
-                                        const float* track_conf, int N, float wx, float wy, float ww, float wh,
-                                        float xform_clip, float clip_w, float clip_h, int tracktor, float* out_boxes,
-                                        float* out_scores, int64_t* out_ids, int64_t* out_labels, smot_stream_t stream) {
-    using namespace smot;
-    SMOT_REQUIRE(N >= 0 && N <= BR_MAXN, "box_refine_post: N=%d not in [0,%d]", N, BR_MAXN);
-    SMOT_REQUIRE(num_classes >= 2 && (reg_classes == num_classes || reg_classes == 2) &&
-                     ld >= num_classes + 4 * reg_classes,
-                 "box_refine_post: bad head shape K=%d KR=%d ld=%d", num_classes, reg_classes, ld);
-    SMOT_REQUIRE(wx > 0.f && wy > 0.f && ww > 0.f && wh > 0.f, "box_refine_post: regression weights must be positive");
-    if (N == 0) return SMOT_OK;
-    SMOT_REQUIRE(head_out && boxes && labels && ids && track_conf && out_boxes && out_scores && out_ids && out_labels,
-                 "box_refine_post: null pointer");
+// The kernels' arguments, for the form that reads finished logits (the PART form sets A.part / S / rows_pad / biases after it)
+static BoxRefineArgs box_refine_args(const float* head_out, int ld, int num_classes, int reg_classes, const float* boxes,
+                                     const int64_t* labels, const int64_t* ids, const float* track_conf, float wx, float wy,
+                                     float ww, float wh, float xform_clip, float clip_w, float clip_h, int tracktor,
+                                     float* out_boxes, float* out_scores, int64_t* out_ids, int64_t* out_labels) {
     BoxRefineArgs A;
     A.logits = head_out;
     A.ldo = ld;
@@ -189,15 +204,78 @@ extern "C" int smot_box_refine_post_fwd(const float* head_out, int ld, int num_c
     A.part = nullptr;
     A.S = A.rows_pad = 0;
     A.cls_b = A.reg_b = nullptr;
+    return A;
+}
+
+}  // namespace smot
+
+extern "C" int smot_box_refine_post_max_rows(void) { return smot::BR_MAXN; }
+
+extern "C" int smot_box_refine_post_fwd(const float* head_out, int ld, int num_classes, int reg_classes,
+                                        const float* boxes, const int64_t* labels, const int64_t* ids,
+                                        const float* track_conf, int N, float wx, float wy, float ww, float wh,
+                                        float xform_clip, float clip_w, float clip_h, int tracktor, float* out_boxes,
+                                        float* out_scores, int64_t* out_ids, int64_t* out_labels, smot_stream_t stream) {
+    using namespace smot;
+    SMOT_REQUIRE(N >= 0 && N <= BR_MAXN, "box_refine_post: N=%d not in [0,%d]", N, BR_MAXN);
+    SMOT_REQUIRE(num_classes >= 2 && (reg_classes == num_classes || reg_classes == 2) &&
+                     ld >= num_classes + 4 * reg_classes,
+                 "box_refine_post: bad head shape K=%d KR=%d ld=%d", num_classes, reg_classes, ld);
+    SMOT_REQUIRE(wx > 0.f && wy > 0.f && ww > 0.f && wh > 0.f, "box_refine_post: regression weights must be positive");
+    if (N == 0) return SMOT_OK;
+    SMOT_REQUIRE(head_out && boxes && labels && ids && track_conf && out_boxes && out_scores && out_ids && out_labels,
+                 "box_refine_post: null pointer");
+    const BoxRefineArgs A = box_refine_args(head_out, ld, num_classes, reg_classes, boxes, labels, ids, track_conf, wx, wy, ww,
+                                            wh, xform_clip, clip_w, clip_h, tracktor, out_boxes, out_scores, out_ids,
+                                            out_labels);
     hipLaunchKernelGGL(box_refine_post_kernel<false>, dim3(1), dim3(BR_MAXN), 0, (hipStream_t)stream, A, N);
     return check_launch("box_refine_post");
+}
+
+// Checks of a batched call shared by the two entries below: the table (SMOT_ERR_BAD_ARG), then the rows of one image
+static int box_refine_image_rows(smot::ImageRows* I, int num_images, const int* row_start, int N, int max_rows, int err,
+                                 const char* who) {
+    using namespace smot;
+    SMOT_REQUIRE(N >= 0, "%s: N=%d", who, N);
+    const int rc = fill_image_rows(I, num_images, row_start, N, who);
+    if (rc) return rc;
+    for (int b = 0; b < num_images; ++b) {
+        if (row_start[b + 1] - row_start[b] > max_rows) {
+            set_error("%s: image %d has %d rows, at most %d per image", who, b, row_start[b + 1] - row_start[b], max_rows);
+            return err;
+        }
+    }
+    return SMOT_OK;
+}
+
+extern "C" int smot_box_refine_post_batched_fwd(const float* head_out, int ld, int num_classes, int reg_classes,
+                                                const float* boxes, const int64_t* labels, const int64_t* ids,
+                                                const float* track_conf, int N, float wx, float wy, float ww, float wh,
+                                                float xform_clip, float clip_w, float clip_h, int tracktor,
+                                                float* out_boxes, float* out_scores, int64_t* out_ids, int64_t* out_labels,
+                                                smot_stream_t stream, int num_images, const int* row_start) {
+    using namespace smot;
+    ImageRows I;
+    const int rc = box_refine_image_rows(&I, num_images, row_start, N, BR_MAXN, SMOT_ERR_BAD_ARG, "box_refine_post_batched");
+    if (rc) return rc;
+    SMOT_REQUIRE(num_classes >= 2 && (reg_classes == num_classes || reg_classes == 2) &&
+                     ld >= num_classes + 4 * reg_classes,
+                 "box_refine_post_batched: bad head shape K=%d KR=%d ld=%d", num_classes, reg_classes, ld);
+    SMOT_REQUIRE(wx > 0.f && wy > 0.f && ww > 0.f && wh > 0.f, "box_refine_post_batched: regression weights must be positive");
+    if (N == 0) return SMOT_OK;
+    SMOT_REQUIRE(head_out && boxes && labels && ids && track_conf && out_boxes && out_scores && out_ids && out_labels,
+                 "box_refine_post_batched: null pointer");
+    const BoxRefineArgs A = box_refine_args(head_out, ld, num_classes, reg_classes, boxes, labels, ids, track_conf, wx, wy, ww,
+                                            wh, xform_clip, clip_w, clip_h, tracktor, out_boxes, out_scores, out_ids,
+                                            out_labels);
+    hipLaunchKernelGGL(box_refine_post_batched_kernel, dim3(num_images), dim3(BR_MAXN), 0, (hipStream_t)stream, A, I);
+    return check_launch("box_refine_post_batched");
 }
 
 
 // ---- the whole refinement of the propagated tracks behind ONE call ------------------------------------------------------
 // HIP 7x7 pooler -> fc6 + ReLU -> fc7 + ReLU -> cls_score | bbox_pred -> post-processing: eight launches enqueued by one
 // C-ABI crossing (the Python layer paid one ctypes call + one tensor allocation per stage).
-#include "pool_launch.h"
 extern "C" long long smot_linear_rows_ws_floats(int M, int K, int N);
 
 static inline size_t br_align4(size_t n) { return (n + 3) & ~(size_t)3; }
@@ -278,27 +356,8 @@ extern "C" int smot_box_refine_fwd(const float* const* feats, const int* heights
                  num_classes, reg_classes);
     SMOT_REQUIRE(wx > 0.f && wy > 0.f && ww > 0.f && wh > 0.f, "box_refine: regression weights must be positive");
     SMOT_REQUIRE(labels && ids && track_conf && out_boxes && out_scores && out_ids && out_labels, "box_refine: null pointer");
-    BoxRefineArgs A;
-    A.logits = nullptr;
-    A.ldo = NH;
-    A.K = num_classes;
-    A.KR = reg_classes;
-    A.boxes = boxes;
-    A.labels = (const long long*)labels;
-    A.ids = (const long long*)ids;
-    A.track_conf = track_conf;
-    A.wx = wx;
-    A.wy = wy;
-    A.ww = ww;
-    A.wh = wh;
-    A.xform_clip = xform_clip;
-    A.clip_w = clip_w;
-    A.clip_h = clip_h;
-    A.tracktor = tracktor;
-    A.out_boxes = out_boxes;
-    A.out_scores = out_scores;
-    A.out_ids = (long long*)out_ids;
-    A.out_labels = (long long*)out_labels;
+    BoxRefineArgs A = box_refine_args(nullptr, NH, num_classes, reg_classes, boxes, labels, ids, track_conf, wx, wy, ww, wh,
+                                      xform_clip, clip_w, clip_h, tracktor, out_boxes, out_scores, out_ids, out_labels);
     A.part = gh;
     A.S = S;
     A.rows_pad = rows_pad;
@@ -325,4 +384,90 @@ extern "C" int smot_box_refine_typed_fwd(const void* const* feats, int feat_type
                                sampling_ratio, boxes, labels, ids, track_conf, N, fc6_w, fc6_b, dim6, fc7_w, fc7_b, dim7, cls_w,
                                cls_b, num_classes, reg_w, reg_b, reg_classes, wx, wy, ww, wh, xform_clip, clip_w, clip_h,
                                tracktor, ws, out_boxes, out_scores, out_ids, out_labels, stream);
+}
+
+
+// ---- the same for the propagated tracks of several images (cameras) in one call ----------------------------------------------
+// Batched pooler (one launch for the rois of all images) -> fc6, fc7, cls_score | bbox_pred on ALL rows (linear_rows with row
+// blocks: a partial and a reduction launch per layer whatever the row count) -> box_refine_post_batched_kernel: eight launches
+// whatever num_images is, no synchronisation.  The plain launch pairs, not the chained forms of smot_box_refine_fwd (which
+// have no row-block dimension): both give the same bits, so image b's rows equal smot_box_refine_fwd on that image alone.
+constexpr int BR_BATCH_ROWS = 1024, BR_IMAGE_ROWS = 128;
+
+extern "C" int smot_box_refine_batched_max_rows(void) { return BR_BATCH_ROWS; }
+
+static size_t br_batched_scratch(int N, int K0, int dim6, int dim7, int NH) {
+    size_t g = smot::linear_rows_part_floats(N, K0, dim6);
+    const size_t g7 = smot::linear_rows_part_floats(N, dim6, dim7), gh = smot::linear_rows_part_floats(N, dim7, NH);
+    if (g7 > g) g = g7;
+    return gh > g ? gh : g;            // (one region: a layer's slices are reduced before the next layer writes its own)
+}
+
+extern "C" long long smot_box_refine_batched_ws_floats(int N, int C, int pooled, int dim6, int dim7, int num_classes,
+                                                       int reg_classes) {
+    if (N <= 0 || N > BR_BATCH_ROWS || C <= 0 || pooled <= 0 || dim6 <= 0 || dim7 <= 0 || num_classes <= 0 || reg_classes <= 0)
+        return 0;
+    const int K0 = C * pooled * pooled, NH = num_classes + 4 * reg_classes;
+    return (long long)(br_align4((size_t)N * K0) + br_align4((size_t)N * dim6) + br_align4((size_t)N * dim7) +
+                       br_align4((size_t)N * NH) + br_batched_scratch(N, K0, dim6, dim7, NH));
+}
+
+extern "C" int smot_box_refine_batched_typed_fwd(const void* const* feats, int feat_type, const int* heights, const int* widths,
+                                                 const float* scales, int num_levels, int C, int pooled, int sampling_ratio,
+                                                 const float* boxes, const int64_t* labels, const int64_t* ids,
+                                                 const float* track_conf, int N, const float* fc6_w, const float* fc6_b, int dim6,
+                                                 const float* fc7_w, const float* fc7_b, int dim7, const float* cls_w,
+                                                 const float* cls_b, int num_classes, const float* reg_w, const float* reg_b,
+                                                 int reg_classes, float wx, float wy, float ww, float wh, float xform_clip,
+                                                 float clip_w, float clip_h, int tracktor, float* ws, float* out_boxes,
+                                                 float* out_scores, int64_t* out_ids, int64_t* out_labels, smot_stream_t stream,
+                                                 int num_images, const int* row_start) {
+    using namespace smot;
+    const char* who = "box_refine_batched";
+    int rc = check_feat_type(feat_type, who);
+    if (rc) return rc;
+    FeatTypeScope scope(feat_type);
+    ImageRows I;
+    // (an image of more than 128 rows would not take the one-call path alone: nothing to be bit-identical with)
+    if ((rc = box_refine_image_rows(&I, num_images, row_start, N, BR_IMAGE_ROWS, SMOT_ERR_UNSUPPORTED, who))) return rc;
+    if (N > BR_BATCH_ROWS) {
+        set_error("%s: %d rows in %d images, at most %d per call", who, N, num_images, BR_BATCH_ROWS);
+        return SMOT_ERR_UNSUPPORTED;
+    }
+    SMOT_REQUIRE(C > 0 && dim6 > 0 && dim7 > 0, "%s: bad sizes C=%d dim6=%d dim7=%d", who, C, dim6, dim7);
+    const int K0 = C * pooled * pooled;
+    if (!((pooled == 7 || pooled == 15 || pooled == 30) && sampling_ratio == 2 && (K0 & 3) == 0 && (dim6 & 3) == 0 &&
+          (dim7 & 3) == 0)) {
+        set_error("%s: pooler %dx%d / sampling %d / layer widths %d,%d,%d not covered by the one-call path", who, pooled, pooled,
+                  sampling_ratio, K0, dim6, dim7);
+        return SMOT_ERR_UNSUPPORTED;
+    }
+    SMOT_REQUIRE(num_classes >= 2 && (reg_classes == num_classes || reg_classes == 2), "%s: bad head shape K=%d KR=%d", who,
+                 num_classes, reg_classes);
+    SMOT_REQUIRE(wx > 0.f && wy > 0.f && ww > 0.f && wh > 0.f, "%s: regression weights must be positive", who);
+    if (N == 0) return SMOT_OK;
+    SMOT_REQUIRE(boxes && ws && fc6_w && fc7_w && cls_w && reg_w && labels && ids && track_conf && out_boxes && out_scores &&
+                     out_ids && out_labels,
+                 "%s: null pointer", who);
+    SMOT_REQUIRE(((uintptr_t)ws & 15) == 0, "%s: ws must be 16-byte aligned", who);
+    LevelParams P;
+    if ((rc = fill_level_params(&P, reinterpret_cast<const float* const*>(feats), heights, widths, nullptr, scales, num_levels,
+                                who, C)))
+        return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int NH = num_classes + 4 * reg_classes;
+    float* x0 = ws;
+    float* h6 = x0 + br_align4((size_t)N * K0);
+    float* h7 = h6 + br_align4((size_t)N * dim6);
+    float* ho = h7 + br_align4((size_t)N * dim7);
+    float* gw = ho + br_align4((size_t)N * NH);
+    if ((rc = launch_roi_pool_separable(P, C, boxes, boxes, N, pooled, x0, nullptr, st, &I))) return rc;
+    if ((rc = launch_linear_rows(x0, N, K0, fc6_w, fc6_b, dim6, 1, gw, h6, dim6, st))) return rc;
+    if ((rc = launch_linear_rows(h6, N, dim6, fc7_w, fc7_b, dim7, 1, gw, h7, dim7, st))) return rc;
+    if ((rc = launch_linear_rows2(h7, N, dim7, cls_w, cls_b, num_classes, reg_w, reg_b, 4 * reg_classes, 0, gw, ho, NH, st)))
+        return rc;
+    const BoxRefineArgs A = box_refine_args(ho, NH, num_classes, reg_classes, boxes, labels, ids, track_conf, wx, wy, ww, wh,
+                                            xform_clip, clip_w, clip_h, tracktor, out_boxes, out_scores, out_ids, out_labels);
+    hipLaunchKernelGGL(box_refine_post_batched_kernel, dim3(num_images), dim3(BR_MAXN), 0, st, A, I);
+    return check_launch("box_refine_post_batched");
 }

@@ -17,6 +17,10 @@
 //     ReLU): deterministic, and the kernel boundary is the cross-XCD visibility point (no atomics).
 // Rows: up to 128 (1..8 row tiles of 16; round 4: 64 -> 128, so that 100 propagated tracks — BASELINE.json configs[2] —
 // stay on this path instead of the library GEMM); K must be a multiple of 4 (the wrapper falls back to the library otherwise).
+// Inside the library (the batched refinement, box_refine.hip) a layer may have more rows: the partial-sum grid then has a
+// third dimension, row blocks of MT * 16 = 128 rows, and still one partial and one reduction launch.  S and kslice depend
+// on K and N only and a row's k products are accumulated in k order whatever MT is, so a row's result is bit for bit the
+// same in any launch, whichever other rows share it (tests/test_box_refine_batched.py).
 #include "smot_common.h"
 #include "tower_common.h"
 
@@ -39,6 +43,7 @@ linear_rows_partial_kernel(const float* __restrict__ x, int M, int K, const floa
     __shared__ __attribute__((aligned(16))) float xs[QS][MT * 16][LR_XS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nb = blockIdx.x, s = blockIdx.y;
+    const int row0 = blockIdx.z * (MT * 16);          // row block (gridDim.z > 1: more than 128 rows, linear_rows_plan)
     const int k_begin = s * kslice, k_end = min(K, k_begin + kslice);
     const int n = nb * LR_NB + wave * 16 + (lane & 15);
     const int kq = lane >> 4;
@@ -60,7 +65,7 @@ linear_rows_partial_kernel(const float* __restrict__ x, int M, int K, const floa
         for (int u = 0; u < QS; ++u)
 #pragma unroll
             for (int q = 0; q < MT; ++q) {
-                const int r = min(xr + 16 * q, M - 1), k = min(k0 + u * LR_KS + xk, K - 4);
+                const int r = min(row0 + xr + 16 * q, M - 1), k = min(k0 + u * LR_KS + xk, K - 4);
                 xreg[u][q] = *reinterpret_cast<const float4*>(x + (size_t)r * K + k);
             }
 #pragma unroll
@@ -75,7 +80,7 @@ linear_rows_partial_kernel(const float* __restrict__ x, int M, int K, const floa
         for (int u = 0; u < QS; ++u) {
 #pragma unroll
             for (int q = 0; q < MT; ++q)
-                if (!(xr + 16 * q < M && k0 + u * LR_KS + xk < k_end)) xreg[u][q] = zero4;
+                if (!(row0 + xr + 16 * q < M && k0 + u * LR_KS + xk < k_end)) xreg[u][q] = zero4;
 #pragma unroll
             for (int h = 0; h < 4; ++h)
                 if (!(n_ok && k0 + u * LR_KS + 16 * h + 4 * kq < k_end)) wreg[u][h] = zero4;
@@ -107,8 +112,8 @@ linear_rows_partial_kernel(const float* __restrict__ x, int M, int K, const floa
             }
         }
     }
-    // D[neuron = 4 * (lane >> 4) + r][row = lane & 15 (+ 16 t)] -> part[s][nb][row][neuron]
-    float* __restrict__ p = part + ((size_t)(s * gridDim.x + nb) * (MT * 16)) * LR_NB;
+    // D[neuron = 4 * (lane >> 4) + r][row = lane & 15 (+ 16 t)] -> part[s][nb][row0 + row][neuron]
+    float* __restrict__ p = part + ((size_t)(s * gridDim.x + nb) * (gridDim.z * MT * 16) + row0) * LR_NB;
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
         const int row = t * 16 + (lane & 15);
@@ -244,12 +249,13 @@ linear_rows_reduce_kernel(const float* __restrict__ part, int S, int nblk, int r
 
 // Launch geometry shared by the workspace query and the launcher.
 struct LinearRowsPlan {
-    int mt, nblk, S, kslice;
+    int mt, rb, nblk, S, kslice;      // rb: row blocks of mt * 16 rows (1 up to 128 rows)
     size_t part_floats;
 };
 inline LinearRowsPlan linear_rows_plan(int M, int K, int N) {
     LinearRowsPlan P;
-    P.mt = (M + 15) / 16;
+    P.mt = M > 128 ? 8 : (M + 15) / 16;
+    P.rb = (M + P.mt * 16 - 1) / (P.mt * 16);
     P.nblk = (N + LR_NB - 1) / LR_NB;
     const int ksteps = (K + LR_KS - 1) / LR_KS;
     int S = (512 + P.nblk - 1) / P.nblk;            // about two workgroups per CU
@@ -257,7 +263,7 @@ inline LinearRowsPlan linear_rows_plan(int M, int K, int N) {
     if (S < 1) S = 1;
     P.kslice = ((ksteps + S - 1) / S) * LR_KS;
     P.S = (K + P.kslice - 1) / P.kslice;
-    P.part_floats = (size_t)P.S * P.nblk * (P.mt * 16) * LR_NB;
+    P.part_floats = (size_t)P.S * P.nblk * (P.rb * P.mt * 16) * LR_NB;
     return P;
 }
 
@@ -266,7 +272,7 @@ int launch_linear_rows2(const float* x, int M, int K, const float* W, const floa
                         const float* bias2, int N2, int relu, float* ws, float* y, int ldy, hipStream_t st) {
     const int N = N1 + N2;
     const LinearRowsPlan P = linear_rows_plan(M, K, N);
-    dim3 grid(P.nblk, P.S);
+    dim3 grid(P.nblk, P.S, P.rb);
     switch (P.mt) {
         case 1: hipLaunchKernelGGL(linear_rows_partial_kernel<1>, grid, dim3(256), 0, st, x, M, K, W, N, W2, N1, P.kslice, ws); break;
         case 2: hipLaunchKernelGGL(linear_rows_partial_kernel<2>, grid, dim3(256), 0, st, x, M, K, W, N, W2, N1, P.kslice, ws); break;
@@ -281,7 +287,7 @@ int launch_linear_rows2(const float* x, int M, int K, const float* W, const floa
     // box_refine_post_kernel does for cls_score | bbox_pred: one launch fewer on a chain of 3-4 us kernels)
     if (y != nullptr)
         hipLaunchKernelGGL(linear_rows_reduce_kernel, dim3((M * N + 255) / 256), dim3(256), 0, st, (const float*)ws, P.S,
-                           P.nblk, P.mt * 16, M, N, bias, bias2, N1, relu, y, ldy);
+                           P.nblk, P.rb * P.mt * 16, M, N, bias, bias2, N1, relu, y, ldy);
     return check_launch("linear_rows");
 }
 
@@ -295,7 +301,8 @@ int launch_linear_rows_chain(const float* x, int M, int K, const float* WA, cons
     const int NB = N1 + N2;
     const LinearRowsPlan PA = linear_rows_plan(M, K, NA), PB = linear_rows_plan(M, NA, NB);
     *rc = SMOT_OK;
-    if (!(PB.kslice == LR_KS && (NA % LR_NB) == 0 && PB.S == PA.nblk)) return 0;
+    // (one row block: linear_rows_partial_xpart_kernel has no row-block dimension)
+    if (!(PA.rb == 1 && PB.kslice == LR_KS && (NA % LR_NB) == 0 && PB.S == PA.nblk)) return 0;
     dim3 ga(PA.nblk, PA.S), gb(PB.nblk, PB.S);
     switch (PA.mt) {
         case 1: hipLaunchKernelGGL(linear_rows_partial_kernel<1>, ga, dim3(256), 0, st, x, M, K, WA, NA, (const float*)nullptr, NA, PA.kslice, ws_a); break;
@@ -327,13 +334,16 @@ void linear_rows_layout(int M, int K, int N, int* S, int* nblk, int* rows_pad) {
     const LinearRowsPlan P = linear_rows_plan(M, K, N);
     *S = P.S;
     *nblk = P.nblk;
-    *rows_pad = P.mt * 16;
+    *rows_pad = P.rb * P.mt * 16;
 }
 
 int launch_linear_rows(const float* x, int M, int K, const float* W, const float* bias, int N, int relu, float* ws,
                        float* y, int ldy, hipStream_t st) {
     return launch_linear_rows2(x, M, K, W, bias, N, nullptr, nullptr, 0, relu, ws, y, ldy, st);
 }
+
+// K-slice scratch of a layer on M rows, any M (smot_linear_rows_ws_floats answers for its own 128)
+size_t linear_rows_part_floats(int M, int K, int N) { return linear_rows_plan(M, K, N).part_floats; }
 
 }  // namespace smot
 
@@ -357,3 +367,23 @@ extern "C" int smot_linear_rows_fwd(const float* x, int M, int K, const float* W
     SMOT_REQUIRE((((uintptr_t)x | (uintptr_t)W | (uintptr_t)ws) & 15) == 0, "linear_rows: x, W and ws must be 16-byte aligned");
     return launch_linear_rows(x, M, K, W, bias, N, relu, ws, y, ldy, (hipStream_t)stream);
 }
+
+#ifdef SMOT_DEBUG
+// Measurement library only: a layer on more than 128 rows, as the batched refinement runs it (row blocks), for the test that
+// compares its rows with smot_linear_rows_fwd on chunks of them (ws: smot_debug_linear_rows_blocks_ws_floats(M, K, N) floats).
+extern "C" long long smot_debug_linear_rows_blocks_ws_floats(int M, int K, int N) {
+    if (M <= 0 || M > 1024 || K <= 0 || N <= 0) return 0;
+    return (long long)smot::linear_rows_part_floats(M, K, N);
+}
+
+extern "C" int smot_debug_linear_rows_blocks_fwd(const float* x, int M, int K, const float* W, const float* bias, int N,
+                                                 int relu, float* ws, float* y, int ldy, smot_stream_t stream) {
+    using namespace smot;
+    SMOT_REQUIRE(M >= 0 && M <= 1024 && K > 0 && (K & 3) == 0 && N > 0 && ldy >= N,
+                 "linear_rows_blocks: bad sizes M=%d K=%d N=%d ldy=%d", M, K, N, ldy);
+    if (M == 0) return SMOT_OK;
+    SMOT_REQUIRE(x && W && ws && y, "linear_rows_blocks: null pointer");
+    SMOT_REQUIRE((((uintptr_t)x | (uintptr_t)W | (uintptr_t)ws) & 15) == 0, "linear_rows_blocks: x, W and ws must be 16-byte aligned");
+    return launch_linear_rows(x, M, K, W, bias, N, relu, ws, y, ldy, (hipStream_t)stream);
+}
+#endif

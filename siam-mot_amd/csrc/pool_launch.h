@@ -73,6 +73,9 @@ int launch_linear_rows(const float* x, int M, int K, const float* W, const float
 int launch_linear_rows2(const float* x, int M, int K, const float* W, const float* bias, int N1, const float* W2,
                         const float* bias2, int N2, int relu, float* ws, float* y, int ldy, hipStream_t st);
 void linear_rows_layout(int M, int K, int N, int* S, int* nblk, int* rows_pad);
+// K-slice scratch (floats) of launch_linear_rows / launch_linear_rows2 on M rows — any M: beyond 128 the launchers run row
+// blocks of 128 in the same two launches (the C entry smot_linear_rows_fwd keeps its 128)
+size_t linear_rows_part_floats(int M, int K, int N);
 int launch_linear_rows_chain(const float* x, int M, int K, const float* WA, const float* bA, int NA, int reluA, float* ws_a,
                              const float* WB, int N1, const float* WB2, int N2, float* ws_b, hipStream_t st, int* rc);
 

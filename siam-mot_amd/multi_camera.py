@@ -1,5 +1,5 @@
-"""The tracking step for B cameras that share a GPU: one head call, one solver launch per 16 cameras, one host
-synchronisation and one template extraction per step, whatever B is.
+"""The tracking step for B cameras that share a GPU: one head call, one box-head refinement call (§3j), one solver launch
+per 16 cameras, one host synchronisation and one template extraction per step, whatever B is.
 
 ``MultiCameraTrackingLoop`` is the general path of ``TrackingLoop._forward`` (roi_heads.py:38-50 of the reference: head,
 [box-head refinement,] solver, track memory) over B independent video streams: ONE ``EMM`` shared by all cameras, and per
@@ -21,6 +21,11 @@ from .track_head import TrackHead, TrackingLoop
 class MultiCameraTrackingLoop(torch.nn.Module):
     """``forward(features, detections) -> [BoxList] * B``: ``features`` a tuple of ``[B, C, H_l, W_l]`` maps (what the batched
     head accepts: fp32 / fp16 / bf16, NCHW or channels-last), ``detections`` one BoxList per camera, all of one image size."""
+
+    # the refinement of the cameras' propagated boxes in ONE ``refine_tracks(features, [tracks_b ...])`` call per step when
+    # the callable offers it (``offers_batched``: ``box_refine.RefineTracks`` over a ``TrackBoxHead`` on the device);
+    # False: camera by camera, as for any other callable
+    batched_refinement = True
 
     def __init__(self, emm, track_heads, solvers, refine_tracks=None):
         super(MultiCameraTrackingLoop, self).__init__()
@@ -80,6 +85,25 @@ class MultiCameraTrackingLoop(torch.nn.Module):
             tracks[b] = out[b]
         return tracks
 
+    def _refine_batched(self, features, tracks):
+        """The propagated boxes of all cameras through ONE ``refine_tracks`` call, in place in ``tracks``; False when the
+        step is to refine camera by camera (a callable without the batched form, the switch, one camera, or row counts the
+        batched call does not take — counted in ``ops.FALLBACKS["refine_per_camera"]``).  The row counts are the sizes of the
+        memories the head ran on: nothing is read from the device."""
+        offers = getattr(self.refine_tracks, "offers_batched", None)
+        live = [b for b in range(self.num_cameras) if tracks[b] is not None]
+        if offers is None or not self.batched_refinement or self.num_cameras == 1 or not live or not offers():
+            return False
+        first = tracks[live[0]]
+        lists = [tracks[b] if tracks[b] is not None else self._empty(first) for b in range(self.num_cameras)]
+        if not self.refine_tracks.batch_ok(lists):
+            ops.FALLBACKS["refine_per_camera"] += 1
+            return False
+        out = self.refine_tracks(features, lists)
+        for b in live:
+            tracks[b] = out[b]
+        return True
+
     def _forward(self, features, detections):
         B = self.num_cameras
         if len(detections) != B:
@@ -87,11 +111,12 @@ class MultiCameraTrackingLoop(torch.nn.Module):
         mems_before = list(self.track_memory)
         tracks = self._propagate(features)                                         # roi_heads.py:38
         bias = 1.0
-        if self.refine_tracks is not None:                                         # roi_heads.py:43-45, camera by camera
+        if self.refine_tracks is not None:                                         # roi_heads.py:43-45
             bias = 0.0
-            for b in range(B):
-                if tracks[b] is not None:
-                    tracks[b] = self.refine_tracks(tuple(f[b:b + 1] for f in features), [tracks[b]])[0]
+            if not self._refine_batched(features, tracks):                         # camera by camera
+                for b in range(B):
+                    if tracks[b] is not None:
+                        tracks[b] = self.refine_tracks(tuple(f[b:b + 1] for f in features), [tracks[b]])[0]
         pre = {}
 
         def extract(outs):
@@ -123,7 +148,8 @@ class MultiCameraTrackingLoop(torch.nn.Module):
 
 def build_multi_camera_tracking_loop(cfg, num_cameras, device="cuda", refine_tracks=None):
     """``build_tracking_loop`` for ``num_cameras`` video streams on one device: one EMM head, and a pool, a solver and a
-    ``TrackHead`` per camera around it.  ``refine_tracks`` as there (called camera by camera; ``False``: none, explicitly)."""
+    ``TrackHead`` per camera around it.  ``refine_tracks`` as there (``box_refine.RefineTracks``: one batched call per step, any other callable camera by camera;
+    ``False``: none, explicitly)."""
     if refine_tracks is False:
         refine_tracks = None
     elif refine_tracks is None:

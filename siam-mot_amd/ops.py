@@ -137,11 +137,21 @@ _SIGNATURES = {
                                                         _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     # the track solver over several images: num_images, smot_track_solve_fwd's 27 arguments as host arrays, stream
     "smot_track_solve_batched_fwd": (ctypes.c_int, [_i] + [_vp] * 27 + [_vp]),
+    # the refinement of the propagated tracks over several images: the twins' arguments + num_images, row_start (host int array)
+    "smot_box_refine_batched_max_rows": (ctypes.c_int, []),
+    "smot_box_refine_batched_ws_floats": (ctypes.c_longlong, [_i, _i, _i, _i, _i, _i, _i]),
+    "smot_box_refine_post_batched_fwd": (ctypes.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _f, _f, _f, _f, _i,
+                                                        _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "smot_box_refine_batched_typed_fwd": (ctypes.c_int, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i,
+                                                         _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i,
+                                                         _f, _f, _f, _f, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 _DEBUG_SIGNATURES = {
     "smot_debug_set_knob": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p]),
     "smot_debug_sr_xcorr_fused_hint_fwd": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "smot_debug_linear_rows_blocks_ws_floats": (ctypes.c_longlong, [_i, _i, _i]),
+    "smot_debug_linear_rows_blocks_fwd": (ctypes.c_int, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp]),
 }
 DEBUG_EXPORTED_SYMBOLS = tuple(_DEBUG_SIGNATURES.keys())
 
@@ -1143,8 +1153,12 @@ TIMER_XCORR, TIMER_TOWER = 0, 1
 #   multi_camera_per_camera  a ``solver.solve_batched`` call that ran camera by camera (an image failed ``_device_path``)
 #   rpn_torch            an RPN proposal selection on device tensors beyond ``rpn_proposals``' capacities (torch composition)
 #   box_detect_torch     a box-head call on id-less device proposals that ``box_detect_post`` does not take (torch composition)
+#   refine_per_camera    a multi-camera step whose refinement wanted the batched call and ran camera by camera (an image of
+#                        more than ``BOX_REFINE_IMAGE_ROWS`` rows, the call's caps); present from import so that a step that
+#                        does not fall back leaves the table as it was
 import collections as _collections
 FALLBACKS = _collections.Counter()
+FALLBACKS["refine_per_camera"] = 0
 # speculative next-frame heads of the tracking loop (TrackingLoop.forward(..., next_features=...)): launched / used as they
 # were / discarded because the row count, the memory, the features or the parameters were not what the launch assumed
 SPECULATION = _collections.Counter()
@@ -1867,6 +1881,118 @@ def linear_rows(x, weight, bias=None, relu=False, out=None):
 
 def linear_rows_max_rows():
     return (_lib or load_library()).smot_linear_rows_max_rows()
+
+
+def linear_rows_blocks(x, weight, bias=None, relu=False):
+    """Measurement library only (inside ``debug_library()``): ``linear_rows`` on up to ``box_refine_batched_max_rows()`` rows
+    in the form the batched refinement runs its layers — row blocks of 128 in the same two launches."""
+    lib = _lib or load_library()
+    if not hasattr(lib, "smot_debug_linear_rows_blocks_fwd"):
+        raise RuntimeError("siammot_amd.linear_rows_blocks: an entry of the measurement library (ops.debug_library())")
+    x = _dev_f32(x, "x")
+    weight = _dev_f32(weight, "weight")
+    M, K = x.shape
+    N = weight.shape[0]
+    if weight.shape[1] != K:
+        raise RuntimeError("siammot_amd.linear_rows_blocks: x is [%d,%d], weight [%d,%d]" % (M, K, N, weight.shape[1]))
+    if bias is not None:
+        bias = _dev_f32(bias, "bias")
+    y = torch.empty((M, N), dtype=_F32, device=x.device)
+    need = int(lib.smot_debug_linear_rows_blocks_ws_floats(M, K, N))
+    ws = _workspace(x.device, need, ("linear_rows", _stream(x.device).value))
+    with _Launch(x, weight, y) as ln:
+        rc = lib.smot_debug_linear_rows_blocks_fwd(_ptr(x), M, K, _ptr(weight), _ptr(bias), N, int(bool(relu)), _ptr(ws),
+                                                   _ptr(y), N, ln.stream)
+    _check(rc, "linear_rows_blocks")
+    return y
+
+
+def box_refine_batched_max_rows():
+    return (_lib or load_library()).smot_box_refine_batched_max_rows()
+
+
+BOX_REFINE_IMAGE_ROWS = 128          # rows of ONE image in a batched refinement call (the one-call path's own limit)
+
+
+def _refine_outputs(N, dev):
+    return (torch.empty((N, 4), dtype=_F32, device=dev), torch.empty((N,), dtype=_F32, device=dev),
+            torch.empty((N,), dtype=torch.int64, device=dev), torch.empty((N,), dtype=torch.int64, device=dev))
+
+
+def box_refine_post_batched(head_out, num_classes, reg_classes, boxes, labels, ids, track_conf, rows_per_image, weights,
+                            xform_clip, clip_wh, tracktor=False):
+    """``smot_box_refine_post_batched_fwd``: ``box_refine_post`` over the B images of a call in one launch (a workgroup per
+    image).  The rows of all images are concatenated, image b the ``rows_per_image[b]`` (host ints, zero is fine) consecutive
+    rows after those of images 0..b-1; ``clip_wh``: the one image size.  Returns ``(boxes [N,4], scores [N], ids [N], labels
+    [N])`` with image b's rows in its input segment, bit for bit what ``box_refine_post`` returns on them alone."""
+    lib = _lib or load_library()
+    head_out = _dev_f32(head_out, "head_out")
+    boxes = _dev_f32(boxes, "boxes")
+    track_conf = _dev_f32(track_conf, "track_conf")
+    N, dev = boxes.shape[0], boxes.device
+    rows = [int(r) for r in rows_per_image]
+    B = len(rows)
+    for name, t in (("labels", labels), ("ids", ids)):
+        if not (t.is_cuda and t.dtype is torch.int64 and t.is_contiguous() and t.device == dev and t.shape[0] == N):
+            raise RuntimeError("siammot_amd.box_refine_post_batched: %s must be a contiguous int64 [N] tensor on the boxes' "
+                               "device" % name)
+    if head_out.dim() != 2 or head_out.shape[0] != N or head_out.shape[1] < num_classes + 4 * reg_classes:
+        raise RuntimeError("siammot_amd.box_refine_post_batched: head_out %s does not hold %d logits + %d deltas for %d rows"
+                           % (tuple(head_out.shape), num_classes, 4 * reg_classes, N))
+    if not 1 <= B <= MAX_IMAGES:
+        raise RuntimeError("siammot_amd.box_refine_post_batched: %d images, need 1..%d per call" % (B, MAX_IMAGES))
+    starts = _row_starts(rows, B, N)
+    out = _refine_outputs(N, dev)
+    cw, ch = (0.0, 0.0) if clip_wh is None else (float(clip_wh[0]), float(clip_wh[1]))
+    with _Launch(head_out, boxes, track_conf, labels, ids) as ln:
+        rc = lib.smot_box_refine_post_batched_fwd(_ptr(head_out), head_out.shape[1], int(num_classes), int(reg_classes),
+                                                  _ptr(boxes), _ptr(labels), _ptr(ids), _ptr(track_conf), N,
+                                                  float(weights[0]), float(weights[1]), float(weights[2]), float(weights[3]),
+                                                  float(xform_clip), cw, ch, int(bool(tracktor)), _ptr(out[0]), _ptr(out[1]),
+                                                  _ptr(out[2]), _ptr(out[3]), ln.stream, B, _cast(starts))
+    _check(rc, "box_refine_post_batched")
+    return out
+
+
+def box_refine_batched(features, scales, pooled, sampling_ratio, boxes, labels, ids, track_conf, rows_per_image, layers,
+                       weights, xform_clip, clip_wh, tracktor=False):
+    """``smot_box_refine_batched_typed_fwd``: ``box_refine`` over the B images of a call — ``features[l]`` = ``[B, C, H_l,
+    W_l]``, the rows of all images concatenated, image b the ``rows_per_image[b]`` (host ints, zero is fine, at most
+    ``BOX_REFINE_IMAGE_ROWS`` each and ``box_refine_batched_max_rows()`` in all) rows after those of images 0..b-1 — in eight
+    launches whatever B is, no synchronisation.  Returns ``(boxes, scores, ids, labels)`` with image b's rows in its input
+    segment, bit for bit what ``box_refine`` returns on ``features[l][b:b+1]`` and those rows."""
+    lib = _lib or load_library()
+    L = len(scales)
+    feats, fp, hs, wsz, sc, ft = _level_arrays(features, scales, what=".box_refine_batched", batched=True)
+    boxes = _dev_f32(boxes, "boxes")
+    track_conf = _dev_f32(track_conf, "track_conf")
+    w6, b6, w7, b7, wc, bc, wr, br = [_dev_f32(t, "box head parameter") for t in layers]
+    N, dev = boxes.shape[0], boxes.device
+    B, C = feats[0].shape[0], feats[0].shape[1]
+    K, KR = wc.shape[0], wr.shape[0] // 4
+    for name, t in (("labels", labels), ("ids", ids)):
+        if not (t.is_cuda and t.dtype is torch.int64 and t.is_contiguous() and t.device == dev and t.shape[0] == N):
+            raise RuntimeError("siammot_amd.box_refine_batched: %s must be a contiguous int64 [N] tensor on the boxes' device"
+                               % name)
+    if w6.shape[1] != C * pooled * pooled or w7.shape[1] != w6.shape[0] or wc.shape[1] != w7.shape[0] or wr.shape[1] != w7.shape[0]:
+        raise RuntimeError("siammot_amd.box_refine_batched: layer shapes do not chain")
+    if B > MAX_IMAGES:
+        raise RuntimeError("siammot_amd.box_refine_batched: %d images, at most %d per call" % (B, MAX_IMAGES))
+    starts = _row_starts(rows_per_image, B, N)
+    need = int(lib.smot_box_refine_batched_ws_floats(N, C, int(pooled), w6.shape[0], w7.shape[0], K, KR))
+    ws = _workspace(dev, need, ("box_refine", _stream(dev).value))
+    out = _refine_outputs(N, dev)
+    cw, ch = (0.0, 0.0) if clip_wh is None else (float(clip_wh[0]), float(clip_wh[1]))
+    with _Launch(boxes, track_conf, labels, ids, w6, *feats) as ln:
+        rc = lib.smot_box_refine_batched_typed_fwd(_cast(fp), ft, _cast(hs), _cast(wsz), _cast(sc), L, C, int(pooled),
+                                                   int(sampling_ratio), _ptr(boxes), _ptr(labels), _ptr(ids), _ptr(track_conf),
+                                                   N, _ptr(w6), _ptr(b6), w6.shape[0], _ptr(w7), _ptr(b7), w7.shape[0],
+                                                   _ptr(wc), _ptr(bc), K, _ptr(wr), _ptr(br), KR,
+                                                   float(weights[0]), float(weights[1]), float(weights[2]), float(weights[3]),
+                                                   float(xform_clip), cw, ch, int(bool(tracktor)), _ptr(ws), _ptr(out[0]),
+                                                   _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), ln.stream, B, _cast(starts))
+    _check(rc, "box_refine_batched")
+    return out
 
 
 def box_refine_post_max_rows():
