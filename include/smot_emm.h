@@ -1055,6 +1055,49 @@ int smot_box_refine_batched_typed_fwd(const void* const* feats, int feat_type, c
                                       float* out_boxes, float* out_scores, int64_t* out_ids, int64_t* out_labels,
                                       smot_stream_t stream, int num_images, const int* row_start);
 
+/*
+ * RPN HEAD (csrc/rpn_head.hip): [UPSTREAM] maskrcnn_benchmark RPNHead.forward — conv3x3 C -> C (pad 1) + bias + ReLU, then
+ * the 1x1 heads cls_logits (C -> A) and bbox_pred (C -> 4A), the weights shared by all levels — for every image and every
+ * FPN level of a call in ONE launch (its workgroups are (image, level, 8 x 16 tile of positions); their number is all that
+ * depends on num_images and num_levels) and without a host synchronisation.  Both stages run on the fp32 matrix cores
+ * (exact fp32 products, fp32 accumulation); the C-channel activation between them never leaves the chip.
+ *
+ *   feats[l]       [num_images, C, H_l, W_l], contiguous NCHW, all of element type `feat_type` (SMOT_FEAT_F32 / F16 / BF16).
+ *                  A half call returns bit for bit what the call returns on the upcast maps (converted on load).  The
+ *                  layout flag SMOT_FEAT_CHANNELS_LAST is SMOT_ERR_UNSUPPORTED: pass NCHW copies.
+ *   heights/widths host arrays [num_levels]: H_l, W_l.  Maps are not padded: edge tiles and levels smaller than a tile are
+ *                  masked on load and on store; the convolution's zero padding is virtual.
+ *   packed         smot_rpn_head_packed_floats(C, A) floats, 16-byte aligned, written by smot_rpn_head_pack from upstream's
+ *                  parameters: conv.weight [C, C, 3, 3], conv.bias [C], cls_logits.weight [A, C(, 1, 1)], cls_logits.bias
+ *                  [A], bbox_pred.weight [4A, C(, 1, 1)], bbox_pred.bias [4A] (one launch on `stream`; pack again when a
+ *                  parameter changes).
+ *   outputs        objectness_out[l] [num_images, A, H_l, W_l], regression_out[l] [num_images, 4A, H_l, W_l] (channel of
+ *                  coordinate c of anchor a: 4a + c): contiguous fp32 NCHW — what smot_rpn_proposals_fwd reads in place.
+ *   contract       an output's value depends on its own image's map of its own level alone, with a summation order fixed
+ *                  by (C, A): image i of a call equals the one-image call on it, level l the one-level call on it, bit for
+ *                  bit; deterministic.  A NaN or infinite input cell makes non-finite exactly the outputs whose 3x3 window
+ *                  covers it.
+ *   capacities     C % 32 == 0, 32 <= C <= 512, 1 <= A, 5 A <= 64 (SMOT_ERR_UNSUPPORTED beyond, also for a level of 2^28
+ *                  cells or more); 1 <= num_images <= SMOT_MAX_IMAGES, 1 <= num_levels <= SMOT_MAX_LEVELS, non-null
+ *                  pointers, H_l, W_l >= 1 (SMOT_ERR_BAD_ARG).  smot_rpn_head_packed_floats returns -1 for an unsupported
+ *                  (C, A).  Nothing is launched by a refused call.
+ *
+ * RPN ANCHORS: [UPSTREAM] AnchorGenerator.grid_anchors for all levels in one launch:
+ *   out[l][(h W_l + w) A_l + a] = cell_anchors[l][a] + (w s_l, h s_l, w s_l, h s_l), one fp32 addition per coordinate (the
+ *   shifts are exact), i.e. bit for bit upstream's broadcast sum.  cell_anchors / out: HOST arrays [num_levels] of DEVICE
+ *   pointers to fp32 [A_l, 4] / [H_l W_l A_l, 4], 16-byte aligned; num_anchors / strides / heights / widths: host int arrays
+ *   [num_levels].  SMOT_ERR_BAD_ARG for num_levels outside [1, SMOT_MAX_LEVELS], a null or misaligned pointer, a
+ *   non-positive size; SMOT_ERR_UNSUPPORTED for a level that spans more than 2^24 pixels or 2^31 anchors in all.
+ */
+long long smot_rpn_head_packed_floats(int C, int A);
+int smot_rpn_head_pack(const float* conv_w, const float* conv_b, const float* cls_w, const float* cls_b,
+                       const float* bbox_w, const float* bbox_b, int C, int A, float* packed, smot_stream_t stream);
+int smot_rpn_head_fwd(const void* const* feats, int feat_type, const int* heights, const int* widths, int num_levels,
+                      int num_images, int C, int A, const float* packed, float* const* objectness_out,
+                      float* const* regression_out, smot_stream_t stream);
+int smot_rpn_anchors_fwd(const float* const* cell_anchors, const int* num_anchors, const int* strides, const int* heights,
+                         const int* widths, int num_levels, float* const* out, smot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

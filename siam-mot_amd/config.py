@@ -36,7 +36,11 @@ def get_default_cfg(conv_body="DLA-34-FPN", channels=128):
     # what rpn.make_rpn_postprocessor reads at inference: the three counts from siammot/configs/defaults.py:13-15, the
     # rest [UPSTREAM] maskrcnn_benchmark defaults (with INPUT.AMODAL above)
     cfg.MODEL.RPN = CfgNode(PRE_NMS_TOP_N_TEST=1000, POST_NMS_TOP_N_TEST=300, FPN_POST_NMS_TOP_N_TEST=300,
-                            NMS_THRESH=0.7, MIN_SIZE=0, FPN_POST_NMS_PER_BATCH=True)
+                            NMS_THRESH=0.7, MIN_SIZE=0, FPN_POST_NMS_PER_BATCH=True,
+                            # what rpn.make_anchor_generator reads: sizes and strides from siammot/configs/defaults.py:10-11,
+                            # ratios and the straddle threshold [UPSTREAM] defaults
+                            ANCHOR_SIZES=(32, 64, 128, 256, 512), ANCHOR_STRIDE=(4, 8, 16, 32, 64),
+                            ASPECT_RATIOS=(0.5, 1.0, 2.0), STRADDLE_THRESH=0)
     th = CfgNode()
     th.TRACKTOR = False
     th.POOLER_SCALES = (0.25, 0.125, 0.0625, 0.03125)

@@ -9,22 +9,29 @@ Several images of one size per call (``features[l]`` = ``[N, C, H_l, W_l]``) tak
 cap, 4]`` and ``count [N]`` go to ``TrackBoxHead.detect_raw_batched`` as they are and the N detection counts are the call's
 one copy.  When either half is over its capacity or not on the device, or the images differ in size, the two modules'
 ``forward``s are composed as they are today.
+
+``forward_features(features, image_size)`` starts one step earlier, at the FPN maps: the RPN head's convolutions
+(``rpn.RPNHead``: one launch for all images and levels), the cached anchor grid (``rpn.AnchorGenerator``: no launch once the
+map sizes have been seen) and then ``forward`` — still the one copy.
 """
 import torch
 
 from . import ops
 from .box_refine import TrackBoxHead
-from .rpn import make_rpn_postprocessor
+from .rpn import RPNHead, make_anchor_generator, make_rpn_postprocessor
 
 
 class DetectionHead(torch.nn.Module):
     """``forward(anchors, objectness, box_regression, features) -> [BoxList]`` per image (fields ``scores``, ``ids`` = -1,
-    ``labels``): ``rpn_post`` is an ``rpn.RPNPostProcessor``, ``box_head`` a ``TrackBoxHead``."""
+    ``labels``): ``rpn_post`` is an ``rpn.RPNPostProcessor``, ``box_head`` a ``TrackBoxHead``.  With an ``rpn.RPNHead`` and an
+    ``rpn.AnchorGenerator`` as well: ``forward_features(features, image_size)``, the same from the FPN maps."""
 
-    def __init__(self, rpn_post, box_head):
+    def __init__(self, rpn_post, box_head, rpn_head=None, anchor_generator=None):
         super(DetectionHead, self).__init__()
         self.rpn_post = rpn_post
         self.box_head = box_head
+        self.rpn_head = rpn_head
+        self.anchor_generator = anchor_generator
 
     def raw_ok(self, anchors, objectness):
         """Both halves take their device paths for this call."""
@@ -61,10 +68,29 @@ class DetectionHead(torch.nn.Module):
         det_boxes, scores, labels, _, out_count, _, _ = box.detect_raw_batched(features, boxes.view(-1, 4), rows, count, size)
         return box.wrap_detections_batched(det_boxes, scores, labels, out_count, rows, size)   # the one copy: N counts
 
+    @torch.no_grad()
+    def forward_features(self, features, image_size):
+        """FPN maps ``features[l]`` = ``[N, C, H_l, W_l]`` of N images of one size ``image_size`` = (width, height) ->
+        what ``forward(anchor_generator(...), *rpn_head(features), features)`` returns, bit for bit."""
+        if self.rpn_head is None or self.anchor_generator is None:
+            raise RuntimeError("siammot_amd.detector.DetectionHead: forward_features needs an RPN head and an anchor generator "
+                               "(build_detection_head(..., rpn_head=True))")
+        if self.training:
+            raise NotImplementedError("siammot_amd.detector.DetectionHead is an inference path")
+        objectness, box_regression = self.rpn_head(features)
+        anchors = self.anchor_generator([tuple(image_size)] * int(features[0].shape[0]), features)
+        return self.forward(anchors, objectness, box_regression, features)
 
-def build_detection_head(cfg, rpn_box_coder, in_channels, box_head=None):
+
+def build_detection_head(cfg, rpn_box_coder, in_channels, box_head=None, rpn_head=True):
     """``DetectionHead`` from a config: the reference's RPN factory keys (``MODEL.RPN.*_TEST``) and the given box head or a
-    fresh ``TrackBoxHead``."""
+    fresh ``TrackBoxHead``.  ``rpn_head``: True for a fresh ``rpn.RPNHead`` and the config's anchor generator
+    (``MODEL.RPN.ANCHOR_*``, ``ASPECT_RATIOS``), an ``RPNHead`` to use that one, False / None for a head that starts at the
+    anchors (``forward`` only)."""
     if box_head is None:
         box_head = TrackBoxHead(cfg, in_channels).eval()
-    return DetectionHead(make_rpn_postprocessor(cfg, rpn_box_coder, is_train=False).eval(), box_head).eval()
+    head, generator = None, None
+    if rpn_head:
+        generator = make_anchor_generator(cfg)
+        head = RPNHead(cfg, in_channels, generator.num_anchors_per_location()[0]) if rpn_head is True else rpn_head
+    return DetectionHead(make_rpn_postprocessor(cfg, rpn_box_coder, is_train=False).eval(), box_head, head, generator).eval()

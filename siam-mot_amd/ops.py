@@ -145,6 +145,11 @@ _SIGNATURES = {
     "smot_box_refine_batched_typed_fwd": (ctypes.c_int, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i,
                                                          _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i,
                                                          _f, _f, _f, _f, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    # RPN head (conv3x3 + ReLU + the two 1x1 heads) and anchor grid: all images and levels of a call in one launch each
+    "smot_rpn_head_packed_floats": (ctypes.c_longlong, [_i, _i]),
+    "smot_rpn_head_pack": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "smot_rpn_head_fwd": (ctypes.c_int, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "smot_rpn_anchors_fwd": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 _DEBUG_SIGNATURES = {
@@ -1159,6 +1164,9 @@ TIMER_XCORR, TIMER_TOWER = 0, 1
 import collections as _collections
 FALLBACKS = _collections.Counter()
 FALLBACKS["refine_per_camera"] = 0
+#   rpn_head_torch       an ``rpn.RPNHead`` call on device maps that ``rpn_head`` does not take (training mode, C or A beyond
+#                        its capacities, more images or levels): the ``F.conv2d`` composition; present from import
+FALLBACKS["rpn_head_torch"] = 0
 # speculative next-frame heads of the tracking loop (TrackingLoop.forward(..., next_features=...)): launched / used as they
 # were / discarded because the row count, the memory, the features or the parameters were not what the launch assumed
 SPECULATION = _collections.Counter()
@@ -1393,6 +1401,90 @@ def rpn_proposals(objectness, box_regression, anchors, image_sizes, pre_nms_top_
             "logit": work[o2:o2 + NL * pre].view(N, L, pre),
             "box": work[o3:o3 + NL * pre * 4].view(N, L, pre, 4)}
     return boxes, scores, count, cand
+
+
+# capacities of ``rpn_head`` (include/smot_emm.h): beyond them ``siammot_amd.rpn.RPNHead`` takes its torch composition
+RPN_HEAD_MAX_CHANNELS = 512
+RPN_HEAD_CHANNEL_STEP = 32
+RPN_HEAD_MAX_ROWS = 64               # 5 A: the objectness and regression rows of the two 1x1 heads
+
+
+def rpn_head_shapes_ok(C, A):
+    return C >= 32 and C % RPN_HEAD_CHANNEL_STEP == 0 and C <= RPN_HEAD_MAX_CHANNELS and 1 <= A and 5 * A <= RPN_HEAD_MAX_ROWS
+
+
+def rpn_head_pack(conv_w, conv_b, cls_w, cls_b, bbox_w, bbox_b):
+    """The RPN head's parameters (upstream's ``conv`` ``[C, C, 3, 3]``, ``cls_logits`` ``[A, C, 1, 1]``, ``bbox_pred``
+    ``[4A, C, 1, 1]`` and their biases, fp32 device tensors) in the operand order of ``rpn_head`` (``smot_rpn_head_pack``:
+    one launch, no synchronisation).  -> fp32 ``[smot_rpn_head_packed_floats(C, A)]``."""
+    lib = _lib or load_library()
+    C, A = int(conv_w.shape[0]), int(cls_w.shape[0])
+    ts = [_chk(conv_w, "conv.weight", (C, C, 3, 3)), _chk(conv_b, "conv.bias", (C,)),
+          _chk(cls_w.reshape(A, -1), "cls_logits.weight", (A, C)), _chk(cls_b, "cls_logits.bias", (A,)),
+          _chk(bbox_w.reshape(4 * A, -1), "bbox_pred.weight", (4 * A, C)), _chk(bbox_b, "bbox_pred.bias", (4 * A,))]
+    n = lib.smot_rpn_head_packed_floats(C, A)
+    if n < 0:
+        _check(-2, "rpn_head_pack")
+    packed = torch.empty((n,), dtype=_F32, device=conv_w.device)
+    with _Launch(*ts) as ln:
+        rc = lib.smot_rpn_head_pack(*([_ptr(t) for t in ts] + [C, A, _ptr(packed), ln.stream]))
+    _check(rc, "rpn_head_pack")
+    return packed
+
+
+def rpn_head(features, packed, C, A):
+    """Upstream's ``RPNHead.forward`` on all images and levels of a call in one launch (``smot_rpn_head_fwd``), free of host
+    synchronisation.  features: L maps ``[N, C, H_l, W_l]`` of one dtype (fp32, fp16 or bf16; a half call returns the bits
+    of the call on ``.float()``); anything but contiguous NCHW (channels-last, strided views) is copied.  packed:
+    ``rpn_head_pack``'s tensor.  -> (objectness: L fp32 ``[N, A, H_l, W_l]``, regression: L fp32 ``[N, 4A, H_l, W_l]``)."""
+    lib = _lib or load_library()
+    L = len(features)
+    if L < 1:
+        raise RuntimeError("siammot_amd.rpn_head: no feature level")
+    feats = [_dev_feat(f, "features[%d]" % l) for l, f in enumerate(features)]
+    ft = _feat_type(feats)
+    N = feats[0].shape[0]
+    for l, f in enumerate(feats):
+        if f.dim() != 4 or f.shape[0] != N or f.shape[1] != C:
+            raise RuntimeError("siammot_amd.rpn_head: features[%d] has shape %s, expected [%d, %d, H, W]"
+                               % (l, tuple(f.shape), N, C))
+    dev = feats[0].device
+    obj = [torch.empty((N, A) + tuple(f.shape[2:]), dtype=_F32, device=dev) for f in feats]
+    reg = [torch.empty((N, 4 * A) + tuple(f.shape[2:]), dtype=_F32, device=dev) for f in feats]
+    fp = (ctypes.c_void_p * L)(*[t.data_ptr() for t in feats])
+    po = (ctypes.c_void_p * L)(*[t.data_ptr() for t in obj])
+    pr = (ctypes.c_void_p * L)(*[t.data_ptr() for t in reg])
+    ih = (ctypes.c_int * L)(*[f.shape[2] for f in feats])
+    iw = (ctypes.c_int * L)(*[f.shape[3] for f in feats])
+    with _Launch(*(feats + [packed])) as ln:
+        rc = lib.smot_rpn_head_fwd(_cast(fp), ft, _cast(ih), _cast(iw), L, N, int(C), int(A), _ptr(packed), _cast(po),
+                                   _cast(pr), ln.stream)
+    _check(rc, "rpn_head")
+    return obj, reg
+
+
+def rpn_anchors(cell_anchors, strides, grid_sizes):
+    """Upstream's ``AnchorGenerator.grid_anchors`` for all levels in one launch (``smot_rpn_anchors_fwd``).  cell_anchors: L
+    fp32 device tensors ``[A_l, 4]``; strides: L ints; grid_sizes: L pairs ``(H_l, W_l)``.  -> L fp32 ``[H_l*W_l*A_l, 4]``
+    in the flattened order (h*W + w)*A + a."""
+    lib = _lib or load_library()
+    L = len(cell_anchors)
+    if L < 1 or len(strides) != L or len(grid_sizes) != L:
+        raise RuntimeError("siammot_amd.rpn_anchors: %d cell-anchor levels, %d strides, %d grid sizes"
+                           % (L, len(strides), len(grid_sizes)))
+    cells = [_chk(c, "cell_anchors[%d]" % l, (c.shape[0], 4)) for l, c in enumerate(cell_anchors)]
+    dev = cells[0].device
+    out = [torch.empty((int(h) * int(w) * c.shape[0], 4), dtype=_F32, device=dev) for c, (h, w) in zip(cells, grid_sizes)]
+    pc = (ctypes.c_void_p * L)(*[t.data_ptr() for t in cells])
+    po = (ctypes.c_void_p * L)(*[t.data_ptr() for t in out])
+    ia = (ctypes.c_int * L)(*[c.shape[0] for c in cells])
+    is_ = (ctypes.c_int * L)(*[int(s) for s in strides])
+    ih = (ctypes.c_int * L)(*[int(g[0]) for g in grid_sizes])
+    iw = (ctypes.c_int * L)(*[int(g[1]) for g in grid_sizes])
+    with _Launch(*cells) as ln:
+        rc = lib.smot_rpn_anchors_fwd(_cast(pc), _cast(ia), _cast(is_), _cast(ih), _cast(iw), L, _cast(po), ln.stream)
+    _check(rc, "rpn_anchors")
+    return out
 
 
 _rec_pinned = {}
