@@ -158,6 +158,85 @@ __device__ __forceinline__ float rl_f(float v, int lane_const) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane_const));
 }
 
+// ---- row runs (sr_xcorr_fused9_body.h: the two-column pipeline of the 33 .. 64-column windows) -------------------------
+// A batch of NE samples names 2 NE rows (lo_0, hi_0, lo_1, hi_1, ...) and loads each of them, although consecutive
+// samples almost always share a row (hi(s) == lo(s + 1), or both rows when the sample step is below one row).  Where all
+// rows of a batch lie within RMAX rows from its first entry's — a RUN — those consecutive rows are loaded ONCE into one
+// register tuple, and every tap of the vertical FMA chain reads its row out of the tuple by its wave-uniform index.
+// Same cells, same operands in the same order: bit-identical.
+// How the uniform index selects a register (profiles/pool_row_runs_ab.json; the parent is at 52.82 us per step):
+//   * chosen, 51.65 us: the GPR index mode on the FMA's own source operand (s_set_gpr_idx_on idx, SRC0 — the instruction
+//     hipcc itself emits for a uniform dynamic index), one switch for the two columns of a lane — no vector instruction
+//     beside the FMAs that were there already;
+//   * measured and dropped, 54.34 us: the compiler's form of `rows[idx]`, the same mode around a v_mov_b32 per operand — 40
+//     more vector instructions per batch beside its 40 FMAs, more than the 8 loads it saves;
+//   * not built: a scalar-compare select chain (RMAX - 1 v_cndmask per operand: worse than the v_mov) and staging the rows
+//     in the wave's own image rows (the taps then go through the LDS pipe, which the horizontal taps already load).
+typedef float fx_rows_t __attribute__((ext_vector_type(32)));
+
+// The vertical chains of a pooled row (G = 2: lo_0, hi_0, lo_1, hi_1) for the two adjacent columns of a lane, which are
+// registers i and i + 1 of the tuple: c = fmaf(w3, r[i3], fmaf(w2, r[i2], fmaf(w1, r[i1], fmaf(w0, r[i0], 0)))), the registers
+// read through the GPR index; the mode is off again behind the chains.
+// The indexed operand must be written as the tuple's FIRST register, and inline assembly cannot name a sub-register of an
+// operand: the tuple is therefore bound to v[32:63] by its constraint and the text says v32 / v33.  The constraint makes that
+// correct whatever the allocator does; it puts the row loads straight into v[32:55] (no copies, read off the ISA).
+__device__ __forceinline__ void fx_run_fma4x2(const fx_rows_t r, int i0, int i1, int i2, int i3, float w0, float w1, float w2, float w3,
+                                              float* c0, float* c1) {
+    float a, b;
+    asm volatile("s_set_gpr_idx_on %3, gpr_idx(SRC0)\n\t"
+                 "v_fma_f32 %0, v32, %7, 0\n\t"
+                 "v_fma_f32 %1, v33, %7, 0\n\t"
+                 "s_set_gpr_idx_on %4, gpr_idx(SRC0)\n\t"
+                 "v_fma_f32 %0, v32, %8, %0\n\t"
+                 "v_fma_f32 %1, v33, %8, %1\n\t"
+                 "s_set_gpr_idx_on %5, gpr_idx(SRC0)\n\t"
+                 "v_fma_f32 %0, v32, %9, %0\n\t"
+                 "v_fma_f32 %1, v33, %9, %1\n\t"
+                 "s_set_gpr_idx_on %6, gpr_idx(SRC0)\n\t"
+                 "v_fma_f32 %0, v32, %10, %0\n\t"
+                 "v_fma_f32 %1, v33, %10, %1\n\t"
+                 "s_set_gpr_idx_off"
+                 : "=&v"(a), "=&v"(b)
+                 : "{v[32:63]}"(r), "s"(i0), "s"(i1), "s"(i2), "s"(i3), "s"(w0), "s"(w1), "s"(w2), "s"(w3));
+    *c0 = a;
+    *c1 = b;
+}
+
+// Do the NB batches of NE samples in `ye` (lane = sample: {row offset lo, hi, weight lo, hi}, offsets in bytes of an fp32
+// map with rows of `row_bytes`) each lie within `rows` rows from their first entry's row?  Wave-uniform.  That is ALL a run
+// needs: every entry then names a row of the loaded set, and the chain reads exactly the row it names.  (Rows that never
+// step back and span at most `rows` are the common case; an order is not required — at a sample step below one row the
+// entries of consecutive samples read 3, 4, 3, 4.)  Only the first n_real lanes are judged: the samples behind them belong to
+// masked tail rows, whose sums are never stored.  Not a run: an entry re-based to the window's first row when that row lies
+// before the batch's first (zero weight at the bottom border, or an integral coordinate), a bin more than two rows tall,
+// a NaN weight.
+template <int NE, int NB>
+__device__ __forceinline__ int fx_run_base(const int4 ye, const int lane) {       // the first entry's row of the lane's batch
+    int base = __builtin_amdgcn_readlane(ye.x, 0);
+#pragma unroll
+    for (int b = 1; b < NB; ++b) base = lane >= b * NE ? __builtin_amdgcn_readlane(ye.x, b * NE) : base;
+    return base;
+}
+template <int NE, int NB>
+__device__ __forceinline__ bool fx_run_within(const int rows, const int4 ye, const int lane, const int n_real, const unsigned row_bytes) {
+    static_assert(NE * NB <= 64, "one lane per sample");
+    const int base = fx_run_base<NE, NB>(ye, lane);
+    const unsigned dl = (unsigned)(ye.x - base), dh = (unsigned)(ye.y - base), far = (unsigned)(rows - 1) * row_bytes;   // (a row before the base wraps)
+    const float wl = __int_as_float(ye.z), wh = __int_as_float(ye.w);
+    const bool ok = (dl <= far) & (dh <= far) & (wl == wl) & (wh == wh);
+    // (row_bytes: the bound under which fx_run_index's quotient is exact)
+    return row_bytes <= (1u << 18) && n_real > 0 && __ballot((lane < n_real) & !ok) == 0ull;
+}
+// The tuple indices of a run's entries: the row relative to the batch's first entry, times NV registers per row; 0 for the
+// unjudged lanes.  Offsets are whole multiples of row_bytes and below 2^23: the rounded quotient is exact.
+template <int NE, int NB, int NV>
+__device__ __forceinline__ void fx_run_index(const int4 ye, const int lane, const int n_real, const unsigned row_bytes, int* il, int* ih) {
+    const int base = fx_run_base<NE, NB>(ye, lane);
+    const float inv = __builtin_amdgcn_rcpf((float)row_bytes);
+    *il = lane < n_real ? NV * (int)((float)(unsigned)(ye.x - base) * inv + 0.5f) : 0;
+    *ih = lane < n_real ? NV * (int)((float)(unsigned)(ye.y - base) * inv + 0.5f) : 0;
+}
+
 // update_boxes_in_pad_images + extend_bbox (track_utils.py:62-85,109-135) for one box: the next frame's search region.
 __device__ __forceinline__ float4 search_region_of(float b0, float b1, float b2, float b3, const SrOut& S) {
     const float bx1 = add_rn(b0, S.pad), by1 = add_rn(b1, S.pad);

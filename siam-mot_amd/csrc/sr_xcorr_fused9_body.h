@@ -300,6 +300,8 @@
     const unsigned plane_bytes = (unsigned)(H * W) * (unsigned)sizeof(FT);
     // the tables (and a hint's) hold row offsets in bytes of an fp32 map: 2-byte maps halve them where they are used
     constexpr int ROW_SHIFT = sizeof(FT) == 2 ? 1 : 0;
+    // (row runs, fx_run_within: a row and the window's last row in the tables' unit)
+    const unsigned row_bytes = (unsigned)W * 4u, last_row = (unsigned)(ymax * W) * 4u;
     // One batch = ROWS pooled rows of one plane (or of a plane pair side by side).  `PAIR`: lanes 32..63 pool the
     // wave's second plane and the two waves of the pair split the pooled rows; `CHUNKED`: windows wider than 64
     // columns (rare: small batches keep its loop-carried accumulators out of the register peak).
@@ -355,10 +357,105 @@
             typename fx_pair<FT>::type vl[ROWS][G], vh[ROWS][G];
             // (fast: the wave's own 30 y entries sit in ye_early, batch b's at lanes 10 b ..; else a batch's entries from LDS)
             int4 ye = fast ? ye_early : tab[0][min(lane + row0 * G, 63 + 2 * RH * G)];
+            int yoff = 0;
+            // the staged horizontal taps of a batch's column sums and the store of its pooled rows (both loops below)
+            auto htaps = [&](const float (&cs)[ROWS][NV], const int r0) {
+                float acc[ROWS];
+                float* stage = xdst + r0 * XS;
+#pragma unroll
+                for (int g0 = 0; g0 < ROWS; g0 += GR) {
+#pragma unroll
+                    for (int b = g0; b < g0 + GR && b < ROWS; ++b)
+#pragma unroll
+                        for (int k = 0; k < NV; ++k) stage[(b - g0) * SW + wcol + k] = cs[b][k];
+                    float p[GR][G][2];
+#pragma unroll
+                    for (int b = g0; b < g0 + GR && b < ROWS; ++b)
+#pragma unroll
+                        for (int ix = 0; ix < G; ++ix) {
+                            p[b - g0][ix][0] = stage[(b - g0) * SW + sxl[ix]];
+                            p[b - g0][ix][1] = stage[(b - g0) * SW + sxh[ix]];
+                        }
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int b = g0; b < g0 + GR && b < ROWS; ++b)
+#pragma unroll
+                        for (int ix = 0; ix < G; ++ix) {
+                            acc[b] = fmaf(hxw[ix], p[b - g0][ix][0], ix == 0 ? 0.0f : acc[b]);
+                            acc[b] = fmaf(lxw[ix], p[b - g0][ix][1], acc[b]);
+                        }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+#pragma unroll
+                for (int b = 0; b < ROWS; ++b) {
+                    const int ph = r0 + b;
+                    if (col < RX && ph < row0 + nrows && ph < RX && mine) xdst[ph * XS + col] = acc[b] * (1.0f / (float)(G * G));
+                }
+            };
+            // ROW RUNS (fx_run_within, sr_xcorr.hip).  A batch's 10 samples name 20 rows and loaded each of them; in a 65-row
+            // window they are 11 or 12 DISTINCT rows.  `ye` holds all of the wave's 30 entries here, with or without a hint: where
+            // each of its three batches lies within RMAX = 12 rows from its first entry's, a batch loads those 12 consecutive rows
+            // once (clamped to the window's last row) into one register tuple and the vertical chains read their rows out of it by
+            // wave-uniform index (fx_run_fma4x2): 12 loads and 24 registers in flight per batch instead of 20 and 40, the same
+            // cells into the same FMA chains — bit-identical.  The decision is taken once for the wave, not per batch: the
+            // pipeline carries a batch's load registers round the loop, and a loop that could take either form per batch would
+            // carry both sets.  A wave with one batch that is not a run (entries re-based to a row before the batch's first: the
+            // bottom border, integral coordinates; a bin more than two rows tall; NaN tables) takes today's loop below, unchanged.
+            // Measured (profiles/pool_row_runs_ab.json, seven alternating pairs, two sessions): 52.82 -> 51.65 and 52.54 -> 51.73 us
+            // per step, this form's pooling 9.5 k -> 8.4 k ticks (profiles/pool_row_runs_before.md: the address unit was issuing
+            // for ~80 % of that phase).
+            // Measured and dropped: the same for the one-column forms below (windows <= 32 columns: 30 samples, RMAX 32, loads
+            // of 20 / 28 / 32 rows by the rows the batch needs; the extraction: 16 samples, RMAX 18) — bit-identical, but their
+            // pooling got SLOWER (7.2 k -> 8.0 k, extraction 3.2 k -> 4.0 k ticks, 52.98 us per step): a one-column load costs the
+            // address unit half of a two-column one, and every tap pays a switch of the register index, which two columns share
+            // here.  Also dropped: the compiler's own form of a uniformly indexed register (54.34 us, see fx_run_fma4x2).
+            constexpr int NE = ROWS * G, RMAX = NE + 2;
+            static_assert(RMAX * NV <= 32, "a run fits the register tuple");
+            if (fx_run_within<NE, RH / ROWS>(RMAX, ye, lane, RH * G, row_bytes)) {
+                int il, ih;
+                fx_run_index<NE, RH / ROWS, NV>(ye, lane, RH * G, row_bytes, &il, &ih);
+                fx_rows_t rr;
+#define SMOT_FX_ISSUE_RUN()                                                                                         \
+                {                                                                                                   \
+                    const unsigned rb_ = (unsigned)__builtin_amdgcn_readlane(ye.x, yoff);                           \
+                    _Pragma("unroll") for (int j = 0; j < RMAX; ++j) {                                              \
+                        const auto v2_ = fx_load2<FT>(rsrc, voff, (int)(min(rb_ + j * row_bytes, last_row) >> ROW_SHIFT)); \
+                        rr[NV * j] = fx_pair_elem<FT>(v2_, 0);                                                      \
+                        rr[NV * j + 1] = fx_pair_elem<FT>(v2_, 1);                                                  \
+                    }                                                                                               \
+                }
+                SMOT_FX_ISSUE_RUN()
+                __builtin_amdgcn_sched_barrier(0);
+                if (owns) {
+                    unsigned char* tzw = reinterpret_cast<unsigned char*>(sm + (wave >> 1) * (2 * XP + 2 * ZP) + 2 * XP + (wave & 1) * ZP);
+                    isz = xh_template_store(zq, tzw, lane);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll 1
+                for (int r0 = row0; r0 < row0 + nrows; r0 += ROWS) {
+                    const float wl = __int_as_float(ye.z), wh = __int_as_float(ye.w);
+                    float cs[ROWS][NV];
+#pragma unroll
+                    for (int b = 0; b < ROWS; ++b) {
+                        const int e = yoff + b * G;
+                        const int i0 = __builtin_amdgcn_readlane(il, e), i1 = __builtin_amdgcn_readlane(ih, e);
+                        const int i2 = __builtin_amdgcn_readlane(il, e + 1), i3 = __builtin_amdgcn_readlane(ih, e + 1);
+                        fx_run_fma4x2(rr, i0, i1, i2, i3, rl_f(wl, e), rl_f(wh, e), rl_f(wl, e + 1), rl_f(wh, e + 1), &cs[b][0], &cs[b][1]);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (r0 + ROWS < row0 + nrows) {                  // (wave-uniform) the next batch's run
+                        yoff += NE;
+                        SMOT_FX_ISSUE_RUN()
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    htaps(cs, r0);
+                }
+#undef SMOT_FX_ISSUE_RUN
+                return;
+            }
             ye.x = (int)((unsigned)ye.x >> ROW_SHIFT);
             ye.y = (int)((unsigned)ye.y >> ROW_SHIFT);
-            int yoff = 0;
-#define SMOT_FX_ISSUE()                                                                                             \
+#define SMOT_FX_ISSUE()                                                                                           \
             _Pragma("unroll") for (int b = 0; b < ROWS; ++b)                                                        \
                 _Pragma("unroll") for (int iy = 0; iy < G; ++iy) {                                                  \
                     vl[b][iy] = fx_load2<FT>(rsrc, voff, __builtin_amdgcn_readlane(ye.x, yoff + b * G + iy));         \
@@ -399,37 +496,7 @@
                     SMOT_FX_ISSUE()
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                float acc[ROWS];
-                float* stage = xdst + r0 * XS;
-#pragma unroll
-                for (int g0 = 0; g0 < ROWS; g0 += GR) {
-#pragma unroll
-                    for (int b = g0; b < g0 + GR && b < ROWS; ++b)
-#pragma unroll
-                        for (int k = 0; k < NV; ++k) stage[(b - g0) * SW + wcol + k] = cs[b][k];
-                    float p[GR][G][2];
-#pragma unroll
-                    for (int b = g0; b < g0 + GR && b < ROWS; ++b)
-#pragma unroll
-                        for (int ix = 0; ix < G; ++ix) {
-                            p[b - g0][ix][0] = stage[(b - g0) * SW + sxl[ix]];
-                            p[b - g0][ix][1] = stage[(b - g0) * SW + sxh[ix]];
-                        }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int b = g0; b < g0 + GR && b < ROWS; ++b)
-#pragma unroll
-                        for (int ix = 0; ix < G; ++ix) {
-                            acc[b] = fmaf(hxw[ix], p[b - g0][ix][0], ix == 0 ? 0.0f : acc[b]);
-                            acc[b] = fmaf(lxw[ix], p[b - g0][ix][1], acc[b]);
-                        }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-#pragma unroll
-                for (int b = 0; b < ROWS; ++b) {
-                    const int ph = r0 + b;
-                    if (col < RX && ph < row0 + nrows && ph < RX && mine) xdst[ph * XS + col] = acc[b] * (1.0f / (float)(G * G));
-                }
+                htaps(cs, r0);
             }
 #undef SMOT_FX_ISSUE
             return;
