@@ -56,7 +56,8 @@ typedef void* smot_stream_t; /* hipStream_t */
  *     symbols it needs): the _typed_ entry points, smot_rpn_proposals_*, smot_box_detect_post_*, and the box head over
  *     several images: smot_roi_align_levels_batched_typed_fwd, smot_box_detect_post_batched_ws_bytes,
  *     smot_box_detect_post_batched_fwd; the frames of several cameras in one call: smot_preprocess_batch_fwd; the track
- *     solver over several images: smot_track_solve_batched_fwd.
+ *     solver over several images: smot_track_solve_batched_fwd; the RPN head and anchors: smot_rpn_head_*,
+ *     smot_rpn_anchors_fwd; the feature pyramid: smot_fpn_packed_floats, smot_fpn_pack, smot_fpn_ws_bytes, smot_fpn_fwd.
  */
 #define SMOT_ABI_VERSION 14
 
@@ -1097,6 +1098,51 @@ int smot_rpn_head_fwd(const void* const* feats, int feat_type, const int* height
                       float* const* regression_out, smot_stream_t stream);
 int smot_rpn_anchors_fwd(const float* const* cell_anchors, const int* num_anchors, const int* strides, const int* heights,
                          const int* widths, int num_levels, float* const* out, smot_stream_t stream);
+
+/*
+ * FEATURE PYRAMID (csrc/fpn.hip): [UPSTREAM] maskrcnn_benchmark FPN.forward with the top-down path resized bilinearly to
+ * the lateral's size (the stage maps need not halve exactly) — backbone stage maps to the pyramid's maps for every image of
+ * a call in num_levels + 1 launches (one lateral launch per level, coarsest first, then ONE launch for the 3x3 convolutions
+ * of all levels and images) and without a host synchronisation.  All products run on the fp32 matrix cores (exact fp32
+ * products, fp32 accumulation).
+ *
+ *   last[L-1] = conv1x1(x[L-1], inner_w) + inner_b
+ *   last[l]   = conv1x1(x[l], inner_w) + inner_b + resize(last[l+1] -> (H_l, W_l))       l = L-2 .. 0
+ *   P[l]      = conv3x3(last[l], layer_w, pad 1) + layer_b                               every l
+ *   P[L]      = P[L-1][:, :, ::2, ::2]                                                   top_block = 1 (LastLevelMaxPool)
+ *
+ *   resize         torch's F.interpolate(size=, mode="bilinear", align_corners=False) in fp32: scale = float(in) /
+ *                  float(out), src = scale * (dst + 0.5f) - 0.5f (0 where negative), i0 = (int)src, i1 = i0 + (i0 < in - 1),
+ *                  w1 = src - i0, w0 = 1 - w1, value = h0 * (w0 v00 + w1 v01) + h1 * (w0 v10 + w1 v11), every operation
+ *                  rounded on its own and all four products evaluated: a non-finite cell spreads as it does in torch.
+ *   stages[l]      [num_images, in_channels[l], H_l, W_l], finest first, contiguous NCHW, all of element type `stage_type`
+ *                  (SMOT_FEAT_F32 / F16 / BF16): a half call returns bit for bit what the call returns on the upcast maps.
+ *                  The layout flag SMOT_FEAT_CHANNELS_LAST is SMOT_ERR_UNSUPPORTED.
+ *   packed         smot_fpn_packed_floats(...) floats, 16-byte aligned, written by smot_fpn_pack (one launch on `stream`;
+ *                  pack again when a parameter changes) from upstream's parameters, HOST arrays [num_levels] of DEVICE
+ *                  pointers: inner_w[l] = fpn_inner{l+1}.weight [C, in_channels[l](, 1, 1)], inner_b[l] [C], layer_w[l] =
+ *                  fpn_layer{l+1}.weight [C, C, 3, 3], layer_b[l] [C], all fp32.
+ *   ws             smot_fpn_ws_bytes(...) bytes, 16-byte aligned, owned by the caller: the fp32 last[l] maps.
+ *   out            HOST array of num_levels + top_block DEVICE pointers: out[l] [num_images, C, H_l, W_l], out[num_levels]
+ *                  [num_images, C, (H + 1) / 2, (W + 1) / 2] of the coarsest level; contiguous NCHW of element type
+ *                  `out_type` (SMOT_FEAT_F32, or F16 / BF16: the fp32 value rounded to nearest even, NaN kept).
+ *   contract       an output's value depends on its own image alone, with a summation order fixed by (in_channels[l], C)
+ *                  and the position: image i of a call equals the one-image call on it bit for bit; deterministic.
+ *   capacities     C % 32 == 0, 32 <= C <= 512, in_channels[l] % 16 == 0, 16 <= in_channels[l] <= 2048
+ *                  (SMOT_ERR_UNSUPPORTED beyond, also for a level of 2^31 / max(C, in_channels[l]) cells or more);
+ *                  1 <= num_levels <= SMOT_MAX_LEVELS - 1, 1 <= num_images <= SMOT_MAX_IMAGES, non-null pointers at
+ *                  their alignment, H_l, W_l >= 1, top_block 0 or 1 (SMOT_ERR_BAD_ARG).  smot_fpn_packed_floats returns
+ *                  -1 for unsupported channel counts, smot_fpn_ws_bytes -1 for counts or sizes out of range.  Nothing is
+ *                  launched by a refused call.
+ */
+long long smot_fpn_packed_floats(int num_levels, const int* in_channels, int C);
+int smot_fpn_pack(const float* const* inner_w, const float* const* inner_b, const float* const* layer_w,
+                  const float* const* layer_b, int num_levels, const int* in_channels, int C, float* packed,
+                  smot_stream_t stream);
+long long smot_fpn_ws_bytes(int num_levels, const int* heights, const int* widths, int num_images, int C);
+int smot_fpn_fwd(const void* const* stages, int stage_type, const int* in_channels, const int* heights, const int* widths,
+                 int num_levels, int num_images, int C, const float* packed, float* ws, void* const* out, int out_type,
+                 int top_block, smot_stream_t stream);
 
 #ifdef __cplusplus
 }

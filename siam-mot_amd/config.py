@@ -30,7 +30,11 @@ def get_default_cfg(conv_body="DLA-34-FPN", channels=128):
     cfg.DATALOADER = CfgNode(SIZE_DIVISIBILITY=32)
     cfg.MODEL = CfgNode()
     cfg.MODEL.BACKBONE = CfgNode(CONV_BODY=conv_body)
-    cfg.MODEL.DLA = CfgNode(BACKBONE_OUT_CHANNELS=channels)
+    # what fpn.build_fpn reads: the DLA-34 stage widths and the FPN's conv blocks (siammot/configs/defaults.py:31-35,
+    # [UPSTREAM] MODEL.FPN defaults)
+    cfg.MODEL.DLA = CfgNode(DLA_STAGE2_OUT_CHANNELS=64, DLA_STAGE3_OUT_CHANNELS=128, DLA_STAGE4_OUT_CHANNELS=256,
+                            DLA_STAGE5_OUT_CHANNELS=512, BACKBONE_OUT_CHANNELS=channels)
+    cfg.MODEL.FPN = CfgNode(USE_GN=False, USE_RELU=False)
     cfg.MODEL.RESNETS = CfgNode(BACKBONE_OUT_CHANNELS=256)
     cfg.MODEL.GROUP_NORM = CfgNode(DIM_PER_GP=-1, NUM_GROUPS=32, EPSILON=1e-5)
     # what rpn.make_rpn_postprocessor reads at inference: the three counts from siammot/configs/defaults.py:13-15, the

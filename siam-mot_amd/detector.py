@@ -13,25 +13,31 @@ one copy.  When either half is over its capacity or not on the device, or the im
 ``forward_features(features, image_size)`` starts one step earlier, at the FPN maps: the RPN head's convolutions
 (``rpn.RPNHead``: one launch for all images and levels), the cached anchor grid (``rpn.AnchorGenerator``: no launch once the
 map sizes have been seen) and then ``forward`` — still the one copy.
+
+``forward_stages(stages, image_size)`` starts at the backbone's stage maps: the pyramid (``fpn.FPN``: L + 1 launches, no
+synchronisation) and then ``forward_features``; the FPN maps are handed back with the detections for the tracker.
 """
 import torch
 
 from . import ops
 from .box_refine import TrackBoxHead
+from .fpn import build_fpn
 from .rpn import RPNHead, make_anchor_generator, make_rpn_postprocessor
 
 
 class DetectionHead(torch.nn.Module):
     """``forward(anchors, objectness, box_regression, features) -> [BoxList]`` per image (fields ``scores``, ``ids`` = -1,
     ``labels``): ``rpn_post`` is an ``rpn.RPNPostProcessor``, ``box_head`` a ``TrackBoxHead``.  With an ``rpn.RPNHead`` and an
-    ``rpn.AnchorGenerator`` as well: ``forward_features(features, image_size)``, the same from the FPN maps."""
+    ``rpn.AnchorGenerator`` as well: ``forward_features(features, image_size)``, the same from the FPN maps; with an
+    ``fpn.FPN`` too: ``forward_stages(stages, image_size)``, the same from the backbone's stage maps."""
 
-    def __init__(self, rpn_post, box_head, rpn_head=None, anchor_generator=None):
+    def __init__(self, rpn_post, box_head, rpn_head=None, anchor_generator=None, fpn=None):
         super(DetectionHead, self).__init__()
         self.rpn_post = rpn_post
         self.box_head = box_head
         self.rpn_head = rpn_head
         self.anchor_generator = anchor_generator
+        self.fpn = fpn
 
     def raw_ok(self, anchors, objectness):
         """Both halves take their device paths for this call."""
@@ -81,16 +87,31 @@ class DetectionHead(torch.nn.Module):
         anchors = self.anchor_generator([tuple(image_size)] * int(features[0].shape[0]), features)
         return self.forward(anchors, objectness, box_regression, features)
 
+    @torch.no_grad()
+    def forward_stages(self, stages, image_size):
+        """Backbone stage maps ``stages[l]`` = ``[N, Cin_l, H_l, W_l]`` of N images of one size -> ``(features, detections)``:
+        ``features = fpn(stages)`` and ``forward_features(features, image_size)``, bit for bit."""
+        if self.fpn is None:
+            raise RuntimeError("siammot_amd.detector.DetectionHead: forward_stages needs an FPN "
+                               "(build_detection_head(..., fpn=True))")
+        if self.training:
+            raise NotImplementedError("siammot_amd.detector.DetectionHead is an inference path")
+        features = self.fpn(stages)
+        return features, self.forward_features(features, image_size)
 
-def build_detection_head(cfg, rpn_box_coder, in_channels, box_head=None, rpn_head=True):
+
+def build_detection_head(cfg, rpn_box_coder, in_channels, box_head=None, rpn_head=True, fpn=False):
     """``DetectionHead`` from a config: the reference's RPN factory keys (``MODEL.RPN.*_TEST``) and the given box head or a
     fresh ``TrackBoxHead``.  ``rpn_head``: True for a fresh ``rpn.RPNHead`` and the config's anchor generator
     (``MODEL.RPN.ANCHOR_*``, ``ASPECT_RATIOS``), an ``RPNHead`` to use that one, False / None for a head that starts at the
-    anchors (``forward`` only)."""
+    anchors (``forward`` only).  ``fpn``: True for the config's pyramid (``fpn.build_fpn``), an ``fpn.FPN`` to use that one,
+    False / None for a head that starts at the FPN maps."""
     if box_head is None:
         box_head = TrackBoxHead(cfg, in_channels).eval()
     head, generator = None, None
     if rpn_head:
         generator = make_anchor_generator(cfg)
         head = RPNHead(cfg, in_channels, generator.num_anchors_per_location()[0]) if rpn_head is True else rpn_head
-    return DetectionHead(make_rpn_postprocessor(cfg, rpn_box_coder, is_train=False).eval(), box_head, head, generator).eval()
+    pyramid = (build_fpn(cfg) if fpn is True else fpn) if fpn else None
+    return DetectionHead(make_rpn_postprocessor(cfg, rpn_box_coder, is_train=False).eval(), box_head, head, generator,
+                         pyramid).eval()

@@ -32,3 +32,13 @@ def patch_upstream():
     import maskrcnn_benchmark.layers as L
     L.ROIAlign.forward = ROIAlign.forward
     return L.ROIAlign
+
+
+def patch_upstream_fpn():
+    """``maskrcnn_benchmark.modeling.backbone.fpn.FPN = siammot_amd.fpn.FPN`` — the reference's own idiom
+    (operator_patch/fpn_patch.py assigns its class the same way): backbones built afterwards get this package's pyramid, whose
+    ``state_dict`` keys are upstream's."""
+    import maskrcnn_benchmark.modeling.backbone.fpn as upstream_fpn
+    from .fpn import FPN
+    upstream_fpn.FPN = FPN
+    return FPN

@@ -150,6 +150,11 @@ _SIGNATURES = {
     "smot_rpn_head_pack": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "smot_rpn_head_fwd": (ctypes.c_int, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "smot_rpn_anchors_fwd": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    # feature pyramid: backbone stage maps to the FPN maps of all images in num_levels + 1 launches
+    "smot_fpn_packed_floats": (ctypes.c_longlong, [_i, _vp, _i]),
+    "smot_fpn_pack": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),
+    "smot_fpn_ws_bytes": (ctypes.c_longlong, [_i, _vp, _vp, _i, _i]),
+    "smot_fpn_fwd": (ctypes.c_int, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 _DEBUG_SIGNATURES = {
@@ -1167,6 +1172,9 @@ FALLBACKS["refine_per_camera"] = 0
 #   rpn_head_torch       an ``rpn.RPNHead`` call on device maps that ``rpn_head`` does not take (training mode, C or A beyond
 #                        its capacities, more images or levels): the ``F.conv2d`` composition; present from import
 FALLBACKS["rpn_head_torch"] = 0
+#   fpn_torch            an ``fpn.FPN`` call on device maps that ``fpn`` does not take (training or grad mode, a GroupNorm /
+#                        ReLU conv block, ``LastLevelP6P7``, channel counts beyond the kernels' capacities)
+FALLBACKS["fpn_torch"] = 0
 # speculative next-frame heads of the tracking loop (TrackingLoop.forward(..., next_features=...)): launched / used as they
 # were / discarded because the row count, the memory, the features or the parameters were not what the launch assumed
 SPECULATION = _collections.Counter()
@@ -1461,6 +1469,86 @@ def rpn_head(features, packed, C, A):
                                    _cast(pr), ln.stream)
     _check(rc, "rpn_head")
     return obj, reg
+
+
+# capacities of ``fpn`` (include/smot_emm.h): beyond them ``siammot_amd.fpn.FPN`` takes its torch composition
+FPN_MAX_LEVELS = 7
+FPN_MAX_CHANNELS = 512
+FPN_CHANNEL_STEP = 32
+FPN_MAX_IN_CHANNELS = 2048
+FPN_IN_CHANNEL_STEP = 16
+
+
+def fpn_shapes_ok(in_channels, C):
+    return (1 <= len(in_channels) <= FPN_MAX_LEVELS and C >= 32 and C % FPN_CHANNEL_STEP == 0 and C <= FPN_MAX_CHANNELS
+            and all(16 <= c <= FPN_MAX_IN_CHANNELS and c % FPN_IN_CHANNEL_STEP == 0 for c in in_channels))
+
+
+def fpn_pack(inner, layer):
+    """The pyramid's parameters (per level, finest first: ``inner[l]`` = upstream's ``fpn_inner{l+1}`` ``(weight [C, Cin_l,
+    1, 1], bias [C])``, ``layer[l]`` = ``fpn_layer{l+1}`` ``(weight [C, C, 3, 3], bias [C])``, fp32 device tensors) in the
+    operand order of ``fpn`` (``smot_fpn_pack``: one launch, no synchronisation).  -> fp32 ``[smot_fpn_packed_floats]``."""
+    lib = _lib or load_library()
+    L = len(inner)
+    if L < 1 or len(layer) != L:
+        raise RuntimeError("siammot_amd.fpn_pack: %d lateral and %d output blocks" % (L, len(layer)))
+    C = int(inner[0][0].shape[0])
+    cin = [int(w.shape[1]) for w, _ in inner]
+    iw = [_chk(w.reshape(C, -1), "fpn_inner%d.weight" % (l + 1), (C, cin[l])) for l, (w, _) in enumerate(inner)]
+    ib = [_chk(b, "fpn_inner%d.bias" % (l + 1), (C,)) for l, (_, b) in enumerate(inner)]
+    lw = [_chk(w, "fpn_layer%d.weight" % (l + 1), (C, C, 3, 3)) for l, (w, _) in enumerate(layer)]
+    lb = [_chk(b, "fpn_layer%d.bias" % (l + 1), (C,)) for l, (_, b) in enumerate(layer)]
+    ic = (ctypes.c_int * L)(*cin)
+    n = lib.smot_fpn_packed_floats(L, _cast(ic), C)
+    if n < 0:
+        _check(-2, "fpn_pack")
+    packed = torch.empty((n,), dtype=_F32, device=iw[0].device)
+    arrays = [(ctypes.c_void_p * L)(*[t.data_ptr() for t in ts]) for ts in (iw, ib, lw, lb)]
+    with _Launch(*(iw + ib + lw + lb)) as ln:
+        rc = lib.smot_fpn_pack(*([_cast(a) for a in arrays] + [L, _cast(ic), C, _ptr(packed), ln.stream]))
+    _check(rc, "fpn_pack")
+    return packed
+
+
+def fpn(stages, packed, in_channels, C, out_dtype=torch.float32, top_block=True):
+    """Upstream's ``FPN.forward`` (top-down path resized bilinearly to the lateral's size) on all images of a call in L + 1
+    launches (``smot_fpn_fwd``), free of host synchronisation.  stages: L maps ``[N, Cin_l, H_l, W_l]``, finest first, of
+    one dtype (fp32, fp16 or bf16; a half call returns the bits of the call on ``.float()``); anything but contiguous NCHW
+    is copied.  packed: ``fpn_pack``'s tensor.  -> L (+ 1 with ``top_block``: ``LastLevelMaxPool``) contiguous NCHW maps
+    ``[N, C, H_l, W_l]`` of ``out_dtype`` (a half output is the fp32 value rounded to nearest even)."""
+    lib = _lib or load_library()
+    L = len(stages)
+    if L < 1 or len(in_channels) != L:
+        raise RuntimeError("siammot_amd.fpn: %d stage maps for %d levels" % (L, len(in_channels)))
+    if out_dtype not in FEAT_TYPES:
+        raise RuntimeError("siammot_amd.fpn: out_dtype must be float32, float16 or bfloat16, got %s" % (out_dtype,))
+    feats = [_dev_feat(f, "stages[%d]" % l) for l, f in enumerate(stages)]
+    ft = _feat_type(feats)
+    N = feats[0].shape[0]
+    for l, f in enumerate(feats):
+        if f.dim() != 4 or f.shape[0] != N or f.shape[1] != in_channels[l]:
+            raise RuntimeError("siammot_amd.fpn: stages[%d] has shape %s, expected [%d, %d, H, W]"
+                               % (l, tuple(f.shape), N, in_channels[l]))
+    dev = feats[0].device
+    sizes = [(int(f.shape[2]), int(f.shape[3])) for f in feats]
+    ic = (ctypes.c_int * L)(*[int(c) for c in in_channels])
+    ih = (ctypes.c_int * L)(*[s[0] for s in sizes])
+    iw = (ctypes.c_int * L)(*[s[1] for s in sizes])
+    nbytes = lib.smot_fpn_ws_bytes(L, _cast(ih), _cast(iw), N, int(C))
+    if nbytes < 0:
+        raise RuntimeError("siammot_amd.fpn: %d levels of %d images (at most %d levels, %d images, no empty map)"
+                           % (L, N, FPN_MAX_LEVELS, RPN_MAX_IMAGES))
+    ws = torch.empty((max(nbytes // 4, 4),), dtype=_F32, device=dev)
+    if top_block:
+        sizes = sizes + [((sizes[-1][0] + 1) // 2, (sizes[-1][1] + 1) // 2)]
+    out = [torch.empty((N, int(C), h, w), dtype=out_dtype, device=dev) for (h, w) in sizes]
+    fp = (ctypes.c_void_p * L)(*[t.data_ptr() for t in feats])
+    po = (ctypes.c_void_p * len(out))(*[t.data_ptr() for t in out])
+    with _Launch(*(feats + [packed])) as ln:
+        rc = lib.smot_fpn_fwd(_cast(fp), ft, _cast(ic), _cast(ih), _cast(iw), L, N, int(C), _ptr(packed), _ptr(ws), _cast(po),
+                              FEAT_TYPES[out_dtype], 1 if top_block else 0, ln.stream)
+    _check(rc, "fpn")
+    return out
 
 
 def rpn_anchors(cell_anchors, strides, grid_sizes):
