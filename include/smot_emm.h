@@ -57,7 +57,9 @@ typedef void* smot_stream_t; /* hipStream_t */
  *     several images: smot_roi_align_levels_batched_typed_fwd, smot_box_detect_post_batched_ws_bytes,
  *     smot_box_detect_post_batched_fwd; the frames of several cameras in one call: smot_preprocess_batch_fwd; the track
  *     solver over several images: smot_track_solve_batched_fwd; the RPN head and anchors: smot_rpn_head_*,
- *     smot_rpn_anchors_fwd; the feature pyramid: smot_fpn_packed_floats, smot_fpn_pack, smot_fpn_ws_bytes, smot_fpn_fwd.
+ *     smot_rpn_anchors_fwd; the feature pyramid: smot_fpn_packed_floats, smot_fpn_pack, smot_fpn_ws_bytes, smot_fpn_fwd;
+ *     the DLA backbone body: smot_dla_packed_floats, smot_dla_pack, smot_dla_ws_bytes, smot_dla_fwd and its operators alone:
+ *     smot_dla_conv_packed_floats, smot_dla_conv3x3_fwd, smot_dla_conv3x3_form, smot_dla_conv1x1_fwd, smot_dla_stem_ws_bytes, smot_dla_stem_fwd.
  */
 #define SMOT_ABI_VERSION 14
 
@@ -1143,6 +1145,87 @@ long long smot_fpn_ws_bytes(int num_levels, const int* heights, const int* width
 int smot_fpn_fwd(const void* const* stages, int stage_type, const int* in_channels, const int* heights, const int* widths,
                  int num_levels, int num_images, int C, const float* packed, float* ws, void* const* out, int out_type,
                  int top_block, smot_stream_t stream);
+
+/*
+ * DLA BACKBONE (csrc/dla.hip): [UPSTREAM] siammot/modelling/backbone/dla.py with DlaBasic blocks and maskrcnn_benchmark's
+ * FrozenBatchNorm2d, inference — an image batch to the four stage maps x2 .. x5 (strides 4, 8, 16, 32) that smot_fpn_fwd
+ * reads, without a host synchronisation or an allocation.  Every convolution runs on the fp32 matrix cores (exact fp32
+ * products, fp32 accumulation) and has no bias; a frozen BN is y = x * scale + shift with scale = weight * rsqrt(running_var)
+ * (no epsilon) and shift = bias - running_mean * scale, both computed by the caller; cbr = conv, BN, ReLU; cb = conv, BN.
+ * ReLU is v < 0 ? 0 : v (a NaN stays); the 2x2 max-pool hands a NaN on, as torch's.  3x3 convolutions use pad 1.
+ *
+ *   x  = cbr7x7(image, 3 -> c0, pad 3);  x0 = cbr3x3(x, c0 -> c0);  x1 = cbr3x3(x0, c0 -> c1, stride 2)
+ *   xk = tree(levels[k], x_{k-1}, c_{k-1} -> c_k, stride 2, level_root = (k > 2))         k = 2 .. 5; returned: x2 .. x5
+ *   basic(x, s, residual) = relu(cb3x3(relu(cb3x3(x, stride s))) + residual)
+ *   tree(1, x, cin -> cout, s, level_root, handed):
+ *       bottom = maxpool2x2(x) if s == 2 else x;  residual = cb1x1(bottom) if cin != cout else bottom      ("project")
+ *       x1 = basic(x, s, residual);  x2 = basic(x1, 1, x1)
+ *       relu(cb1x1(cat(x2, x1, [bottom if level_root], *handed)))                                           ("root")
+ *   tree(2, x, ...): bottom as above;  t = tree(1, x, cin -> cout, s, no level_root, nothing handed)
+ *       tree(1, t, cout -> cout, 1, no level_root, handed = [bottom if level_root] + [t])
+ *       (upstream evaluates the outer tree's project and discards it: it is not computed and not in the packed image)
+ *
+ *   launches       3 for the stem (7x7, 3x3, 3x3 stride 2; the two c0-channel maps go through the workspace), 6 per
+ *                  levels = 1 tree, 11 per levels = 2 tree: 37 for DLA-34.  No cat and no pooled map is materialised.
+ *   convolutions   "launch order": base_layer, level0, level1, then per tree(1): project (if cin != cout), tree1.conv1,
+ *                  tree1.conv2, tree2.conv1, tree2.conv2, root; a tree(2) is its tree1 then its tree2 (37 for DLA-34;
+ *                  smot_dla_pack checks the count).
+ *   packed         smot_dla_packed_floats(...) floats, 16-byte aligned, written by smot_dla_pack (one launch per
+ *                  convolution on `stream`; pack again when a parameter changes) from HOST arrays [num_convs] of DEVICE
+ *                  pointers in launch order: w[i] the filters [Cout, Cin, k, k], scale[i], shift[i] [Cout], all fp32.
+ *   image          [num_images, 3, H, W] contiguous NCHW of `in_type` (SMOT_FEAT_F32 / F16 / BF16; a half call returns bit
+ *                  for bit what the call returns on the upcast image)
+ *   ws             smot_dla_ws_bytes(...) bytes, 16-byte aligned, owned by the caller: the fp32 intermediates (and, for a
+ *                  half `out_type`, the fp32 twins of x2 .. x4 that the next level reads)
+ *   out            HOST array of four DEVICE pointers: out[k] [num_images, channels[k + 2], H >> (k + 2), W >> (k + 2)],
+ *                  contiguous NCHW of `out_type` (fp32, or fp16 / bf16: the fp32 value rounded to nearest even, NaN kept)
+ *   contract       an output depends on its own image alone, with a summation order fixed by the channel counts and the
+ *                  position: image i of a call equals the one-image call on it bit for bit; deterministic.
+ *   capacities     levels[0] == levels[1] == 1, levels[2..5] in {1, 2}; channels[0] in {16, 32}; channels[1..5] % 32 == 0,
+ *                  32 <= . <= 1024;
+ *                  H % 32 == 0, W % 32 == 0, H, W >= 32 (the stride-2 convolution gives ceil(H / 2) and the pool
+ *                  floor(H / 2): upstream itself raises on any other size); every map of one image below 2^31 elements
+ *                  (SMOT_ERR_UNSUPPORTED beyond).  1 <= num_images <= SMOT_MAX_IMAGES, non-null pointers at their
+ *                  alignment, in_type / out_type as above (SMOT_ERR_BAD_ARG).  smot_dla_packed_floats and
+ *                  smot_dla_ws_bytes return -1 for what smot_dla_fwd refuses.  Nothing is launched by a refused call.
+ *
+ * The operators alone (each packs its filters into caller memory, then runs: two or more launches):
+ *   smot_dla_conv3x3_fwd   x [N, Cin, H, W] fp32 -> out [N, Cout, Ho, Wo] fp32, Ho = H (stride 1) or (H - 1) / 2 + 1
+ *                  (stride 2), any H, W >= 1 with zeros beyond the map; w [Cout, Cin, 3, 3]; residual [N, Cout, Ho, Wo] or
+ *                  null, with residual_h = residual_w = 0; or [N, Cout, residual_h, residual_w] read through a 2x2
+ *                  max-pool (residual_h / 2 == Ho, residual_w / 2 == Wo: what a stage that keeps its width adds);
+ *                  relu 0 / 1; packed: smot_dla_conv_packed_floats(3, Cin, Cout) floats, 16-byte aligned.
+ *   smot_dla_conv3x3_form  which form of the 3x3 kernel that call runs: 10 * WR + NM (WR = 1, 2 or 4 row groups of the
+ *                  workgroup's four waves, NM = M-tiles per pair: 41 42 22 12); chosen by Cout, the stride and the
+ *                  number of 8 x 16 output tiles of all images; an output's value does not depend on it.  -1: bad argument.
+ *                  Cin % 8 == 0, Cout 16 or % 32 == 0, both <= 1024 (SMOT_ERR_UNSUPPORTED beyond).
+ *   smot_dla_conv1x1_fwd   a 1x1 convolution over the concatenation of num_sources (1 .. 4) fp32 maps, HOST arrays:
+ *                  sources[s] [N, source_channels[s], source_heights[s], source_widths[s]]; source_pooled[s] != 0: read
+ *                  through a 2x2 max-pool (heights / 2 == H, widths / 2 == W), else the map is H x W; w [Cout, sum of the
+ *                  channels]; out [N, Cout, H, W] of out_type; packed: smot_dla_conv_packed_floats(1, sum, Cout) floats.
+ *                  source_channels[s] % 16 == 0, Cout % 32 == 0, all <= 1024 (SMOT_ERR_UNSUPPORTED beyond).
+ *   smot_dla_stem_fwd      image -> x1 [N, c1, H / 2, W / 2] fp32; w / scale / shift: HOST arrays of the three layers'
+ *                  DEVICE pointers (base_layer, level0, level1); ws: smot_dla_stem_ws_bytes(...) bytes, 16-byte aligned.
+ *                  c0 in {16, 32}, c1 % 32 == 0, c1 <= 1024, H and W even (SMOT_ERR_UNSUPPORTED beyond).
+ */
+long long smot_dla_packed_floats(const int* levels, const int* channels);
+int smot_dla_pack(const int* levels, const int* channels, const float* const* w, const float* const* scale,
+                  const float* const* shift, int num_convs, float* packed, smot_stream_t stream);
+long long smot_dla_ws_bytes(const int* levels, const int* channels, int num_images, int H, int W);
+int smot_dla_fwd(const void* image, int in_type, int num_images, int H, int W, const int* levels, const int* channels,
+                 const float* packed, float* ws, void* const* out, int out_type, smot_stream_t stream);
+long long smot_dla_conv_packed_floats(int kernel_size, int Cin, int Cout);
+int smot_dla_conv3x3_fwd(const float* x, int num_images, int Cin, int H, int W, const float* w, const float* scale,
+                         const float* shift, int Cout, int stride, const float* residual, int residual_h, int residual_w,
+                         int relu, float* packed, float* out, smot_stream_t stream);
+int smot_dla_conv3x3_form(int num_images, int H, int W, int Cout, int stride);
+int smot_dla_conv1x1_fwd(const float* const* sources, const int* source_channels, const int* source_pooled,
+                         const int* source_heights, const int* source_widths, int num_sources, int num_images, int H, int W,
+                         const float* w, const float* scale, const float* shift, int Cout, int relu, float* packed, void* out,
+                         int out_type, smot_stream_t stream);
+long long smot_dla_stem_ws_bytes(int num_images, int H, int W, int c0, int c1);
+int smot_dla_stem_fwd(const void* image, int in_type, int num_images, int H, int W, int c0, int c1, const float* const* w,
+                      const float* const* scale, const float* const* shift, float* ws, float* out, smot_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -33,7 +33,9 @@ def get_default_cfg(conv_body="DLA-34-FPN", channels=128):
     # what fpn.build_fpn reads: the DLA-34 stage widths and the FPN's conv blocks (siammot/configs/defaults.py:31-35,
     # [UPSTREAM] MODEL.FPN defaults)
     cfg.MODEL.DLA = CfgNode(DLA_STAGE2_OUT_CHANNELS=64, DLA_STAGE3_OUT_CHANNELS=128, DLA_STAGE4_OUT_CHANNELS=256,
-                            DLA_STAGE5_OUT_CHANNELS=512, BACKBONE_OUT_CHANNELS=channels)
+                            DLA_STAGE5_OUT_CHANNELS=512, BACKBONE_OUT_CHANNELS=channels,
+                            # what dla.build_dla reads: no deformable convolutions (siammot/configs/defaults.py)
+                            STAGE_WITH_DCN=(False, False, False, False, False, False))
     cfg.MODEL.FPN = CfgNode(USE_GN=False, USE_RELU=False)
     cfg.MODEL.RESNETS = CfgNode(BACKBONE_OUT_CHANNELS=256)
     cfg.MODEL.GROUP_NORM = CfgNode(DIM_PER_GP=-1, NUM_GROUPS=32, EPSILON=1e-5)

@@ -13,6 +13,9 @@
 //
 // A column of the product depends on that column of B alone: a non-finite input cell reaches exactly the outputs whose 3x3
 // window covers it.  An output's sum order is fixed by the channel count and the position in its tile.
+//
+// The same stage with a stride of 1 or 2, Cin != Cout and a wave split between channels and rows (cvg_*, for csrc/dla.hip)
+// follows at the end of the file.
 #pragma once
 #include "roi_common.h"
 
@@ -136,6 +139,131 @@ __device__ __forceinline__ void cv_block(float* sm, const FT* __restrict__ in, i
                 }
         }
         if (c + 1 < nch) stash(sm + ((c + 1) & 1) * CV_BUF);     // the other buffer: its readers passed a barrier
+        __syncthreads();
+    }
+}
+
+// ---- the stage generalised (csrc/dla.hip): stride 1 or 2, Cin != Cout, the waves split between channel pairs and tile rows --
+// Nothing above is touched: fpn_layer_kernel instantiates cv_plan / cv_block as they were.
+//
+//   STRIDE 2: the haloed input tile of an 8 x 16 output tile is 17 x 33 cells and a row's B reads are two dwords apart: the
+//   16 lanes of one channel fall on 16 banks of ONE parity (ds_read_b32: 32 banks, conflicts within a 32-lane half).  The plane
+//   stride is the cell count itself, 561, which is ODD: the second channel of the half lands on the banks of the other
+//   parity, so a k-step's read is conflict-free with no padding at all (2 x 8 x 561 x 4 = 35,904 B of LDS).
+//   WR: the four waves are WP = 4 / WR channel pairs x WR groups of 8 / WR tile rows, so that a layer of 32 (64) output
+//   channels keeps four (two x two) waves busy instead of one (two); NM = 1: the pair's second M-tile does not exist
+//   (Cout = 16) and is not multiplied.
+template <int STRIDE>
+struct CvGeom {
+    static_assert(STRIDE == 1 || STRIDE == 2, "stride 1 or 2");
+    static constexpr int PW = CV_TW * STRIDE + 3 - STRIDE;       // 18 | 33
+    static constexpr int PH = CV_TH * STRIDE + 3 - STRIDE;       // 10 | 17
+    static constexpr int CELLS = PW * PH;                        // 180 | 561
+    static constexpr int PLANE = STRIDE == 1 ? CV_PLANE : CELLS;  // 208 = 16 (mod 32) | 561 = 1 (mod 2)
+    static constexpr int BUF = CV_IC * PLANE;
+    static constexpr int NLD = (CV_IC * CELLS + 255) / 256;      // 6 | 18
+    static constexpr int SMEM_FLOATS = 2 * BUF;
+};
+
+// cv_pack_index for filters W [Cout, Cin, 3, 3], Cin % 8 == 0, the pairs padded to 32 output channels: -1 is a zero
+__host__ __device__ inline long long cvg_pack_index(long long i, int Cin, int Cout) {
+    const int e = (int)(i & 3), lane = (int)((i >> 2) & 63);
+    long long r = i >> 8;
+    const int q = (int)(r % 9);
+    r /= 9;
+    const int nch = Cin / CV_IC;
+    const int c = (int)(r % nch), p = (int)(r / nch);
+    const int j = 4 * q + e, m = j / 18, ks = (j % 18) / 9, tap = j % 9;
+    const int oc = 32 * p + 16 * m + (lane & 15), ic = CV_IC * c + 4 * ks + (lane >> 4);
+    return oc < Cout ? ((long long)oc * Cin + ic) * 9 + tap : -1;
+}
+__host__ __device__ inline long long cvg_packed_floats(int Cin, int Cout) {
+    return (long long)((Cout + 31) / 32) * (Cin / CV_IC) * 9 * 256;
+}
+
+template <int STRIDE>
+struct CvgPlan {
+    int src[CvGeom<STRIDE>::NLD];                                // (the LDS offset follows from e: cvg_block's stash)
+};
+// (y0, x0): the OUTPUT tile's first position; H, W: the INPUT map
+template <int STRIDE>
+__device__ __forceinline__ void cvg_plan(CvgPlan<STRIDE>& pl, int tid, int y0, int x0, int H, int W) {
+    using G = CvGeom<STRIDE>;
+    const int HW = H * W;
+#pragma unroll
+    for (int j = 0; j < G::NLD; ++j) {
+        const int e = tid + 256 * j;
+        const int ic = e / G::CELLS, cell = e - ic * G::CELLS;
+        const int r = cell / G::PW, col = cell - r * G::PW;
+        const int gy = y0 * STRIDE - 1 + r, gx = x0 * STRIDE - 1 + col;
+        const bool live = e < CV_IC * G::CELLS;
+        pl.src[j] = (live && gy >= 0 && gy < H && gx >= 0 && gx < W) ? ic * HW + gy * W + gx : -1;
+    }
+}
+
+// cv_block over Cin input channels for the wave's tile rows [row0, row0 + 8 / WR): acc[m][nt] is tile row row0 + nt.
+template <typename FT, int STRIDE, int WR, int NM>
+__device__ __forceinline__ void cvg_block(float* sm, const FT* __restrict__ in, int HW, int Cin, const CvgPlan<STRIDE>& pl,
+                                          const float* __restrict__ packed, int pair, bool active, int tid, int row0,
+                                          cv_f32x4 (&acc)[NM][CV_TH / WR]) {
+    using G = CvGeom<STRIDE>;
+    constexpr int ROWS = CV_TH / WR;
+    const int lane = tid & 63, kq = lane >> 4, xl = lane & 15;
+    const int nch = Cin / CV_IC;
+    const int boff = kq * G::PLANE + row0 * STRIDE * G::PW + xl * STRIDE;
+    float pre[G::NLD];
+    auto fetch = [&](int chunk) {
+        const FT* __restrict__ base = in + (size_t)chunk * CV_IC * HW;
+#pragma unroll
+        for (int j = 0; j < G::NLD; ++j) pre[j] = pl.src[j] >= 0 ? feat_ld<FT>(base + pl.src[j]) : 0.0f;
+    };
+    auto stash = [&](float* buf) {
+#pragma unroll
+        for (int j = 0; j < G::NLD; ++j) {
+            if constexpr (G::PLANE == G::CELLS) {                // element e of the chunk lies at e: no table
+                if (tid + 256 * j < CV_IC * G::CELLS) buf[tid + 256 * j] = pre[j];
+            } else {
+                const int e = tid + 256 * j, ic = e / G::CELLS;  // (recomputed per chunk: the table would cost registers)
+                if (e < CV_IC * G::CELLS) buf[ic * G::PLANE + (e - ic * G::CELLS)] = pre[j];
+            }
+        }
+    };
+    const cv_f32x4* __restrict__ ap = reinterpret_cast<const cv_f32x4*>(packed) + (size_t)(active ? pair : 0) * nch * 9 * 64 + lane;
+#pragma unroll
+    for (int m = 0; m < NM; ++m)
+#pragma unroll
+        for (int nt = 0; nt < ROWS; ++nt) acc[m][nt] = (cv_f32x4){0.f, 0.f, 0.f, 0.f};
+    cv_f32x4 an[9], ac[9];
+    fetch(0);
+#pragma unroll
+    for (int q = 0; q < 9; ++q) an[q] = ap[q * 64];
+    stash(sm);
+    __syncthreads();
+    for (int c = 0; c < nch; ++c) {
+        const float* buf = sm + (c & 1) * G::BUF;
+#pragma unroll
+        for (int q = 0; q < 9; ++q) ac[q] = an[q];
+        if (c + 1 < nch) {
+            fetch(c + 1);
+#pragma unroll
+            for (int q = 0; q < 9; ++q) an[q] = ap[((size_t)(c + 1) * 9 + q) * 64];
+        }
+        if (active) {
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+                for (int tap = 0; tap < 9; ++tap) {
+                    const int j0 = ks * 9 + tap, j1 = 18 + ks * 9 + tap;
+                    const float a0 = ac[j0 >> 2][j0 & 3], a1 = ac[j1 >> 2][j1 & 3];
+#pragma unroll
+                    for (int nt = 0; nt < ROWS; ++nt) {
+                        const float b = buf[boff + ks * 4 * G::PLANE + (nt * STRIDE + tap / 3) * G::PW + (tap % 3)];
+                        acc[0][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b, acc[0][nt], 0, 0, 0);
+                        if constexpr (NM == 2) acc[1][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b, acc[1][nt], 0, 0, 0);
+                    }
+                }
+        }
+        if (c + 1 < nch) stash(sm + ((c + 1) & 1) * G::BUF);     // the other buffer: its readers passed a barrier
         __syncthreads();
     }
 }

@@ -1,0 +1,830 @@
+// DLA backbone body — [UPSTREAM] siammot/modelling/backbone/dla.py with DlaBasic blocks and maskrcnn_benchmark's
+// FrozenBatchNorm2d (DLA-34 and its family), inference: an image batch -> the four stage maps x2 .. x5.
+//
+//   x  = cbr7x7(image, 3 -> c0)              base_layer          cbr = conv (no bias) -> y * scale + shift -> ReLU
+//   x0 = cbr3x3(x, c0 -> c0)                 level0              cb  = the same without the ReLU
+//   x1 = cbr3x3(x0, c0 -> c1, stride 2)      level1
+//   xk = tree_k(x_{k-1}), stride 2           level2 .. level5    (include/smot_emm.h, DLA BACKBONE, states the trees)
+//
+// Every convolution runs on v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 accumulation); the weights are packed once
+// into the A operand's lane order with the frozen BN's scale and shift behind them; the epilogue is acc * scale + shift
+// (two roundings, as torch's x * scale + shift), + residual, ReLU (v < 0 ? 0 : v: a NaN stays), store.
+//
+// dla_conv3x3_kernel<FT, STRIDE, WR, NM>: conv3x3_mfma.h's generalised stage (cvg_block): workgroup = (image, 8 x 16 output
+//   tile, block of 32 * 4 / WR output channels), chunks of 8 input channels through two LDS buffers.  The four waves are
+//   4 / WR channel pairs x WR row groups: Cout <= 32 -> WR = 4 (all waves share the pair and split the rows); wider layers
+//   take the widest block that still gives every CU a workgroup (dl_conv3_pick): the coarse levels have few tiles.
+//   LDS 13,312 B (stride 1) / 35,904 B (stride 2: 17 x 33 cells per plane, plane stride 561, odd).
+// dla_conv1x1_kernel<OT>: fpn_lateral_kernel's scheme (64 positions x 32 output channels per workgroup, B operand read in
+//   place) over a VIRTUAL concatenation of up to four source maps, each read as it is or through a 2 x 2 max-pool of a map
+//   twice as fine (torch's max_pool2d: a NaN in the window is the result).  Serves every root and every project.  No LDS.
+// dla_conv7x7_kernel<FT>: base_layer.  K = 3 * 49 = 147 padded to 148 (37 k-steps; the pad reads a zero cell of LDS, so a
+//   non-finite image cell meets no 0 * inf); the 14 x 22 x 3 window of an 8 x 16 tile is staged once; wave w owns rows 2w, 2w + 1.
+//
+// The stem (base_layer, level0, level1) is three launches here (7x7, 3x3 WR = 4 NM = 1 | 2, 3x3 stride 2 WR = 4): the
+// c0-channel full-resolution maps go through the workspace.  DESIGN.md §7 states what that costs.
+//
+// An output's sum order is fixed by the channel counts and the position in its tile: it does not depend on the image's index
+// or the number of images.
+#include "conv3x3_mfma.h"
+
+namespace smot {
+
+constexpr int DL_POS = 64, DL_MT = 2;                // 1x1: positions and M-tiles per workgroup
+constexpr int DL_MAX_SRC = 4;
+constexpr int DL_MAX_CONVS = 64;
+constexpr int S7_PW = CV_TW + 6, S7_PH = CV_TH + 6, S7_PLANE = S7_PW * S7_PH;   // 22 x 14 = 308
+constexpr int S7_ZERO = 3 * S7_PLANE;                // a run of zeros behind the planes: the K pad's B operand
+constexpr int S7_SMEM = S7_ZERO + 160;
+constexpr int S7_KS = 37, S7_Q = 10;                 // k-steps; 16-byte A loads per lane and M-tile
+
+// ---- packed image of one convolution --------------------------------------------------------------------------------
+//   kind 3: cvg_pack_index image (pairs padded to 32 channels), scale [32 pairs], shift [32 pairs]
+//   kind 1: [M-tile][group of four k-steps][lane][e] -> W[16 m + lane % 16][16 g + 4 e + lane / 16], scale [Cout], shift [Cout]
+//   kind 7: [M-tile][q 0..9][lane][e] -> W[16 m + lane % 16][k = 4 (4 q + e) + lane / 16] (k < 147, else 0), scale, shift
+__host__ __device__ inline long long dl_conv_floats(int kind, int Cin, int Cout) {
+    if (kind == 3) return cvg_packed_floats(Cin, Cout) + 2LL * 32 * ((Cout + 31) / 32);
+    if (kind == 1) return (long long)Cout * Cin + 2LL * Cout;
+    return (long long)(Cout / 16) * S7_Q * 256 + 2LL * Cout;
+}
+
+__global__ void __launch_bounds__(256)
+dla_pack_kernel(int kind, const float* __restrict__ w, const float* __restrict__ scale, const float* __restrict__ shift,
+                int Cin, int Cout, long long total, float* __restrict__ packed) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const long long nw = total - (kind == 3 ? 2LL * 32 * ((Cout + 31) / 32) : 2LL * Cout);
+    float v = 0.0f;
+    if (i < nw) {
+        if (kind == 3) {
+            const long long s = cvg_pack_index(i, Cin, Cout);
+            v = s >= 0 ? w[s] : 0.0f;
+        } else if (kind == 1) {
+            const int e = (int)(i & 3), lane = (int)((i >> 2) & 63);
+            const long long t = i >> 8;
+            const int ng = Cin / 16;
+            const int g = (int)(t % ng), m = (int)(t / ng);
+            v = w[(size_t)(16 * m + (lane & 15)) * Cin + 16 * g + 4 * e + (lane >> 4)];
+        } else {
+            const int e = (int)(i & 3), lane = (int)((i >> 2) & 63);
+            const long long t = i >> 8;
+            const int q = (int)(t % S7_Q), m = (int)(t / S7_Q);
+            const int k = 4 * (4 * q + e) + (lane >> 4);
+            v = k < 147 ? w[(size_t)(16 * m + (lane & 15)) * 147 + k] : 0.0f;
+        }
+    } else {
+        const long long r = i - nw;
+        const int half = (int)((total - nw) / 2);
+        const int ch = (int)(r % half);
+        v = ch < Cout ? (r < half ? scale[ch] : shift[ch]) : 0.0f;
+    }
+    packed[i] = v;
+}
+
+// ---- 3x3 ----------------------------------------------------------------------------------------------------------------
+struct DlaConv3Args {
+    const void* in;          // [N, Cin, H, W]
+    const float* w;          // the convolution's packed image
+    const float* res;        // [N, Cout, Ho, Wo], or nullptr; res_w != 0: [N, Cout, res_h, res_w] read through a 2 x 2 max-pool
+    float* out;              // [N, Cout, Ho, Wo]
+    int Cin, Cout, H, W, Ho, Wo;
+    int tiles_x, tiles_per_image, relu, res_h, res_w;
+};
+
+// torch's max_pool2d: `if (v > m || isnan(v)) m = v` over the window in row-major order
+__device__ __forceinline__ float dl_pool_step(float m, float v) { return (v > m || v != v) ? v : m; }
+__device__ __forceinline__ float dl_pool(const float* __restrict__ q, int Ws) {
+    return dl_pool_step(dl_pool_step(dl_pool_step(q[0], q[1]), q[Ws]), q[Ws + 1]);
+}
+
+template <typename FT, int STRIDE, int WR, int NM>
+__global__ void __launch_bounds__(256, 2)
+dla_conv3x3_kernel(DlaConv3Args P) {
+    using G = CvGeom<STRIDE>;
+    constexpr int WP = 4 / WR, ROWS = CV_TH / WR;
+    __shared__ __attribute__((aligned(16))) float sm[G::SMEM_FLOATS];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int kq = lane >> 4, xl = lane & 15;
+    const int n = blockIdx.x / P.tiles_per_image;
+    const int t = blockIdx.x - n * P.tiles_per_image;
+    const int ty = t / P.tiles_x, tx = t - ty * P.tiles_x;
+    const int y0 = ty * CV_TH, x0 = tx * CV_TW;
+    const int HW = P.H * P.W, HWo = P.Ho * P.Wo, Cout = P.Cout;
+    const FT* __restrict__ in = reinterpret_cast<const FT*>(P.in) + (size_t)n * P.Cin * HW;
+    const int npairs = (Cout + 31) >> 5;
+    const float* __restrict__ scale = P.w + cvg_packed_floats(P.Cin, Cout);
+    const float* __restrict__ shift = scale + 32 * npairs;
+    const int HWr = P.res_w ? P.res_h * P.res_w : HWo;
+    const float* __restrict__ res = P.res ? P.res + (size_t)n * Cout * HWr : nullptr;
+    float* __restrict__ out = P.out + (size_t)n * Cout * HWo;
+    const int wp = WR == 1 ? wave : wave % WP, row0 = WR == 1 ? 0 : (wave / WP) * ROWS;
+
+    CvgPlan<STRIDE> pl;
+    cvg_plan<STRIDE>(pl, tid, y0, x0, P.H, P.W);
+    const int x = x0 + xl;
+    {
+        const int pair = blockIdx.y * WP + wp;                  // grid.y: the blocks of 32 WP output channels
+        const bool active = pair < npairs;
+        cv_f32x4 acc[NM][ROWS];
+        cvg_block<FT, STRIDE, WR, NM>(sm, in, HW, P.Cin, pl, P.w, pair, active, tid, row0, acc);
+        if (active && x < P.Wo) {
+#pragma unroll
+            for (int m = 0; m < NM; ++m)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int ch = 32 * pair + 16 * m + 4 * kq + r;
+                    if (ch >= Cout) continue;
+                    const float sc = scale[ch], sh = shift[ch];
+#pragma unroll
+                    for (int nt = 0; nt < ROWS; ++nt) {
+                        const int y = y0 + row0 + nt;
+                        if (y < P.Ho) {
+                            const int o = ch * HWo + y * P.Wo + x;
+                            float v = add_rn(mul_rn(acc[m][nt][r], sc), sh);
+                            if (res) v = add_rn(v, P.res_w ? dl_pool(res + ch * HWr + 2 * y * P.res_w + 2 * x, P.res_w) : res[o]);
+                            out[o] = P.relu ? relu_nan(v) : v;
+                        }
+                    }
+                }
+        }
+    }
+}
+
+// ---- 1x1 over a virtual concatenation ---------------------------------------------------------------------------------------
+struct DlaSrc {
+    const float* p;          // [N, C, Hs, Ws]
+    int C;                   // % 16 == 0
+    int pooled;              // 1: position (y, x) is the max of (2y .. 2y + 1, 2x .. 2x + 1) of a map with Hs / 2 == H, Ws / 2 == W
+    int Hs, Ws;
+};
+struct DlaConv1Args {
+    DlaSrc src[DL_MAX_SRC];
+    const float* a;          // the convolution's packed image
+    void* out;               // [N, Cout, H, W] of OT
+    float* out32;            // the same in fp32 as well, or nullptr
+    int nsrc, K, Cout, H, W, tiles_per_image, relu;
+};
+
+template <typename OT>
+__global__ void __launch_bounds__(256, 4)
+dla_conv1x1_kernel(DlaConv1Args P) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int kq = lane >> 4, xl = lane & 15;
+    const int Cout = P.Cout, HW = P.H * P.W;
+    const int n = blockIdx.x / P.tiles_per_image;
+    const int tile = blockIdx.x - n * P.tiles_per_image;
+    const int p = tile * DL_POS + wave * 16 + xl;
+    const bool live = p < HW;
+    const int y = live ? p / P.W : 0, x = live ? p - y * P.W : 0;
+    const int ng = P.K >> 4;
+    const float* __restrict__ scale = P.a + (size_t)Cout * P.K;
+    const float* __restrict__ shift = scale + Cout;
+    const int m0 = blockIdx.y * DL_MT;
+    const cv_f32x4* __restrict__ ap = reinterpret_cast<const cv_f32x4*>(P.a) + (size_t)m0 * ng * 64 + lane;
+    cv_f32x4 acc[DL_MT];
+#pragma unroll
+    for (int m = 0; m < DL_MT; ++m) acc[m] = (cv_f32x4){0.f, 0.f, 0.f, 0.f};
+    cv_f32x4 an[DL_MT], ac[DL_MT];
+    float bn[4], bc[4];
+    // one source after the other (the K order of the concatenation); within a source the next 16 channels' operands are in
+    // flight while the current ones multiply
+    int g0 = 0;
+    auto source = [&](const float* __restrict__ sp, int sC, int spool, int sHs, int sWs) {
+        const int sg = sC >> 4;
+        const int HWs = spool ? sHs * sWs : HW;
+        const float* __restrict__ bp = sp + ((size_t)n * sC + kq) * HWs + (spool ? (2 * y) * sWs + 2 * x : p);
+        auto fetch = [&](int gl) {
+#pragma unroll
+            for (int m = 0; m < DL_MT; ++m) an[m] = ap[((size_t)m * ng + g0 + gl) * 64];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float v = 0.0f;
+                if (live) {
+                    const float* __restrict__ q = bp + (size_t)(16 * gl + 4 * e) * HWs;
+                    v = spool ? dl_pool(q, sWs) : q[0];
+                }
+                bn[e] = v;
+            }
+        };
+        fetch(0);
+#pragma unroll 1
+        for (int gl = 0; gl < sg; ++gl) {
+#pragma unroll
+            for (int m = 0; m < DL_MT; ++m) ac[m] = an[m];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) bc[e] = bn[e];
+            if (gl + 1 < sg) fetch(gl + 1);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int m = 0; m < DL_MT; ++m)
+                    acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(ac[m][e], bc[e], acc[m], 0, 0, 0);
+        }
+        g0 += sg;
+    };
+    source(P.src[0].p, P.src[0].C, P.src[0].pooled, P.src[0].Hs, P.src[0].Ws);
+    if (P.nsrc > 1) source(P.src[1].p, P.src[1].C, P.src[1].pooled, P.src[1].Hs, P.src[1].Ws);
+    if (P.nsrc > 2) source(P.src[2].p, P.src[2].C, P.src[2].pooled, P.src[2].Hs, P.src[2].Ws);
+    if (P.nsrc > 3) source(P.src[3].p, P.src[3].C, P.src[3].pooled, P.src[3].Hs, P.src[3].Ws);
+    if (live) {
+        OT* __restrict__ oimg = reinterpret_cast<OT*>(P.out) + (size_t)n * Cout * HW;
+        float* __restrict__ o32 = P.out32 ? P.out32 + (size_t)n * Cout * HW : nullptr;
+#pragma unroll
+        for (int m = 0; m < DL_MT; ++m)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int ch = 16 * (m0 + m) + 4 * kq + r;
+                float v = add_rn(mul_rn(acc[m][r], scale[ch]), shift[ch]);
+                if (P.relu) v = relu_nan(v);
+                cv_store<OT>(oimg + (size_t)ch * HW + p, v);
+                if (o32) o32[(size_t)ch * HW + p] = v;
+            }
+    }
+}
+
+// ---- 7x7 (base_layer) -------------------------------------------------------------------------------------------------------
+struct DlaConv7Args {
+    const void* in;          // [N, 3, H, W] of FT
+    const float* a;          // the convolution's packed image
+    float* out;              // [N, C0, H, W]
+    int C0, H, W, tiles_x, tiles_per_image;
+};
+
+template <typename FT>
+__global__ void __launch_bounds__(256, 2)
+dla_conv7x7_kernel(DlaConv7Args P) {
+    __shared__ __attribute__((aligned(16))) float sm[S7_SMEM];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int kq = lane >> 4, xl = lane & 15;
+    const int n = blockIdx.x / P.tiles_per_image;
+    const int t = blockIdx.x - n * P.tiles_per_image;
+    const int ty = t / P.tiles_x, tx = t - ty * P.tiles_x;
+    const int y0 = ty * CV_TH, x0 = tx * CV_TW;
+    const int H = P.H, W = P.W, HW = H * W, C0 = P.C0;
+    const FT* __restrict__ in = reinterpret_cast<const FT*>(P.in) + (size_t)n * 3 * HW;
+    for (int e = tid; e < S7_SMEM; e += 256) {
+        float v = 0.0f;
+        if (e < S7_ZERO) {
+            const int ic = e / S7_PLANE, cell = e - ic * S7_PLANE;
+            const int r = cell / S7_PW, col = cell - r * S7_PW;
+            const int gy = y0 - 3 + r, gx = x0 - 3 + col;
+            if (gy >= 0 && gy < H && gx >= 0 && gx < W) v = feat_ld<FT>(in + ic * HW + gy * W + gx);
+        }
+        sm[e] = v;
+    }
+    __syncthreads();
+    const int mt = C0 >> 4;
+    const float* __restrict__ scale = P.a + (size_t)mt * S7_Q * 256;
+    const float* __restrict__ shift = scale + C0;
+    float* __restrict__ out = P.out + (size_t)n * C0 * HW;
+    const int x = x0 + xl;
+    // B operand of lane (kq, xl) at k-step ks: cell (ic, ky, kx) of k = 4 ks + kq, or the zero run for the K pad; it depends on
+    // the lane alone, so it is worked out once, in front of the M-tiles
+    int off[S7_KS];
+#pragma unroll
+    for (int ks = 0; ks < S7_KS; ++ks) {
+        const int k = 4 * ks + kq;
+        const int ic = k / 49, tap = k - ic * 49, ky = tap / 7, kx = tap - ky * 7;
+        off[ks] = (k < 147 ? ic * S7_PLANE + ky * S7_PW + kx + xl : S7_ZERO) + 2 * wave * S7_PW;
+    }
+    for (int m = 0; m < mt; ++m) {
+        const cv_f32x4* __restrict__ ap = reinterpret_cast<const cv_f32x4*>(P.a) + (size_t)m * S7_Q * 64 + lane;
+        cv_f32x4 a[S7_Q];
+#pragma unroll
+        for (int q = 0; q < S7_Q; ++q) a[q] = ap[q * 64];
+        cv_f32x4 acc[2] = {(cv_f32x4){0.f, 0.f, 0.f, 0.f}, (cv_f32x4){0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+        for (int ks = 0; ks < S7_KS; ++ks) {
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) {
+                const float b = sm[off[ks] + nt * S7_PW];
+                acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ks >> 2][ks & 3], b, acc[nt], 0, 0, 0);
+            }
+        }
+        if (x < W) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int ch = 16 * m + 4 * kq + r;
+                const float sc = scale[ch], sh = shift[ch];
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt) {
+                    const int y = y0 + 2 * wave + nt;
+                    if (y < H) out[ch * HW + y * W + x] = relu_nan(add_rn(mul_rn(acc[nt][r], sc), sh));
+                }
+            }
+        }
+    }
+}
+
+// ---- host: one launch each -------------------------------------------------------------------------------------------------
+static int dl_pack_launch(int kind, const float* w, const float* scale, const float* shift, int Cin, int Cout, float* packed,
+                          hipStream_t st) {
+    const long long total = dl_conv_floats(kind, Cin, Cout);
+    SMOT_LAUNCH(dla_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, kind, w, scale, shift, Cin, Cout, total,
+                packed);
+    return check_launch("dla_pack");
+}
+
+// The wave split of a launch: the fewest row groups (the widest channel block: the input is staged once per block) that
+// still give every CU a workgroup; a coarse level has few tiles and gets them from its channels instead.  The split does not
+// touch an output's sum order.  (Stride 2 with four pairs x eight rows does not fit 256 registers beside its 18 staged cells
+// per thread — hipcc spills two —: its widest block is 64 channels.)
+// DL_MIN_WORKGROUPS is the CU count of the part this library is built for (MI355X, gfx950: 256 CUs): below one workgroup
+// per CU a launch leaves CUs idle whatever the workgroups do.  It decides WHICH FORM a shape and image count run, so a
+// retune moves shapes between forms: tests/test_dla.py::test_conv3x3_forms pins, through smot_dla_conv3x3_form, that its
+// cases reach every form, and checks each against the oracle.
+constexpr int DL_MIN_WORKGROUPS = 256;
+// -> WR (1, 2 or 4) of a launch of `tiles` (8 x 16 output tiles of all images) with Cout output channels
+static int dl_conv3_wr(int stride, int Cout, long long tiles) {
+    const int npairs = (Cout + 31) >> 5;
+    int wr = stride == 2 ? 2 : 1;
+    while (wr < 4 && (4 / wr > npairs || tiles * ((npairs + 4 / wr - 1) / (4 / wr)) < DL_MIN_WORKGROUPS)) wr *= 2;
+    return wr;
+}
+template <typename FT, int STRIDE>
+static int dl_conv3_pick(const DlaConv3Args& P, int grid, hipStream_t st) {
+    const int npairs = (P.Cout + 31) >> 5;
+    const int wr = dl_conv3_wr(STRIDE, P.Cout, grid);
+    const dim3 g(grid, (npairs + 4 / wr - 1) / (4 / wr));
+    if (P.Cout <= 16) {
+        SMOT_LAUNCH((dla_conv3x3_kernel<FT, STRIDE, 4, 1>), g, dim3(256), 0, st, P);
+    } else if (wr == 4) {
+        SMOT_LAUNCH((dla_conv3x3_kernel<FT, STRIDE, 4, 2>), g, dim3(256), 0, st, P);
+    } else if (wr == 2) {
+        SMOT_LAUNCH((dla_conv3x3_kernel<FT, STRIDE, 2, 2>), g, dim3(256), 0, st, P);
+    } else {
+        if constexpr (STRIDE == 1) SMOT_LAUNCH((dla_conv3x3_kernel<FT, 1, 1, 2>), g, dim3(256), 0, st, P);
+    }
+    return check_launch("dla_conv3x3");
+}
+
+// in [N, Cin, H, W] fp32 -> out [N, Cout, Ho, Wo]; the shapes were checked by the caller (dl_conv3_ok)
+static int dl_conv3(const float* in, int N, int Cin, int H, int W, const float* w, int Cout, int stride, const float* res,
+                    int relu, float* out, hipStream_t st, int res_h = 0, int res_w = 0) {
+    DlaConv3Args P = {};
+    P.in = in;
+    P.w = w;
+    P.res = res;
+    P.out = out;
+    P.Cin = Cin;
+    P.Cout = Cout;
+    P.H = H;
+    P.W = W;
+    P.Ho = stride == 2 ? (H - 1) / 2 + 1 : H;
+    P.Wo = stride == 2 ? (W - 1) / 2 + 1 : W;
+    P.tiles_x = (P.Wo + CV_TW - 1) / CV_TW;
+    P.tiles_per_image = P.tiles_x * ((P.Ho + CV_TH - 1) / CV_TH);
+    P.relu = relu;
+    P.res_h = res_h;
+    P.res_w = res_w;
+    const int grid = P.tiles_per_image * N;
+    return stride == 2 ? dl_conv3_pick<float, 2>(P, grid, st) : dl_conv3_pick<float, 1>(P, grid, st);
+}
+
+template <typename OT>
+static int dl_conv1_launch(const DlaConv1Args& P, int grid, hipStream_t st) {
+    SMOT_LAUNCH(dla_conv1x1_kernel<OT>, dim3(grid, (P.Cout >> 4) / DL_MT), dim3(256), 0, st, P);
+    return check_launch("dla_conv1x1");
+}
+
+static int dl_conv1(const DlaSrc* src, int nsrc, int N, int H, int W, const float* a, int Cout, int relu, void* out,
+                    int out_type, float* out32, hipStream_t st) {
+    DlaConv1Args P = {};
+    int K = 0;
+    for (int s = 0; s < nsrc; ++s) {
+        P.src[s] = src[s];
+        K += src[s].C;
+    }
+    P.a = a;
+    P.out = out;
+    P.out32 = out32;
+    P.nsrc = nsrc;
+    P.K = K;
+    P.Cout = Cout;
+    P.H = H;
+    P.W = W;
+    P.tiles_per_image = (int)(((long long)H * W + DL_POS - 1) / DL_POS);
+    P.relu = relu;
+    const int grid = P.tiles_per_image * N;
+    if (out_type == SMOT_FEAT_F32) return dl_conv1_launch<float>(P, grid, st);
+    if (out_type == SMOT_FEAT_F16) return dl_conv1_launch<f16_t>(P, grid, st);
+    return dl_conv1_launch<bf16_t>(P, grid, st);
+}
+
+static int dl_conv7(const void* image, int in_type, int N, int H, int W, const float* a, int C0, float* out, hipStream_t st) {
+    DlaConv7Args P = {};
+    P.in = image;
+    P.a = a;
+    P.out = out;
+    P.C0 = C0;
+    P.H = H;
+    P.W = W;
+    P.tiles_x = (W + CV_TW - 1) / CV_TW;
+    P.tiles_per_image = P.tiles_x * ((H + CV_TH - 1) / CV_TH);
+    const dim3 grid(P.tiles_per_image * N);
+    if (in_type == SMOT_FEAT_F32) {
+        SMOT_LAUNCH(dla_conv7x7_kernel<float>, grid, dim3(256), 0, st, P);
+    } else if (in_type == SMOT_FEAT_F16) {
+        SMOT_LAUNCH(dla_conv7x7_kernel<f16_t>, grid, dim3(256), 0, st, P);
+    } else {
+        SMOT_LAUNCH(dla_conv7x7_kernel<bf16_t>, grid, dim3(256), 0, st, P);
+    }
+    return check_launch("dla_conv7x7");
+}
+
+// ---- host: the network ----------------------------------------------------------------------------------------------------
+struct DlaConv {
+    int kind, cin, cout;
+    long long off;           // first float in the packed image
+};
+struct DlaNet {
+    int n;
+    DlaConv conv[DL_MAX_CONVS];
+    long long total;
+};
+
+static void dl_add(DlaNet& net, int kind, int cin, int cout) {
+    DlaConv& c = net.conv[net.n++];
+    c.kind = kind;
+    c.cin = cin;
+    c.cout = cout;
+    c.off = net.total;
+    net.total += dl_conv_floats(kind, cin, cout);
+}
+// a levels = 1 tree, in the order its launches run: project, tree1.conv1, tree1.conv2, tree2.conv1, tree2.conv2, root
+static void dl_add_tree1(DlaNet& net, int cin, int cout, int root_extra) {
+    if (cin != cout) dl_add(net, 1, cin, cout);
+    dl_add(net, 3, cin, cout);
+    dl_add(net, 3, cout, cout);
+    dl_add(net, 3, cout, cout);
+    dl_add(net, 3, cout, cout);
+    dl_add(net, 1, 2 * cout + root_extra, cout);
+}
+
+// The convolutions of the network in launch order.  SMOT_ERR_BAD_ARG for null arrays, SMOT_ERR_UNSUPPORTED beyond the capacities.
+static int dla_net(const int* levels, const int* ch, DlaNet& net, const char* who) {
+    if (!levels || !ch) {
+        set_error("%s: null pointer", who);
+        return SMOT_ERR_BAD_ARG;
+    }
+    bool ok = levels[0] == 1 && levels[1] == 1 && (ch[0] == 16 || ch[0] == 32) && ch[1] >= 32 && ch[1] % 32 == 0 && ch[1] <= 1024;
+    for (int k = 2; k < 6; ++k)
+        ok = ok && (levels[k] == 1 || levels[k] == 2) && ch[k] >= 32 && ch[k] % 32 == 0 && ch[k] <= 1024;
+    if (!ok) {
+        set_error("%s: levels (%d,%d,%d,%d,%d,%d), channels (%d,%d,%d,%d,%d,%d) (supported: levels[0] = levels[1] = 1, levels[2..5] "
+                  "in {1, 2}; channels[0] in {16, 32}, the others multiples of 32 up to 1024)",
+                  who, levels[0], levels[1], levels[2], levels[3], levels[4], levels[5], ch[0], ch[1], ch[2], ch[3], ch[4], ch[5]);
+        return SMOT_ERR_UNSUPPORTED;
+    }
+    net.n = 0;
+    net.total = 0;
+    dl_add(net, 7, 3, ch[0]);
+    dl_add(net, 3, ch[0], ch[0]);
+    dl_add(net, 3, ch[0], ch[1]);
+    for (int k = 2; k < 6; ++k) {
+        const int cin = ch[k - 1], cout = ch[k], root = k > 2 ? cin : 0;      // level_root: level3 .. level5
+        if (levels[k] == 1) {
+            dl_add_tree1(net, cin, cout, root);
+        } else {
+            dl_add_tree1(net, cin, cout, 0);
+            dl_add_tree1(net, cout, cout, root + cout);
+        }
+    }
+    return SMOT_OK;
+}
+
+static int dla_size_ok(int N, int H, int W, const char* who) {
+    if (N < 1 || N > SMOT_MAX_IMAGES) {
+        set_error("%s: num_images = %d (1 .. %d)", who, N, SMOT_MAX_IMAGES);
+        return SMOT_ERR_BAD_ARG;
+    }
+    if (H < 32 || W < 32 || H % 32 != 0 || W % 32 != 0) {
+        set_error("%s: image %d x %d (supported: both sides positive multiples of 32, as upstream)", who, H, W);
+        return SMOT_ERR_UNSUPPORTED;
+    }
+    return SMOT_OK;
+}
+
+// The walk over the network: `dry` counts the workspace and launches nothing.
+struct DlaCtx {
+    const DlaNet* net;
+    int ci;                  // the next convolution
+    const float* packed;
+    float* ws;
+    long long bump, peak;    // floats
+    bool dry;
+    int N, rc;
+    hipStream_t st;
+};
+static float* dl_alloc(DlaCtx& c, long long floats) {
+    float* p = c.dry ? nullptr : c.ws + c.bump;
+    c.bump += (floats + 3) & ~3LL;
+    if (c.bump > c.peak) c.peak = c.bump;
+    return p;
+}
+static const float* dl_next(DlaCtx& c, int kind, int cin, int cout) {
+    const DlaConv& v = c.net->conv[c.ci++];
+    if (v.kind != kind || v.cin != cin || v.cout != cout) c.rc = SMOT_ERR_BAD_ARG;      // (the two walks disagree: a bug)
+    return c.dry ? nullptr : c.packed + v.off;
+}
+static void dl_run3(DlaCtx& c, const float* in, int Cin, int H, int W, int Cout, int stride, const float* res, float* out,
+                    int res_h = 0, int res_w = 0) {
+    const float* w = dl_next(c, 3, Cin, Cout);
+    if (!c.dry && !c.rc) c.rc = dl_conv3(in, c.N, Cin, H, W, w, Cout, stride, res, 1, out, c.st, res_h, res_w);
+}
+static void dl_run1(DlaCtx& c, const DlaSrc* src, int nsrc, int H, int W, int Cout, int relu, void* out, int out_type, float* out32) {
+    int K = 0;
+    for (int s = 0; s < nsrc; ++s) K += src[s].C;
+    const float* a = dl_next(c, 1, K, Cout);
+    if (!c.dry && !c.rc) c.rc = dl_conv1(src, nsrc, c.N, H, W, a, Cout, relu, out, out_type, out32, c.st);
+}
+
+// A levels = 1 tree on x [N, cin, H, W] -> [N, cout, Ho, Wo] at `out` (of out_type; fp32 at out32 as well if non-null), or in
+// the workspace if `out` is null.  extra: what the parent handed down, concatenated behind (x2, x1, [bottom]).  -> the fp32 map.
+static const float* dl_tree1(DlaCtx& c, const float* x, int cin, int H, int W, int cout, int stride, bool level_root,
+                             const DlaSrc* extra, int nextra, void* out, int out_type, float* out32) {
+    const int Ho = H / stride, Wo = W / stride;
+    const long long on = (long long)c.N * cout * Ho * Wo;
+    const DlaSrc bottom = {x, cin, stride == 2 ? 1 : 0, H, W};
+    const float* residual = x;
+    if (cin != cout) {
+        float* r = dl_alloc(c, on);
+        dl_run1(c, &bottom, 1, Ho, Wo, cout, 0, r, SMOT_FEAT_F32, nullptr);
+        residual = r;
+    }
+    float* t1 = dl_alloc(c, on);
+    float* x1 = dl_alloc(c, on);
+    float* t2 = dl_alloc(c, on);
+    float* x2 = dl_alloc(c, on);
+    dl_run3(c, x, cin, H, W, cout, stride, nullptr, t1);
+    // (cin == cout at stride 2: the residual is the pooled input itself, read through the pool)
+    const bool rpool = cin == cout && stride == 2;
+    dl_run3(c, t1, cout, Ho, Wo, cout, 1, residual, x1, rpool ? H : 0, rpool ? W : 0);
+    dl_run3(c, x1, cout, Ho, Wo, cout, 1, nullptr, t2);
+    dl_run3(c, t2, cout, Ho, Wo, cout, 1, x1, x2);
+    DlaSrc src[DL_MAX_SRC] = {{x2, cout, 0, Ho, Wo}, {x1, cout, 0, Ho, Wo}};
+    int ns = 2;
+    if (level_root) src[ns++] = bottom;
+    for (int e = 0; e < nextra; ++e) src[ns++] = extra[e];
+    const float* result;
+    if (out) {
+        dl_run1(c, src, ns, Ho, Wo, cout, 1, out, out_type, out32);
+        result = out_type == SMOT_FEAT_F32 ? (const float*)out : out32;
+    } else {
+        float* o = dl_alloc(c, on);
+        dl_run1(c, src, ns, Ho, Wo, cout, 1, o, SMOT_FEAT_F32, nullptr);
+        result = o;
+    }
+    return result;
+}
+
+// image -> x1 [N, c1, H / 2, W / 2] at `x1` (fp32); the two c0-channel maps in the workspace
+static void dl_stem(DlaCtx& c, const void* image, int in_type, int H, int W, int c0, int c1, float* x1) {
+    const long long n0 = (long long)c.N * c0 * H * W;
+    float* x = dl_alloc(c, n0);
+    float* x0 = dl_alloc(c, n0);
+    const float* a = dl_next(c, 7, 3, c0);
+    if (!c.dry && !c.rc) c.rc = dl_conv7(image, in_type, c.N, H, W, a, c0, x, c.st);
+    dl_run3(c, x, c0, H, W, c0, 1, nullptr, x0);
+    dl_run3(c, x0, c0, H, W, c1, 2, nullptr, x1);
+}
+
+static void dl_walk(DlaCtx& c, const void* image, int in_type, int H, int W, const int* levels, const int* ch, void* const* out,
+                    int out_type) {
+    float* x1 = dl_alloc(c, (long long)c.N * ch[1] * (H / 2) * (W / 2));
+    long long mark = c.bump;
+    dl_stem(c, image, in_type, H, W, ch[0], ch[1], x1);
+    const float* x = x1;
+    int h = H / 2, w = W / 2;
+    for (int k = 2; k < 6; ++k) {
+        c.bump = mark;
+        const int cin = ch[k - 1], cout = ch[k], ho = h / 2, wo = w / 2;
+        const bool root = k > 2;
+        // a half output map that the next level reads: its fp32 twin lives below the mark until that level is done
+        float* out32 = (out_type != SMOT_FEAT_F32 && k < 5) ? dl_alloc(c, (long long)c.N * cout * ho * wo) : nullptr;
+        const long long next_mark = c.bump;
+        void* o = c.dry ? (void*)&c : out[k - 2];              // (dry: only "is there an output" is read)
+        if (levels[k] == 1) {
+            x = dl_tree1(c, x, cin, h, w, cout, 2, root, nullptr, 0, o, out_type, out32);
+        } else {
+            DlaSrc children[2];
+            int nc = 0;
+            if (root) children[nc++] = DlaSrc{x, cin, 1, h, w};
+            const float* t = dl_tree1(c, x, cin, h, w, cout, 2, false, nullptr, 0, nullptr, 0, nullptr);
+            children[nc++] = DlaSrc{t, cout, 0, ho, wo};
+            x = dl_tree1(c, t, cout, ho, wo, cout, 1, false, children, nc, o, out_type, out32);
+        }
+        mark = next_mark;
+        h = ho;
+        w = wo;
+    }
+}
+
+static int dl_f32_ptr(const void* p) { return p && ((uintptr_t)p & 3) == 0; }
+
+}  // namespace smot
+
+using namespace smot;
+
+extern "C" long long smot_dla_packed_floats(const int* levels, const int* channels) {
+    DlaNet net;
+    if (dla_net(levels, channels, net, "dla_packed_floats")) return -1;
+    return net.total;
+}
+
+extern "C" int smot_dla_pack(const int* levels, const int* channels, const float* const* w, const float* const* scale,
+                             const float* const* shift, int num_convs, float* packed, smot_stream_t stream) {
+    DlaNet net;
+    const int rn = dla_net(levels, channels, net, "dla_pack");
+    if (rn) return rn;
+    SMOT_REQUIRE(w && scale && shift && packed, "dla_pack: null pointer");
+    SMOT_REQUIRE(num_convs == net.n, "dla_pack: %d convolutions passed, the network has %d in launch order", num_convs, net.n);
+    SMOT_REQUIRE(((uintptr_t)packed & 15) == 0, "dla_pack: packed must be 16-byte aligned");
+    for (int i = 0; i < net.n; ++i)
+        SMOT_REQUIRE(dl_f32_ptr(w[i]) && dl_f32_ptr(scale[i]) && dl_f32_ptr(shift[i]),
+                     "dla_pack: a tensor of convolution %d is null or not 4-byte aligned", i);
+    for (int i = 0; i < net.n; ++i) {
+        const DlaConv& c = net.conv[i];
+        const int rc = dl_pack_launch(c.kind, w[i], scale[i], shift[i], c.cin, c.cout, packed + c.off, (hipStream_t)stream);
+        if (rc) return rc;
+    }
+    return SMOT_OK;
+}
+
+extern "C" long long smot_dla_ws_bytes(const int* levels, const int* channels, int num_images, int H, int W) {
+    DlaNet net;
+    if (dla_net(levels, channels, net, "dla_ws_bytes") || dla_size_ok(num_images, H, W, "dla_ws_bytes")) return -1;
+    DlaCtx c = {};
+    c.net = &net;
+    c.dry = true;
+    c.N = num_images;
+    // (the half form: it holds the fp32 twins of the returned maps as well, an upper bound of the fp32 form)
+    dl_walk(c, nullptr, SMOT_FEAT_F32, H, W, levels, channels, nullptr, SMOT_FEAT_F16);
+    return c.rc ? -1 : c.peak * (long long)sizeof(float);
+}
+
+extern "C" int smot_dla_fwd(const void* image, int in_type, int num_images, int H, int W, const int* levels, const int* channels,
+                            const float* packed, float* ws, void* const* out, int out_type, smot_stream_t stream) {
+    SMOT_REQUIRE(in_type == SMOT_FEAT_F32 || in_type == SMOT_FEAT_F16 || in_type == SMOT_FEAT_BF16,
+                 "dla: in_type = %d (SMOT_FEAT_F32, _F16 or _BF16, NCHW)", in_type);
+    SMOT_REQUIRE(out_type == SMOT_FEAT_F32 || out_type == SMOT_FEAT_F16 || out_type == SMOT_FEAT_BF16,
+                 "dla: out_type = %d (SMOT_FEAT_F32, _F16 or _BF16)", out_type);
+    DlaNet net;
+    const int rn = dla_net(levels, channels, net, "dla");
+    if (rn == SMOT_ERR_BAD_ARG) return rn;
+    SMOT_REQUIRE(num_images >= 1 && num_images <= SMOT_MAX_IMAGES, "dla: num_images = %d (1 .. %d)", num_images, SMOT_MAX_IMAGES);
+    SMOT_REQUIRE(image && packed && ws && out, "dla: null pointer");
+    SMOT_REQUIRE(((uintptr_t)image & (in_type == SMOT_FEAT_F32 ? 3 : 1)) == 0, "dla: the image is misaligned");
+    SMOT_REQUIRE((((uintptr_t)packed | (uintptr_t)ws) & 15) == 0, "dla: packed and ws must be 16-byte aligned");
+    for (int k = 0; k < 4; ++k)
+        SMOT_REQUIRE(out[k] && ((uintptr_t)out[k] & (out_type == SMOT_FEAT_F32 ? 3 : 1)) == 0, "dla: output %d is null or misaligned", k);
+    if (rn) return rn;
+    const int rs = dla_size_ok(num_images, H, W, "dla");
+    if (rs) return rs;
+    long long widest = (long long)H * W * channels[0];         // the largest map of one image, in elements
+    for (int k = 1; k < 6; ++k) {
+        const long long m = (long long)(H >> k) * (W >> k) * channels[k];
+        if (m > widest) widest = m;
+    }
+    if (widest >= (1LL << 31) || (long long)H * W / 128 * num_images >= (1LL << 31)) {
+        set_error("dla: %d images of %d x %d are beyond the kernels' 32-bit offsets", num_images, H, W);
+        return SMOT_ERR_UNSUPPORTED;
+    }
+    DlaCtx c = {};
+    c.net = &net;
+    c.packed = packed;
+    c.ws = ws;
+    c.N = num_images;
+    c.st = (hipStream_t)stream;
+    dl_walk(c, image, in_type, H, W, levels, channels, out, out_type);
+    return c.rc;
+}
+
+// ---- the three operators alone -------------------------------------------------------------------------------------------------
+extern "C" int smot_dla_conv3x3_fwd(const float* x, int num_images, int Cin, int H, int W, const float* w, const float* scale,
+                                    const float* shift, int Cout, int stride, const float* residual, int residual_h,
+                                    int residual_w, int relu, float* packed, float* out, smot_stream_t stream) {
+    SMOT_REQUIRE(dl_f32_ptr(x) && dl_f32_ptr(w) && dl_f32_ptr(scale) && dl_f32_ptr(shift) && dl_f32_ptr(out) &&
+                     (!residual || dl_f32_ptr(residual)),
+                 "dla_conv3x3: a null or misaligned pointer");
+    SMOT_REQUIRE(packed && ((uintptr_t)packed & 15) == 0, "dla_conv3x3: packed must be 16-byte aligned");
+    SMOT_REQUIRE(num_images >= 1 && num_images <= SMOT_MAX_IMAGES && H >= 1 && W >= 1 && (stride == 1 || stride == 2),
+                 "dla_conv3x3: %d images of %d x %d, stride %d", num_images, H, W, stride);
+    const int Ho = stride == 2 ? (H - 1) / 2 + 1 : H, Wo = stride == 2 ? (W - 1) / 2 + 1 : W;
+    const bool rpool = residual && (residual_h != 0 || residual_w != 0);
+    SMOT_REQUIRE(!rpool || (residual_h / 2 == Ho && residual_w / 2 == Wo),
+                 "dla_conv3x3: a pooled residual of %d x %d for an output of %d x %d", residual_h, residual_w, Ho, Wo);
+    if (Cin < 8 || Cin % 8 != 0 || Cin > 1024 || Cout < 16 || Cout % 16 != 0 || (Cout > 16 && Cout % 32 != 0) || Cout > 1024) {
+        set_error("dla_conv3x3: Cin = %d, Cout = %d (supported: Cin a multiple of 8, Cout 16 or a multiple of 32, up to 1024)", Cin, Cout);
+        return SMOT_ERR_UNSUPPORTED;
+    }
+    if ((long long)H * W * (Cin > Cout ? Cin : Cout) >= (1LL << 31) || (long long)H * W / 128 * num_images >= (1LL << 31) ||
+        (rpool && (long long)residual_h * residual_w * Cout >= (1LL << 31))) {
+        set_error("dla_conv3x3: %d images of %d x %d are beyond the kernel's 32-bit offsets", num_images, H, W);
+        return SMOT_ERR_UNSUPPORTED;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int rp = dl_pack_launch(3, w, scale, shift, Cin, Cout, packed, st);
+    if (rp) return rp;
+    return dl_conv3(x, num_images, Cin, H, W, packed, Cout, stride, residual, relu ? 1 : 0, out, st, rpool ? residual_h : 0,
+                    rpool ? residual_w : 0);
+}
+
+extern "C" int smot_dla_conv3x3_form(int num_images, int H, int W, int Cout, int stride) {
+    if (num_images < 1 || H < 1 || W < 1 || Cout < 16 || (stride != 1 && stride != 2)) return -1;
+    const int Ho = stride == 2 ? (H - 1) / 2 + 1 : H, Wo = stride == 2 ? (W - 1) / 2 + 1 : W;
+    const long long tiles = (long long)((Wo + CV_TW - 1) / CV_TW) * ((Ho + CV_TH - 1) / CV_TH) * num_images;
+    return 10 * dl_conv3_wr(stride, Cout, tiles) + (Cout <= 16 ? 1 : 2);
+}
+
+extern "C" long long smot_dla_conv_packed_floats(int kernel_size, int Cin, int Cout) {
+    if ((kernel_size != 1 && kernel_size != 3 && kernel_size != 7) || Cin < 1 || Cout < 16 || Cout % 16 != 0) return -1;
+    if (kernel_size == 3 && Cin % 8 != 0) return -1;
+    if (kernel_size == 1 && Cin % 16 != 0) return -1;
+    return dl_conv_floats(kernel_size, Cin, Cout);
+}
+
+extern "C" int smot_dla_conv1x1_fwd(const float* const* sources, const int* source_channels, const int* source_pooled,
+                                    const int* source_heights, const int* source_widths, int num_sources, int num_images, int H,
+                                    int W, const float* w, const float* scale, const float* shift, int Cout, int relu,
+                                    float* packed, void* out, int out_type, smot_stream_t stream) {
+    SMOT_REQUIRE(out_type == SMOT_FEAT_F32 || out_type == SMOT_FEAT_F16 || out_type == SMOT_FEAT_BF16,
+                 "dla_conv1x1: out_type = %d (SMOT_FEAT_F32, _F16 or _BF16)", out_type);
+    SMOT_REQUIRE(num_sources >= 1 && num_sources <= DL_MAX_SRC, "dla_conv1x1: %d sources (1 .. %d)", num_sources, DL_MAX_SRC);
+    SMOT_REQUIRE(sources && source_channels && source_pooled && source_heights && source_widths, "dla_conv1x1: null pointer");
+    SMOT_REQUIRE(dl_f32_ptr(w) && dl_f32_ptr(scale) && dl_f32_ptr(shift), "dla_conv1x1: a null or misaligned pointer");
+    SMOT_REQUIRE(out && ((uintptr_t)out & (out_type == SMOT_FEAT_F32 ? 3 : 1)) == 0, "dla_conv1x1: the output is null or misaligned");
+    SMOT_REQUIRE(packed && ((uintptr_t)packed & 15) == 0, "dla_conv1x1: packed must be 16-byte aligned");
+    SMOT_REQUIRE(num_images >= 1 && num_images <= SMOT_MAX_IMAGES && H >= 1 && W >= 1, "dla_conv1x1: %d images of %d x %d",
+                 num_images, H, W);
+    DlaSrc src[DL_MAX_SRC];
+    long long K = 0;
+    bool ok = Cout >= 32 && Cout % 32 == 0 && Cout <= 1024;
+    for (int s = 0; s < num_sources; ++s) {
+        SMOT_REQUIRE(dl_f32_ptr(sources[s]), "dla_conv1x1: source %d is null or misaligned", s);
+        const int pooled = source_pooled[s] ? 1 : 0, hs = source_heights[s], wsrc = source_widths[s];
+        SMOT_REQUIRE(pooled ? (hs / 2 == H && wsrc / 2 == W) : (hs == H && wsrc == W),
+                     "dla_conv1x1: source %d is %d x %d for an output of %d x %d (pooled: %d)", s, hs, wsrc, H, W, pooled);
+        src[s] = DlaSrc{sources[s], source_channels[s], pooled, hs, wsrc};
+        ok = ok && source_channels[s] >= 16 && source_channels[s] % 16 == 0 && source_channels[s] <= 1024;
+        K += source_channels[s] > 0 ? source_channels[s] : 0;
+        if ((long long)hs * wsrc * (source_channels[s] > 0 ? source_channels[s] : 1) >= (1LL << 31)) ok = false;
+    }
+    if (!ok || (long long)H * W * Cout >= (1LL << 31) || (long long)H * W / 64 * num_images >= (1LL << 31)) {
+        set_error("dla_conv1x1: Cout = %d over %lld concatenated channels (supported: Cout a multiple of 32 up to 1024, every source a "
+                  "multiple of 16 channels up to 1024, maps within 32-bit offsets)", Cout, K);
+        return SMOT_ERR_UNSUPPORTED;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int rp = dl_pack_launch(1, w, scale, shift, (int)K, Cout, packed, st);
+    if (rp) return rp;
+    return dl_conv1(src, num_sources, num_images, H, W, packed, Cout, relu ? 1 : 0, out, out_type, nullptr, st);
+}
+
+extern "C" long long smot_dla_stem_ws_bytes(int num_images, int H, int W, int c0, int c1) {
+    if (num_images < 1 || num_images > SMOT_MAX_IMAGES || H < 1 || W < 1 || c0 < 1 || c1 < 1) return -1;
+    const long long n0 = ((long long)num_images * c0 * H * W + 3) & ~3LL;
+    const long long packed = dl_conv_floats(7, 3, c0) + dl_conv_floats(3, c0, c0) + dl_conv_floats(3, c0, c1);
+    return (2 * n0 + packed) * (long long)sizeof(float);
+}
+
+extern "C" int smot_dla_stem_fwd(const void* image, int in_type, int num_images, int H, int W, int c0, int c1,
+                                 const float* const* w, const float* const* scale, const float* const* shift, float* ws,
+                                 float* out, smot_stream_t stream) {
+    SMOT_REQUIRE(in_type == SMOT_FEAT_F32 || in_type == SMOT_FEAT_F16 || in_type == SMOT_FEAT_BF16,
+                 "dla_stem: in_type = %d (SMOT_FEAT_F32, _F16 or _BF16, NCHW)", in_type);
+    SMOT_REQUIRE(image && ((uintptr_t)image & (in_type == SMOT_FEAT_F32 ? 3 : 1)) == 0, "dla_stem: the image is null or misaligned");
+    SMOT_REQUIRE(w && scale && shift && dl_f32_ptr(out), "dla_stem: a null or misaligned pointer");
+    SMOT_REQUIRE(ws && ((uintptr_t)ws & 15) == 0, "dla_stem: ws must be 16-byte aligned");
+    for (int i = 0; i < 3; ++i)
+        SMOT_REQUIRE(dl_f32_ptr(w[i]) && dl_f32_ptr(scale[i]) && dl_f32_ptr(shift[i]),
+                     "dla_stem: a tensor of layer %d is null or not 4-byte aligned", i);
+    SMOT_REQUIRE(num_images >= 1 && num_images <= SMOT_MAX_IMAGES, "dla_stem: num_images = %d (1 .. %d)", num_images, SMOT_MAX_IMAGES);
+    if (!(c0 == 16 || c0 == 32) || c1 < 32 || c1 % 32 != 0 || c1 > 1024 || H < 2 || W < 2 || H % 2 != 0 || W % 2 != 0 ||
+        (long long)H * W * (c0 > c1 / 4 ? c0 : c1 / 4) >= (1LL << 31) || (long long)H * W / 128 * num_images >= (1LL << 31)) {
+        set_error("dla_stem: c0 = %d, c1 = %d, image %d x %d (supported: c0 in {16, 32}, c1 a multiple of 32 up to 1024, even sides "
+                  "within 32-bit offsets)", c0, c1, H, W);
+        return SMOT_ERR_UNSUPPORTED;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int kinds[3] = {7, 3, 3}, cins[3] = {3, c0, c0}, couts[3] = {c0, c0, c1};
+    DlaNet net = {};
+    for (int i = 0; i < 3; ++i) dl_add(net, kinds[i], cins[i], couts[i]);
+    const long long n0 = ((long long)num_images * c0 * H * W + 3) & ~3LL;
+    float* packed = ws + 2 * n0;
+    for (int i = 0; i < 3; ++i) {
+        const int rc = dl_pack_launch(kinds[i], w[i], scale[i], shift[i], cins[i], couts[i], packed + net.conv[i].off, st);
+        if (rc) return rc;
+    }
+    DlaCtx c = {};
+    c.net = &net;
+    c.packed = packed;
+    c.ws = ws;
+    c.N = num_images;
+    c.st = st;
+    dl_stem(c, image, in_type, H, W, c0, c1, out);
+    return c.rc;
+}

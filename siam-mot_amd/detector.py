@@ -16,11 +16,15 @@ map sizes have been seen) and then ``forward`` — still the one copy.
 
 ``forward_stages(stages, image_size)`` starts at the backbone's stage maps: the pyramid (``fpn.FPN``: L + 1 launches, no
 synchronisation) and then ``forward_features``; the FPN maps are handed back with the detections for the tracker.
+
+``forward_images(images, image_size)`` starts at the pre-processed frames: the backbone body (``dla.DLA``: 37 launches for
+DLA-34, no synchronisation) and then ``forward_stages`` — frames to detections on this package's kernels, still the one copy.
 """
 import torch
 
 from . import ops
 from .box_refine import TrackBoxHead
+from .backbone import build_backbone
 from .fpn import build_fpn
 from .rpn import RPNHead, make_anchor_generator, make_rpn_postprocessor
 
@@ -29,15 +33,20 @@ class DetectionHead(torch.nn.Module):
     """``forward(anchors, objectness, box_regression, features) -> [BoxList]`` per image (fields ``scores``, ``ids`` = -1,
     ``labels``): ``rpn_post`` is an ``rpn.RPNPostProcessor``, ``box_head`` a ``TrackBoxHead``.  With an ``rpn.RPNHead`` and an
     ``rpn.AnchorGenerator`` as well: ``forward_features(features, image_size)``, the same from the FPN maps; with an
-    ``fpn.FPN`` too: ``forward_stages(stages, image_size)``, the same from the backbone's stage maps."""
+    ``fpn.FPN`` too: ``forward_stages(stages, image_size)``, the same from the backbone's stage maps; with a ``backbone``
+    (``backbone.build_backbone``: ``body`` and ``fpn``) instead of the ``fpn``: ``forward_images(images, image_size)``."""
 
-    def __init__(self, rpn_post, box_head, rpn_head=None, anchor_generator=None, fpn=None):
+    def __init__(self, rpn_post, box_head, rpn_head=None, anchor_generator=None, fpn=None, backbone=None):
         super(DetectionHead, self).__init__()
         self.rpn_post = rpn_post
         self.box_head = box_head
         self.rpn_head = rpn_head
         self.anchor_generator = anchor_generator
         self.fpn = fpn
+        self.backbone = backbone
+
+    def _pyramid(self):
+        return self.fpn if self.fpn is not None else getattr(self.backbone, "fpn", None)
 
     def raw_ok(self, anchors, objectness):
         """Both halves take their device paths for this call."""
@@ -91,27 +100,44 @@ class DetectionHead(torch.nn.Module):
     def forward_stages(self, stages, image_size):
         """Backbone stage maps ``stages[l]`` = ``[N, Cin_l, H_l, W_l]`` of N images of one size -> ``(features, detections)``:
         ``features = fpn(stages)`` and ``forward_features(features, image_size)``, bit for bit."""
-        if self.fpn is None:
+        fpn = self._pyramid()
+        if fpn is None:
             raise RuntimeError("siammot_amd.detector.DetectionHead: forward_stages needs an FPN "
                                "(build_detection_head(..., fpn=True))")
         if self.training:
             raise NotImplementedError("siammot_amd.detector.DetectionHead is an inference path")
-        features = self.fpn(stages)
+        features = fpn(stages)
         return features, self.forward_features(features, image_size)
 
+    @torch.no_grad()
+    def forward_images(self, images, image_size):
+        """Pre-processed frames ``images`` = ``[N, 3, H, W]`` (``FramePreprocessor.batch``; H and W multiples of 32) of N
+        images of one size -> ``(features, detections)``: ``forward_stages(backbone.body(images), image_size)``, bit for bit."""
+        if self.backbone is None:
+            raise RuntimeError("siammot_amd.detector.DetectionHead: forward_images needs a backbone "
+                               "(build_detection_head(..., backbone=True))")
+        if self.training:
+            raise NotImplementedError("siammot_amd.detector.DetectionHead is an inference path")
+        return self.forward_stages(self.backbone.body(images), image_size)
 
-def build_detection_head(cfg, rpn_box_coder, in_channels, box_head=None, rpn_head=True, fpn=False):
+
+def build_detection_head(cfg, rpn_box_coder, in_channels, box_head=None, rpn_head=True, fpn=False, backbone=False):
     """``DetectionHead`` from a config: the reference's RPN factory keys (``MODEL.RPN.*_TEST``) and the given box head or a
     fresh ``TrackBoxHead``.  ``rpn_head``: True for a fresh ``rpn.RPNHead`` and the config's anchor generator
     (``MODEL.RPN.ANCHOR_*``, ``ASPECT_RATIOS``), an ``RPNHead`` to use that one, False / None for a head that starts at the
     anchors (``forward`` only).  ``fpn``: True for the config's pyramid (``fpn.build_fpn``), an ``fpn.FPN`` to use that one,
-    False / None for a head that starts at the FPN maps."""
+    False / None for a head that starts at the FPN maps.  ``backbone``: True for the config's body and pyramid
+    (``backbone.build_backbone``; it brings the pyramid, so ``fpn`` is not passed with it), a module with ``body`` and ``fpn``
+    to use that one."""
     if box_head is None:
         box_head = TrackBoxHead(cfg, in_channels).eval()
     head, generator = None, None
     if rpn_head:
         generator = make_anchor_generator(cfg)
         head = RPNHead(cfg, in_channels, generator.num_anchors_per_location()[0]) if rpn_head is True else rpn_head
+    if backbone and fpn:
+        raise ValueError("build_detection_head: a backbone brings its pyramid; pass `backbone` or `fpn`, not both")
     pyramid = (build_fpn(cfg) if fpn is True else fpn) if fpn else None
+    trunk = (build_backbone(cfg) if backbone is True else backbone) if backbone else None
     return DetectionHead(make_rpn_postprocessor(cfg, rpn_box_coder, is_train=False).eval(), box_head, head, generator,
-                         pyramid).eval()
+                         pyramid, trunk).eval()

@@ -1,0 +1,224 @@
+"""DLA backbone body: the reference's ``siammot/modelling/backbone/dla.py`` for its ``DlaBasic`` networks (DLA-34, the
+``CONV_BODY`` of the default config) with [UPSTREAM] maskrcnn_benchmark's ``FrozenBatchNorm2d``, under upstream's module tree
+and ``state_dict`` keys (``base_layer.0.weight``, ``level3.tree2.root.conv.weight``, ...: 195 for DLA-34), so that a reference
+checkpoint's ``backbone.body.*`` loads.  Inference only.
+
+    x  = cbr7x7(image, 3 -> c0)                           base_layer.{0,1}       cbr = conv (no bias), frozen BN, ReLU
+    x0 = cbr3x3(x, c0 -> c0)                              level0.{0,1}           cb  = conv, frozen BN
+    x1 = cbr3x3(x0, c0 -> c1, stride 2)                   level1.{0,1}
+    x2 .. x5 = level2 .. level5 (DlaTree, stride 2 each)  -> [x2, x3, x4, x5]
+
+Two forms of the operator live here:
+
+* ``DLA.forward`` on device images within ``ops.dla``'s capacities: every convolution on the fp32 matrix cores with the BN,
+  the residual and the ReLU in its epilogue, the ``cat`` and the max-pool read in place by the 1x1 kernel (37 launches for
+  DLA-34, no host synchronisation); ``out_dtype`` half stores the stage maps rounded once;
+* ``dla_torch``: the same as a plain torch composition over the module tree.  It is the path for CPU tensors, images that
+  are not contiguous NCHW, trainable parameters under grad mode and shapes beyond the capacities (counted in
+  ``ops.FALLBACKS["dla_torch"]`` for device tensors), and the baseline of tools/dla_bench.py.
+"""
+import torch
+import torch.nn.functional as F
+from torch import nn
+
+from . import ops
+
+
+class FrozenBatchNorm2d(nn.Module):
+    """[UPSTREAM] ``maskrcnn_benchmark.layers.FrozenBatchNorm2d``: four buffers, ``y = x * scale + shift`` with ``scale =
+    weight * running_var.rsqrt()`` (no epsilon) and ``shift = bias - running_mean * scale``."""
+
+    def __init__(self, n):
+        super(FrozenBatchNorm2d, self).__init__()
+        self.register_buffer("weight", torch.ones(n))
+        self.register_buffer("bias", torch.zeros(n))
+        self.register_buffer("running_mean", torch.zeros(n))
+        self.register_buffer("running_var", torch.ones(n))
+
+    def scale_shift(self):
+        scale = self.weight * self.running_var.rsqrt()
+        return scale, self.bias - self.running_mean * scale
+
+    def forward(self, x):
+        scale, shift = self.scale_shift()
+        return x * scale.to(x.dtype).reshape(1, -1, 1, 1) + shift.to(x.dtype).reshape(1, -1, 1, 1)
+
+
+def _conv(cin, cout, k, stride=1):
+    return nn.Conv2d(cin, cout, kernel_size=k, stride=stride, padding=(k - 1) // 2, bias=False)
+
+
+class DlaBasic(nn.Module):
+    """``relu(bn2(conv2(relu(bn1(conv1(x))))) + residual)``, ``conv1`` with the stride; ``residual`` None: ``x``."""
+
+    def __init__(self, cin, cout, stride=1):
+        super(DlaBasic, self).__init__()
+        for i, (c, s) in enumerate(((cin, stride), (cout, 1)), 1):
+            self.add_module("conv%d" % i, _conv(c, cout, 3, s))
+            self.add_module("bn%d" % i, FrozenBatchNorm2d(cout))
+
+    def forward(self, x, residual=None):
+        out = F.relu(self.bn1(self.conv1(x)))
+        return F.relu(self.bn2(self.conv2(out)) + (x if residual is None else residual))
+
+
+class DlaRoot(nn.Module):
+    """``relu(bn(conv1x1(cat(x))))``."""
+
+    def __init__(self, cin, cout):
+        super(DlaRoot, self).__init__()
+        self.conv, self.bn = _conv(cin, cout, 1), FrozenBatchNorm2d(cout)
+
+    def forward(self, *x):
+        return F.relu(self.bn(self.conv(torch.cat(x, 1))))
+
+
+class DlaTree(nn.Module):
+    """The aggregation tree over ``DlaBasic`` blocks (keys ``tree1``, ``tree2``, ``root``, ``project``, in that order).  A
+    ``levels`` = 1 tree is two blocks and a root over (x2, x1, [bottom if ``level_root``], what the parent handed down:
+    ``handed`` channels); a deeper tree is two trees one level shallower, the second at stride 1 and handed this tree's
+    bottom (if ``level_root``) and the first one's output.  ``project`` exists wherever ``cin != cout``, as upstream; the
+    one of a tree with ``levels`` > 1 is evaluated and discarded there and is not evaluated here (its parameters are kept
+    for the ``state_dict``)."""
+
+    def __init__(self, levels, cin, cout, stride=1, level_root=False, handed=0):
+        super(DlaTree, self).__init__()
+        own = cin if level_root else 0                            # the channels of `bottom`, where it joins the root
+        if levels == 1:
+            self.tree1, self.tree2 = DlaBasic(cin, cout, stride), DlaBasic(cout, cout)
+            self.root = DlaRoot(2 * cout + own + handed, cout)
+        else:
+            self.tree1 = DlaTree(levels - 1, cin, cout, stride)
+            self.tree2 = DlaTree(levels - 1, cout, cout, handed=handed + own + cout)
+        self.project = nn.Sequential(_conv(cin, cout, 1), FrozenBatchNorm2d(cout)) if cin != cout else None
+        self.levels, self.level_root, self.stride = levels, level_root, stride
+
+    def forward(self, x, children=()):
+        bottom = F.max_pool2d(x, self.stride, self.stride) if self.stride > 1 else x
+        children = list(children) + ([bottom] if self.level_root else [])
+        if self.levels == 1:
+            x1 = self.tree1(x, bottom if self.project is None else self.project(bottom))
+            return self.root(self.tree2(x1), x1, *children)
+        x1 = self.tree1(x)
+        return self.tree2(x1, children + [x1])
+
+    def convs(self):
+        """(conv, bn) in the launch order of ``ops.dla``."""
+        if self.levels > 1:
+            return self.tree1.convs() + self.tree2.convs()
+        head = [tuple(self.project)] if self.project is not None else []
+        return head + [(self.tree1.conv1, self.tree1.bn1), (self.tree1.conv2, self.tree1.bn2), (self.tree2.conv1, self.tree2.bn1),
+                       (self.tree2.conv2, self.tree2.bn2), (self.root.conv, self.root.bn)]
+
+
+def dla_torch(model, images):
+    """The body as torch operators on any device: -> [x2, x3, x4, x5] in the parameters' dtype (half images are upcast
+    first, as the kernels convert on load)."""
+    x = images.to(model.base_layer[0].weight.dtype)
+    x = model.level1(model.level0(model.base_layer(x)))
+    out = []
+    for level in (model.level2, model.level3, model.level4, model.level5):
+        x = level(x)
+        out.append(x)
+    return out
+
+
+class DLA(nn.Module):
+    """Upstream's ``DLA(levels, channels, block=DlaBasic)`` as a feature extractor: ``forward(images [N, 3, H, W])`` -> the
+    list of the four stage maps (strides 4, 8, 16, 32), H and W multiples of 32.  ``out_dtype``: the element type of the
+    returned maps (float32, float16 or bfloat16: the fp32 result rounded once; the next stage reads the fp32 value).  On
+    the device path the packed weights are rebuilt when a parameter's or buffer's ``_version``, storage or device changes."""
+
+    def __init__(self, levels, channels, out_dtype=torch.float32):
+        super(DLA, self).__init__()
+        levels, channels = tuple(int(v) for v in levels), tuple(int(v) for v in channels)
+        if len(levels) != 6 or len(channels) != 6:
+            raise ValueError("DLA: six levels and six channel counts, got %r and %r" % (levels, channels))
+        self.levels, self.channels = levels, channels
+        self.out_dtype = out_dtype
+        self.base_layer = nn.Sequential(_conv(3, channels[0], 7), FrozenBatchNorm2d(channels[0]), nn.ReLU(inplace=True))
+        self.level0 = self._conv_level(channels[0], channels[0], levels[0])
+        self.level1 = self._conv_level(channels[0], channels[1], levels[1], stride=2)
+        self.level2 = DlaTree(levels[2], channels[1], channels[2], 2, level_root=False)
+        self.level3 = DlaTree(levels[3], channels[2], channels[3], 2, level_root=True)
+        self.level4 = DlaTree(levels[4], channels[3], channels[4], 2, level_root=True)
+        self.level5 = DlaTree(levels[5], channels[4], channels[5], 2, level_root=True)
+        self.out_channels = channels[2:]
+        self._packed_key, self._packed = None, None
+
+    @staticmethod
+    def _conv_level(cin, cout, count, stride=1):
+        """``count`` cbr3x3 layers, the first with the stride and the change of width: keys 0, 1, (2: the ReLU), 3, 4, ..."""
+        layers = []
+        for i in range(count):
+            layers += [_conv(cout if i else cin, cout, 3, 1 if i else stride), FrozenBatchNorm2d(cout), nn.ReLU(inplace=True)]
+        return nn.Sequential(*layers)
+
+    def convs(self):
+        """(conv, bn) of every convolution that is evaluated, in the launch order of ``ops.dla``."""
+        out = [(self.base_layer[0], self.base_layer[1])]
+        if len(self.level0) == 3 and len(self.level1) == 3:
+            out += [(self.level0[0], self.level0[1]), (self.level1[0], self.level1[1])]
+        for level in (self.level2, self.level3, self.level4, self.level5):
+            out += level.convs()
+        return out
+
+    def kernel_ok(self, images):
+        """This call takes ``ops.dla``."""
+        if not (isinstance(images, torch.Tensor) and images.is_cuda and images.dim() == 4 and images.shape[1] == 3):
+            return False
+        if images.dtype not in ops.FEAT_TYPES or self.out_dtype not in ops.FEAT_TYPES or not images.is_contiguous():
+            return False
+        tensors = list(self.parameters()) + list(self.buffers())
+        if not all(t.dtype is torch.float32 and t.device == images.device for t in tensors):
+            return False
+        if torch.is_grad_enabled() and (images.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return False
+        N, _, H, W = images.shape
+        return N >= 1 and ops.dla_shapes_ok(self.levels, self.channels, H, W, N)
+
+    def packed(self):
+        tensors = list(self.parameters()) + list(self.buffers())
+        key = tuple((t.data_ptr(), t._version, t.device) for t in tensors)
+        if key != self._packed_key:
+            with torch.no_grad():
+                convs = [(c.weight.detach(),) + tuple(t.contiguous() for t in bn.scale_shift()) for c, bn in self.convs()]
+                self._packed = ops.dla_pack(convs, self.levels, self.channels)
+            self._packed_key = key
+        return self._packed
+
+    def forward(self, images):
+        if self.kernel_ok(images):
+            return ops.dla(images, self.packed(), self.levels, self.channels, out_dtype=self.out_dtype)
+        if isinstance(images, torch.Tensor) and images.is_cuda:
+            ops.FALLBACKS["dla_torch"] += 1
+        out = dla_torch(self, images)
+        if self.out_dtype is not torch.float32:
+            out = [o.to(self.out_dtype) for o in out]
+        return out
+
+
+def dla_34(out_dtype=torch.float32):
+    return DLA((1, 1, 1, 2, 2, 1), (16, 32, 64, 128, 256, 512), out_dtype=out_dtype)
+
+
+BODIES = {"DLA-34-FPN": dla_34}
+
+
+def build_dla(cfg, out_dtype=torch.float32):
+    """The body of the config's ``MODEL.BACKBONE.CONV_BODY``.  ``DLA-34-FPN`` is the one this package has; any other body, and
+    any true entry of ``MODEL.DLA.STAGE_WITH_DCN`` (deformable convolutions), raises a ``ValueError`` that names it."""
+    name = cfg.MODEL.BACKBONE.CONV_BODY
+    if name not in BODIES:
+        raise ValueError("build_dla: CONV_BODY %r is not in this package (it has %s)" % (name, ", ".join(sorted(BODIES))))
+    dcn = tuple(getattr(cfg.MODEL.DLA, "STAGE_WITH_DCN", ()) or ())
+    if any(dcn):
+        raise ValueError("build_dla: MODEL.DLA.STAGE_WITH_DCN = %r asks for deformable convolutions, which this package does "
+                         "not have" % (dcn,))
+    body = BODIES[name](out_dtype=out_dtype)
+    dla = cfg.MODEL.DLA
+    stages = (dla.DLA_STAGE2_OUT_CHANNELS, dla.DLA_STAGE3_OUT_CHANNELS, dla.DLA_STAGE4_OUT_CHANNELS, dla.DLA_STAGE5_OUT_CHANNELS)
+    if tuple(stages) != tuple(body.out_channels):
+        raise ValueError("build_dla: %s has stage widths %r, the config's MODEL.DLA.DLA_STAGE*_OUT_CHANNELS are %r"
+                         % (name, tuple(body.out_channels), tuple(stages)))
+    return body

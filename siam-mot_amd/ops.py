@@ -155,6 +155,17 @@ _SIGNATURES = {
     "smot_fpn_pack": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),
     "smot_fpn_ws_bytes": (ctypes.c_longlong, [_i, _vp, _vp, _i, _i]),
     "smot_fpn_fwd": (ctypes.c_int, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
+    # DLA backbone body: an image batch to the four stage maps; and its three operators alone
+    "smot_dla_packed_floats": (ctypes.c_longlong, [_vp, _vp]),
+    "smot_dla_pack": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "smot_dla_ws_bytes": (ctypes.c_longlong, [_vp, _vp, _i, _i, _i]),
+    "smot_dla_fwd": (ctypes.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "smot_dla_conv_packed_floats": (ctypes.c_longlong, [_i, _i, _i]),
+    "smot_dla_conv3x3_fwd": (ctypes.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "smot_dla_conv3x3_form": (ctypes.c_int, [_i, _i, _i, _i, _i]),
+    "smot_dla_conv1x1_fwd": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp]),
+    "smot_dla_stem_ws_bytes": (ctypes.c_longlong, [_i, _i, _i, _i, _i]),
+    "smot_dla_stem_fwd": (ctypes.c_int, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 _DEBUG_SIGNATURES = {
@@ -1175,6 +1186,10 @@ FALLBACKS["rpn_head_torch"] = 0
 #   fpn_torch            an ``fpn.FPN`` call on device maps that ``fpn`` does not take (training or grad mode, a GroupNorm /
 #                        ReLU conv block, ``LastLevelP6P7``, channel counts beyond the kernels' capacities)
 FALLBACKS["fpn_torch"] = 0
+#   dla_torch            a ``dla.DLA`` call on device images that ``dla`` does not take (grad mode with trainable parameters,
+#                        images that are not contiguous NCHW, sizes that are no multiple of 32, levels / channels beyond the
+#                        kernels' capacities)
+FALLBACKS["dla_torch"] = 0
 # speculative next-frame heads of the tracking loop (TrackingLoop.forward(..., next_features=...)): launched / used as they
 # were / discarded because the row count, the memory, the features or the parameters were not what the launch assumed
 SPECULATION = _collections.Counter()
@@ -1548,6 +1563,174 @@ def fpn(stages, packed, in_channels, C, out_dtype=torch.float32, top_block=True)
         rc = lib.smot_fpn_fwd(_cast(fp), ft, _cast(ic), _cast(ih), _cast(iw), L, N, int(C), _ptr(packed), _ptr(ws), _cast(po),
                               FEAT_TYPES[out_dtype], 1 if top_block else 0, ln.stream)
     _check(rc, "fpn")
+    return out
+
+
+# capacities of ``dla`` (include/smot_emm.h, DLA BACKBONE): beyond them ``siammot_amd.dla.DLA`` takes its torch composition
+DLA_MAX_CHANNELS = 1024
+DLA_CHANNEL_STEP = 32
+DLA_SIZE_STEP = 32
+
+
+def dla_shapes_ok(levels, channels, H=None, W=None, N=1):
+    """``dla`` takes a network of these ``levels`` / ``channels`` (and, if given, ``N`` images of ``H x W``)."""
+    levels, channels = tuple(int(v) for v in levels), tuple(int(v) for v in channels)
+    if len(levels) != 6 or len(channels) != 6 or levels[:2] != (1, 1) or any(v not in (1, 2) for v in levels[2:]):
+        return False
+    if channels[0] not in (16, 32) or any(c < 32 or c % DLA_CHANNEL_STEP or c > DLA_MAX_CHANNELS for c in channels[1:]):
+        return False
+    if H is None and W is None:
+        return True
+    H, W = int(H), int(W)
+    if H < 32 or W < 32 or H % DLA_SIZE_STEP or W % DLA_SIZE_STEP or not 1 <= N <= RPN_MAX_IMAGES:
+        return False
+    return max(channels[k] * (H >> k) * (W >> k) for k in range(6)) < 2 ** 31
+
+
+def _int6(v):
+    return (ctypes.c_int * 6)(*[int(x) for x in v])
+
+
+def dla_pack(convs, levels, channels):
+    """The body's parameters in the operand order of ``dla`` (``smot_dla_pack``: one launch per convolution, no
+    synchronisation).  convs: ``(weight [Cout, Cin, k, k], scale [Cout], shift [Cout])`` per convolution in LAUNCH ORDER
+    (include/smot_emm.h; ``dla.DLA.convs()``), fp32 device tensors, ``scale`` / ``shift`` the frozen BN's.  -> fp32
+    ``[smot_dla_packed_floats]``."""
+    lib = _lib or load_library()
+    lv, ch = _int6(levels), _int6(channels)
+    n = lib.smot_dla_packed_floats(_cast(lv), _cast(ch))
+    if n < 0:
+        _check(-2, "dla_pack")
+    ts = [[_chk(t, "dla_pack: convs[%d][%d]" % (i, j), tuple(t.shape)) for j, t in enumerate(c)] for i, c in enumerate(convs)]
+    packed = torch.empty((n,), dtype=_F32, device=ts[0][0].device)
+    arrays = [(ctypes.c_void_p * len(ts))(*[c[j].data_ptr() for c in ts]) for j in range(3)]
+    with _Launch(*[t for c in ts for t in c]) as ln:
+        rc = lib.smot_dla_pack(_cast(lv), _cast(ch), _cast(arrays[0]), _cast(arrays[1]), _cast(arrays[2]), len(ts), _ptr(packed),
+                               ln.stream)
+    _check(rc, "dla_pack")
+    return packed
+
+
+def dla(images, packed, levels, channels, out_dtype=torch.float32):
+    """Upstream's ``DLA.forward`` (DlaBasic blocks, frozen BN) on all images of a call (``smot_dla_fwd``: 37 launches for
+    DLA-34), free of host synchronisation.  images: ``[N, 3, H, W]`` fp32, fp16 or bf16 (a half call returns the bits of the
+    call on ``.float()``), H and W multiples of 32; anything but contiguous NCHW is copied.  packed: ``dla_pack``'s tensor.
+    -> the four contiguous NCHW stage maps ``[N, channels[k], H >> k, W >> k]``, k = 2 .. 5, of ``out_dtype`` (a half output
+    is the fp32 value rounded to nearest even; the next stage reads the fp32 value)."""
+    lib = _lib or load_library()
+    if out_dtype not in FEAT_TYPES:
+        raise RuntimeError("siammot_amd.dla: out_dtype must be float32, float16 or bfloat16, got %s" % (out_dtype,))
+    x = _dev_feat(images, "images")
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise RuntimeError("siammot_amd.dla: images has shape %s, expected [N, 3, H, W]" % (tuple(x.shape),))
+    N, H, W = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+    lv, ch = _int6(levels), _int6(channels)
+    nbytes = lib.smot_dla_ws_bytes(_cast(lv), _cast(ch), N, H, W)
+    if nbytes < 0:
+        _check(-2, "dla")
+    ws = torch.empty((max(nbytes // 4, 4),), dtype=_F32, device=x.device)
+    out = [torch.empty((N, int(channels[k]), H >> k, W >> k), dtype=out_dtype, device=x.device) for k in range(2, 6)]
+    po = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in out])
+    with _Launch(x, packed) as ln:
+        rc = lib.smot_dla_fwd(_ptr(x), FEAT_TYPES[x.dtype], N, H, W, _cast(lv), _cast(ch), _ptr(packed), _ptr(ws), _cast(po),
+                              FEAT_TYPES[out_dtype], ln.stream)
+    _check(rc, "dla")
+    return out
+
+
+def dla_conv3x3_form(N, H, W, Cout, stride):
+    """Which form of the 3x3 kernel ``dla_conv3x3`` runs for ``N`` images of ``H x W`` (``smot_dla_conv3x3_form``): ``(WR,
+    NM)`` — the row groups of a workgroup's four waves (1, 2 or 4) and the M-tiles per channel pair."""
+    form = (_lib or load_library()).smot_dla_conv3x3_form(int(N), int(H), int(W), int(Cout), int(stride))
+    if form < 0:
+        raise RuntimeError("siammot_amd.dla_conv3x3_form: bad argument")
+    return form // 10, form % 10
+
+
+def dla_conv3x3(x, w, scale, shift, stride, residual=None, relu=True, residual_pooled=False):
+    """``relu(conv3x3(x, w, stride, pad 1) * scale + shift + residual)`` (``smot_dla_conv3x3_fwd``; residual and ReLU
+    optional): x ``[N, Cin, H, W]`` fp32 -> ``[N, Cout, Ho, Wo]`` fp32, any H, W >= 1.  ``residual_pooled``: the residual is
+    ``[N, Cout, Hr, Wr]`` with ``Hr // 2 == Ho``, ``Wr // 2 == Wo`` and is read through ``max_pool2d(., 2, 2)``."""
+    lib = _lib or load_library()
+    x = _dev_f32(x, "x")
+    N, Cin, H, W = (int(v) for v in x.shape)
+    Cout = int(w.shape[0])
+    w = _chk(w, "w", (Cout, Cin, 3, 3))
+    scale, shift = _chk(scale, "scale", (Cout,)), _chk(shift, "shift", (Cout,))
+    Ho, Wo = ((H - 1) // 2 + 1, (W - 1) // 2 + 1) if stride == 2 else (H, W)
+    rh = rw = 0
+    if residual is not None and residual_pooled:
+        rh, rw = int(residual.shape[-2]), int(residual.shape[-1])
+        residual = _chk(residual, "residual", (N, Cout, rh, rw))
+    elif residual is not None:
+        residual = _chk(residual, "residual", (N, Cout, Ho, Wo))
+    n = lib.smot_dla_conv_packed_floats(3, Cin, Cout)
+    packed = torch.empty((max(n, 4),), dtype=_F32, device=x.device)
+    out = torch.empty((N, Cout, Ho, Wo), dtype=_F32, device=x.device)
+    with _Launch(x, w, scale, shift, residual) as ln:
+        rc = lib.smot_dla_conv3x3_fwd(_ptr(x), N, Cin, H, W, _ptr(w), _ptr(scale), _ptr(shift), Cout, int(stride), _ptr(residual),
+                                      rh, rw, 1 if relu else 0, _ptr(packed), _ptr(out), ln.stream)
+    _check(rc, "dla_conv3x3")
+    return out
+
+
+def dla_conv1x1(sources, pooled, w, scale, shift, relu, out_dtype=torch.float32):
+    """``relu(conv1x1(cat(sources, 1), w) * scale + shift)`` (``smot_dla_conv1x1_fwd``; ReLU optional) with no ``cat``:
+    sources: up to four fp32 maps ``[N, C_s, ., .]``; ``pooled[s]``: the source is read through ``max_pool2d(., 2, 2)``
+    (a map twice as fine), else it has the output's size.  -> ``[N, Cout, H, W]`` of ``out_dtype``."""
+    lib = _lib or load_library()
+    S = len(sources)
+    if not 1 <= S <= 4 or len(pooled) != S:
+        raise RuntimeError("siammot_amd.dla_conv1x1: %d sources, %d pooled flags (1 .. 4 of each)" % (S, len(pooled)))
+    if out_dtype not in FEAT_TYPES:
+        raise RuntimeError("siammot_amd.dla_conv1x1: out_dtype must be float32, float16 or bfloat16, got %s" % (out_dtype,))
+    src = [_dev_f32(t, "sources[%d]" % s) for s, t in enumerate(sources)]
+    N = int(src[0].shape[0])
+    H, W = (int(src[0].shape[2]) // 2, int(src[0].shape[3]) // 2) if pooled[0] else (int(src[0].shape[2]), int(src[0].shape[3]))
+    K = sum(int(t.shape[1]) for t in src)
+    Cout = int(w.shape[0])
+    w = _chk(w.reshape(Cout, -1), "w", (Cout, K))
+    scale, shift = _chk(scale, "scale", (Cout,)), _chk(shift, "shift", (Cout,))
+    for s, t in enumerate(src):
+        if t.dim() != 4 or t.shape[0] != N:
+            raise RuntimeError("siammot_amd.dla_conv1x1: sources[%d] has shape %s" % (s, tuple(t.shape)))
+    arr = lambda vals: (ctypes.c_int * S)(*[int(v) for v in vals])
+    sp = (ctypes.c_void_p * S)(*[t.data_ptr() for t in src])
+    sc, sf = arr(t.shape[1] for t in src), arr(1 if f else 0 for f in pooled)
+    sh, sw = arr(t.shape[2] for t in src), arr(t.shape[3] for t in src)
+    n = lib.smot_dla_conv_packed_floats(1, K, Cout)
+    packed = torch.empty((max(n, 4),), dtype=_F32, device=src[0].device)
+    out = torch.empty((N, Cout, H, W), dtype=out_dtype, device=src[0].device)
+    with _Launch(*(src + [w, scale, shift])) as ln:
+        rc = lib.smot_dla_conv1x1_fwd(_cast(sp), _cast(sc), _cast(sf), _cast(sh), _cast(sw), S, N, H, W, _ptr(w), _ptr(scale),
+                                      _ptr(shift), Cout, 1 if relu else 0, _ptr(packed), _ptr(out), FEAT_TYPES[out_dtype], ln.stream)
+    _check(rc, "dla_conv1x1")
+    return out
+
+
+def dla_stem(images, layers):
+    """The body's first three layers (``smot_dla_stem_fwd``): images ``[N, 3, H, W]`` fp32, fp16 or bf16, H and W even;
+    layers: ``(weight, scale, shift)`` of ``base_layer`` ``[c0, 3, 7, 7]``, ``level0`` ``[c0, c0, 3, 3]`` and ``level1``
+    ``[c1, c0, 3, 3]``.  -> ``x1 [N, c1, H / 2, W / 2]`` fp32."""
+    lib = _lib or load_library()
+    x = _dev_feat(images, "images")
+    if x.dim() != 4 or x.shape[1] != 3 or len(layers) != 3:
+        raise RuntimeError("siammot_amd.dla_stem: images %s, %d layers (expected [N, 3, H, W] and three)" % (tuple(x.shape), len(layers)))
+    N, H, W = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+    c0, c1 = int(layers[0][0].shape[0]), int(layers[2][0].shape[0])
+    shapes = ((c0, 3, 7, 7), (c0, c0, 3, 3), (c1, c0, 3, 3))
+    ts = [(_chk(w, "layers[%d] weight" % i, shapes[i]), _chk(a, "layers[%d] scale" % i, shapes[i][:1]),
+           _chk(b, "layers[%d] shift" % i, shapes[i][:1])) for i, (w, a, b) in enumerate(layers)]
+    nbytes = lib.smot_dla_stem_ws_bytes(N, H, W, c0, c1)
+    if nbytes < 0:
+        _check(-2, "dla_stem")
+    ws = torch.empty((max(nbytes // 4, 4),), dtype=_F32, device=x.device)
+    out = torch.empty((N, c1, H // 2, W // 2), dtype=_F32, device=x.device)
+    arrays = [(ctypes.c_void_p * 3)(*[t[j].data_ptr() for t in ts]) for j in range(3)]
+    with _Launch(*([x] + [t for c in ts for t in c])) as ln:
+        rc = lib.smot_dla_stem_fwd(_ptr(x), FEAT_TYPES[x.dtype], N, H, W, c0, c1, _cast(arrays[0]), _cast(arrays[1]),
+                                   _cast(arrays[2]), _ptr(ws), _ptr(out), ln.stream)
+    _check(rc, "dla_stem")
     return out
 
 
