@@ -7,7 +7,13 @@
 #include "pool_launch.h"
 #include "knobs.h"
 
-static inline bool p12_form3(int N, int C, int ho) { return smot_emm_tower_form(N, C, ho) == 3; }
+#include "tower_common.h"
+
+// whether the towers that follow will launch the split form and so want the response's plane maxima from the pooling +
+// correlation kernel (the launchers' own choice: tower_wino.hip; a bad group count is refused by predictor_impl later)
+static inline bool towers_want_plane_max(int N, int C, int ho, int gn_groups, const float* packed) {
+    return packed != nullptr && gn_groups > 0 && C % gn_groups == 0 && smot::tower_split_form(N, C, ho, C / gn_groups);
+}
 
 extern "C" long long smot_emm_track_ws_floats(int N, int C, int rx, int rz) {
     if (N < 0 || C <= 0 || rz <= 0 || rx < rz) return -1;
@@ -46,14 +52,14 @@ static int emm_track_impl(const float* const* feats, const int* heights, const i
     if (rx == 30 && rz == 15 && sampling_ratio == 2 && !no_fuse) {
         // pooling feeds the correlation inside one kernel: the search-region tensor never reaches HBM
         // (a hint the kernel honours is VERIFIED against `boxes` / `sr` by it; `poison` = the list's status word)
-        float* pm = (C <= 7 * ho * ho && p12_form3(N, C, ho)) ? logits : nullptr;
+        float* pm = (C <= 7 * ho * ho && towers_want_plane_max(N, C, ho, gn_groups, predictor_params[12])) ? logits : nullptr;
         rc = sr_xcorr_fused_impl(feats, heights, widths, pad_cells, scales, num_levels, C, boxes, sr, templates, N, resp, nullptr,
                                  order_hint, (hipStream_t)stream, &poison, pm, I);
         if (rc) return rc;
         plane_max = pm;
     } else if (rx == 35 && rz == 7 && sampling_ratio == 2 && !no_fuse) {
         // the second yaml family's shape: gathers + correlation in one kernel (sr_xcorr_small.hip), same arithmetic
-        float* pm = (C <= 7 * ho * ho && p12_form3(N, C, ho)) ? logits : nullptr;
+        float* pm = (C <= 7 * ho * ho && towers_want_plane_max(N, C, ho, gn_groups, predictor_params[12])) ? logits : nullptr;
         rc = sr_xcorr_gather_impl(feats, heights, widths, pad_cells, scales, num_levels, C, boxes, sr, templates, N, resp,
                                   (hipStream_t)stream, pm, I);
         if (rc) return rc;

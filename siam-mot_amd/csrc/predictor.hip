@@ -527,8 +527,9 @@ int predictor_impl(const float* resp, int N, int C, int Ho, const float* cls_tow
     // largest |response| of its planes (tower_wino.hip).  The pooling + correlation kernel hands the plane maxima over
     // (`plane_max`); for a response that came without them one small launch makes them, in the head of the `logits`
     // buffer — N C <= N 7 Ho^2 floats that nothing reads before the tower kernel has and the logits overwrite afterwards.
-    if (plane_max == nullptr && tower_packed != nullptr && !knobs().tower_direct && smot_emm_tower_form(N, C, Ho) == 3 &&
-        (mfma_ok || Ho == 29)) {
+    // tower_split_form is the launchers' own choice of form: the maxima exist exactly when the split form will be launched
+    // (every C % 32 == 0 at Ho = 29, not only the powers of two), and a shape that no matrix-core kernel takes writes nothing.
+    if (plane_max == nullptr && tower_packed != nullptr && tower_split_form(N, C, Ho, cpg)) {
         SMOT_REQUIRE(C <= 7 * Ho * Ho, "predictor: C=%d too large for the plane maxima's scratch", C);
         const int rcm = launch_plane_absmax(resp, N * C, Ho * Ho, logits, st);
         if (rcm) return rcm;

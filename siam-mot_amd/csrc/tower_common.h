@@ -54,6 +54,8 @@ constexpr int T_PLANE = 336;                      // 18*18 = 324 padded to 336
 // plane_max: |resp| maximum of every (track, channel) plane [N][C] — read by the split (fp16 x 2) form only
 int launch_tower_wino(const float* resp, const float* packed, const TowerParams& P, int N, int C, int cpg, float eps,
                       float* part, unsigned* zero_words, hipStream_t st, const float* plane_max);
+// tower_wino.hip: whether the towers of this shape (packed filters given) will launch the split form, i.e. need `plane_max`
+bool tower_split_form(int N, int C, int Ho, int cpg);
 // tower_wino.hip: the plane maxima of a response that did not come with them (one wave per plane)
 int launch_plane_absmax(const float* resp, int planes, int hw, float* pm, hipStream_t st);
 

@@ -1114,6 +1114,21 @@ int launch_tower_wino_blocks(const float* resp, const float* packed, const Tower
     return check_launch("predictor towers (winograd, 29x29 in blocks)");
 }
 
+// Whether the towers of N tracks' [C, Ho, Ho] responses with `cpg` channels per GroupNorm group, packed filters given, will
+// launch the split (fp16 x 2) form — the one form that reads the response's plane maxima.  The gates of predictor_impl's
+// 16 x 16 path and of launch_tower_conv_wino and the form choices of the two launchers above, in one place: whoever has to
+// provide the maxima asks here, so that the launchers never meet the split form without them (smot_emm_tower_form answers
+// for power-of-two C <= 512 only; the blocked launcher takes every C % 32 == 0).
+bool tower_split_form(int N, int C, int Ho, int cpg) {
+    if (N <= 0 || C <= 0 || C % 32 != 0 || cpg <= 0 || cpg > 16 || 16 % cpg != 0 || knobs().tower_direct) return false;
+    if (Ho == 16) {
+        const bool pow2 = (C & (C - 1)) == 0;
+        return pow2 && C <= 512 && tower_form(tower_tiles_per_workgroup(N, C)).split;
+    }
+    if (Ho == 29) return tower_blocks_tiles_per_workgroup(N, C) == 2 && knobs().tower_bf3 != 0;
+    return false;
+}
+
 }  // namespace smot
 
 extern "C" int smot_emm_tower_form(int N, int C, int Ho) {
