@@ -59,7 +59,9 @@ typedef void* smot_stream_t; /* hipStream_t */
  *     solver over several images: smot_track_solve_batched_fwd; the RPN head and anchors: smot_rpn_head_*,
  *     smot_rpn_anchors_fwd; the feature pyramid: smot_fpn_packed_floats, smot_fpn_pack, smot_fpn_ws_bytes, smot_fpn_fwd;
  *     the DLA backbone body: smot_dla_packed_floats, smot_dla_pack, smot_dla_ws_bytes, smot_dla_fwd and its operators alone:
- *     smot_dla_conv_packed_floats, smot_dla_conv3x3_fwd, smot_dla_conv3x3_form, smot_dla_conv1x1_fwd, smot_dla_stem_ws_bytes, smot_dla_stem_fwd.
+ *     smot_dla_conv_packed_floats, smot_dla_conv3x3_fwd, smot_dla_conv3x3_form, smot_dla_conv1x1_fwd, smot_dla_stem_ws_bytes, smot_dla_stem_fwd;
+ *     the body with split operands: smot_dla_split_packed_floats, smot_dla_split_pack, smot_dla_split_fwd,
+ *     smot_dla_conv_split_packed_floats, smot_dla_conv3x3_split_fwd, smot_dla_conv3x3_split_form.
  */
 #define SMOT_ABI_VERSION 14
 
@@ -1226,6 +1228,33 @@ int smot_dla_conv1x1_fwd(const float* const* sources, const int* source_channels
 long long smot_dla_stem_ws_bytes(int num_images, int H, int W, int c0, int c1);
 int smot_dla_stem_fwd(const void* image, int in_type, int num_images, int H, int W, int c0, int c1, const float* const* w,
                       const float* const* scale, const float* const* shift, float* ws, float* out, smot_stream_t stream);
+
+/* DLA BACKBONE, SPLIT OPERANDS: the same network with the 3x3 convolutions of the trees (level2 .. level5) on
+ * v_mfma_f32_16x16x32_bf16.  Every fp32 input value and filter is split into three bf16 parts (x = x1 + x2 + x3, round to
+ * nearest even; exact for normal values), six of the nine part products are accumulated in fp32 (the dropped ones are
+ * <= 2^-26 of a term): the result is an fp32-grade evaluation in another summation order, needs no knowledge of the data's
+ * range (bf16 has fp32's exponents: no scaling, no maxima), and a non-finite input cell still reaches exactly the outputs
+ * whose window covers it (as NaN, also where the fp32 kernel gives inf).  The 7x7, the stem's two 3x3 and every 1x1
+ * convolution are the fp32 mode's kernels and packed images.  Each function is the twin of the one named without `split`:
+ * same arguments, checks and error codes, with these differences:
+ *   smot_dla_split_packed_floats / smot_dla_split_pack   the packed image holds the trees' 3x3 filters as split parts (1.5
+ *                  times the fp32 image's size for them); it is NOT interchangeable with smot_dla_pack's.
+ *   smot_dla_split_fwd             packed: smot_dla_split_pack's; ws: smot_dla_ws_bytes(...) bytes, as in fp32 mode.
+ *   smot_dla_conv3x3_split_fwd     Cin % 32 == 0 (SMOT_ERR_UNSUPPORTED otherwise, nothing launched); packed:
+ *                  smot_dla_conv_split_packed_floats(3, Cin, Cout) floats.
+ *   smot_dla_conv3x3_split_form    the form that call runs (today the fp32 mode's rule).
+ *   smot_dla_conv_split_packed_floats   kernel_size 3: the split image (-1 unless Cin % 32 == 0); 1 and 7: the fp32 mode's.
+ */
+long long smot_dla_split_packed_floats(const int* levels, const int* channels);
+int smot_dla_split_pack(const int* levels, const int* channels, const float* const* w, const float* const* scale,
+                        const float* const* shift, int num_convs, float* packed, smot_stream_t stream);
+int smot_dla_split_fwd(const void* image, int in_type, int num_images, int H, int W, const int* levels, const int* channels,
+                       const float* packed, float* ws, void* const* out, int out_type, smot_stream_t stream);
+long long smot_dla_conv_split_packed_floats(int kernel_size, int Cin, int Cout);
+int smot_dla_conv3x3_split_fwd(const float* x, int num_images, int Cin, int H, int W, const float* w, const float* scale,
+                               const float* shift, int Cout, int stride, const float* residual, int residual_h, int residual_w,
+                               int relu, float* packed, float* out, smot_stream_t stream);
+int smot_dla_conv3x3_split_form(int num_images, int H, int W, int Cout, int stride);
 
 #ifdef __cplusplus
 }

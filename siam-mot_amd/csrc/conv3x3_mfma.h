@@ -268,4 +268,198 @@ __device__ __forceinline__ void cvg_block(float* sm, const FT* __restrict__ in, 
     }
 }
 
+// ---- the generalised stage with THREE-PART bf16 OPERANDS on v_mfma_f32_16x16x32_bf16 (cvs_*, for csrc/dla.hip) ---------------
+// Nothing above is touched.  Same tiling (8 x 16 output tile, WR / NM as cvg_block), chunks of 32 input channels.
+//
+//   x = x1 + x2 + x3, x1 = bf16(x), x2 = bf16(x - x1), x3 = bf16(x - x1 - x2) (round to nearest even; the differences are
+//   exact in fp32): |x2| <= 2^-9 |x|, |x3| <= 2^-18 |x|, and x is met to 2^-27 |x| or exactly.  Filters are split the same
+//   way, once, by the pack kernel.  Of the nine part products the six with part indices i + j <= 4 are kept, (w3 x1), (w1 x3),
+//   (w2 x2), (w2 x1), (w1 x2), (w1 x1) in this order, into ONE fp32 accumulator per tile: what is dropped is <= 2^-26 of a
+//   term.  bf16 has fp32's exponent range: no scaling, no per-map maximum, and a column of the product still depends on that
+//   column of B alone — an inf cell has x1 = inf, x2 = NaN (inf - inf), a NaN cell x1 = NaN: the outputs whose window covers
+//   it are NaN, the others are untouched.  (A finite value that bf16() would round to inf — within 2^-9 of the largest —
+//   keeps its first part truncated instead; the other two parts hold the rest.)
+//   A operand = packed parts (cvs_pack_index): per tap 3 parts x NM M-tiles of 16 bytes per lane, straight into registers,
+//               the next tap's in flight while the current tap multiplies (a chunk's 216 registers cannot be held).
+//   B operand = the chunk's haloed cells in LDS as [part][group of 8 channels kq][cell] 16-byte slots: a lane's fragment
+//               (channels 8 kq .. 8 kq + 7 of one position) is ONE aligned ds_read_b128 per part.  ds_read_b128 is served in
+//               four groups of 16 lanes, each 8 lanes of one kq and 8 of the next, over 16 slots of a 256-byte bank row:
+//               stride 1: a kq's lanes read consecutive slots and the group pitch GP = 192 = 0 (mod 16) puts the other
+//               kq's eight on the eight slots left; stride 2: they read every other slot and GP = 561 is odd.  Conflict-free.
+//   Staging   = a thread takes (kq, cell) units: eight coalesced-over-cells global loads (masked: cells outside the map are
+//               ZEROS WRITTEN TO LDS), the split in registers, one ds_write_b128 per part.
+//   LDS       = stride 1: two buffers of 3 x 4 x 192 x 16 = 36,864 B (73,728 B: two workgroups per CU); stride 2: 3 x 4 x
+//               561 x 16 = 107,712 B, which fits once: ONE buffer, the next chunk's cells wait in registers across the
+//               multiply (one workgroup per CU, hence 512 registers) and are stored between two barriers.
+// An output's sum order is fixed by the channel counts and the position in its tile, as above.
+constexpr int CVS_IC = 32;                                       // input channels per chunk
+typedef unsigned cvs_u32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 cvs_bf16x8 __attribute__((ext_vector_type(8)));
+
+template <int STRIDE>
+struct CvsGeom {
+    using G = CvGeom<STRIDE>;
+    static constexpr int GP = STRIDE == 1 ? 192 : G::CELLS;      // slots between channel groups: = 0 (mod 16) | odd
+    static constexpr int UNITS = 4 * G::CELLS;                   // (kq, cell): 720 | 2244
+    static constexpr int NLD = (UNITS + 255) / 256;              // 3 | 9
+    static constexpr int BUF = 3 * 4 * GP;                       // slots per stage buffer
+    static constexpr int NBUF = STRIDE == 1 ? 2 : 1;
+    static constexpr int SMEM_SLOTS = NBUF * BUF;
+    static_assert(G::CELLS <= GP && (STRIDE == 1 ? GP % 16 == 0 : GP % 2 == 1), "the group pitch");
+};
+
+// bf16(v) by round-to-nearest-even in the low 16 bits; a NaN stays a NaN
+__device__ __forceinline__ unsigned cvs_bf16(float v) {
+    const unsigned u = __float_as_uint(v);
+    return (v != v) ? 0x7fc0u : (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+// v -> its three bf16 parts (header comment)
+__device__ __forceinline__ void cvs_split(float v, unsigned (&p)[3]) {
+    const unsigned u = __float_as_uint(v);
+    unsigned p1 = cvs_bf16(v);
+    if ((p1 & 0x7f80u) == 0x7f80u && (u & 0x7f800000u) != 0x7f800000u) p1 = u >> 16;
+    const float r1 = v - __uint_as_float(p1 << 16);
+    const unsigned p2 = cvs_bf16(r1);
+    const float r2 = r1 - __uint_as_float(p2 << 16);
+    p[0] = p1;
+    p[1] = p2;
+    p[2] = cvs_bf16(r2);
+}
+
+// Dword i of the packed image of the split filters W [Cout, Cin, 3, 3], Cin % 32 == 0, the pairs padded to 32 output
+// channels -> the index in W of its LOW bf16 (the high one is the next input channel, 9 floats on), or -1: zeros; *part: 0..2.
+// The image is [pair p][chunk c][tap][part][M-tile m][lane][e 0..3]: the lane's A fragment of v_mfma_f32_16x16x32_bf16,
+// A[row lane % 16][k = 8 (lane / 16) + j], j = 2e, 2e + 1 -> W[32p + 16m + lane % 16][32c + 8 (lane / 16) + j][tap].
+__host__ __device__ inline long long cvs_pack_index(long long i, int Cin, int Cout, int* part) {
+    const int e = (int)(i & 3), lane = (int)((i >> 2) & 63);
+    long long r = i >> 8;
+    const int m = (int)(r & 1);
+    r >>= 1;
+    *part = (int)(r % 3);
+    r /= 3;
+    const int tap = (int)(r % 9);
+    r /= 9;
+    const int nch = Cin / CVS_IC;
+    const int c = (int)(r % nch), p = (int)(r / nch);
+    const int oc = 32 * p + 16 * m + (lane & 15), ic = CVS_IC * c + 8 * (lane >> 4) + 2 * e;
+    return oc < Cout ? ((long long)oc * Cin + ic) * 9 + tap : -1;
+}
+__host__ __device__ inline long long cvs_packed_floats(int Cin, int Cout) {
+    return (long long)((Cout + 31) / 32) * (Cin / CVS_IC) * 9 * 3 * 2 * 256;
+}
+
+template <int STRIDE>
+struct CvsPlan {
+    int src[CvsGeom<STRIDE>::NLD];                               // unit u = tid + 256 j: offset of its first channel, or -1
+};
+// (y0, x0): the OUTPUT tile's first position; H, W: the INPUT map
+template <int STRIDE>
+__device__ __forceinline__ void cvs_plan(CvsPlan<STRIDE>& pl, int tid, int y0, int x0, int H, int W) {
+    using S = CvsGeom<STRIDE>;
+    using G = CvGeom<STRIDE>;
+    const int HW = H * W;
+#pragma unroll
+    for (int j = 0; j < S::NLD; ++j) {
+        const int u = tid + 256 * j;
+        const int kq = u / G::CELLS, cell = u - kq * G::CELLS;
+        const int r = cell / G::PW, col = cell - r * G::PW;
+        const int gy = y0 * STRIDE - 1 + r, gx = x0 * STRIDE - 1 + col;
+        pl.src[j] = (u < S::UNITS && gy >= 0 && gy < H && gx >= 0 && gx < W) ? 8 * kq * HW + gy * W + gx : -1;
+    }
+}
+
+// cvg_block with split operands: sm: CvsGeom<STRIDE>::SMEM_SLOTS 16-byte slots; packed: the cvs_pack_index image
+template <typename FT, int STRIDE, int WR, int NM>
+__device__ __forceinline__ void cvs_block(cvs_u32x4* sm, const FT* __restrict__ in, int HW, int Cin, const CvsPlan<STRIDE>& pl,
+                                          const float* __restrict__ packed, int pair, bool active, int tid, int row0,
+                                          cv_f32x4 (&acc)[NM][CV_TH / WR]) {
+    using S = CvsGeom<STRIDE>;
+    using G = CvGeom<STRIDE>;
+    constexpr int ROWS = CV_TH / WR;
+    static_assert(ROWS % 2 == 0, "rows are multiplied two at a time");
+    const int lane = tid & 63, kq = lane >> 4, xl = lane & 15;
+    const int nch = Cin / CVS_IC;
+    const int boff = kq * S::GP + row0 * STRIDE * G::PW + xl * STRIDE;
+    float pre[S::NLD][8];
+    auto fetch = [&](int chunk) {
+        const FT* __restrict__ base = in + (size_t)chunk * CVS_IC * HW;
+#pragma unroll
+        for (int j = 0; j < S::NLD; ++j)
+#pragma unroll
+            for (int k = 0; k < 8; ++k) pre[j][k] = pl.src[j] >= 0 ? feat_ld<FT>(base + pl.src[j] + k * HW) : 0.0f;
+    };
+    auto stash = [&](cvs_u32x4* buf) {
+#pragma unroll
+        for (int j = 0; j < S::NLD; ++j) {
+            const int u = tid + 256 * j, g = u / G::CELLS;
+            if (u < S::UNITS) {
+                unsigned lo[3], hi[3];
+                cvs_u32x4 v[3];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    cvs_split(pre[j][2 * e], lo);
+                    cvs_split(pre[j][2 * e + 1], hi);
+#pragma unroll
+                    for (int p = 0; p < 3; ++p) v[p][e] = lo[p] | (hi[p] << 16);
+                }
+#pragma unroll
+                for (int p = 0; p < 3; ++p) buf[(4 * p + g) * S::GP + (u - g * G::CELLS)] = v[p];
+            }
+        }
+    };
+    constexpr int AT = 3 * 2 * 64;                               // 16-byte values per (pair, chunk, tap)
+    const cvs_u32x4* __restrict__ ap = reinterpret_cast<const cvs_u32x4*>(packed) + (size_t)(active ? pair : 0) * nch * 9 * AT + lane;
+#pragma unroll
+    for (int m = 0; m < NM; ++m)
+#pragma unroll
+        for (int nt = 0; nt < ROWS; ++nt) acc[m][nt] = (cv_f32x4){0.f, 0.f, 0.f, 0.f};
+    cvs_u32x4 an[3][NM], ac[3][NM];
+    auto fetch_a = [&](int t) {                                  // t = 9 chunk + tap
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int m = 0; m < NM; ++m) an[p][m] = ap[(size_t)t * AT + (2 * p + m) * 64];
+    };
+    fetch(0);
+    fetch_a(0);
+    stash(sm);
+    __syncthreads();
+    for (int c = 0; c < nch; ++c) {
+        const cvs_u32x4* buf = sm + (S::NBUF == 2 ? (c & 1) * S::BUF : 0);
+        if (c + 1 < nch) fetch(c + 1);
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+#pragma unroll
+            for (int p = 0; p < 3; ++p)
+#pragma unroll
+                for (int m = 0; m < NM; ++m) ac[p][m] = an[p][m];
+            if (9 * c + tap + 1 < 9 * nch) fetch_a(9 * c + tap + 1);
+            if (active) {
+#pragma unroll
+                for (int nt = 0; nt < ROWS; nt += 2) {
+                    cvs_u32x4 b[2][3];
+#pragma unroll
+                    for (int r = 0; r < 2; ++r)
+#pragma unroll
+                        for (int p = 0; p < 3; ++p)
+                            b[r][p] = buf[4 * p * S::GP + boff + ((nt + r) * STRIDE + tap / 3) * G::PW + (tap % 3)];
+                    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};      // (filter part, input part)
+#pragma unroll
+                    for (int q = 0; q < 6; ++q)
+#pragma unroll
+                        for (int r = 0; r < 2; ++r)
+#pragma unroll
+                            for (int m = 0; m < NM; ++m)
+                                acc[m][nt + r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                                    __builtin_bit_cast(cvs_bf16x8, ac[PA[q]][m]), __builtin_bit_cast(cvs_bf16x8, b[r][PB[q]]),
+                                    acc[m][nt + r], 0, 0, 0);
+                }
+            }
+        }
+        if constexpr (S::NBUF == 1) __syncthreads();             // the one buffer: every wave is done reading it
+        if (c + 1 < nch) stash(sm + (S::NBUF == 2 ? ((c + 1) & 1) * S::BUF : 0));
+        __syncthreads();
+    }
+}
+
 }  // namespace smot

@@ -15,6 +15,9 @@
 //   4 / WR channel pairs x WR row groups: Cout <= 32 -> WR = 4 (all waves share the pair and split the rows); wider layers
 //   take the widest block that still gives every CU a workgroup (dl_conv3_pick): the coarse levels have few tiles.
 //   LDS 13,312 B (stride 1) / 35,904 B (stride 2: 17 x 33 cells per plane, plane stride 561, odd).
+// dla_conv3x3_split_kernel<FT, STRIDE, WR, NM>: the same workgroup for the trees' 3x3 convolutions in SPLIT MODE (the
+//   smot_dla_split_* entry points): three-part bf16 operands on v_mfma_f32_16x16x32_bf16, fp32 accumulation, chunks of 32
+//   input channels (conv3x3_mfma.h, cvs_block); fp32-grade results in another summation order.  The other kernels are shared.
 // dla_conv1x1_kernel<OT>: fpn_lateral_kernel's scheme (64 positions x 32 output channels per workgroup, B operand read in
 //   place) over a VIRTUAL concatenation of up to four source maps, each read as it is or through a 2 x 2 max-pool of a map
 //   twice as fine (torch's max_pool2d: a NaN in the window is the result).  Serves every root and every project.  No LDS.
@@ -40,10 +43,13 @@ constexpr int S7_KS = 37, S7_Q = 10;                 // k-steps; 16-byte A loads
 
 // ---- packed image of one convolution --------------------------------------------------------------------------------
 //   kind 3: cvg_pack_index image (pairs padded to 32 channels), scale [32 pairs], shift [32 pairs]
+//   kind 4: a 3x3 convolution's filters split into three bf16 parts: cvs_pack_index image (dwords of two bf16 each; Cin % 32
+//           == 0), scale [32 pairs], shift [32 pairs] in fp32 as for kind 3
 //   kind 1: [M-tile][group of four k-steps][lane][e] -> W[16 m + lane % 16][16 g + 4 e + lane / 16], scale [Cout], shift [Cout]
 //   kind 7: [M-tile][q 0..9][lane][e] -> W[16 m + lane % 16][k = 4 (4 q + e) + lane / 16] (k < 147, else 0), scale, shift
 __host__ __device__ inline long long dl_conv_floats(int kind, int Cin, int Cout) {
     if (kind == 3) return cvg_packed_floats(Cin, Cout) + 2LL * 32 * ((Cout + 31) / 32);
+    if (kind == 4) return cvs_packed_floats(Cin, Cout) + 2LL * 32 * ((Cout + 31) / 32);
     if (kind == 1) return (long long)Cout * Cin + 2LL * Cout;
     return (long long)(Cout / 16) * S7_Q * 256 + 2LL * Cout;
 }
@@ -53,12 +59,21 @@ dla_pack_kernel(int kind, const float* __restrict__ w, const float* __restrict__
                 int Cin, int Cout, long long total, float* __restrict__ packed) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
-    const long long nw = total - (kind == 3 ? 2LL * 32 * ((Cout + 31) / 32) : 2LL * Cout);
+    const long long nw = total - (kind == 3 || kind == 4 ? 2LL * 32 * ((Cout + 31) / 32) : 2LL * Cout);
     float v = 0.0f;
     if (i < nw) {
         if (kind == 3) {
             const long long s = cvg_pack_index(i, Cin, Cout);
             v = s >= 0 ? w[s] : 0.0f;
+        } else if (kind == 4) {                                  // (a dword of two bf16: stored through the float as bits)
+            int part;
+            const long long s = cvs_pack_index(i, Cin, Cout, &part);
+            if (s >= 0) {
+                unsigned lo[3], hi[3];
+                cvs_split(w[s], lo);
+                cvs_split(w[s + 9], hi);
+                v = __uint_as_float(lo[part] | (hi[part] << 16));
+            }
         } else if (kind == 1) {
             const int e = (int)(i & 3), lane = (int)((i >> 2) & 63);
             const long long t = i >> 8;
@@ -95,6 +110,35 @@ struct DlaConv3Args {
 __device__ __forceinline__ float dl_pool_step(float m, float v) { return (v > m || v != v) ? v : m; }
 __device__ __forceinline__ float dl_pool(const float* __restrict__ q, int Ws) {
     return dl_pool_step(dl_pool_step(dl_pool_step(q[0], q[1]), q[Ws]), q[Ws + 1]);
+}
+
+// dla_conv3x3_kernel's epilogue as a function, for the split kernel below: acc[m][nt] of channel pair `pair`, tile rows
+// row0 + nt at (y0, x) of image planes res / out -> acc * scale + shift (+ the plain or 2 x 2 max-pooled residual), ReLU,
+// store.  (dla_conv3x3_kernel itself keeps the loop in its body, which follows: calling this function from it gives the
+// same values and another register allocation, and the fp32 mode's code is to stay what it was.)
+template <int NM, int ROWS>
+__device__ __forceinline__ void dl_conv3_store(const cv_f32x4 (&acc)[NM][ROWS], int pair, int kq, int x, int y0, int row0, int Cout,
+                                               int Ho, int Wo, int HWo, int res_w, int HWr, int relu,
+                                               const float* __restrict__ scale, const float* __restrict__ shift,
+                                               const float* __restrict__ res, float* __restrict__ out) {
+#pragma unroll
+    for (int m = 0; m < NM; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int ch = 32 * pair + 16 * m + 4 * kq + r;
+            if (ch >= Cout) continue;
+            const float sc = scale[ch], sh = shift[ch];
+#pragma unroll
+            for (int nt = 0; nt < ROWS; ++nt) {
+                const int y = y0 + row0 + nt;
+                if (y < Ho) {
+                    const int o = ch * HWo + y * Wo + x;
+                    float v = add_rn(mul_rn(acc[m][nt][r], sc), sh);
+                    if (res) v = add_rn(v, res_w ? dl_pool(res + ch * HWr + 2 * y * res_w + 2 * x, res_w) : res[o]);
+                    out[o] = relu ? relu_nan(v) : v;
+                }
+            }
+        }
 }
 
 template <typename FT, int STRIDE, int WR, int NM>
@@ -149,6 +193,42 @@ dla_conv3x3_kernel(DlaConv3Args P) {
                 }
         }
     }
+}
+
+// dla_conv3x3_split_kernel<FT, STRIDE, WR, NM>: the same workgroup on v_mfma_f32_16x16x32_bf16 with three-part bf16 operands
+//   (conv3x3_mfma.h, cvs_block): chunks of 32 input channels, P.w the kind-4 packed image, the same epilogue.  LDS 73,728 B
+//   (stride 1: two workgroups per CU) / 107,712 B (stride 2: one, with 512 registers).
+template <typename FT, int STRIDE, int WR, int NM>
+__global__ void __launch_bounds__(256, STRIDE == 1 ? 2 : 1)
+dla_conv3x3_split_kernel(DlaConv3Args P) {
+    using S = CvsGeom<STRIDE>;
+    constexpr int WP = 4 / WR, ROWS = CV_TH / WR;
+    __shared__ __attribute__((aligned(16))) cvs_u32x4 sm[S::SMEM_SLOTS];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int kq = lane >> 4, xl = lane & 15;
+    const int n = blockIdx.x / P.tiles_per_image;
+    const int t = blockIdx.x - n * P.tiles_per_image;
+    const int ty = t / P.tiles_x, tx = t - ty * P.tiles_x;
+    const int y0 = ty * CV_TH, x0 = tx * CV_TW;
+    const int HW = P.H * P.W, HWo = P.Ho * P.Wo, Cout = P.Cout;
+    const FT* __restrict__ in = reinterpret_cast<const FT*>(P.in) + (size_t)n * P.Cin * HW;
+    const int npairs = (Cout + 31) >> 5;
+    const float* __restrict__ scale = P.w + cvs_packed_floats(P.Cin, Cout);
+    const float* __restrict__ shift = scale + 32 * npairs;
+    const int HWr = P.res_w ? P.res_h * P.res_w : HWo;
+    const float* __restrict__ res = P.res ? P.res + (size_t)n * Cout * HWr : nullptr;
+    float* __restrict__ out = P.out + (size_t)n * Cout * HWo;
+    const int wp = WR == 1 ? wave : wave % WP, row0 = WR == 1 ? 0 : (wave / WP) * ROWS;
+
+    CvsPlan<STRIDE> pl;
+    cvs_plan<STRIDE>(pl, tid, y0, x0, P.H, P.W);
+    const int x = x0 + xl;
+    const int pair = blockIdx.y * WP + wp;                      // grid.y: the blocks of 32 WP output channels
+    const bool active = pair < npairs;
+    cv_f32x4 acc[NM][ROWS];
+    cvs_block<FT, STRIDE, WR, NM>(sm, in, HW, P.Cin, pl, P.w, pair, active, tid, row0, acc);
+    if (active && x < P.Wo) dl_conv3_store<NM, ROWS>(acc, pair, kq, x, y0, row0, Cout, P.Ho, P.Wo, HWo, P.res_w, HWr, P.relu, scale, shift, res, out);
 }
 
 // ---- 1x1 over a virtual concatenation ---------------------------------------------------------------------------------------
@@ -361,9 +441,29 @@ static int dl_conv3_pick(const DlaConv3Args& P, int grid, hipStream_t st) {
     return check_launch("dla_conv3x3");
 }
 
-// in [N, Cin, H, W] fp32 -> out [N, Cout, Ho, Wo]; the shapes were checked by the caller (dl_conv3_ok)
+// The split kernel's launch: the same wave split by the same rule (dl_conv3_wr), so a shape runs the same (WR, NM) in both
+// modes; stride 2 has no WR = 1 form here either.
+template <typename FT, int STRIDE>
+static int dl_conv3_pick_split(const DlaConv3Args& P, int grid, hipStream_t st) {
+    const int npairs = (P.Cout + 31) >> 5;
+    const int wr = dl_conv3_wr(STRIDE, P.Cout, grid);
+    const dim3 g(grid, (npairs + 4 / wr - 1) / (4 / wr));
+    if (P.Cout <= 16) {
+        SMOT_LAUNCH((dla_conv3x3_split_kernel<FT, STRIDE, 4, 1>), g, dim3(256), 0, st, P);
+    } else if (wr == 4) {
+        SMOT_LAUNCH((dla_conv3x3_split_kernel<FT, STRIDE, 4, 2>), g, dim3(256), 0, st, P);
+    } else if (wr == 2) {
+        SMOT_LAUNCH((dla_conv3x3_split_kernel<FT, STRIDE, 2, 2>), g, dim3(256), 0, st, P);
+    } else {
+        if constexpr (STRIDE == 1) SMOT_LAUNCH((dla_conv3x3_split_kernel<FT, 1, 1, 2>), g, dim3(256), 0, st, P);
+    }
+    return check_launch("dla_conv3x3_split");
+}
+
+// in [N, Cin, H, W] fp32 -> out [N, Cout, Ho, Wo]; the shapes were checked by the caller (dl_conv3_ok); split: w is a kind-4
+// image and Cin % 32 == 0
 static int dl_conv3(const float* in, int N, int Cin, int H, int W, const float* w, int Cout, int stride, const float* res,
-                    int relu, float* out, hipStream_t st, int res_h = 0, int res_w = 0) {
+                    int relu, float* out, hipStream_t st, int res_h = 0, int res_w = 0, bool split = false) {
     DlaConv3Args P = {};
     P.in = in;
     P.w = w;
@@ -381,6 +481,7 @@ static int dl_conv3(const float* in, int N, int Cin, int H, int W, const float* 
     P.res_h = res_h;
     P.res_w = res_w;
     const int grid = P.tiles_per_image * N;
+    if (split) return stride == 2 ? dl_conv3_pick_split<float, 2>(P, grid, st) : dl_conv3_pick_split<float, 1>(P, grid, st);
     return stride == 2 ? dl_conv3_pick<float, 2>(P, grid, st) : dl_conv3_pick<float, 1>(P, grid, st);
 }
 
@@ -441,7 +542,7 @@ struct DlaConv {
     long long off;           // first float in the packed image
 };
 struct DlaNet {
-    int n;
+    int n, k3;               // k3: the kind of the trees' 3x3 images (3; 4: split operands)
     DlaConv conv[DL_MAX_CONVS];
     long long total;
 };
@@ -455,17 +556,19 @@ static void dl_add(DlaNet& net, int kind, int cin, int cout) {
     net.total += dl_conv_floats(kind, cin, cout);
 }
 // a levels = 1 tree, in the order its launches run: project, tree1.conv1, tree1.conv2, tree2.conv1, tree2.conv2, root
-static void dl_add_tree1(DlaNet& net, int cin, int cout, int root_extra) {
+// (k3: the kind of the tree's 3x3 images: 3, or 4 in split mode)
+static void dl_add_tree1(DlaNet& net, int cin, int cout, int root_extra, int k3) {
     if (cin != cout) dl_add(net, 1, cin, cout);
-    dl_add(net, 3, cin, cout);
-    dl_add(net, 3, cout, cout);
-    dl_add(net, 3, cout, cout);
-    dl_add(net, 3, cout, cout);
+    dl_add(net, k3, cin, cout);
+    dl_add(net, k3, cout, cout);
+    dl_add(net, k3, cout, cout);
+    dl_add(net, k3, cout, cout);
     dl_add(net, 1, 2 * cout + root_extra, cout);
 }
 
 // The convolutions of the network in launch order.  SMOT_ERR_BAD_ARG for null arrays, SMOT_ERR_UNSUPPORTED beyond the capacities.
-static int dla_net(const int* levels, const int* ch, DlaNet& net, const char* who) {
+// split: the trees' 3x3 convolutions are kind 4 (every one has Cin = a channels[k >= 1], a multiple of 32); the stem's stay kind 3.
+static int dla_net(const int* levels, const int* ch, DlaNet& net, const char* who, bool split = false) {
     if (!levels || !ch) {
         set_error("%s: null pointer", who);
         return SMOT_ERR_BAD_ARG;
@@ -481,16 +584,17 @@ static int dla_net(const int* levels, const int* ch, DlaNet& net, const char* wh
     }
     net.n = 0;
     net.total = 0;
+    net.k3 = split ? 4 : 3;
     dl_add(net, 7, 3, ch[0]);
     dl_add(net, 3, ch[0], ch[0]);
     dl_add(net, 3, ch[0], ch[1]);
     for (int k = 2; k < 6; ++k) {
         const int cin = ch[k - 1], cout = ch[k], root = k > 2 ? cin : 0;      // level_root: level3 .. level5
         if (levels[k] == 1) {
-            dl_add_tree1(net, cin, cout, root);
+            dl_add_tree1(net, cin, cout, root, net.k3);
         } else {
-            dl_add_tree1(net, cin, cout, 0);
-            dl_add_tree1(net, cout, cout, root + cout);
+            dl_add_tree1(net, cin, cout, 0, net.k3);
+            dl_add_tree1(net, cout, cout, root + cout, net.k3);
         }
     }
     return SMOT_OK;
@@ -530,10 +634,10 @@ static const float* dl_next(DlaCtx& c, int kind, int cin, int cout) {
     if (v.kind != kind || v.cin != cin || v.cout != cout) c.rc = SMOT_ERR_BAD_ARG;      // (the two walks disagree: a bug)
     return c.dry ? nullptr : c.packed + v.off;
 }
-static void dl_run3(DlaCtx& c, const float* in, int Cin, int H, int W, int Cout, int stride, const float* res, float* out,
-                    int res_h = 0, int res_w = 0) {
-    const float* w = dl_next(c, 3, Cin, Cout);
-    if (!c.dry && !c.rc) c.rc = dl_conv3(in, c.N, Cin, H, W, w, Cout, stride, res, 1, out, c.st, res_h, res_w);
+static void dl_run3(DlaCtx& c, int kind, const float* in, int Cin, int H, int W, int Cout, int stride, const float* res,
+                    float* out, int res_h = 0, int res_w = 0) {
+    const float* w = dl_next(c, kind, Cin, Cout);
+    if (!c.dry && !c.rc) c.rc = dl_conv3(in, c.N, Cin, H, W, w, Cout, stride, res, 1, out, c.st, res_h, res_w, kind == 4);
 }
 static void dl_run1(DlaCtx& c, const DlaSrc* src, int nsrc, int H, int W, int Cout, int relu, void* out, int out_type, float* out32) {
     int K = 0;
@@ -559,12 +663,13 @@ static const float* dl_tree1(DlaCtx& c, const float* x, int cin, int H, int W, i
     float* x1 = dl_alloc(c, on);
     float* t2 = dl_alloc(c, on);
     float* x2 = dl_alloc(c, on);
-    dl_run3(c, x, cin, H, W, cout, stride, nullptr, t1);
+    const int k3 = c.net->k3;
+    dl_run3(c, k3, x, cin, H, W, cout, stride, nullptr, t1);
     // (cin == cout at stride 2: the residual is the pooled input itself, read through the pool)
     const bool rpool = cin == cout && stride == 2;
-    dl_run3(c, t1, cout, Ho, Wo, cout, 1, residual, x1, rpool ? H : 0, rpool ? W : 0);
-    dl_run3(c, x1, cout, Ho, Wo, cout, 1, nullptr, t2);
-    dl_run3(c, t2, cout, Ho, Wo, cout, 1, x1, x2);
+    dl_run3(c, k3, t1, cout, Ho, Wo, cout, 1, residual, x1, rpool ? H : 0, rpool ? W : 0);
+    dl_run3(c, k3, x1, cout, Ho, Wo, cout, 1, nullptr, t2);
+    dl_run3(c, k3, t2, cout, Ho, Wo, cout, 1, x1, x2);
     DlaSrc src[DL_MAX_SRC] = {{x2, cout, 0, Ho, Wo}, {x1, cout, 0, Ho, Wo}};
     int ns = 2;
     if (level_root) src[ns++] = bottom;
@@ -588,8 +693,8 @@ static void dl_stem(DlaCtx& c, const void* image, int in_type, int H, int W, int
     float* x0 = dl_alloc(c, n0);
     const float* a = dl_next(c, 7, 3, c0);
     if (!c.dry && !c.rc) c.rc = dl_conv7(image, in_type, c.N, H, W, a, c0, x, c.st);
-    dl_run3(c, x, c0, H, W, c0, 1, nullptr, x0);
-    dl_run3(c, x0, c0, H, W, c1, 2, nullptr, x1);
+    dl_run3(c, 3, x, c0, H, W, c0, 1, nullptr, x0);
+    dl_run3(c, 3, x0, c0, H, W, c1, 2, nullptr, x1);
 }
 
 static void dl_walk(DlaCtx& c, const void* image, int in_type, int H, int W, const int* levels, const int* ch, void* const* out,
@@ -629,16 +734,24 @@ static int dl_f32_ptr(const void* p) { return p && ((uintptr_t)p & 3) == 0; }
 
 using namespace smot;
 
-extern "C" long long smot_dla_packed_floats(const int* levels, const int* channels) {
+// Every entry point below exists for both operand modes (include/smot_emm.h): `split` selects the trees' 3x3 kernel and
+// packed image, and nothing else.
+static long long dla_packed_floats_impl(const int* levels, const int* channels, bool split) {
     DlaNet net;
-    if (dla_net(levels, channels, net, "dla_packed_floats")) return -1;
+    if (dla_net(levels, channels, net, "dla_packed_floats", split)) return -1;
     return net.total;
 }
+extern "C" long long smot_dla_packed_floats(const int* levels, const int* channels) {
+    return dla_packed_floats_impl(levels, channels, false);
+}
+extern "C" long long smot_dla_split_packed_floats(const int* levels, const int* channels) {
+    return dla_packed_floats_impl(levels, channels, true);
+}
 
-extern "C" int smot_dla_pack(const int* levels, const int* channels, const float* const* w, const float* const* scale,
-                             const float* const* shift, int num_convs, float* packed, smot_stream_t stream) {
+static int dla_pack_impl(const int* levels, const int* channels, const float* const* w, const float* const* scale,
+                         const float* const* shift, int num_convs, float* packed, smot_stream_t stream, bool split) {
     DlaNet net;
-    const int rn = dla_net(levels, channels, net, "dla_pack");
+    const int rn = dla_net(levels, channels, net, "dla_pack", split);
     if (rn) return rn;
     SMOT_REQUIRE(w && scale && shift && packed, "dla_pack: null pointer");
     SMOT_REQUIRE(num_convs == net.n, "dla_pack: %d convolutions passed, the network has %d in launch order", num_convs, net.n);
@@ -653,6 +766,14 @@ extern "C" int smot_dla_pack(const int* levels, const int* channels, const float
     }
     return SMOT_OK;
 }
+extern "C" int smot_dla_pack(const int* levels, const int* channels, const float* const* w, const float* const* scale,
+                             const float* const* shift, int num_convs, float* packed, smot_stream_t stream) {
+    return dla_pack_impl(levels, channels, w, scale, shift, num_convs, packed, stream, false);
+}
+extern "C" int smot_dla_split_pack(const int* levels, const int* channels, const float* const* w, const float* const* scale,
+                                   const float* const* shift, int num_convs, float* packed, smot_stream_t stream) {
+    return dla_pack_impl(levels, channels, w, scale, shift, num_convs, packed, stream, true);
+}
 
 extern "C" long long smot_dla_ws_bytes(const int* levels, const int* channels, int num_images, int H, int W) {
     DlaNet net;
@@ -666,14 +787,14 @@ extern "C" long long smot_dla_ws_bytes(const int* levels, const int* channels, i
     return c.rc ? -1 : c.peak * (long long)sizeof(float);
 }
 
-extern "C" int smot_dla_fwd(const void* image, int in_type, int num_images, int H, int W, const int* levels, const int* channels,
-                            const float* packed, float* ws, void* const* out, int out_type, smot_stream_t stream) {
+static int dla_fwd_impl(const void* image, int in_type, int num_images, int H, int W, const int* levels, const int* channels,
+                        const float* packed, float* ws, void* const* out, int out_type, smot_stream_t stream, bool split) {
     SMOT_REQUIRE(in_type == SMOT_FEAT_F32 || in_type == SMOT_FEAT_F16 || in_type == SMOT_FEAT_BF16,
                  "dla: in_type = %d (SMOT_FEAT_F32, _F16 or _BF16, NCHW)", in_type);
     SMOT_REQUIRE(out_type == SMOT_FEAT_F32 || out_type == SMOT_FEAT_F16 || out_type == SMOT_FEAT_BF16,
                  "dla: out_type = %d (SMOT_FEAT_F32, _F16 or _BF16)", out_type);
     DlaNet net;
-    const int rn = dla_net(levels, channels, net, "dla");
+    const int rn = dla_net(levels, channels, net, "dla", split);
     if (rn == SMOT_ERR_BAD_ARG) return rn;
     SMOT_REQUIRE(num_images >= 1 && num_images <= SMOT_MAX_IMAGES, "dla: num_images = %d (1 .. %d)", num_images, SMOT_MAX_IMAGES);
     SMOT_REQUIRE(image && packed && ws && out, "dla: null pointer");
@@ -702,11 +823,21 @@ extern "C" int smot_dla_fwd(const void* image, int in_type, int num_images, int 
     dl_walk(c, image, in_type, H, W, levels, channels, out, out_type);
     return c.rc;
 }
+extern "C" int smot_dla_fwd(const void* image, int in_type, int num_images, int H, int W, const int* levels, const int* channels,
+                            const float* packed, float* ws, void* const* out, int out_type, smot_stream_t stream) {
+    return dla_fwd_impl(image, in_type, num_images, H, W, levels, channels, packed, ws, out, out_type, stream, false);
+}
+// (the workspace is the fp32 mode's: smot_dla_ws_bytes)
+extern "C" int smot_dla_split_fwd(const void* image, int in_type, int num_images, int H, int W, const int* levels,
+                                  const int* channels, const float* packed, float* ws, void* const* out, int out_type,
+                                  smot_stream_t stream) {
+    return dla_fwd_impl(image, in_type, num_images, H, W, levels, channels, packed, ws, out, out_type, stream, true);
+}
 
 // ---- the three operators alone -------------------------------------------------------------------------------------------------
-extern "C" int smot_dla_conv3x3_fwd(const float* x, int num_images, int Cin, int H, int W, const float* w, const float* scale,
-                                    const float* shift, int Cout, int stride, const float* residual, int residual_h,
-                                    int residual_w, int relu, float* packed, float* out, smot_stream_t stream) {
+static int dla_conv3x3_impl(const float* x, int num_images, int Cin, int H, int W, const float* w, const float* scale,
+                            const float* shift, int Cout, int stride, const float* residual, int residual_h, int residual_w,
+                            int relu, float* packed, float* out, smot_stream_t stream, bool split) {
     SMOT_REQUIRE(dl_f32_ptr(x) && dl_f32_ptr(w) && dl_f32_ptr(scale) && dl_f32_ptr(shift) && dl_f32_ptr(out) &&
                      (!residual || dl_f32_ptr(residual)),
                  "dla_conv3x3: a null or misaligned pointer");
@@ -717,8 +848,10 @@ extern "C" int smot_dla_conv3x3_fwd(const float* x, int num_images, int Cin, int
     const bool rpool = residual && (residual_h != 0 || residual_w != 0);
     SMOT_REQUIRE(!rpool || (residual_h / 2 == Ho && residual_w / 2 == Wo),
                  "dla_conv3x3: a pooled residual of %d x %d for an output of %d x %d", residual_h, residual_w, Ho, Wo);
-    if (Cin < 8 || Cin % 8 != 0 || Cin > 1024 || Cout < 16 || Cout % 16 != 0 || (Cout > 16 && Cout % 32 != 0) || Cout > 1024) {
-        set_error("dla_conv3x3: Cin = %d, Cout = %d (supported: Cin a multiple of 8, Cout 16 or a multiple of 32, up to 1024)", Cin, Cout);
+    const int cstep = split ? CVS_IC : CV_IC;
+    if (Cin < cstep || Cin % cstep != 0 || Cin > 1024 || Cout < 16 || Cout % 16 != 0 || (Cout > 16 && Cout % 32 != 0) || Cout > 1024) {
+        set_error("dla_conv3x3: Cin = %d, Cout = %d (supported: Cin a multiple of %d, Cout 16 or a multiple of 32, up to 1024)", Cin,
+                  Cout, cstep);
         return SMOT_ERR_UNSUPPORTED;
     }
     if ((long long)H * W * (Cin > Cout ? Cin : Cout) >= (1LL << 31) || (long long)H * W / 128 * num_images >= (1LL << 31) ||
@@ -727,10 +860,28 @@ extern "C" int smot_dla_conv3x3_fwd(const float* x, int num_images, int Cin, int
         return SMOT_ERR_UNSUPPORTED;
     }
     hipStream_t st = (hipStream_t)stream;
-    const int rp = dl_pack_launch(3, w, scale, shift, Cin, Cout, packed, st);
+    const int rp = dl_pack_launch(split ? 4 : 3, w, scale, shift, Cin, Cout, packed, st);
     if (rp) return rp;
     return dl_conv3(x, num_images, Cin, H, W, packed, Cout, stride, residual, relu ? 1 : 0, out, st, rpool ? residual_h : 0,
-                    rpool ? residual_w : 0);
+                    rpool ? residual_w : 0, split);
+}
+extern "C" int smot_dla_conv3x3_fwd(const float* x, int num_images, int Cin, int H, int W, const float* w, const float* scale,
+                                    const float* shift, int Cout, int stride, const float* residual, int residual_h,
+                                    int residual_w, int relu, float* packed, float* out, smot_stream_t stream) {
+    return dla_conv3x3_impl(x, num_images, Cin, H, W, w, scale, shift, Cout, stride, residual, residual_h, residual_w, relu, packed,
+                            out, stream, false);
+}
+extern "C" int smot_dla_conv3x3_split_fwd(const float* x, int num_images, int Cin, int H, int W, const float* w,
+                                          const float* scale, const float* shift, int Cout, int stride, const float* residual,
+                                          int residual_h, int residual_w, int relu, float* packed, float* out,
+                                          smot_stream_t stream) {
+    return dla_conv3x3_impl(x, num_images, Cin, H, W, w, scale, shift, Cout, stride, residual, residual_h, residual_w, relu, packed,
+                            out, stream, true);
+}
+
+// (both modes pick the wave split by dl_conv3_wr: the split twin answers for its own launch site)
+extern "C" int smot_dla_conv3x3_split_form(int num_images, int H, int W, int Cout, int stride) {
+    return smot_dla_conv3x3_form(num_images, H, W, Cout, stride);
 }
 
 extern "C" int smot_dla_conv3x3_form(int num_images, int H, int W, int Cout, int stride) {
@@ -745,6 +896,13 @@ extern "C" long long smot_dla_conv_packed_floats(int kernel_size, int Cin, int C
     if (kernel_size == 3 && Cin % 8 != 0) return -1;
     if (kernel_size == 1 && Cin % 16 != 0) return -1;
     return dl_conv_floats(kernel_size, Cin, Cout);
+}
+
+// the same in split mode: the 3x3 image is kind 4 (Cin % 32 == 0); the 1x1 and 7x7 images are the fp32 mode's
+extern "C" long long smot_dla_conv_split_packed_floats(int kernel_size, int Cin, int Cout) {
+    if (kernel_size != 3) return smot_dla_conv_packed_floats(kernel_size, Cin, Cout);
+    if (Cin < 1 || Cin % CVS_IC != 0 || Cout < 16 || Cout % 16 != 0) return -1;
+    return dl_conv_floats(4, Cin, Cout);
 }
 
 extern "C" int smot_dla_conv1x1_fwd(const float* const* sources, const int* source_channels, const int* source_pooled,

@@ -12,7 +12,9 @@ Two forms of the operator live here:
 
 * ``DLA.forward`` on device images within ``ops.dla``'s capacities: every convolution on the fp32 matrix cores with the BN,
   the residual and the ReLU in its epilogue, the ``cat`` and the max-pool read in place by the 1x1 kernel (37 launches for
-  DLA-34, no host synchronisation); ``out_dtype`` half stores the stage maps rounded once;
+  DLA-34, no host synchronisation); ``out_dtype`` half stores the stage maps rounded once; ``operands="split16"`` runs the
+  trees' 3x3 convolutions on the 16-bit matrix instruction with three-part bf16 operands and fp32 accumulation instead
+  (fp32-grade results in another summation order, no dependence on the data's range; INTEGRATION.md §3n);
 * ``dla_torch``: the same as a plain torch composition over the module tree.  It is the path for CPU tensors, images that
   are not contiguous NCHW, trainable parameters under grad mode and shapes beyond the capacities (counted in
   ``ops.FALLBACKS["dla_torch"]`` for device tensors), and the baseline of tools/dla_bench.py.
@@ -127,10 +129,15 @@ class DLA(nn.Module):
     """Upstream's ``DLA(levels, channels, block=DlaBasic)`` as a feature extractor: ``forward(images [N, 3, H, W])`` -> the
     list of the four stage maps (strides 4, 8, 16, 32), H and W multiples of 32.  ``out_dtype``: the element type of the
     returned maps (float32, float16 or bfloat16: the fp32 result rounded once; the next stage reads the fp32 value).  On
-    the device path the packed weights are rebuilt when a parameter's or buffer's ``_version``, storage or device changes."""
+    the device path the packed weights are rebuilt when a parameter's or buffer's ``_version``, storage or device changes.
+    ``operands``: "fp32" (the default) or "split16": which kernel the device path runs for the trees' 3x3 convolutions
+    (module docstring); the torch composition, the ``state_dict`` and what ``kernel_ok`` admits do not depend on it."""
 
-    def __init__(self, levels, channels, out_dtype=torch.float32):
+    def __init__(self, levels, channels, out_dtype=torch.float32, operands="fp32"):
         super(DLA, self).__init__()
+        if operands not in ops.DLA_OPERANDS:
+            raise ValueError("DLA: operands must be \"fp32\" or \"split16\", got %r" % (operands,))
+        self.operands = operands
         levels, channels = tuple(int(v) for v in levels), tuple(int(v) for v in channels)
         if len(levels) != 6 or len(channels) != 6:
             raise ValueError("DLA: six levels and six channel counts, got %r and %r" % (levels, channels))
@@ -179,17 +186,17 @@ class DLA(nn.Module):
 
     def packed(self):
         tensors = list(self.parameters()) + list(self.buffers())
-        key = tuple((t.data_ptr(), t._version, t.device) for t in tensors)
+        key = (self.operands,) + tuple((t.data_ptr(), t._version, t.device) for t in tensors)
         if key != self._packed_key:
             with torch.no_grad():
                 convs = [(c.weight.detach(),) + tuple(t.contiguous() for t in bn.scale_shift()) for c, bn in self.convs()]
-                self._packed = ops.dla_pack(convs, self.levels, self.channels)
+                self._packed = ops.dla_pack(convs, self.levels, self.channels, operands=self.operands)
             self._packed_key = key
         return self._packed
 
     def forward(self, images):
         if self.kernel_ok(images):
-            return ops.dla(images, self.packed(), self.levels, self.channels, out_dtype=self.out_dtype)
+            return ops.dla(images, self.packed(), self.levels, self.channels, out_dtype=self.out_dtype, operands=self.operands)
         if isinstance(images, torch.Tensor) and images.is_cuda:
             ops.FALLBACKS["dla_torch"] += 1
         out = dla_torch(self, images)
@@ -198,14 +205,14 @@ class DLA(nn.Module):
         return out
 
 
-def dla_34(out_dtype=torch.float32):
-    return DLA((1, 1, 1, 2, 2, 1), (16, 32, 64, 128, 256, 512), out_dtype=out_dtype)
+def dla_34(out_dtype=torch.float32, operands="fp32"):
+    return DLA((1, 1, 1, 2, 2, 1), (16, 32, 64, 128, 256, 512), out_dtype=out_dtype, operands=operands)
 
 
 BODIES = {"DLA-34-FPN": dla_34}
 
 
-def build_dla(cfg, out_dtype=torch.float32):
+def build_dla(cfg, out_dtype=torch.float32, operands="fp32"):
     """The body of the config's ``MODEL.BACKBONE.CONV_BODY``.  ``DLA-34-FPN`` is the one this package has; any other body, and
     any true entry of ``MODEL.DLA.STAGE_WITH_DCN`` (deformable convolutions), raises a ``ValueError`` that names it."""
     name = cfg.MODEL.BACKBONE.CONV_BODY
@@ -215,7 +222,7 @@ def build_dla(cfg, out_dtype=torch.float32):
     if any(dcn):
         raise ValueError("build_dla: MODEL.DLA.STAGE_WITH_DCN = %r asks for deformable convolutions, which this package does "
                          "not have" % (dcn,))
-    body = BODIES[name](out_dtype=out_dtype)
+    body = BODIES[name](out_dtype=out_dtype, operands=operands)
     dla = cfg.MODEL.DLA
     stages = (dla.DLA_STAGE2_OUT_CHANNELS, dla.DLA_STAGE3_OUT_CHANNELS, dla.DLA_STAGE4_OUT_CHANNELS, dla.DLA_STAGE5_OUT_CHANNELS)
     if tuple(stages) != tuple(body.out_channels):

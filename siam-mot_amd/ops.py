@@ -166,6 +166,12 @@ _SIGNATURES = {
     "smot_dla_conv1x1_fwd": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp]),
     "smot_dla_stem_ws_bytes": (ctypes.c_longlong, [_i, _i, _i, _i, _i]),
     "smot_dla_stem_fwd": (ctypes.c_int, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "smot_dla_split_packed_floats": (ctypes.c_longlong, [_vp, _vp]),
+    "smot_dla_split_pack": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "smot_dla_split_fwd": (ctypes.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "smot_dla_conv_split_packed_floats": (ctypes.c_longlong, [_i, _i, _i]),
+    "smot_dla_conv3x3_split_fwd": (ctypes.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "smot_dla_conv3x3_split_form": (ctypes.c_int, [_i, _i, _i, _i, _i]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 _DEBUG_SIGNATURES = {
@@ -1591,33 +1597,48 @@ def _int6(v):
     return (ctypes.c_int * 6)(*[int(x) for x in v])
 
 
-def dla_pack(convs, levels, channels):
-    """The body's parameters in the operand order of ``dla`` (``smot_dla_pack``: one launch per convolution, no
-    synchronisation).  convs: ``(weight [Cout, Cin, k, k], scale [Cout], shift [Cout])`` per convolution in LAUNCH ORDER
+# ``operands`` of the DLA operators: "fp32": every convolution on the fp32 matrix instruction; "split16": the trees' 3x3
+# convolutions on the 16-bit matrix instruction with three-part bf16 operands and fp32 accumulation (fp32-grade results;
+# include/smot_emm.h, DLA BACKBONE, SPLIT OPERANDS)
+DLA_OPERANDS = ("fp32", "split16")
+
+
+def _dla_split(operands, who):
+    if operands not in DLA_OPERANDS:
+        raise ValueError("siammot_amd.%s: operands must be \"fp32\" or \"split16\", got %r" % (who, operands))
+    return operands == "split16"
+
+
+def dla_pack(convs, levels, channels, operands="fp32"):
+    """The body's parameters in the operand order of ``dla`` (``smot_dla_pack``, or ``smot_dla_split_pack`` for ``operands``
+    "split16": the image of one mode does not serve the other; one launch per convolution, no synchronisation).  convs: ``(weight [Cout, Cin, k, k], scale [Cout], shift [Cout])`` per convolution in LAUNCH ORDER
     (include/smot_emm.h; ``dla.DLA.convs()``), fp32 device tensors, ``scale`` / ``shift`` the frozen BN's.  -> fp32
     ``[smot_dla_packed_floats]``."""
     lib = _lib or load_library()
+    split = _dla_split(operands, "dla_pack")
     lv, ch = _int6(levels), _int6(channels)
-    n = lib.smot_dla_packed_floats(_cast(lv), _cast(ch))
+    n = (lib.smot_dla_split_packed_floats if split else lib.smot_dla_packed_floats)(_cast(lv), _cast(ch))
     if n < 0:
         _check(-2, "dla_pack")
     ts = [[_chk(t, "dla_pack: convs[%d][%d]" % (i, j), tuple(t.shape)) for j, t in enumerate(c)] for i, c in enumerate(convs)]
     packed = torch.empty((n,), dtype=_F32, device=ts[0][0].device)
     arrays = [(ctypes.c_void_p * len(ts))(*[c[j].data_ptr() for c in ts]) for j in range(3)]
     with _Launch(*[t for c in ts for t in c]) as ln:
-        rc = lib.smot_dla_pack(_cast(lv), _cast(ch), _cast(arrays[0]), _cast(arrays[1]), _cast(arrays[2]), len(ts), _ptr(packed),
-                               ln.stream)
+        rc = (lib.smot_dla_split_pack if split else lib.smot_dla_pack)(
+            _cast(lv), _cast(ch), _cast(arrays[0]), _cast(arrays[1]), _cast(arrays[2]), len(ts), _ptr(packed), ln.stream)
     _check(rc, "dla_pack")
     return packed
 
 
-def dla(images, packed, levels, channels, out_dtype=torch.float32):
+def dla(images, packed, levels, channels, out_dtype=torch.float32, operands="fp32"):
     """Upstream's ``DLA.forward`` (DlaBasic blocks, frozen BN) on all images of a call (``smot_dla_fwd``: 37 launches for
     DLA-34), free of host synchronisation.  images: ``[N, 3, H, W]`` fp32, fp16 or bf16 (a half call returns the bits of the
     call on ``.float()``), H and W multiples of 32; anything but contiguous NCHW is copied.  packed: ``dla_pack``'s tensor.
     -> the four contiguous NCHW stage maps ``[N, channels[k], H >> k, W >> k]``, k = 2 .. 5, of ``out_dtype`` (a half output
-    is the fp32 value rounded to nearest even; the next stage reads the fp32 value)."""
+    is the fp32 value rounded to nearest even; the next stage reads the fp32 value).  ``operands``: the mode ``packed`` was
+    made for (``smot_dla_split_fwd`` for "split16")."""
     lib = _lib or load_library()
+    split = _dla_split(operands, "dla")
     if out_dtype not in FEAT_TYPES:
         raise RuntimeError("siammot_amd.dla: out_dtype must be float32, float16 or bfloat16, got %s" % (out_dtype,))
     x = _dev_feat(images, "images")
@@ -1632,26 +1653,31 @@ def dla(images, packed, levels, channels, out_dtype=torch.float32):
     out = [torch.empty((N, int(channels[k]), H >> k, W >> k), dtype=out_dtype, device=x.device) for k in range(2, 6)]
     po = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in out])
     with _Launch(x, packed) as ln:
-        rc = lib.smot_dla_fwd(_ptr(x), FEAT_TYPES[x.dtype], N, H, W, _cast(lv), _cast(ch), _ptr(packed), _ptr(ws), _cast(po),
-                              FEAT_TYPES[out_dtype], ln.stream)
+        rc = (lib.smot_dla_split_fwd if split else lib.smot_dla_fwd)(
+            _ptr(x), FEAT_TYPES[x.dtype], N, H, W, _cast(lv), _cast(ch), _ptr(packed), _ptr(ws), _cast(po), FEAT_TYPES[out_dtype],
+            ln.stream)
     _check(rc, "dla")
     return out
 
 
-def dla_conv3x3_form(N, H, W, Cout, stride):
+def dla_conv3x3_form(N, H, W, Cout, stride, operands="fp32"):
     """Which form of the 3x3 kernel ``dla_conv3x3`` runs for ``N`` images of ``H x W`` (``smot_dla_conv3x3_form``): ``(WR,
     NM)`` — the row groups of a workgroup's four waves (1, 2 or 4) and the M-tiles per channel pair."""
-    form = (_lib or load_library()).smot_dla_conv3x3_form(int(N), int(H), int(W), int(Cout), int(stride))
+    lib = _lib or load_library()
+    fn = lib.smot_dla_conv3x3_split_form if _dla_split(operands, "dla_conv3x3_form") else lib.smot_dla_conv3x3_form
+    form = fn(int(N), int(H), int(W), int(Cout), int(stride))
     if form < 0:
         raise RuntimeError("siammot_amd.dla_conv3x3_form: bad argument")
     return form // 10, form % 10
 
 
-def dla_conv3x3(x, w, scale, shift, stride, residual=None, relu=True, residual_pooled=False):
+def dla_conv3x3(x, w, scale, shift, stride, residual=None, relu=True, residual_pooled=False, operands="fp32"):
     """``relu(conv3x3(x, w, stride, pad 1) * scale + shift + residual)`` (``smot_dla_conv3x3_fwd``; residual and ReLU
     optional): x ``[N, Cin, H, W]`` fp32 -> ``[N, Cout, Ho, Wo]`` fp32, any H, W >= 1.  ``residual_pooled``: the residual is
-    ``[N, Cout, Hr, Wr]`` with ``Hr // 2 == Ho``, ``Wr // 2 == Wo`` and is read through ``max_pool2d(., 2, 2)``."""
+    ``[N, Cout, Hr, Wr]`` with ``Hr // 2 == Ho``, ``Wr // 2 == Wo`` and is read through ``max_pool2d(., 2, 2)``.
+    ``operands`` "split16": ``smot_dla_conv3x3_split_fwd`` (``Cin`` a multiple of 32)."""
     lib = _lib or load_library()
+    split = _dla_split(operands, "dla_conv3x3")
     x = _dev_f32(x, "x")
     N, Cin, H, W = (int(v) for v in x.shape)
     Cout = int(w.shape[0])
@@ -1664,12 +1690,13 @@ def dla_conv3x3(x, w, scale, shift, stride, residual=None, relu=True, residual_p
         residual = _chk(residual, "residual", (N, Cout, rh, rw))
     elif residual is not None:
         residual = _chk(residual, "residual", (N, Cout, Ho, Wo))
-    n = lib.smot_dla_conv_packed_floats(3, Cin, Cout)
+    n = (lib.smot_dla_conv_split_packed_floats if split else lib.smot_dla_conv_packed_floats)(3, Cin, Cout)
     packed = torch.empty((max(n, 4),), dtype=_F32, device=x.device)
     out = torch.empty((N, Cout, Ho, Wo), dtype=_F32, device=x.device)
     with _Launch(x, w, scale, shift, residual) as ln:
-        rc = lib.smot_dla_conv3x3_fwd(_ptr(x), N, Cin, H, W, _ptr(w), _ptr(scale), _ptr(shift), Cout, int(stride), _ptr(residual),
-                                      rh, rw, 1 if relu else 0, _ptr(packed), _ptr(out), ln.stream)
+        rc = (lib.smot_dla_conv3x3_split_fwd if split else lib.smot_dla_conv3x3_fwd)(
+            _ptr(x), N, Cin, H, W, _ptr(w), _ptr(scale), _ptr(shift), Cout, int(stride), _ptr(residual), rh, rw, 1 if relu else 0,
+            _ptr(packed), _ptr(out), ln.stream)
     _check(rc, "dla_conv3x3")
     return out
 

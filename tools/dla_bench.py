@@ -2,6 +2,7 @@
 detections.
 
     python tools/dla_bench.py [--steps K] [--warmup W] [--out profiles/dla_bench.json] [--quick] [--forms AHB]
+    python tools/dla_bench.py --forms AHBC --out profiles/dla_split_bench.json
 
 Cases: the headline 704 x 1280 frame with 1 and with 4 images, fp32 and fp16 images; the recipe's parameters
 (tests/dla_cases.py: activations of the size a trained network has, about half of them zero).  One step = all images.  Forms,
@@ -10,10 +11,12 @@ timed in ONE process, interleaved (A B A B ...) so that clock drift favours neit
     A  ``siammot_amd.dla.dla_torch`` on the device: 36 convolutions, 36 frozen-BN affines, ReLUs, cats and max-pools as torch
        operators (MIOpen), fp32 arithmetic on the upcast image — the arithmetic of B;
     H  (fp16 images only) the same composition with fp16 parameters: what an all-half pipeline would run, other arithmetic;
-    B  ``siammot_amd.dla.DLA.forward``: 37 launches of csrc/dla.hip.
+    B  ``siammot_amd.dla.DLA.forward``: 37 launches of csrc/dla.hip;
+    C  the same module with ``operands="split16"`` (the trees' 3x3 convolutions on three-part bf16 operands); with C the
+       result also carries ``B_spread_us``, ``B_minus_C_us`` and whether C is below B by more than B's spread.
 
 ``frames_to_fpn``: A = the torch body and ``fpn_torch``, B = ``backbone(images)``.  ``frames_to_detections``: A = the torch body,
-then ``DetectionHead.forward_stages``; B = ``DetectionHead.forward_images``.
+then ``DetectionHead.forward_stages``; B = ``DetectionHead.forward_images``.  C = B with a split-mode body of the same parameters.
 
 Timed with device events around a loop; the K steps of a form are split over four interleaved repeats and ``A_spread_us`` is
 the spread (max - min) of A's per-call time over them.  Nothing is promised: the tool reports A, B and the spread as measured
@@ -45,10 +48,21 @@ def make_images(N, dtype, dev, seed):
     return torch.randn((N, 3) + NET_HW, generator=g).to(dev).to(dtype)
 
 
-def make_body(dev):
+def make_body(dev, operands="fp32"):
     from siammot_amd.dla import dla_34
-    body = dla_34()
+    body = dla_34(operands=operands)
     return D.load(body, D.params(body, D.SEED), dev)
+
+
+def against_b(out):
+    """B's spread over the repeats and where C stands against B, as ``interleave`` does for B against A."""
+    b, c = out.get("B_hip_kernel"), out.get("C_hip_split16")
+    if b and c:
+        out["B_spread_us"] = max(b["us_per_call_repeats"]) - min(b["us_per_call_repeats"])
+        out["B_minus_C_us"] = b["us_per_call"] - c["us_per_call"]
+        out["B_over_C_time"] = b["us_per_call"] / c["us_per_call"]
+        out["C_below_B_by_more_than_B_spread"] = bool(out["B_minus_C_us"] > out["B_spread_us"])
+    return out
 
 
 def run_body_case(N, dtype, steps, warmup, dev, forms):
@@ -63,8 +77,15 @@ def run_body_case(N, dtype, steps, warmup, dev, forms):
         steppers["H"] = lambda k: dla_torch(half, sets[k & 1])
     if "B" in forms:
         steppers["B"] = lambda k: body(sets[k & 1])
+    if "C" in forms:
+        split = make_body(dev, "split16")
+        steppers["C"] = lambda k: split(sets[k & 1])
     out = {"case": "body", "images": N, "image_dtype": str(dtype).replace("torch.", ""), "net_hw": list(NET_HW), "steps": steps}
-    out.update(interleave(steppers, steps, warmup))
+    out.update(against_b(interleave(steppers, steps, warmup)))
+    if "B" in steppers and "C" in steppers:
+        with torch.no_grad():
+            b, c = steppers["B"](0), steppers["C"](0)
+        out["max_difference_B_C_of_stage_max"] = [float((x - y).abs().max() / x.abs().max()) for x, y in zip(b, c)]
     if "A" in steppers and "B" in steppers:
         with torch.no_grad():
             a, b = steppers["A"](0), steppers["B"](0)
@@ -86,21 +107,30 @@ def run_pipeline_case(N, steps, warmup, dev, forms):
     with torch.no_grad():
         for p in det.rpn_head._params():
             p.normal_(0.0, 0.05)
+    det_c = None
+    if "C" in forms:                                                  # the same detector over a split-mode body
+        from siammot_amd.backbone import build_backbone
+        torch.manual_seed(4)
+        det_c = build_detection_head(cfg, BoxCoder((1.0, 1.0, 1.0, 1.0)), CHANNELS,
+                                     backbone=build_backbone(cfg, operands="split16")).to(dev).eval()
+        det_c.load_state_dict(det.state_dict())
     sets = [make_images(N, torch.float32, dev, 21 + k) for k in range(2)]
     size = (NET_HW[1], NET_HW[0])
     inner, layer = fpn._blocks()
     results = []
-    for case, a, b in (("frames_to_fpn", lambda k: fpn_torch(dla_torch(body, sets[k & 1]), inner, layer, fpn.top_blocks),
-                        lambda k: det.backbone(sets[k & 1])),
-                       ("frames_to_detections", lambda k: det.forward_stages(dla_torch(body, sets[k & 1]), size)[1],
-                        lambda k: det.forward_images(sets[k & 1], size)[1])):
+    for case, a, b, c in (("frames_to_fpn", lambda k: fpn_torch(dla_torch(body, sets[k & 1]), inner, layer, fpn.top_blocks),
+                           lambda k: det.backbone(sets[k & 1]), lambda k: det_c.backbone(sets[k & 1])),
+                          ("frames_to_detections", lambda k: det.forward_stages(dla_torch(body, sets[k & 1]), size)[1],
+                           lambda k: det.forward_images(sets[k & 1], size)[1], lambda k: det_c.forward_images(sets[k & 1], size)[1])):
         steppers = {}
         if "A" in forms:
             steppers["A"] = a
         if "B" in forms:
             steppers["B"] = b
+        if det_c is not None:
+            steppers["C"] = c
         out = {"case": case, "images": N, "image_dtype": "float32", "net_hw": list(NET_HW), "channels": CHANNELS, "steps": steps}
-        out.update(interleave(steppers, steps, warmup))
+        out.update(against_b(interleave(steppers, steps, warmup)))
         results.append(out)
     return results
 
@@ -111,7 +141,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None, help="write the JSON result here as well")
     ap.add_argument("--quick", action="store_true", help="one fp32 image, the body only (for the kernel-trace runs)")
-    ap.add_argument("--forms", default="AHB", help="which of the forms A, H, B to run")
+    ap.add_argument("--forms", default="AHB", help="which of the forms A, H, B, C to run")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a ROCm device"
     dev = torch.device("cuda:0")

@@ -40,7 +40,7 @@ REPEATS = 4
 NET_HW = (704, 1280)
 STRIDES = (4, 8, 16, 32, 64)
 CHANNELS = 128
-LABELS = {"A": "A_torch_composition", "H": "H_torch_half_weights", "B": "B_hip_kernel"}
+LABELS = {"A": "A_torch_composition", "H": "H_torch_half_weights", "B": "B_hip_kernel", "C": "C_hip_split16"}
 
 
 def make_maps(N, dtype, dev, seed):
