@@ -1256,6 +1256,66 @@ int smot_dla_conv3x3_split_fwd(const float* x, int num_images, int Cin, int H, i
                                int relu, float* packed, float* out, smot_stream_t stream);
 int smot_dla_conv3x3_split_form(int num_images, int H, int W, int Cout, int stride);
 
+/* DLA BACKBONE, BOTTLENECK BLOCKS AND DEEPER TREES: upstream's DLA(levels, channels, block, residual_root) for block =
+ * DlaBasic or DlaBottleneck (cardinality 1, base width 64) and trees of depth 1 .. 5: DLA-34, DLA-46-C, DLA-60, DLA-102,
+ * DLA-169.  A second family next to smot_dla_*, with the DLA BACKBONE block's conventions (frozen BN, ReLU, pool, image, out,
+ * ws, packed, "launch order", alignment, error codes) and these definitions:
+ *
+ *   bottleneck(x, s, residual) = relu(cb1x1(relu(cb3x3(relu(cb1x1(x, cin -> mid)), mid -> mid, stride s)), mid -> cout)
+ *                                     + residual),  mid = cout / 2; conv1 runs at the block's INPUT resolution, the stride
+ *                                is on the 3x3, as upstream
+ *   block          SMOT_DLA_BLOCK_BASIC: basic(x, s, residual) of the DLA BACKBONE block; SMOT_DLA_BLOCK_BOTTLENECK: the above
+ *   tree(1, x, cin -> cout, s, level_root, handed):  as in the DLA BACKBONE block with `block` for `basic`; with
+ *       residual_root != 0 the root is relu(cb1x1(cat(x2, x1, ...)) + x2): every root adds its first source before the ReLU
+ *   tree(n, x, cin -> cout, s, level_root, handed), n = 2 .. 5:  bottom as above
+ *       t = tree(n - 1, x, cin -> cout, s, no level_root, nothing handed)
+ *       tree(n - 1, t, cout -> cout, 1, no level_root, [bottom if level_root] + handed + [t])
+ *       so the innermost root reads (x2, x1, [bottom], t of the outermost tree, ..., t of its parent): n + 2 maps for a
+ *       level with level_root, n + 1 for level2.  A project is evaluated only in a depth-1 tree with cin != cout; the outer
+ *       ones are not computed and not in the packed image.
+ *   launches       = evaluated convolutions (smot_dla_net_num_convs; the stem's 3 included): per depth-1 tree project (if cin
+ *                  != cout), tree1.conv1 .. conv3 (conv1, conv2 for basic), tree2.conv1 .., root; a deeper tree is its tree1
+ *                  then its tree2.  DLA-34 37, DLA-46-C 48, DLA-60 63, DLA-102 105, DLA-169 168.
+ *   split          != 0: the trees' 3x3 convolutions on the split-operand kernel and image (SPLIT OPERANDS above); every 1x1,
+ *                  the stem and the workspace are the fp32 mode's.
+ *   ws             smot_dla_net_ws_bytes(...) bytes.  A block's intermediate maps are released when the block returns and a
+ *                  subtree's maps when its root has been written: a depth-n tree holds n - 1 tree1 results, one depth-1
+ *                  tree's project, x1 and x2 and one block's intermediates at a time, whatever the number of blocks.
+ *   contract       image i of a call equals the one-image call bit for bit; deterministic; no host synchronisation and no
+ *                  allocation.  With block = BASIC, residual_root = 0 and levels[2..5] in {1, 2} the packed image has
+ *                  smot_dla_packed_floats' (smot_dla_split_packed_floats') size and layout and smot_dla_net_fwd returns bit
+ *                  for bit what smot_dla_fwd (smot_dla_split_fwd) returns.
+ *   capacities     levels[0] == levels[1] == 1, levels[2..5] in 1 .. 5; channels[0] in {16, 32}; channels[1] % 32 == 0;
+ *                  channels[2..5] % 32 == 0 (basic) or % 64 == 0 (bottleneck: mid % 32 == 0), all <= 1024; images as for
+ *                  smot_dla_fwd, with a bottleneck's conv1 map (twice a level's own map) below 2^31 elements as well
+ *                  (SMOT_ERR_UNSUPPORTED beyond).  block another value, null or misaligned pointers, num_images, in_type,
+ *                  out_type: SMOT_ERR_BAD_ARG.  The size functions and smot_dla_net_num_convs return -1 for what
+ *                  smot_dla_net_fwd refuses.  Nothing is launched by a refused call.
+ *
+ *   smot_dla_conv1x1_res_fwd   smot_dla_conv1x1_fwd with num_sources 1 .. 8 and an optional residual:
+ *                  out = relu?(conv1x1(cat(sources)) * scale + shift + residual), one fp32 addition after the BN and before
+ *                  the ReLU (a NaN or inf residual cell reaches exactly its own output cell).  residual: null, or
+ *                  [N, Cout, H, W] fp32 with residual_h = residual_w = 0, or [N, Cout, residual_h, residual_w] read through
+ *                  the 2x2 max-pool (residual_h / 2 == H, residual_w / 2 == W; SMOT_ERR_BAD_ARG otherwise), as
+ *                  smot_dla_conv3x3_fwd's.  It is only read and may be one of the sources.  The K order is the
+ *                  concatenation's order; with <= 4 sources and no residual the call returns the bits of smot_dla_conv1x1_fwd.
+ */
+#define SMOT_DLA_BLOCK_BASIC 0
+#define SMOT_DLA_BLOCK_BOTTLENECK 1
+int smot_dla_net_num_convs(const int* levels, const int* channels, int block);
+long long smot_dla_net_packed_floats(const int* levels, const int* channels, int block, int residual_root, int split);
+int smot_dla_net_pack(const int* levels, const int* channels, int block, int residual_root, int split, const float* const* w,
+                      const float* const* scale, const float* const* shift, int num_convs, float* packed, smot_stream_t stream);
+long long smot_dla_net_ws_bytes(const int* levels, const int* channels, int block, int residual_root, int num_images, int H,
+                                int W);
+int smot_dla_net_fwd(const void* image, int in_type, int num_images, int H, int W, const int* levels, const int* channels,
+                     int block, int residual_root, int split, const float* packed, float* ws, void* const* out, int out_type,
+                     smot_stream_t stream);
+int smot_dla_conv1x1_res_fwd(const float* const* sources, const int* source_channels, const int* source_pooled,
+                             const int* source_heights, const int* source_widths, int num_sources, int num_images, int H, int W,
+                             const float* w, const float* scale, const float* shift, int Cout, int relu, const float* residual,
+                             int residual_h, int residual_w, float* packed, void* out, int out_type, smot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,18 +22,25 @@ class CfgNode(dict):
         return CfgNode({k: (v.clone() if isinstance(v, CfgNode) else v) for k, v in self.items()})
 
 
+# MODEL.DLA.DLA_STAGE2 .. 5_OUT_CHANNELS per CONV_BODY (the bodies of dla.BODIES; the reference's yamls set them per body)
+DLA_STAGE_CHANNELS = {"DLA-34-FPN": (64, 128, 256, 512), "DLA-46-C-FPN": (64, 64, 128, 256), "DLA-60-FPN": (128, 256, 512, 1024),
+                      "DLA-102-FPN": (128, 256, 512, 1024), "DLA-169-FPN": (128, 256, 512, 1024)}
+
+
 def get_default_cfg(conv_body="DLA-34-FPN", channels=128):
+    """``conv_body``: the body whose stage widths fill ``MODEL.DLA`` (any other name keeps DLA-34's)."""
     cfg = CfgNode()
+    s2, s3, s4, s5 = DLA_STAGE_CHANNELS.get(conv_body, DLA_STAGE_CHANNELS["DLA-34-FPN"])
     # INPUT.* / DATALOADER.*: the DLA_34_FPN_EMM.yaml values (reference configs/dla/DLA_34_FPN_EMM.yaml:4-8,38)
     cfg.INPUT = CfgNode(AMODAL=False, MIN_SIZE_TEST=800, MAX_SIZE_TEST=1280, PIXEL_MEAN=[0.485, 0.456, 0.406],
                         PIXEL_STD=[0.229, 0.224, 0.225], TO_BGR255=False)
     cfg.DATALOADER = CfgNode(SIZE_DIVISIBILITY=32)
     cfg.MODEL = CfgNode()
     cfg.MODEL.BACKBONE = CfgNode(CONV_BODY=conv_body)
-    # what fpn.build_fpn reads: the DLA-34 stage widths and the FPN's conv blocks (siammot/configs/defaults.py:31-35,
-    # [UPSTREAM] MODEL.FPN defaults)
-    cfg.MODEL.DLA = CfgNode(DLA_STAGE2_OUT_CHANNELS=64, DLA_STAGE3_OUT_CHANNELS=128, DLA_STAGE4_OUT_CHANNELS=256,
-                            DLA_STAGE5_OUT_CHANNELS=512, BACKBONE_OUT_CHANNELS=channels,
+    # what fpn.build_fpn reads: the body's stage widths (DLA-34's: siammot/configs/defaults.py:31-35) and the FPN's conv
+    # blocks ([UPSTREAM] MODEL.FPN defaults)
+    cfg.MODEL.DLA = CfgNode(DLA_STAGE2_OUT_CHANNELS=s2, DLA_STAGE3_OUT_CHANNELS=s3, DLA_STAGE4_OUT_CHANNELS=s4,
+                            DLA_STAGE5_OUT_CHANNELS=s5, BACKBONE_OUT_CHANNELS=channels,
                             # what dla.build_dla reads: no deformable convolutions (siammot/configs/defaults.py)
                             STAGE_WITH_DCN=(False, False, False, False, False, False))
     cfg.MODEL.FPN = CfgNode(USE_GN=False, USE_RELU=False)

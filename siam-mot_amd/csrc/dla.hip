@@ -1,5 +1,6 @@
-// DLA backbone body — [UPSTREAM] siammot/modelling/backbone/dla.py with DlaBasic blocks and maskrcnn_benchmark's
-// FrozenBatchNorm2d (DLA-34 and its family), inference: an image batch -> the four stage maps x2 .. x5.
+// DLA backbone body — [UPSTREAM] siammot/modelling/backbone/dla.py with DlaBasic blocks (DLA-34 and its family) or
+// DlaBottleneck blocks at cardinality 1 (DLA-46-C, DLA-60, DLA-102, DLA-169) and maskrcnn_benchmark's FrozenBatchNorm2d,
+// inference: an image batch -> the four stage maps x2 .. x5.
 //
 //   x  = cbr7x7(image, 3 -> c0)              base_layer          cbr = conv (no bias) -> y * scale + shift -> ReLU
 //   x0 = cbr3x3(x, c0 -> c0)                 level0              cb  = the same without the ReLU
@@ -21,6 +22,9 @@
 // dla_conv1x1_kernel<OT>: fpn_lateral_kernel's scheme (64 positions x 32 output channels per workgroup, B operand read in
 //   place) over a VIRTUAL concatenation of up to four source maps, each read as it is or through a 2 x 2 max-pool of a map
 //   twice as fine (torch's max_pool2d: a NaN in the window is the result).  Serves every root and every project.  No LDS.
+// dla_conv1x1_res_kernel<OT>: the same over up to eight sources with a plain or 2 x 2 max-pooled residual in the epilogue: the
+//   last third of a DlaBottleneck block, the residual roots and the roots of trees more than two levels deep (the
+//   smot_dla_net_* entry points: DLA-46-C, DLA-60, DLA-102, DLA-169; dn_tree walks trees of any depth).
 // dla_conv7x7_kernel<FT>: base_layer.  K = 3 * 49 = 147 padded to 148 (37 k-steps; the pad reads a zero cell of LDS, so a
 //   non-finite image cell meets no 0 * inf); the 14 x 22 x 3 window of an 8 x 16 tile is staged once; wave w owns rows 2w, 2w + 1.
 //
@@ -35,7 +39,7 @@ namespace smot {
 
 constexpr int DL_POS = 64, DL_MT = 2;                // 1x1: positions and M-tiles per workgroup
 constexpr int DL_MAX_SRC = 4;
-constexpr int DL_MAX_CONVS = 64;
+constexpr int DL_MAX_CONVS = 512;              // (four depth-5 bottleneck trees and the stem: 455)
 constexpr int S7_PW = CV_TW + 6, S7_PH = CV_TH + 6, S7_PLANE = S7_PW * S7_PH;   // 22 x 14 = 308
 constexpr int S7_ZERO = 3 * S7_PLANE;                // a run of zeros behind the planes: the K pad's B operand
 constexpr int S7_SMEM = S7_ZERO + 160;
@@ -324,6 +328,102 @@ dla_conv1x1_kernel(DlaConv1Args P) {
     }
 }
 
+// dla_conv1x1_res_kernel<OT>: the same workgroup, operand order and k-loop over up to EIGHT sources, with an optional
+//   residual in the epilogue: out = relu?(acc * scale + shift + residual), one fp32 add_rn after the BN and before the ReLU,
+//   as in the 3x3 kernel.  The residual is [N, Cout, H, W], or (res_w != 0) [N, Cout, res_h, res_w] read through the 2 x 2
+//   max-pool; it is only read, so it may be one of the sources (a residual root adds its first source).  Serves a bottleneck
+//   block's conv3, the residual roots and every root over more than four maps.  (dla_conv1x1_kernel keeps its body, which
+//   precedes: one template over both argument structs gives the same values and another register allocation, and the code
+//   that DLA-34 runs is to stay what it was.  With <= 4 sources and no residual the two give the same bits: the sequence
+//   of matrix instructions is the same.)
+constexpr int DL_MAX_SRC_RES = 8;
+struct DlaConv1ResArgs {
+    DlaSrc src[DL_MAX_SRC_RES];
+    const float* a;          // the convolution's packed image
+    void* out;               // [N, Cout, H, W] of OT
+    float* out32;            // the same in fp32 as well, or nullptr
+    const float* res;        // [N, Cout, H, W], or nullptr; res_w != 0: [N, Cout, res_h, res_w] read through a 2 x 2 max-pool
+    int nsrc, K, Cout, H, W, tiles_per_image, relu, res_h, res_w;
+};
+
+template <typename OT>
+__global__ void __launch_bounds__(256, 4)
+dla_conv1x1_res_kernel(DlaConv1ResArgs P) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int kq = lane >> 4, xl = lane & 15;
+    const int Cout = P.Cout, HW = P.H * P.W;
+    const int n = blockIdx.x / P.tiles_per_image;
+    const int tile = blockIdx.x - n * P.tiles_per_image;
+    const int p = tile * DL_POS + wave * 16 + xl;
+    const bool live = p < HW;
+    const int y = live ? p / P.W : 0, x = live ? p - y * P.W : 0;
+    const int ng = P.K >> 4;
+    const float* __restrict__ scale = P.a + (size_t)Cout * P.K;
+    const float* __restrict__ shift = scale + Cout;
+    const int m0 = blockIdx.y * DL_MT;
+    const cv_f32x4* __restrict__ ap = reinterpret_cast<const cv_f32x4*>(P.a) + (size_t)m0 * ng * 64 + lane;
+    cv_f32x4 acc[DL_MT];
+#pragma unroll
+    for (int m = 0; m < DL_MT; ++m) acc[m] = (cv_f32x4){0.f, 0.f, 0.f, 0.f};
+    cv_f32x4 an[DL_MT], ac[DL_MT];
+    float bn[4], bc[4];
+    int g0 = 0;
+    auto source = [&](const float* sp, int sC, int spool, int sHs, int sWs) {
+        const int sg = sC >> 4;
+        const int HWs = spool ? sHs * sWs : HW;
+        const float* bp = sp + ((size_t)n * sC + kq) * HWs + (spool ? (2 * y) * sWs + 2 * x : p);
+        auto fetch = [&](int gl) {
+#pragma unroll
+            for (int m = 0; m < DL_MT; ++m) an[m] = ap[((size_t)m * ng + g0 + gl) * 64];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float v = 0.0f;
+                if (live) {
+                    const float* q = bp + (size_t)(16 * gl + 4 * e) * HWs;
+                    v = spool ? dl_pool(q, sWs) : q[0];
+                }
+                bn[e] = v;
+            }
+        };
+        fetch(0);
+#pragma unroll 1
+        for (int gl = 0; gl < sg; ++gl) {
+#pragma unroll
+            for (int m = 0; m < DL_MT; ++m) ac[m] = an[m];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) bc[e] = bn[e];
+            if (gl + 1 < sg) fetch(gl + 1);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int m = 0; m < DL_MT; ++m)
+                    acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(ac[m][e], bc[e], acc[m], 0, 0, 0);
+        }
+        g0 += sg;
+    };
+#pragma unroll
+    for (int s = 0; s < DL_MAX_SRC_RES; ++s)
+        if (s < P.nsrc) source(P.src[s].p, P.src[s].C, P.src[s].pooled, P.src[s].Hs, P.src[s].Ws);
+    if (live) {
+        OT* __restrict__ oimg = reinterpret_cast<OT*>(P.out) + (size_t)n * Cout * HW;
+        float* __restrict__ o32 = P.out32 ? P.out32 + (size_t)n * Cout * HW : nullptr;
+        const int HWr = P.res_w ? P.res_h * P.res_w : HW;
+        const float* res = P.res ? P.res + (size_t)n * Cout * HWr + (P.res_w ? 2 * y * P.res_w + 2 * x : p) : nullptr;
+#pragma unroll
+        for (int m = 0; m < DL_MT; ++m)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int ch = 16 * (m0 + m) + 4 * kq + r;
+                float v = add_rn(mul_rn(acc[m][r], scale[ch]), shift[ch]);
+                if (res) v = add_rn(v, P.res_w ? dl_pool(res + (size_t)ch * HWr, P.res_w) : res[(size_t)ch * HWr]);
+                if (P.relu) v = relu_nan(v);
+                cv_store<OT>(oimg + (size_t)ch * HW + p, v);
+                if (o32) o32[(size_t)ch * HW + p] = v;
+            }
+    }
+}
+
 // ---- 7x7 (base_layer) -------------------------------------------------------------------------------------------------------
 struct DlaConv7Args {
     const void* in;          // [N, 3, H, W] of FT
@@ -491,8 +591,44 @@ static int dl_conv1_launch(const DlaConv1Args& P, int grid, hipStream_t st) {
     return check_launch("dla_conv1x1");
 }
 
+template <typename OT>
+static int dl_conv1_res_launch(const DlaConv1ResArgs& P, int grid, hipStream_t st) {
+    SMOT_LAUNCH(dla_conv1x1_res_kernel<OT>, dim3(grid, (P.Cout >> 4) / DL_MT), dim3(256), 0, st, P);
+    return check_launch("dla_conv1x1_res");
+}
+
+// more than four sources, or a residual (res_w != 0: read through the 2 x 2 max-pool of a res_h x res_w map)
+static int dl_conv1_res(const DlaSrc* src, int nsrc, int N, int H, int W, const float* a, int Cout, int relu, void* out,
+                        int out_type, float* out32, hipStream_t st, const float* res, int res_h, int res_w) {
+    DlaConv1ResArgs P = {};
+    int K = 0;
+    for (int s = 0; s < nsrc; ++s) {
+        P.src[s] = src[s];
+        K += src[s].C;
+    }
+    P.a = a;
+    P.out = out;
+    P.out32 = out32;
+    P.res = res;
+    P.nsrc = nsrc;
+    P.K = K;
+    P.Cout = Cout;
+    P.H = H;
+    P.W = W;
+    P.tiles_per_image = (int)(((long long)H * W + DL_POS - 1) / DL_POS);
+    P.relu = relu;
+    P.res_h = res ? res_h : 0;
+    P.res_w = res ? res_w : 0;
+    const int grid = P.tiles_per_image * N;
+    if (out_type == SMOT_FEAT_F32) return dl_conv1_res_launch<float>(P, grid, st);
+    if (out_type == SMOT_FEAT_F16) return dl_conv1_res_launch<f16_t>(P, grid, st);
+    return dl_conv1_res_launch<bf16_t>(P, grid, st);
+}
+
+// up to four sources and no residual: dla_conv1x1_kernel; anything else: dla_conv1x1_res_kernel
 static int dl_conv1(const DlaSrc* src, int nsrc, int N, int H, int W, const float* a, int Cout, int relu, void* out,
-                    int out_type, float* out32, hipStream_t st) {
+                    int out_type, float* out32, hipStream_t st, const float* res = nullptr, int res_h = 0, int res_w = 0) {
+    if (nsrc > DL_MAX_SRC || res) return dl_conv1_res(src, nsrc, N, H, W, a, Cout, relu, out, out_type, out32, st, res, res_h, res_w);
     DlaConv1Args P = {};
     int K = 0;
     for (int s = 0; s < nsrc; ++s) {
@@ -622,6 +758,7 @@ struct DlaCtx {
     bool dry;
     int N, rc;
     hipStream_t st;
+    int block, rroot;        // dn_walk's: the block type (SMOT_DLA_BLOCK_*) and "every root adds its first source"
 };
 static float* dl_alloc(DlaCtx& c, long long floats) {
     float* p = c.dry ? nullptr : c.ws + c.bump;
@@ -639,11 +776,12 @@ static void dl_run3(DlaCtx& c, int kind, const float* in, int Cin, int H, int W,
     const float* w = dl_next(c, kind, Cin, Cout);
     if (!c.dry && !c.rc) c.rc = dl_conv3(in, c.N, Cin, H, W, w, Cout, stride, res, 1, out, c.st, res_h, res_w, kind == 4);
 }
-static void dl_run1(DlaCtx& c, const DlaSrc* src, int nsrc, int H, int W, int Cout, int relu, void* out, int out_type, float* out32) {
+static void dl_run1(DlaCtx& c, const DlaSrc* src, int nsrc, int H, int W, int Cout, int relu, void* out, int out_type, float* out32,
+                    const float* res = nullptr, int res_h = 0, int res_w = 0) {
     int K = 0;
     for (int s = 0; s < nsrc; ++s) K += src[s].C;
     const float* a = dl_next(c, 1, K, Cout);
-    if (!c.dry && !c.rc) c.rc = dl_conv1(src, nsrc, c.N, H, W, a, Cout, relu, out, out_type, out32, c.st);
+    if (!c.dry && !c.rc) c.rc = dl_conv1(src, nsrc, c.N, H, W, a, Cout, relu, out, out_type, out32, c.st, res, res_h, res_w);
 }
 
 // A levels = 1 tree on x [N, cin, H, W] -> [N, cout, Ho, Wo] at `out` (of out_type; fp32 at out32 as well if non-null), or in
@@ -728,6 +866,154 @@ static void dl_walk(DlaCtx& c, const void* image, int in_type, int H, int W, con
     }
 }
 
+// ---- host: networks of either block type and any depth (smot_dla_net_*) -----------------------------------------------------
+// The convolutions in launch order: per depth-1 tree project (if cin != cout), tree1's convolutions, tree2's, root; a deeper
+// tree is its tree1 (nothing handed down) then its tree2 (cout -> cout, its root wider by what is handed: root_extra + cout).
+static void dn_add_block(DlaNet& net, int block, int cin, int cout, int k3) {
+    if (block == SMOT_DLA_BLOCK_BOTTLENECK) {
+        const int mid = cout / 2;
+        dl_add(net, 1, cin, mid);
+        dl_add(net, k3, mid, mid);
+        dl_add(net, 1, mid, cout);
+    } else {
+        dl_add(net, k3, cin, cout);
+        dl_add(net, k3, cout, cout);
+    }
+}
+static void dn_add_tree(DlaNet& net, int depth, int block, int cin, int cout, int root_extra, int k3) {
+    if (depth > 1) {
+        dn_add_tree(net, depth - 1, block, cin, cout, 0, k3);
+        dn_add_tree(net, depth - 1, block, cout, cout, root_extra + cout, k3);
+        return;
+    }
+    if (cin != cout) dl_add(net, 1, cin, cout);
+    dn_add_block(net, block, cin, cout, k3);
+    dn_add_block(net, block, cout, cout, k3);
+    dl_add(net, 1, 2 * cout + root_extra, cout);
+}
+
+constexpr int DN_MAX_DEPTH = 5;                      // a root reads x2, x1, bottom and depth - 1 handed maps: 7 <= DL_MAX_SRC_RES
+
+static int dn_net(const int* levels, const int* ch, int block, DlaNet& net, const char* who, bool split = false) {
+    if (!levels || !ch) {
+        set_error("%s: null pointer", who);
+        return SMOT_ERR_BAD_ARG;
+    }
+    if (block != SMOT_DLA_BLOCK_BASIC && block != SMOT_DLA_BLOCK_BOTTLENECK) {
+        set_error("%s: block = %d (SMOT_DLA_BLOCK_BASIC or SMOT_DLA_BLOCK_BOTTLENECK)", who, block);
+        return SMOT_ERR_BAD_ARG;
+    }
+    const int step = block == SMOT_DLA_BLOCK_BOTTLENECK ? 64 : 32;     // (bottleneck: mid = cout / 2 is a multiple of 32)
+    bool ok = levels[0] == 1 && levels[1] == 1 && (ch[0] == 16 || ch[0] == 32) && ch[1] >= 32 && ch[1] % 32 == 0 && ch[1] <= 1024;
+    for (int k = 2; k < 6; ++k)
+        ok = ok && levels[k] >= 1 && levels[k] <= DN_MAX_DEPTH && ch[k] >= step && ch[k] % step == 0 && ch[k] <= 1024;
+    if (!ok) {
+        set_error("%s: levels (%d,%d,%d,%d,%d,%d), channels (%d,%d,%d,%d,%d,%d) (supported: levels[0] = levels[1] = 1, levels[2..5] "
+                  "in 1 .. %d; channels[0] in {16, 32}, channels[1] a multiple of 32, channels[2..5] multiples of %d, up to 1024)",
+                  who, levels[0], levels[1], levels[2], levels[3], levels[4], levels[5], ch[0], ch[1], ch[2], ch[3], ch[4], ch[5],
+                  DN_MAX_DEPTH, step);
+        return SMOT_ERR_UNSUPPORTED;
+    }
+    net.n = 0;
+    net.total = 0;
+    net.k3 = split ? 4 : 3;
+    dl_add(net, 7, 3, ch[0]);
+    dl_add(net, 3, ch[0], ch[0]);
+    dl_add(net, 3, ch[0], ch[1]);
+    for (int k = 2; k < 6; ++k) dn_add_tree(net, levels[k], block, ch[k - 1], ch[k], k > 2 ? ch[k - 1] : 0, net.k3);
+    return SMOT_OK;
+}
+
+// One block on x [N, cin, H, W] -> out [N, cout, H / stride, W / stride] fp32, + res (res_w != 0: through the pool) before the
+// last ReLU.  Its intermediate maps are released when it returns (every launch is on one stream: a later launch that reuses
+// the memory runs after the ones that read it).
+static void dn_block(DlaCtx& c, const float* x, int cin, int H, int W, int cout, int stride, const float* res, int res_h, int res_w,
+                     float* out) {
+    const int Ho = H / stride, Wo = W / stride, k3 = c.net->k3;
+    const long long mark = c.bump;
+    if (c.block == SMOT_DLA_BLOCK_BOTTLENECK) {      // conv1 at the input's resolution, the stride on the 3x3, as upstream
+        const int mid = cout / 2;
+        float* m1 = dl_alloc(c, (long long)c.N * mid * H * W);
+        float* m2 = dl_alloc(c, (long long)c.N * mid * Ho * Wo);
+        const DlaSrc s1 = {x, cin, 0, H, W}, s3 = {m2, mid, 0, Ho, Wo};
+        dl_run1(c, &s1, 1, H, W, mid, 1, m1, SMOT_FEAT_F32, nullptr);
+        dl_run3(c, k3, m1, mid, H, W, mid, stride, nullptr, m2);
+        dl_run1(c, &s3, 1, Ho, Wo, cout, 1, out, SMOT_FEAT_F32, nullptr, res, res_h, res_w);
+    } else {
+        float* t = dl_alloc(c, (long long)c.N * cout * Ho * Wo);
+        dl_run3(c, k3, x, cin, H, W, cout, stride, nullptr, t);
+        dl_run3(c, k3, t, cout, Ho, Wo, cout, 1, res, out, res_h, res_w);
+    }
+    c.bump = mark;
+}
+
+struct DlaDst {
+    void* out;               // [N, cout, Ho, Wo] of out_type
+    int out_type;
+    float* out32;            // the same in fp32 as well, or nullptr
+};
+
+// tree(depth) on x [N, cin, H, W] -> dst, which the caller owns.  handed: what the parent handed down.  Everything the
+// subtree allocates is released when its root has been written: a depth-n tree holds n - 1 tree1 results, one depth-1
+// tree's maps (project, x1, x2) and one block's intermediates at a time, whatever the number of blocks.
+static void dn_tree(DlaCtx& c, int depth, const float* x, int cin, int H, int W, int cout, int stride, bool level_root,
+                    const DlaSrc* handed, int nhanded, const DlaDst& dst) {
+    const int Ho = H / stride, Wo = W / stride;
+    const long long on = (long long)c.N * cout * Ho * Wo, mark = c.bump;
+    const DlaSrc bottom = {x, cin, stride == 2 ? 1 : 0, H, W};
+    DlaSrc src[DL_MAX_SRC_RES];
+    int ns = 0;
+    if (depth > 1) {
+        float* t = dl_alloc(c, on);
+        dn_tree(c, depth - 1, x, cin, H, W, cout, stride, false, nullptr, 0, DlaDst{t, SMOT_FEAT_F32, nullptr});
+        if (level_root) src[ns++] = bottom;
+        for (int e = 0; e < nhanded; ++e) src[ns++] = handed[e];
+        src[ns++] = DlaSrc{t, cout, 0, Ho, Wo};
+        dn_tree(c, depth - 1, t, cout, Ho, Wo, cout, 1, false, src, ns, dst);
+        c.bump = mark;
+        return;
+    }
+    const float* residual = x;
+    if (cin != cout) {
+        float* r = dl_alloc(c, on);
+        dl_run1(c, &bottom, 1, Ho, Wo, cout, 0, r, SMOT_FEAT_F32, nullptr);
+        residual = r;
+    }
+    // (cin == cout at stride 2: the residual is the pooled input itself, read through the pool)
+    const bool rpool = cin == cout && stride == 2;
+    float* x1 = dl_alloc(c, on);
+    float* x2 = dl_alloc(c, on);
+    dn_block(c, x, cin, H, W, cout, stride, residual, rpool ? H : 0, rpool ? W : 0, x1);
+    dn_block(c, x1, cout, Ho, Wo, cout, 1, x1, 0, 0, x2);
+    src[ns++] = DlaSrc{x2, cout, 0, Ho, Wo};
+    src[ns++] = DlaSrc{x1, cout, 0, Ho, Wo};
+    if (level_root) src[ns++] = bottom;
+    for (int e = 0; e < nhanded; ++e) src[ns++] = handed[e];
+    dl_run1(c, src, ns, Ho, Wo, cout, 1, dst.out, dst.out_type, dst.out32, c.rroot ? x2 : nullptr);
+    c.bump = mark;
+}
+
+// dl_walk for these networks.  Below the levels' mark live x1 and, for half outputs, the fp32 twins the next level reads.
+static void dn_walk(DlaCtx& c, const void* image, int in_type, int H, int W, const int* levels, const int* ch, void* const* out,
+                    int out_type) {
+    float* x1 = dl_alloc(c, (long long)c.N * ch[1] * (H / 2) * (W / 2));
+    long long mark = c.bump;
+    dl_stem(c, image, in_type, H, W, ch[0], ch[1], x1);
+    const float* x = x1;
+    int h = H / 2, w = W / 2;
+    for (int k = 2; k < 6; ++k) {
+        c.bump = mark;
+        const int cout = ch[k], ho = h / 2, wo = w / 2;
+        float* out32 = (out_type != SMOT_FEAT_F32 && k < 5) ? dl_alloc(c, (long long)c.N * cout * ho * wo) : nullptr;
+        mark = c.bump;
+        void* o = c.dry ? nullptr : out[k - 2];
+        dn_tree(c, levels[k], x, ch[k - 1], h, w, cout, 2, k > 2, nullptr, 0, DlaDst{o, out_type, out32});
+        x = out_type == SMOT_FEAT_F32 ? (const float*)o : out32;
+        h = ho;
+        w = wo;
+    }
+}
+
 static int dl_f32_ptr(const void* p) { return p && ((uintptr_t)p & 3) == 0; }
 
 }  // namespace smot
@@ -748,11 +1034,17 @@ extern "C" long long smot_dla_split_packed_floats(const int* levels, const int* 
     return dla_packed_floats_impl(levels, channels, true);
 }
 
+static int dla_pack_net(const DlaNet& net, const float* const* w, const float* const* scale, const float* const* shift,
+                        int num_convs, float* packed, smot_stream_t stream);
 static int dla_pack_impl(const int* levels, const int* channels, const float* const* w, const float* const* scale,
                          const float* const* shift, int num_convs, float* packed, smot_stream_t stream, bool split) {
     DlaNet net;
     const int rn = dla_net(levels, channels, net, "dla_pack", split);
     if (rn) return rn;
+    return dla_pack_net(net, w, scale, shift, num_convs, packed, stream);
+}
+static int dla_pack_net(const DlaNet& net, const float* const* w, const float* const* scale, const float* const* shift,
+                        int num_convs, float* packed, smot_stream_t stream) {
     SMOT_REQUIRE(w && scale && shift && packed, "dla_pack: null pointer");
     SMOT_REQUIRE(num_convs == net.n, "dla_pack: %d convolutions passed, the network has %d in launch order", num_convs, net.n);
     SMOT_REQUIRE(((uintptr_t)packed & 15) == 0, "dla_pack: packed must be 16-byte aligned");
@@ -787,14 +1079,24 @@ extern "C" long long smot_dla_ws_bytes(const int* levels, const int* channels, i
     return c.rc ? -1 : c.peak * (long long)sizeof(float);
 }
 
+// the checks and the walk of a network that dla_net (block < 0: DlaBasic, depth <= 2, dl_walk) or dn_net (block >= 0: dn_walk)
+// described with the code rn
+static int dla_fwd_net(const void* image, int in_type, int num_images, int H, int W, const int* levels, const int* channels,
+                       const float* packed, float* ws, void* const* out, int out_type, smot_stream_t stream, const DlaNet& net,
+                       int rn, int block, int residual_root);
 static int dla_fwd_impl(const void* image, int in_type, int num_images, int H, int W, const int* levels, const int* channels,
                         const float* packed, float* ws, void* const* out, int out_type, smot_stream_t stream, bool split) {
+    DlaNet net;
+    const int rn = dla_net(levels, channels, net, "dla", split);
+    return dla_fwd_net(image, in_type, num_images, H, W, levels, channels, packed, ws, out, out_type, stream, net, rn, -1, 0);
+}
+static int dla_fwd_net(const void* image, int in_type, int num_images, int H, int W, const int* levels, const int* channels,
+                       const float* packed, float* ws, void* const* out, int out_type, smot_stream_t stream, const DlaNet& net,
+                       int rn, int block, int residual_root) {
     SMOT_REQUIRE(in_type == SMOT_FEAT_F32 || in_type == SMOT_FEAT_F16 || in_type == SMOT_FEAT_BF16,
                  "dla: in_type = %d (SMOT_FEAT_F32, _F16 or _BF16, NCHW)", in_type);
     SMOT_REQUIRE(out_type == SMOT_FEAT_F32 || out_type == SMOT_FEAT_F16 || out_type == SMOT_FEAT_BF16,
                  "dla: out_type = %d (SMOT_FEAT_F32, _F16 or _BF16)", out_type);
-    DlaNet net;
-    const int rn = dla_net(levels, channels, net, "dla", split);
     if (rn == SMOT_ERR_BAD_ARG) return rn;
     SMOT_REQUIRE(num_images >= 1 && num_images <= SMOT_MAX_IMAGES, "dla: num_images = %d (1 .. %d)", num_images, SMOT_MAX_IMAGES);
     SMOT_REQUIRE(image && packed && ws && out, "dla: null pointer");
@@ -807,7 +1109,8 @@ static int dla_fwd_impl(const void* image, int in_type, int num_images, int H, i
     if (rs) return rs;
     long long widest = (long long)H * W * channels[0];         // the largest map of one image, in elements
     for (int k = 1; k < 6; ++k) {
-        const long long m = (long long)(H >> k) * (W >> k) * channels[k];
+        // (a bottleneck's conv1 gives channels[k] / 2 maps at its input's resolution: twice the level's own map)
+        const long long m = (long long)(H >> k) * (W >> k) * channels[k] * (block == SMOT_DLA_BLOCK_BOTTLENECK && k >= 2 ? 2 : 1);
         if (m > widest) widest = m;
     }
     if (widest >= (1LL << 31) || (long long)H * W / 128 * num_images >= (1LL << 31)) {
@@ -820,7 +1123,10 @@ static int dla_fwd_impl(const void* image, int in_type, int num_images, int H, i
     c.ws = ws;
     c.N = num_images;
     c.st = (hipStream_t)stream;
-    dl_walk(c, image, in_type, H, W, levels, channels, out, out_type);
+    c.block = block;
+    c.rroot = residual_root ? 1 : 0;
+    if (block < 0) dl_walk(c, image, in_type, H, W, levels, channels, out, out_type);
+    else dn_walk(c, image, in_type, H, W, levels, channels, out, out_type);
     return c.rc;
 }
 extern "C" int smot_dla_fwd(const void* image, int in_type, int num_images, int H, int W, const int* levels, const int* channels,
@@ -832,6 +1138,54 @@ extern "C" int smot_dla_split_fwd(const void* image, int in_type, int num_images
                                   const int* channels, const float* packed, float* ws, void* const* out, int out_type,
                                   smot_stream_t stream) {
     return dla_fwd_impl(image, in_type, num_images, H, W, levels, channels, packed, ws, out, out_type, stream, true);
+}
+
+// ---- networks of either block type and any depth (include/smot_emm.h, DLA BACKBONE, BOTTLENECK BLOCKS AND DEEPER TREES) ----
+extern "C" int smot_dla_net_num_convs(const int* levels, const int* channels, int block) {
+    DlaNet net;
+    if (dn_net(levels, channels, block, net, "dla_net_num_convs")) return -1;
+    return net.n;
+}
+
+extern "C" long long smot_dla_net_packed_floats(const int* levels, const int* channels, int block, int residual_root, int split) {
+    (void)residual_root;                             // (a residual root has no parameters of its own)
+    DlaNet net;
+    if (dn_net(levels, channels, block, net, "dla_net_packed_floats", split != 0)) return -1;
+    return net.total;
+}
+
+extern "C" int smot_dla_net_pack(const int* levels, const int* channels, int block, int residual_root, int split,
+                                 const float* const* w, const float* const* scale, const float* const* shift, int num_convs,
+                                 float* packed, smot_stream_t stream) {
+    (void)residual_root;
+    DlaNet net;
+    const int rn = dn_net(levels, channels, block, net, "dla_net_pack", split != 0);
+    if (rn) return rn;
+    return dla_pack_net(net, w, scale, shift, num_convs, packed, stream);
+}
+
+extern "C" long long smot_dla_net_ws_bytes(const int* levels, const int* channels, int block, int residual_root, int num_images,
+                                           int H, int W) {
+    DlaNet net;
+    if (dn_net(levels, channels, block, net, "dla_net_ws_bytes") || dla_size_ok(num_images, H, W, "dla_net_ws_bytes")) return -1;
+    DlaCtx c = {};
+    c.net = &net;
+    c.dry = true;
+    c.N = num_images;
+    c.block = block;
+    c.rroot = residual_root ? 1 : 0;
+    // (the half form, as smot_dla_ws_bytes: an upper bound of the fp32 form)
+    dn_walk(c, nullptr, SMOT_FEAT_F32, H, W, levels, channels, nullptr, SMOT_FEAT_F16);
+    return c.rc ? -1 : c.peak * (long long)sizeof(float);
+}
+
+extern "C" int smot_dla_net_fwd(const void* image, int in_type, int num_images, int H, int W, const int* levels, const int* channels,
+                                int block, int residual_root, int split, const float* packed, float* ws, void* const* out,
+                                int out_type, smot_stream_t stream) {
+    DlaNet net;
+    const int rn = dn_net(levels, channels, block, net, "dla_net", split != 0);
+    return dla_fwd_net(image, in_type, num_images, H, W, levels, channels, packed, ws, out, out_type, stream, net, rn,
+                       rn == SMOT_ERR_BAD_ARG ? 0 : block, residual_root);
 }
 
 // ---- the three operators alone -------------------------------------------------------------------------------------------------
@@ -905,22 +1259,28 @@ extern "C" long long smot_dla_conv_split_packed_floats(int kernel_size, int Cin,
     return dl_conv_floats(4, Cin, Cout);
 }
 
-extern "C" int smot_dla_conv1x1_fwd(const float* const* sources, const int* source_channels, const int* source_pooled,
-                                    const int* source_heights, const int* source_widths, int num_sources, int num_images, int H,
-                                    int W, const float* w, const float* scale, const float* shift, int Cout, int relu,
-                                    float* packed, void* out, int out_type, smot_stream_t stream) {
+// max_sources: 4 for smot_dla_conv1x1_fwd (no residual), 8 for smot_dla_conv1x1_res_fwd
+static int dla_conv1x1_impl(const float* const* sources, const int* source_channels, const int* source_pooled,
+                            const int* source_heights, const int* source_widths, int num_sources, int max_sources, int num_images,
+                            int H, int W, const float* w, const float* scale, const float* shift, int Cout, int relu,
+                            const float* residual, int residual_h, int residual_w, float* packed, void* out, int out_type,
+                            smot_stream_t stream) {
     SMOT_REQUIRE(out_type == SMOT_FEAT_F32 || out_type == SMOT_FEAT_F16 || out_type == SMOT_FEAT_BF16,
                  "dla_conv1x1: out_type = %d (SMOT_FEAT_F32, _F16 or _BF16)", out_type);
-    SMOT_REQUIRE(num_sources >= 1 && num_sources <= DL_MAX_SRC, "dla_conv1x1: %d sources (1 .. %d)", num_sources, DL_MAX_SRC);
+    SMOT_REQUIRE(num_sources >= 1 && num_sources <= max_sources, "dla_conv1x1: %d sources (1 .. %d)", num_sources, max_sources);
+    SMOT_REQUIRE(!residual || dl_f32_ptr(residual), "dla_conv1x1: the residual is misaligned");
+    const bool rpool = residual && (residual_h != 0 || residual_w != 0);
+    SMOT_REQUIRE(!rpool || (residual_h / 2 == H && residual_w / 2 == W),
+                 "dla_conv1x1: a pooled residual of %d x %d for an output of %d x %d", residual_h, residual_w, H, W);
     SMOT_REQUIRE(sources && source_channels && source_pooled && source_heights && source_widths, "dla_conv1x1: null pointer");
     SMOT_REQUIRE(dl_f32_ptr(w) && dl_f32_ptr(scale) && dl_f32_ptr(shift), "dla_conv1x1: a null or misaligned pointer");
     SMOT_REQUIRE(out && ((uintptr_t)out & (out_type == SMOT_FEAT_F32 ? 3 : 1)) == 0, "dla_conv1x1: the output is null or misaligned");
     SMOT_REQUIRE(packed && ((uintptr_t)packed & 15) == 0, "dla_conv1x1: packed must be 16-byte aligned");
     SMOT_REQUIRE(num_images >= 1 && num_images <= SMOT_MAX_IMAGES && H >= 1 && W >= 1, "dla_conv1x1: %d images of %d x %d",
                  num_images, H, W);
-    DlaSrc src[DL_MAX_SRC];
+    DlaSrc src[DL_MAX_SRC_RES];
     long long K = 0;
-    bool ok = Cout >= 32 && Cout % 32 == 0 && Cout <= 1024;
+    bool ok = Cout >= 32 && Cout % 32 == 0 && Cout <= 1024 && !(rpool && (long long)residual_h * residual_w * Cout >= (1LL << 31));
     for (int s = 0; s < num_sources; ++s) {
         SMOT_REQUIRE(dl_f32_ptr(sources[s]), "dla_conv1x1: source %d is null or misaligned", s);
         const int pooled = source_pooled[s] ? 1 : 0, hs = source_heights[s], wsrc = source_widths[s];
@@ -939,7 +1299,24 @@ extern "C" int smot_dla_conv1x1_fwd(const float* const* sources, const int* sour
     hipStream_t st = (hipStream_t)stream;
     const int rp = dl_pack_launch(1, w, scale, shift, (int)K, Cout, packed, st);
     if (rp) return rp;
-    return dl_conv1(src, num_sources, num_images, H, W, packed, Cout, relu ? 1 : 0, out, out_type, nullptr, st);
+    return dl_conv1(src, num_sources, num_images, H, W, packed, Cout, relu ? 1 : 0, out, out_type, nullptr, st, residual,
+                    rpool ? residual_h : 0, rpool ? residual_w : 0);
+}
+extern "C" int smot_dla_conv1x1_fwd(const float* const* sources, const int* source_channels, const int* source_pooled,
+                                    const int* source_heights, const int* source_widths, int num_sources, int num_images, int H,
+                                    int W, const float* w, const float* scale, const float* shift, int Cout, int relu,
+                                    float* packed, void* out, int out_type, smot_stream_t stream) {
+    return dla_conv1x1_impl(sources, source_channels, source_pooled, source_heights, source_widths, num_sources, DL_MAX_SRC,
+                            num_images, H, W, w, scale, shift, Cout, relu, nullptr, 0, 0, packed, out, out_type, stream);
+}
+extern "C" int smot_dla_conv1x1_res_fwd(const float* const* sources, const int* source_channels, const int* source_pooled,
+                                        const int* source_heights, const int* source_widths, int num_sources, int num_images,
+                                        int H, int W, const float* w, const float* scale, const float* shift, int Cout, int relu,
+                                        const float* residual, int residual_h, int residual_w, float* packed, void* out,
+                                        int out_type, smot_stream_t stream) {
+    return dla_conv1x1_impl(sources, source_channels, source_pooled, source_heights, source_widths, num_sources, DL_MAX_SRC_RES,
+                            num_images, H, W, w, scale, shift, Cout, relu, residual, residual_h, residual_w, packed, out, out_type,
+                            stream);
 }
 
 extern "C" long long smot_dla_stem_ws_bytes(int num_images, int H, int W, int c0, int c1) {

@@ -1,7 +1,8 @@
 """DLA backbone body: the reference's ``siammot/modelling/backbone/dla.py`` for its ``DlaBasic`` networks (DLA-34, the
-``CONV_BODY`` of the default config) with [UPSTREAM] maskrcnn_benchmark's ``FrozenBatchNorm2d``, under upstream's module tree
-and ``state_dict`` keys (``base_layer.0.weight``, ``level3.tree2.root.conv.weight``, ...: 195 for DLA-34), so that a reference
-checkpoint's ``backbone.body.*`` loads.  Inference only.
+``CONV_BODY`` of the default config) and its ``DlaBottleneck`` networks at cardinality 1 (DLA-46-C, DLA-60, DLA-102, DLA-169:
+trees up to five levels deep, residual roots) with [UPSTREAM] maskrcnn_benchmark's ``FrozenBatchNorm2d``, under upstream's
+module tree and ``state_dict`` keys (``base_layer.0.weight``, ``level3.tree2.root.conv.weight``, ...: 195 for DLA-34, 875 for
+DLA-169), so that a reference checkpoint's ``backbone.body.*`` loads.  Inference only.
 
     x  = cbr7x7(image, 3 -> c0)                           base_layer.{0,1}       cbr = conv (no bias), frozen BN, ReLU
     x0 = cbr3x3(x, c0 -> c0)                              level0.{0,1}           cb  = conv, frozen BN
@@ -10,14 +11,17 @@ checkpoint's ``backbone.body.*`` loads.  Inference only.
 
 Two forms of the operator live here:
 
-* ``DLA.forward`` on device images within ``ops.dla``'s capacities: every convolution on the fp32 matrix cores with the BN,
-  the residual and the ReLU in its epilogue, the ``cat`` and the max-pool read in place by the 1x1 kernel (37 launches for
-  DLA-34, no host synchronisation); ``out_dtype`` half stores the stage maps rounded once; ``operands="split16"`` runs the
-  trees' 3x3 convolutions on the 16-bit matrix instruction with three-part bf16 operands and fp32 accumulation instead
-  (fp32-grade results in another summation order, no dependence on the data's range; INTEGRATION.md §3n);
+* ``DLA.forward`` on device images within the kernels' capacities (``ops.dla_shapes_ok``): every convolution on the fp32
+  matrix cores with the BN, the residual and the ReLU in its epilogue, the ``cat`` and the max-pool read in place by the 1x1
+  kernel, one launch per evaluated convolution (37 for DLA-34, 63 for DLA-60, 168 for DLA-169), no host synchronisation;
+  ``out_dtype`` half stores the stage maps rounded once; ``operands="split16"`` runs the trees' 3x3 convolutions on the
+  16-bit matrix instruction with three-part bf16 operands and fp32 accumulation instead (fp32-grade results in another
+  summation order, no dependence on the data's range).  ``DlaBasic`` networks with trees of depth <= 2
+  take ``ops.dla``, every other one ``ops.dla_net`` (INTEGRATION.md §3o);
 * ``dla_torch``: the same as a plain torch composition over the module tree.  It is the path for CPU tensors, images that
   are not contiguous NCHW, trainable parameters under grad mode and shapes beyond the capacities (counted in
-  ``ops.FALLBACKS["dla_torch"]`` for device tensors), and the baseline of tools/dla_bench.py.
+  ``ops.FALLBACKS["dla_torch"]`` for device tensors), and the baseline of tools/dla_bench.py and
+  tools/dla_bottleneck_bench.py.
 """
 import torch
 import torch.nn.functional as F
@@ -64,34 +68,63 @@ class DlaBasic(nn.Module):
         return F.relu(self.bn2(self.conv2(out)) + (x if residual is None else residual))
 
 
-class DlaRoot(nn.Module):
-    """``relu(bn(conv1x1(cat(x))))``."""
+class DlaBottleneck(nn.Module):
+    """Upstream's ``DlaBottleneck`` at cardinality 1 and base width 64: ``relu(bn3(conv3(relu(bn2(conv2(relu(bn1(conv1(x))))))))
+    + residual)`` with ``conv1`` 1x1 ``cin -> mid`` at the input's resolution, ``conv2`` 3x3 ``mid -> mid`` with the stride,
+    ``conv3`` 1x1 ``mid -> cout`` and ``mid = cout // 2``; ``residual`` None: ``x``."""
 
-    def __init__(self, cin, cout):
+    def __init__(self, cin, cout, stride=1):
+        super(DlaBottleneck, self).__init__()
+        mid = cout // 2
+        for i, (a, b, k, s) in enumerate(((cin, mid, 1, 1), (mid, mid, 3, stride), (mid, cout, 1, 1)), 1):
+            self.add_module("conv%d" % i, _conv(a, b, k, s))
+            self.add_module("bn%d" % i, FrozenBatchNorm2d(b))
+
+    def forward(self, x, residual=None):
+        out = F.relu(self.bn1(self.conv1(x)))
+        out = F.relu(self.bn2(self.conv2(out)))
+        return F.relu(self.bn3(self.conv3(out)) + (x if residual is None else residual))
+
+
+BLOCKS = {"basic": DlaBasic, "bottleneck": DlaBottleneck}
+
+
+def _block_convs(block):
+    """(conv, bn) of a block in its launch order."""
+    return [(getattr(block, "conv%d" % i), getattr(block, "bn%d" % i)) for i in (1, 2, 3) if hasattr(block, "conv%d" % i)]
+
+
+class DlaRoot(nn.Module):
+    """``relu(bn(conv1x1(cat(x))))``; ``residual``: ``relu(bn(conv1x1(cat(x))) + x[0])``."""
+
+    def __init__(self, cin, cout, residual=False):
         super(DlaRoot, self).__init__()
         self.conv, self.bn = _conv(cin, cout, 1), FrozenBatchNorm2d(cout)
+        self.residual = residual
 
     def forward(self, *x):
-        return F.relu(self.bn(self.conv(torch.cat(x, 1))))
+        y = self.bn(self.conv(torch.cat(x, 1)))
+        return F.relu(y + x[0] if self.residual else y)
 
 
 class DlaTree(nn.Module):
-    """The aggregation tree over ``DlaBasic`` blocks (keys ``tree1``, ``tree2``, ``root``, ``project``, in that order).  A
-    ``levels`` = 1 tree is two blocks and a root over (x2, x1, [bottom if ``level_root``], what the parent handed down:
-    ``handed`` channels); a deeper tree is two trees one level shallower, the second at stride 1 and handed this tree's
-    bottom (if ``level_root``) and the first one's output.  ``project`` exists wherever ``cin != cout``, as upstream; the
-    one of a tree with ``levels`` > 1 is evaluated and discarded there and is not evaluated here (its parameters are kept
-    for the ``state_dict``)."""
+    """The aggregation tree over ``block`` blocks ("basic" or "bottleneck"; keys ``tree1``, ``tree2``, ``root``, ``project``,
+    in that order) of any depth.  A ``levels`` = 1 tree is two blocks and a root over (x2, x1, what the parent handed down:
+    ``handed`` channels, [bottom if ``level_root``]); a deeper tree is two trees one level shallower, the second at stride 1
+    and handed what this tree was handed, its bottom (if ``level_root``) and the first one's output (only the outermost
+    tree of a level has ``level_root``, and it is handed nothing).  ``project`` exists wherever ``cin != cout``, as upstream;
+    the one of a tree with ``levels`` > 1 is evaluated and discarded there and is not evaluated here (its parameters are
+    kept for the ``state_dict``).  ``residual_root``: every root adds its first argument before the ReLU."""
 
-    def __init__(self, levels, cin, cout, stride=1, level_root=False, handed=0):
+    def __init__(self, levels, cin, cout, stride=1, level_root=False, handed=0, block="basic", residual_root=False):
         super(DlaTree, self).__init__()
         own = cin if level_root else 0                            # the channels of `bottom`, where it joins the root
         if levels == 1:
-            self.tree1, self.tree2 = DlaBasic(cin, cout, stride), DlaBasic(cout, cout)
-            self.root = DlaRoot(2 * cout + own + handed, cout)
+            self.tree1, self.tree2 = BLOCKS[block](cin, cout, stride), BLOCKS[block](cout, cout)
+            self.root = DlaRoot(2 * cout + own + handed, cout, residual_root)
         else:
-            self.tree1 = DlaTree(levels - 1, cin, cout, stride)
-            self.tree2 = DlaTree(levels - 1, cout, cout, handed=handed + own + cout)
+            self.tree1 = DlaTree(levels - 1, cin, cout, stride, block=block, residual_root=residual_root)
+            self.tree2 = DlaTree(levels - 1, cout, cout, handed=handed + own + cout, block=block, residual_root=residual_root)
         self.project = nn.Sequential(_conv(cin, cout, 1), FrozenBatchNorm2d(cout)) if cin != cout else None
         self.levels, self.level_root, self.stride = levels, level_root, stride
 
@@ -105,12 +138,11 @@ class DlaTree(nn.Module):
         return self.tree2(x1, children + [x1])
 
     def convs(self):
-        """(conv, bn) in the launch order of ``ops.dla``."""
+        """(conv, bn) in the launch order of ``ops.dla`` / ``ops.dla_net``."""
         if self.levels > 1:
             return self.tree1.convs() + self.tree2.convs()
         head = [tuple(self.project)] if self.project is not None else []
-        return head + [(self.tree1.conv1, self.tree1.bn1), (self.tree1.conv2, self.tree1.bn2), (self.tree2.conv1, self.tree2.bn1),
-                       (self.tree2.conv2, self.tree2.bn2), (self.root.conv, self.root.bn)]
+        return head + _block_convs(self.tree1) + _block_convs(self.tree2) + [(self.root.conv, self.root.bn)]
 
 
 def dla_torch(model, images):
@@ -126,18 +158,21 @@ def dla_torch(model, images):
 
 
 class DLA(nn.Module):
-    """Upstream's ``DLA(levels, channels, block=DlaBasic)`` as a feature extractor: ``forward(images [N, 3, H, W])`` -> the
+    """Upstream's ``DLA(levels, channels, block=DlaBasic or DlaBottleneck, residual_root=...)`` as a feature extractor: ``forward(images [N, 3, H, W])`` -> the
     list of the four stage maps (strides 4, 8, 16, 32), H and W multiples of 32.  ``out_dtype``: the element type of the
     returned maps (float32, float16 or bfloat16: the fp32 result rounded once; the next stage reads the fp32 value).  On
     the device path the packed weights are rebuilt when a parameter's or buffer's ``_version``, storage or device changes.
     ``operands``: "fp32" (the default) or "split16": which kernel the device path runs for the trees' 3x3 convolutions
-    (module docstring); the torch composition, the ``state_dict`` and what ``kernel_ok`` admits do not depend on it."""
+    (module docstring); the torch composition, the ``state_dict`` and what ``kernel_ok`` admits do not depend on it.
+    ``block`` ("basic" or "bottleneck") and ``residual_root`` are upstream's, keyword-only."""
 
-    def __init__(self, levels, channels, out_dtype=torch.float32, operands="fp32"):
+    def __init__(self, levels, channels, out_dtype=torch.float32, operands="fp32", *, block="basic", residual_root=False):
         super(DLA, self).__init__()
         if operands not in ops.DLA_OPERANDS:
             raise ValueError("DLA: operands must be \"fp32\" or \"split16\", got %r" % (operands,))
-        self.operands = operands
+        if block not in BLOCKS:
+            raise ValueError("DLA: block must be \"basic\" or \"bottleneck\", got %r" % (block,))
+        self.operands, self.block, self.residual_root = operands, block, bool(residual_root)
         levels, channels = tuple(int(v) for v in levels), tuple(int(v) for v in channels)
         if len(levels) != 6 or len(channels) != 6:
             raise ValueError("DLA: six levels and six channel counts, got %r and %r" % (levels, channels))
@@ -146,10 +181,11 @@ class DLA(nn.Module):
         self.base_layer = nn.Sequential(_conv(3, channels[0], 7), FrozenBatchNorm2d(channels[0]), nn.ReLU(inplace=True))
         self.level0 = self._conv_level(channels[0], channels[0], levels[0])
         self.level1 = self._conv_level(channels[0], channels[1], levels[1], stride=2)
-        self.level2 = DlaTree(levels[2], channels[1], channels[2], 2, level_root=False)
-        self.level3 = DlaTree(levels[3], channels[2], channels[3], 2, level_root=True)
-        self.level4 = DlaTree(levels[4], channels[3], channels[4], 2, level_root=True)
-        self.level5 = DlaTree(levels[5], channels[4], channels[5], 2, level_root=True)
+        for k in range(2, 6):
+            self.add_module("level%d" % k, DlaTree(levels[k], channels[k - 1], channels[k], 2, level_root=k > 2, block=block,
+                                                   residual_root=self.residual_root))
+        # the DlaBasic networks of depth <= 2 keep the entry point they had (ops.dla); every other one takes ops.dla_net
+        self._net = block != "basic" or self.residual_root or max(levels[2:]) > 2
         self.out_channels = channels[2:]
         self._packed_key, self._packed = None, None
 
@@ -182,7 +218,7 @@ class DLA(nn.Module):
         if torch.is_grad_enabled() and (images.requires_grad or any(p.requires_grad for p in self.parameters())):
             return False
         N, _, H, W = images.shape
-        return N >= 1 and ops.dla_shapes_ok(self.levels, self.channels, H, W, N)
+        return N >= 1 and ops.dla_shapes_ok(self.levels, self.channels, H, W, N, self.block)
 
     def packed(self):
         tensors = list(self.parameters()) + list(self.buffers())
@@ -190,12 +226,19 @@ class DLA(nn.Module):
         if key != self._packed_key:
             with torch.no_grad():
                 convs = [(c.weight.detach(),) + tuple(t.contiguous() for t in bn.scale_shift()) for c, bn in self.convs()]
-                self._packed = ops.dla_pack(convs, self.levels, self.channels, operands=self.operands)
+                if self._net:
+                    self._packed = ops.dla_net_pack(convs, self.levels, self.channels, block=self.block,
+                                                    residual_root=self.residual_root, operands=self.operands)
+                else:
+                    self._packed = ops.dla_pack(convs, self.levels, self.channels, operands=self.operands)
             self._packed_key = key
         return self._packed
 
     def forward(self, images):
         if self.kernel_ok(images):
+            if self._net:
+                return ops.dla_net(images, self.packed(), self.levels, self.channels, block=self.block,
+                                   residual_root=self.residual_root, out_dtype=self.out_dtype, operands=self.operands)
             return ops.dla(images, self.packed(), self.levels, self.channels, out_dtype=self.out_dtype, operands=self.operands)
         if isinstance(images, torch.Tensor) and images.is_cuda:
             ops.FALLBACKS["dla_torch"] += 1
@@ -209,13 +252,37 @@ def dla_34(out_dtype=torch.float32, operands="fp32"):
     return DLA((1, 1, 1, 2, 2, 1), (16, 32, 64, 128, 256, 512), out_dtype=out_dtype, operands=operands)
 
 
-BODIES = {"DLA-34-FPN": dla_34}
+def dla_46_c(out_dtype=torch.float32, operands="fp32"):
+    return DLA((1, 1, 1, 2, 2, 1), (16, 32, 64, 64, 128, 256), out_dtype=out_dtype, operands=operands, block="bottleneck")
+
+
+def dla_60(out_dtype=torch.float32, operands="fp32"):
+    return DLA((1, 1, 1, 2, 3, 1), (16, 32, 128, 256, 512, 1024), out_dtype=out_dtype, operands=operands, block="bottleneck")
+
+
+def dla_102(out_dtype=torch.float32, operands="fp32"):
+    return DLA((1, 1, 1, 3, 4, 1), (16, 32, 128, 256, 512, 1024), out_dtype=out_dtype, operands=operands, block="bottleneck",
+               residual_root=True)
+
+
+def dla_169(out_dtype=torch.float32, operands="fp32"):
+    return DLA((1, 1, 2, 3, 5, 1), (16, 32, 128, 256, 512, 1024), out_dtype=out_dtype, operands=operands, block="bottleneck",
+               residual_root=True)
+
+
+BODIES = {"DLA-34-FPN": dla_34, "DLA-46-C-FPN": dla_46_c, "DLA-60-FPN": dla_60, "DLA-102-FPN": dla_102, "DLA-169-FPN": dla_169}
+# upstream's other registered bodies: grouped 3x3 convolutions (DLA-46-XC) and Res2Net blocks, which this package does not have
+UNSUPPORTED_BODIES = ("DLA-46-XC-FPN", "DLA-60-RES2NET-FPN")
 
 
 def build_dla(cfg, out_dtype=torch.float32, operands="fp32"):
-    """The body of the config's ``MODEL.BACKBONE.CONV_BODY``.  ``DLA-34-FPN`` is the one this package has; any other body, and
-    any true entry of ``MODEL.DLA.STAGE_WITH_DCN`` (deformable convolutions), raises a ``ValueError`` that names it."""
+    """The body of the config's ``MODEL.BACKBONE.CONV_BODY``: one of ``BODIES``.  Any other body, any true entry of
+    ``MODEL.DLA.STAGE_WITH_DCN`` (deformable convolutions) and stage widths in ``MODEL.DLA.DLA_STAGE*_OUT_CHANNELS`` that
+    are not the body's raise a ``ValueError`` that names the body or the entry."""
     name = cfg.MODEL.BACKBONE.CONV_BODY
+    if name in UNSUPPORTED_BODIES:
+        raise ValueError("build_dla: CONV_BODY %r needs grouped 3x3 convolutions or Res2Net blocks, which this package does not "
+                         "have (it has %s)" % (name, ", ".join(sorted(BODIES))))
     if name not in BODIES:
         raise ValueError("build_dla: CONV_BODY %r is not in this package (it has %s)" % (name, ", ".join(sorted(BODIES))))
     dcn = tuple(getattr(cfg.MODEL.DLA, "STAGE_WITH_DCN", ()) or ())

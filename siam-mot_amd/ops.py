@@ -172,6 +172,14 @@ _SIGNATURES = {
     "smot_dla_conv_split_packed_floats": (ctypes.c_longlong, [_i, _i, _i]),
     "smot_dla_conv3x3_split_fwd": (ctypes.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "smot_dla_conv3x3_split_form": (ctypes.c_int, [_i, _i, _i, _i, _i]),
+    # DLA bodies of either block type and any tree depth (DLA-46-C / 60 / 102 / 169), and the 1x1 operator with a residual
+    "smot_dla_net_num_convs": (ctypes.c_int, [_vp, _vp, _i]),
+    "smot_dla_net_packed_floats": (ctypes.c_longlong, [_vp, _vp, _i, _i, _i]),
+    "smot_dla_net_pack": (ctypes.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    "smot_dla_net_ws_bytes": (ctypes.c_longlong, [_vp, _vp, _i, _i, _i, _i, _i]),
+    "smot_dla_net_fwd": (ctypes.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    "smot_dla_conv1x1_res_fwd": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp,
+                                                _i, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 _DEBUG_SIGNATURES = {
@@ -1578,19 +1586,30 @@ DLA_CHANNEL_STEP = 32
 DLA_SIZE_STEP = 32
 
 
-def dla_shapes_ok(levels, channels, H=None, W=None, N=1):
-    """``dla`` takes a network of these ``levels`` / ``channels`` (and, if given, ``N`` images of ``H x W``)."""
+# block types of the DLA bodies (SMOT_DLA_BLOCK_* of include/smot_emm.h) and the deepest tree ``dla_net`` walks
+DLA_BLOCKS = {"basic": 0, "bottleneck": 1}
+DLA_MAX_DEPTH = 5
+
+
+def dla_shapes_ok(levels, channels, H=None, W=None, N=1, block="basic"):
+    """``dla`` / ``dla_net`` take a network of these ``levels`` / ``channels`` and this ``block`` (and, if given, ``N`` images of
+    ``H x W``): trees of depth 1 .. 5; a bottleneck network's ``channels[2:]`` are multiples of 64 (``mid`` of 32)."""
     levels, channels = tuple(int(v) for v in levels), tuple(int(v) for v in channels)
-    if len(levels) != 6 or len(channels) != 6 or levels[:2] != (1, 1) or any(v not in (1, 2) for v in levels[2:]):
+    if block not in DLA_BLOCKS or len(levels) != 6 or len(channels) != 6 or levels[:2] != (1, 1):
+        return False
+    if any(not 1 <= v <= DLA_MAX_DEPTH for v in levels[2:]):
         return False
     if channels[0] not in (16, 32) or any(c < 32 or c % DLA_CHANNEL_STEP or c > DLA_MAX_CHANNELS for c in channels[1:]):
+        return False
+    wide = 2 if block == "bottleneck" else 1                     # (a bottleneck's conv1 map: twice the level's own)
+    if wide == 2 and any(c % (2 * DLA_CHANNEL_STEP) for c in channels[2:]):
         return False
     if H is None and W is None:
         return True
     H, W = int(H), int(W)
     if H < 32 or W < 32 or H % DLA_SIZE_STEP or W % DLA_SIZE_STEP or not 1 <= N <= RPN_MAX_IMAGES:
         return False
-    return max(channels[k] * (H >> k) * (W >> k) for k in range(6)) < 2 ** 31
+    return max(channels[k] * (H >> k) * (W >> k) * (wide if k >= 2 else 1) for k in range(6)) < 2 ** 31
 
 
 def _int6(v):
@@ -1732,6 +1751,116 @@ def dla_conv1x1(sources, pooled, w, scale, shift, relu, out_dtype=torch.float32)
         rc = lib.smot_dla_conv1x1_fwd(_cast(sp), _cast(sc), _cast(sf), _cast(sh), _cast(sw), S, N, H, W, _ptr(w), _ptr(scale),
                                       _ptr(shift), Cout, 1 if relu else 0, _ptr(packed), _ptr(out), FEAT_TYPES[out_dtype], ln.stream)
     _check(rc, "dla_conv1x1")
+    return out
+
+
+def dla_conv1x1_res(sources, pooled, w, scale, shift, relu, residual=None, residual_pooled=False, out_dtype=torch.float32):
+    """``relu(conv1x1(cat(sources, 1), w) * scale + shift + residual)`` (``smot_dla_conv1x1_res_fwd``; residual and ReLU
+    optional): ``dla_conv1x1`` over up to EIGHT sources.  ``residual``: ``[N, Cout, H, W]`` fp32, or with ``residual_pooled``
+    ``[N, Cout, Hr, Wr]`` with ``Hr // 2 == H``, ``Wr // 2 == W``, read through ``max_pool2d(., 2, 2)``; it may be one of the
+    sources.  With up to four sources and no residual: the bits of ``dla_conv1x1``."""
+    lib = _lib or load_library()
+    S = len(sources)
+    if S < 1 or len(pooled) != S:
+        raise RuntimeError("siammot_amd.dla_conv1x1_res: %d sources, %d pooled flags" % (S, len(pooled)))
+    if out_dtype not in FEAT_TYPES:
+        raise RuntimeError("siammot_amd.dla_conv1x1_res: out_dtype must be float32, float16 or bfloat16, got %s" % (out_dtype,))
+    src = [_dev_f32(t, "sources[%d]" % s) for s, t in enumerate(sources)]
+    N = int(src[0].shape[0])
+    H, W = (int(src[0].shape[2]) // 2, int(src[0].shape[3]) // 2) if pooled[0] else (int(src[0].shape[2]), int(src[0].shape[3]))
+    K = sum(int(t.shape[1]) for t in src)
+    Cout = int(w.shape[0])
+    w = _chk(w.reshape(Cout, -1), "w", (Cout, K))
+    scale, shift = _chk(scale, "scale", (Cout,)), _chk(shift, "shift", (Cout,))
+    for s, t in enumerate(src):
+        if t.dim() != 4 or t.shape[0] != N:
+            raise RuntimeError("siammot_amd.dla_conv1x1_res: sources[%d] has shape %s" % (s, tuple(t.shape)))
+    rh = rw = 0
+    if residual is not None and residual_pooled:                 # (its size is the library's to check)
+        rh, rw = int(residual.shape[-2]), int(residual.shape[-1])
+        residual = _chk(residual, "residual", (N, Cout, rh, rw))
+    elif residual is not None:
+        residual = _chk(residual, "residual", (N, Cout, H, W))
+    arr = lambda vals: (ctypes.c_int * S)(*[int(v) for v in vals])
+    sp = (ctypes.c_void_p * S)(*[t.data_ptr() for t in src])
+    sc, sf = arr(t.shape[1] for t in src), arr(1 if f else 0 for f in pooled)
+    sh, sw = arr(t.shape[2] for t in src), arr(t.shape[3] for t in src)
+    n = lib.smot_dla_conv_packed_floats(1, K, Cout)
+    packed = torch.empty((max(n, 4),), dtype=_F32, device=src[0].device)
+    out = torch.empty((N, Cout, H, W), dtype=out_dtype, device=src[0].device)
+    with _Launch(*(src + [w, scale, shift, residual])) as ln:
+        rc = lib.smot_dla_conv1x1_res_fwd(_cast(sp), _cast(sc), _cast(sf), _cast(sh), _cast(sw), S, N, H, W, _ptr(w), _ptr(scale),
+                                          _ptr(shift), Cout, 1 if relu else 0, _ptr(residual), rh, rw, _ptr(packed), _ptr(out),
+                                          FEAT_TYPES[out_dtype], ln.stream)
+    _check(rc, "dla_conv1x1_res")
+    return out
+
+
+def _dla_block(block, who):
+    if block not in DLA_BLOCKS:
+        raise ValueError("siammot_amd.%s: block must be \"basic\" or \"bottleneck\", got %r" % (who, block))
+    return DLA_BLOCKS[block]
+
+
+def dla_net_num_convs(levels, channels, block="basic"):
+    """The convolutions ``dla_net`` evaluates = its launches (``smot_dla_net_num_convs``; the stem's three included): 37 for
+    DLA-34, 48 for DLA-46-C, 63 for DLA-60, 105 for DLA-102, 168 for DLA-169.  -1: beyond the capacities."""
+    lib = _lib or load_library()
+    return int(lib.smot_dla_net_num_convs(_cast(_int6(levels)), _cast(_int6(channels)), _dla_block(block, "dla_net_num_convs")))
+
+
+def dla_net_ws_bytes(levels, channels, N, H, W, block="basic", residual_root=False):
+    """The bytes of workspace ``dla_net`` takes for ``N`` images of ``H x W`` (``smot_dla_net_ws_bytes``; no device needed).
+    -1: beyond the capacities."""
+    lib = _lib or load_library()
+    return int(lib.smot_dla_net_ws_bytes(_cast(_int6(levels)), _cast(_int6(channels)), _dla_block(block, "dla_net_ws_bytes"),
+                                         1 if residual_root else 0, int(N), int(H), int(W)))
+
+
+def dla_net_pack(convs, levels, channels, block="basic", residual_root=False, operands="fp32"):
+    """``dla_pack`` for ``dla_net`` (``smot_dla_net_pack``): convs in LAUNCH ORDER (``dla.DLA.convs()``).  With basic blocks and
+    trees of depth <= 2 the tensor is ``dla_pack``'s."""
+    lib = _lib or load_library()
+    split = 1 if _dla_split(operands, "dla_net_pack") else 0
+    blk, rr = _dla_block(block, "dla_net_pack"), 1 if residual_root else 0
+    lv, ch = _int6(levels), _int6(channels)
+    n = lib.smot_dla_net_packed_floats(_cast(lv), _cast(ch), blk, rr, split)
+    if n < 0:
+        _check(-2, "dla_net_pack")
+    ts = [[_chk(t, "dla_net_pack: convs[%d][%d]" % (i, j), tuple(t.shape)) for j, t in enumerate(c)] for i, c in enumerate(convs)]
+    packed = torch.empty((n,), dtype=_F32, device=ts[0][0].device)
+    arrays = [(ctypes.c_void_p * len(ts))(*[c[j].data_ptr() for c in ts]) for j in range(3)]
+    with _Launch(*[t for c in ts for t in c]) as ln:
+        rc = lib.smot_dla_net_pack(_cast(lv), _cast(ch), blk, rr, split, _cast(arrays[0]), _cast(arrays[1]), _cast(arrays[2]),
+                                   len(ts), _ptr(packed), ln.stream)
+    _check(rc, "dla_net_pack")
+    return packed
+
+
+def dla_net(images, packed, levels, channels, block="basic", residual_root=False, out_dtype=torch.float32, operands="fp32"):
+    """Upstream's ``DLA.forward`` for DlaBasic or DlaBottleneck blocks, trees of depth 1 .. 5 and plain or residual roots
+    (``smot_dla_net_fwd``; include/smot_emm.h, DLA BACKBONE, BOTTLENECK BLOCKS AND DEEPER TREES), one launch per evaluated
+    convolution, free of host synchronisation.  Arguments and results as ``dla``'s; packed: ``dla_net_pack``'s tensor."""
+    lib = _lib or load_library()
+    split = 1 if _dla_split(operands, "dla_net") else 0
+    blk, rr = _dla_block(block, "dla_net"), 1 if residual_root else 0
+    if out_dtype not in FEAT_TYPES:
+        raise RuntimeError("siammot_amd.dla_net: out_dtype must be float32, float16 or bfloat16, got %s" % (out_dtype,))
+    x = _dev_feat(images, "images")
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise RuntimeError("siammot_amd.dla_net: images has shape %s, expected [N, 3, H, W]" % (tuple(x.shape),))
+    N, H, W = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+    lv, ch = _int6(levels), _int6(channels)
+    nbytes = lib.smot_dla_net_ws_bytes(_cast(lv), _cast(ch), blk, rr, N, H, W)
+    if nbytes < 0:
+        _check(-2, "dla_net")
+    ws = torch.empty((max(nbytes // 4, 4),), dtype=_F32, device=x.device)
+    out = [torch.empty((N, int(channels[k]), H >> k, W >> k), dtype=out_dtype, device=x.device) for k in range(2, 6)]
+    po = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in out])
+    with _Launch(x, packed) as ln:
+        rc = lib.smot_dla_net_fwd(_ptr(x), FEAT_TYPES[x.dtype], N, H, W, _cast(lv), _cast(ch), blk, rr, split, _ptr(packed),
+                                  _ptr(ws), _cast(po), FEAT_TYPES[out_dtype], ln.stream)
+    _check(rc, "dla_net")
     return out
 
 
