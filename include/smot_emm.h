@@ -61,7 +61,10 @@ typedef void* smot_stream_t; /* hipStream_t */
  *     the DLA backbone body: smot_dla_packed_floats, smot_dla_pack, smot_dla_ws_bytes, smot_dla_fwd and its operators alone:
  *     smot_dla_conv_packed_floats, smot_dla_conv3x3_fwd, smot_dla_conv3x3_form, smot_dla_conv1x1_fwd, smot_dla_stem_ws_bytes, smot_dla_stem_fwd;
  *     the body with split operands: smot_dla_split_packed_floats, smot_dla_split_pack, smot_dla_split_fwd,
- *     smot_dla_conv_split_packed_floats, smot_dla_conv3x3_split_fwd, smot_dla_conv3x3_split_form.
+ *     smot_dla_conv_split_packed_floats, smot_dla_conv3x3_split_fwd, smot_dla_conv3x3_split_form;
+ *     the bodies of either block type: smot_dla_net_*, smot_dla_conv1x1_res_fwd; the bodies in half compute mode:
+ *     smot_dla_half_packed_floats, smot_dla_half_pack, smot_dla_half_fwd, smot_dla_conv_half_packed_floats,
+ *     smot_dla_conv3x3_half_fwd, smot_dla_conv3x3_half_form, smot_dla_conv1x1_half_fwd.
  */
 #define SMOT_ABI_VERSION 14
 
@@ -1315,6 +1318,54 @@ int smot_dla_conv1x1_res_fwd(const float* const* sources, const int* source_chan
                              const int* source_heights, const int* source_widths, int num_sources, int num_images, int H, int W,
                              const float* w, const float* scale, const float* shift, int Cout, int relu, const float* residual,
                              int residual_h, int residual_w, float* packed, void* out, int out_type, smot_stream_t stream);
+
+/* DLA BACKBONE, HALF COMPUTE: the same networks with every TREE convolution (level2 .. level5: the 3x3 convolutions and all
+ * 1x1 convolutions — a bottleneck's conv1 / conv3, every root, every evaluated project) on v_mfma_f32_16x16x32_f16 /
+ * v_mfma_f32_16x16x32_bf16 with ONE 16-bit operand per value.  compute_type: SMOT_FEAT_F16 (1) or SMOT_FEAT_BF16 (2);
+ * anything else is SMOT_ERR_BAD_ARG (-1 from the size functions).
+ *   operands     the input activation is rounded to compute_type as it is loaded, the filters once, by the pack kernels: round
+ *                to nearest even, as torch's tensor.to(dtype).  An fp16 operand beyond 65,504 in magnitude is +-inf (as
+ *                .half() makes it); bf16 keeps fp32's range.  Products are exact, accumulation is fp32.
+ *   epilogue     the fp32 mode's, in fp32: acc * scale + shift (two roundings), + residual, ReLU in which a NaN stays.
+ *   fp32 stays   the stem (base_layer, level0, level1: the fp32 kernels and images), scale / shift, residuals, every map in
+ *                the workspace, the walker, the launches (37 / 48 / 63 / 105 / 168) and the workspace: smot_dla_net_ws_bytes.
+ *   K padding    a K step is 32 channels and every width is a multiple of 32; a dead position of a tile and an absent
+ *                M-tile multiply zeros or nothing, never a loaded value: a non-finite cell reaches exactly the outputs
+ *                whose window covers it.
+ *   contract     as smot_dla_net_fwd's: image i of a call equals the one-image call bit for bit; an output's sum order is
+ *                fixed by the channel counts and its position; no host synchronisation, no allocation.  The result is NOT the
+ *                fp32 mode's: it is the fp32 evaluation of the rounded operands in another summation order.
+ *   smot_dla_half_packed_floats / smot_dla_half_pack / smot_dla_half_fwd   smot_dla_net_*'s arguments, checks and capacities
+ *                with compute_type in place of split (basic and bottleneck blocks, any depth, residual roots).  The packed
+ *                image is of one compute_type and serves no other mode.
+ *   smot_dla_conv_half_packed_floats(kernel_size, Cin, Cout)   3: the one-part 3x3 image; 1: the half 1x1 image (both -1
+ *                unless Cin % 32 == 0); 7: the fp32 mode's.  Each is followed by fp32 scale / shift as in fp32 mode.
+ *   smot_dla_conv3x3_half_fwd   smot_dla_conv3x3_split_fwd's arguments with compute_type before packed; Cin % 32 == 0
+ *                (SMOT_ERR_UNSUPPORTED otherwise, the message names Cin; nothing launched, out and packed untouched).
+ *   smot_dla_conv3x3_half_form  the form that call runs (the fp32 mode's rule).
+ *   smot_dla_conv1x1_half_fwd   smot_dla_conv1x1_res_fwd's arguments with compute_type before packed; every source a multiple
+ *                of 32 channels (SMOT_ERR_UNSUPPORTED otherwise, the message names the source's width; nothing launched).
+ *   smot_dla_conv1x1_half_form  the M-tiles (of 16 output channels) per workgroup that call runs: 4 where that still gives
+ *                every CU a workgroup, else 2; -1: bad argument.  The form does not touch an output's sum order.
+ */
+long long smot_dla_half_packed_floats(const int* levels, const int* channels, int block, int residual_root, int compute_type);
+int smot_dla_half_pack(const int* levels, const int* channels, int block, int residual_root, int compute_type,
+                       const float* const* w, const float* const* scale, const float* const* shift, int num_convs, float* packed,
+                       smot_stream_t stream);
+int smot_dla_half_fwd(const void* image, int in_type, int num_images, int H, int W, const int* levels, const int* channels,
+                      int block, int residual_root, int compute_type, const float* packed, float* ws, void* const* out,
+                      int out_type, smot_stream_t stream);
+long long smot_dla_conv_half_packed_floats(int kernel_size, int Cin, int Cout);
+int smot_dla_conv3x3_half_fwd(const float* x, int num_images, int Cin, int H, int W, const float* w, const float* scale,
+                              const float* shift, int Cout, int stride, const float* residual, int residual_h, int residual_w,
+                              int relu, int compute_type, float* packed, float* out, smot_stream_t stream);
+int smot_dla_conv3x3_half_form(int num_images, int H, int W, int Cout, int stride);
+int smot_dla_conv1x1_half_form(int num_images, int H, int W, int Cout);
+int smot_dla_conv1x1_half_fwd(const float* const* sources, const int* source_channels, const int* source_pooled,
+                              const int* source_heights, const int* source_widths, int num_sources, int num_images, int H, int W,
+                              const float* w, const float* scale, const float* shift, int Cout, int relu, const float* residual,
+                              int residual_h, int residual_w, int compute_type, float* packed, void* out, int out_type,
+                              smot_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -462,4 +462,151 @@ __device__ __forceinline__ void cvs_block(cvs_u32x4* sm, const FT* __restrict__ 
     }
 }
 
+// ---- the generalised stage with ONE 16-bit OPERAND per value on v_mfma_f32_16x16x32_f16 / _bf16 (cvh_*, for csrc/dla.hip) -----
+// Nothing above is touched.  The half compute mode: x and w are rounded to CT (SMOT_FEAT_F16 or SMOT_FEAT_BF16; round to
+// nearest even, torch's .to(): an fp16 value beyond 65,504 becomes +-inf), the products are exact and the accumulation is
+// fp32.  cvs_block's tiling, forms (WR, NM), staging units (cvs_plan), zero-written halo and slot layout with one part
+// instead of three: one matrix instruction per tap, M-tile and row instead of six, a third of the LDS and of the A traffic.
+//   LDS       = [group of 8 channels kq][cell] 16-byte slots, group pitch as cvs_block's (192 | 561: the same conflict-free
+//               ds_read_b128 pattern within the one part): a buffer is 4 x 192 x 16 = 12,288 B (stride 1) / 4 x 561 x 16 =
+//               35,904 B (stride 2).  BOTH strides take two buffers (24,576 B / 71,808 B) and two workgroups per CU (143,616 B
+//               of the CU's 160 KB at stride 2): the next chunk is stored while the current one multiplies, one barrier per
+//               chunk, and the stride-2 stage needs neither the single buffer nor the 512 registers of cvs_block.
+//   Staging   = cvs_block's (kq, cell) units in GROUPS OF THREE: a group is loaded, waits in registers across three taps
+//               (stride 2: 9 units, three groups; stride 1: 3 units, one group across all nine taps) and is rounded and
+//               stored into the other buffer, which no wave reads during this chunk: 24 staging registers at either
+//               stride instead of 72 at stride 2, which is what lets that stage fit the 256 registers of two workgroups per CU.
+//   A operand = per tap NM M-tiles of 16 bytes per lane (cvh_pack_index), the next tap's in flight while this one multiplies.
+// An output's sum order is fixed by the channel counts and the position in its tile, as above.
+typedef _Float16 cvh_f16x8 __attribute__((ext_vector_type(8)));
+
+// the 16 bits of v rounded to CT
+template <int CT>
+__device__ __forceinline__ unsigned cvh_bits(float v) {
+    if constexpr (CT == SMOT_FEAT_F16) return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)v);
+    else return cvs_bf16(v);
+}
+template <int CT>
+__device__ __forceinline__ unsigned cvh_pack2(float lo, float hi) { return cvh_bits<CT>(lo) | (cvh_bits<CT>(hi) << 16); }
+template <int CT>
+__device__ __forceinline__ cv_f32x4 cvh_mfma(const cvs_u32x4& a, const cvs_u32x4& b, const cv_f32x4& c) {
+    if constexpr (CT == SMOT_FEAT_F16)
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(cvh_f16x8, a), __builtin_bit_cast(cvh_f16x8, b), c, 0, 0, 0);
+    else
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(cvs_bf16x8, a), __builtin_bit_cast(cvs_bf16x8, b), c, 0, 0, 0);
+}
+
+template <int STRIDE>
+struct CvhGeom {
+    using G = CvGeom<STRIDE>;
+    static constexpr int GP = CvsGeom<STRIDE>::GP;               // slots between channel groups
+    static constexpr int BUF = 4 * GP;                           // slots per stage buffer
+    static constexpr int SMEM_SLOTS = 2 * BUF;
+};
+
+// Dword i of the packed image of the rounded filters W [Cout, Cin, 3, 3], Cin % 32 == 0, the pairs padded to 32 output
+// channels -> the index in W of its LOW half (the high one is the next input channel, 9 floats on), or -1: zeros.
+// The image is [pair p][chunk c][tap][M-tile m][lane][e 0..3]: the lane's A fragment, A[row lane % 16][k = 8 (lane / 16) + j],
+// j = 2e, 2e + 1 -> W[32p + 16m + lane % 16][32c + 8 (lane / 16) + j][tap].
+__host__ __device__ inline long long cvh_pack_index(long long i, int Cin, int Cout) {
+    const int e = (int)(i & 3), lane = (int)((i >> 2) & 63);
+    long long r = i >> 8;
+    const int m = (int)(r & 1);
+    r >>= 1;
+    const int tap = (int)(r % 9);
+    r /= 9;
+    const int nch = Cin / CVS_IC;
+    const int c = (int)(r % nch), p = (int)(r / nch);
+    const int oc = 32 * p + 16 * m + (lane & 15), ic = CVS_IC * c + 8 * (lane >> 4) + 2 * e;
+    return oc < Cout ? ((long long)oc * Cin + ic) * 9 + tap : -1;
+}
+__host__ __device__ inline long long cvh_packed_floats(int Cin, int Cout) {
+    return (long long)((Cout + 31) / 32) * (Cin / CVS_IC) * 9 * 2 * 256;
+}
+
+// cvs_block with one part: sm: CvhGeom<STRIDE>::SMEM_SLOTS 16-byte slots; pl: cvs_plan's; packed: the cvh_pack_index image
+template <int CT, typename FT, int STRIDE, int WR, int NM>
+__device__ __forceinline__ void cvh_block(cvs_u32x4* sm, const FT* __restrict__ in, int HW, int Cin, const CvsPlan<STRIDE>& pl,
+                                          const float* __restrict__ packed, int pair, bool active, int tid, int row0,
+                                          cv_f32x4 (&acc)[NM][CV_TH / WR]) {
+    using S = CvsGeom<STRIDE>;
+    using Hh = CvhGeom<STRIDE>;
+    using G = CvGeom<STRIDE>;
+    constexpr int ROWS = CV_TH / WR;
+    const int lane = tid & 63, kq = lane >> 4, xl = lane & 15;
+    const int nch = Cin / CVS_IC;
+    const int boff = kq * Hh::GP + row0 * STRIDE * G::PW + xl * STRIDE;
+    // staging in groups of GRP units: a group is fetched, waits in registers across a third of the taps (stride 2: three
+    // groups; stride 1: its three units are one group and wait across all nine) and is stored into the OTHER buffer, which
+    // nobody reads during this chunk: 24 staging registers at either stride
+    constexpr int GRP = 3, NG = S::NLD / GRP, TPG = 9 / NG;
+    static_assert(S::NLD % GRP == 0 && 9 % NG == 0, "whole groups, whole taps per group");
+    float pre[GRP][8];
+    auto fetch = [&](int chunk, int gi) {
+        const FT* __restrict__ base = in + (size_t)chunk * CVS_IC * HW;
+        int hw = HW;
+        asm volatile("" : "+s"(hw));                             // (opaque per chunk: the 72 addresses src + k HW of a
+                                                                 // stride-2 tile are recomputed, not kept in registers)
+#pragma unroll
+        for (int j = 0; j < GRP; ++j)
+#pragma unroll
+            for (int k = 0; k < 8; ++k) pre[j][k] = pl.src[GRP * gi + j] >= 0 ? feat_ld<FT>(base + pl.src[GRP * gi + j] + k * hw) : 0.0f;
+    };
+    auto stash = [&](cvs_u32x4* buf, int gi) {
+#pragma unroll
+        for (int j = 0; j < GRP; ++j) {
+            const int u = tid + 256 * (GRP * gi + j), g = u / G::CELLS;
+            if (u < S::UNITS) {
+                cvs_u32x4 v;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = cvh_pack2<CT>(pre[j][2 * e], pre[j][2 * e + 1]);
+                buf[g * Hh::GP + (u - g * G::CELLS)] = v;
+            }
+        }
+    };
+    constexpr int AT = 2 * 64;                                   // 16-byte values per (pair, chunk, tap)
+    const cvs_u32x4* __restrict__ ap = reinterpret_cast<const cvs_u32x4*>(packed) + (size_t)(active ? pair : 0) * nch * 9 * AT + lane;
+#pragma unroll
+    for (int m = 0; m < NM; ++m)
+#pragma unroll
+        for (int nt = 0; nt < ROWS; ++nt) acc[m][nt] = (cv_f32x4){0.f, 0.f, 0.f, 0.f};
+    cvs_u32x4 an[NM], ac[NM];
+    auto fetch_a = [&](int t) {                                  // t = 9 chunk + tap
+#pragma unroll
+        for (int m = 0; m < NM; ++m) an[m] = ap[(size_t)t * AT + m * 64];
+    };
+    fetch_a(0);
+#pragma unroll
+    for (int gi = 0; gi < NG; ++gi) {
+        fetch(0, gi);
+        stash(sm, gi);
+    }
+    __syncthreads();
+    for (int c = 0; c < nch; ++c) {
+        const cvs_u32x4* buf = sm + (c & 1) * Hh::BUF;
+        cvs_u32x4* nxt = sm + ((c + 1) & 1) * Hh::BUF;           // its readers passed the barrier that ended chunk c - 1
+        const bool more = c + 1 < nch;
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            if (tap % TPG == 0 && more) {
+                if (tap > 0) stash(nxt, tap / TPG - 1);
+                fetch(c + 1, tap / TPG);
+            }
+#pragma unroll
+            for (int m = 0; m < NM; ++m) ac[m] = an[m];
+            if (9 * c + tap + 1 < 9 * nch) fetch_a(9 * c + tap + 1);
+            if (active) {
+#pragma unroll
+                for (int nt = 0; nt < ROWS; ++nt) {
+                    const cvs_u32x4 b = buf[boff + (nt * STRIDE + tap / 3) * G::PW + (tap % 3)];
+#pragma unroll
+                    for (int m = 0; m < NM; ++m) acc[m][nt] = cvh_mfma<CT>(ac[m], b, acc[m][nt]);
+                }
+            }
+        }
+        if (more) stash(nxt, NG - 1);
+        __syncthreads();
+    }
+}
+
 }  // namespace smot

@@ -31,6 +31,14 @@
 // The stem (base_layer, level0, level1) is three launches here (7x7, 3x3 WR = 4 NM = 1 | 2, 3x3 stride 2 WR = 4): the
 // c0-channel full-resolution maps go through the workspace.  DESIGN.md §7 states what that costs.
 //
+// HALF COMPUTE MODE (the smot_dla_half_* entry points): every tree convolution with one fp16 / bf16 operand per value on
+//   v_mfma_f32_16x16x32_f16 / _bf16, fp32 accumulation and the fp32 epilogue; the stem stays on the kernels above.
+// dla_conv3x3_half_kernel<CT, FT, STRIDE, WR, NM>: dla_conv3x3_split_kernel's workgroup and forms over conv3x3_mfma.h's
+//   cvh_block (one part; two LDS buffers and two workgroups per CU at both strides: 24,576 B / 71,808 B).
+// dla_conv1x1_half_kernel<CT, OT, MT>: what dla_conv1x1_res_kernel covers (eight sources, plain or pooled, residual, ReLU,
+//   OT + fp32 copy), 64 positions x 16 MT output channels per workgroup, K steps of 32 channels, the B operand read in
+//   place (eight channels of one position per lane) and rounded in registers.  No LDS.
+//
 // An output's sum order is fixed by the channel counts and the position in its tile: it does not depend on the image's index
 // or the number of images.
 #include "conv3x3_mfma.h"
@@ -51,10 +59,16 @@ constexpr int S7_KS = 37, S7_Q = 10;                 // k-steps; 16-byte A loads
 //           == 0), scale [32 pairs], shift [32 pairs] in fp32 as for kind 3
 //   kind 1: [M-tile][group of four k-steps][lane][e] -> W[16 m + lane % 16][16 g + 4 e + lane / 16], scale [Cout], shift [Cout]
 //   kind 7: [M-tile][q 0..9][lane][e] -> W[16 m + lane % 16][k = 4 (4 q + e) + lane / 16] (k < 147, else 0), scale, shift
+//   kind 5: a 3x3 convolution's filters rounded to fp16 / bf16: cvh_pack_index image (dwords of two halves; Cin % 32 == 0),
+//           scale [32 pairs], shift [32 pairs] in fp32 as for kind 3
+//   kind 6: a 1x1 convolution's filters rounded to fp16 / bf16 (Cin % 32 == 0): [M-tile][K step of 32][lane][e] dwords of two
+//           halves -> W[16 m + lane % 16][32 g + 8 (lane / 16) + 2 e, + 1], scale [Cout], shift [Cout] in fp32
 __host__ __device__ inline long long dl_conv_floats(int kind, int Cin, int Cout) {
     if (kind == 3) return cvg_packed_floats(Cin, Cout) + 2LL * 32 * ((Cout + 31) / 32);
     if (kind == 4) return cvs_packed_floats(Cin, Cout) + 2LL * 32 * ((Cout + 31) / 32);
     if (kind == 1) return (long long)Cout * Cin + 2LL * Cout;
+    if (kind == 5) return cvh_packed_floats(Cin, Cout) + 2LL * 32 * ((Cout + 31) / 32);
+    if (kind == 6) return (long long)Cout * Cin / 2 + 2LL * Cout;
     return (long long)(Cout / 16) * S7_Q * 256 + 2LL * Cout;
 }
 
@@ -90,6 +104,37 @@ dla_pack_kernel(int kind, const float* __restrict__ w, const float* __restrict__
             const int q = (int)(t % S7_Q), m = (int)(t / S7_Q);
             const int k = 4 * (4 * q + e) + (lane >> 4);
             v = k < 147 ? w[(size_t)(16 * m + (lane & 15)) * 147 + k] : 0.0f;
+        }
+    } else {
+        const long long r = i - nw;
+        const int half = (int)((total - nw) / 2);
+        const int ch = (int)(r % half);
+        v = ch < Cout ? (r < half ? scale[ch] : shift[ch]) : 0.0f;
+    }
+    packed[i] = v;
+}
+
+// kinds 5 and 6: the filters rounded to CT (round to nearest even, as torch's .to(); fp16: beyond 65,504 -> +-inf), two to a
+// dword stored through the float as bits; scale and shift behind them as dla_pack_kernel writes them
+template <int CT>
+__global__ void __launch_bounds__(256)
+dla_pack_half_kernel(int kind, const float* __restrict__ w, const float* __restrict__ scale, const float* __restrict__ shift,
+                     int Cin, int Cout, long long total, float* __restrict__ packed) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const long long nw = total - (kind == 5 ? 2LL * 32 * ((Cout + 31) / 32) : 2LL * Cout);
+    float v = 0.0f;
+    if (i < nw) {
+        if (kind == 5) {
+            const long long s = cvh_pack_index(i, Cin, Cout);
+            if (s >= 0) v = __uint_as_float(cvh_pack2<CT>(w[s], w[s + 9]));
+        } else {
+            const int e = (int)(i & 3), lane = (int)((i >> 2) & 63);
+            const long long t = i >> 8;
+            const int ng = Cin / 32;
+            const int g = (int)(t % ng), m = (int)(t / ng);
+            const float* __restrict__ q = w + (size_t)(16 * m + (lane & 15)) * Cin + 32 * g + 8 * (lane >> 4) + 2 * e;
+            v = __uint_as_float(cvh_pack2<CT>(q[0], q[1]));
         }
     } else {
         const long long r = i - nw;
@@ -232,6 +277,42 @@ dla_conv3x3_split_kernel(DlaConv3Args P) {
     const bool active = pair < npairs;
     cv_f32x4 acc[NM][ROWS];
     cvs_block<FT, STRIDE, WR, NM>(sm, in, HW, P.Cin, pl, P.w, pair, active, tid, row0, acc);
+    if (active && x < P.Wo) dl_conv3_store<NM, ROWS>(acc, pair, kq, x, y0, row0, Cout, P.Ho, P.Wo, HWo, P.res_w, HWr, P.relu, scale, shift, res, out);
+}
+
+// dla_conv3x3_half_kernel<CT, FT, STRIDE, WR, NM>: the same workgroup in HALF COMPUTE MODE (conv3x3_mfma.h, cvh_block): one
+//   fp16 / bf16 operand per value, chunks of 32 input channels, P.w the kind-5 packed image, the same epilogue.  LDS 24,576 B
+//   (stride 1) / 71,808 B (stride 2), two workgroups per CU at both.
+template <int CT, typename FT, int STRIDE, int WR, int NM>
+__global__ void __launch_bounds__(256, 2)
+dla_conv3x3_half_kernel(DlaConv3Args P) {
+    using Hh = CvhGeom<STRIDE>;
+    constexpr int WP = 4 / WR, ROWS = CV_TH / WR;
+    __shared__ __attribute__((aligned(16))) cvs_u32x4 sm[Hh::SMEM_SLOTS];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int kq = lane >> 4, xl = lane & 15;
+    const int n = blockIdx.x / P.tiles_per_image;
+    const int t = blockIdx.x - n * P.tiles_per_image;
+    const int ty = t / P.tiles_x, tx = t - ty * P.tiles_x;
+    const int y0 = ty * CV_TH, x0 = tx * CV_TW;
+    const int HW = P.H * P.W, HWo = P.Ho * P.Wo, Cout = P.Cout;
+    const FT* __restrict__ in = reinterpret_cast<const FT*>(P.in) + (size_t)n * P.Cin * HW;
+    const int npairs = (Cout + 31) >> 5;
+    const float* __restrict__ scale = P.w + cvh_packed_floats(P.Cin, Cout);
+    const float* __restrict__ shift = scale + 32 * npairs;
+    const int HWr = P.res_w ? P.res_h * P.res_w : HWo;
+    const float* __restrict__ res = P.res ? P.res + (size_t)n * Cout * HWr : nullptr;
+    float* __restrict__ out = P.out + (size_t)n * Cout * HWo;
+    const int wp = WR == 1 ? wave : wave % WP, row0 = WR == 1 ? 0 : (wave / WP) * ROWS;
+
+    CvsPlan<STRIDE> pl;
+    cvs_plan<STRIDE>(pl, tid, y0, x0, P.H, P.W);
+    const int x = x0 + xl;
+    const int pair = blockIdx.y * WP + wp;                      // grid.y: the blocks of 32 WP output channels
+    const bool active = pair < npairs;
+    cv_f32x4 acc[NM][ROWS];
+    cvh_block<CT, FT, STRIDE, WR, NM>(sm, in, HW, P.Cin, pl, P.w, pair, active, tid, row0, acc);
     if (active && x < P.Wo) dl_conv3_store<NM, ROWS>(acc, pair, kq, x, y0, row0, Cout, P.Ho, P.Wo, HWo, P.res_w, HWr, P.relu, scale, shift, res, out);
 }
 
@@ -424,6 +505,98 @@ dla_conv1x1_res_kernel(DlaConv1ResArgs P) {
     }
 }
 
+// dla_conv1x1_half_kernel<CT, OT, MT>: dla_conv1x1_res_kernel's job in HALF COMPUTE MODE on v_mfma_f32_16x16x32_f16 / _bf16.
+//   workgroup = 64 positions (wave w: positions 16 w .. 16 w + 15 of the tile) x MT M-tiles (16 MT output channels; M-tiles
+//   beyond Cout / 16 — the tail of the last block — are neither loaded nor multiplied).  One K step is 32 channels of ONE
+//   source (every source is a multiple of 32 wide).
+//   A operand: the kind-6 image, 16 bytes per lane and M-tile, straight into registers.
+//   B operand: lane (kq, xl) loads channels 8 kq .. 8 kq + 7 of its position in place (plain, or the 2 x 2 max-pool of the
+//   window) as fp32 and rounds them to CT in registers; a dead position of the last tile supplies zeros, never a loaded value.
+//   The next K step's A and B are in flight while the current one multiplies.  No LDS: a B value is used by one lane
+//   only, so staging it would add a write and a read per value for nothing but the coalescing, which a lane group's sixteen
+//   consecutive positions (64 bytes per channel) already have; what is re-read is B once per block of 16 MT output
+//   channels, and MT = 4 halves that against dla_conv1x1_res_kernel wherever the launch still fills the CUs (dl_conv1_half_mt).
+//   An output's sum order is the K order of the concatenation: fixed by the channel counts alone.
+template <int CT, typename OT, int MT>
+__global__ void __launch_bounds__(256, 2)
+dla_conv1x1_half_kernel(DlaConv1ResArgs P) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int kq = lane >> 4, xl = lane & 15;
+    const int Cout = P.Cout, HW = P.H * P.W;
+    const int n = blockIdx.x / P.tiles_per_image;
+    const int tile = blockIdx.x - n * P.tiles_per_image;
+    const int p = tile * DL_POS + wave * 16 + xl;
+    const bool live = p < HW;
+    const int y = live ? p / P.W : 0, x = live ? p - y * P.W : 0;
+    const int ng = P.K >> 5;
+    const float* __restrict__ scale = P.a + (size_t)Cout * P.K / 2;
+    const float* __restrict__ shift = scale + Cout;
+    const int m0 = blockIdx.y * MT;
+    const int nm = min(MT, (Cout >> 4) - m0);                   // (block-uniform) the M-tiles this block has
+    const cvs_u32x4* __restrict__ ap = reinterpret_cast<const cvs_u32x4*>(P.a) + (size_t)m0 * ng * 64 + lane;
+    cv_f32x4 acc[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) acc[m] = (cv_f32x4){0.f, 0.f, 0.f, 0.f};
+    cvs_u32x4 an[MT], ac[MT], bc;
+    float bn[8];
+    int g0 = 0;
+    auto source = [&](const float* sp, int sC, int spool, int sHs, int sWs) {
+        const int sg = sC >> 5;
+        const int HWs = spool ? sHs * sWs : HW;
+        const float* bp = sp + ((size_t)n * sC + 8 * kq) * HWs + (spool ? (2 * y) * sWs + 2 * x : p);
+        auto fetch = [&](int gl) {
+#pragma unroll
+            for (int m = 0; m < MT; ++m)
+                if (m < nm) an[m] = ap[((size_t)m * ng + g0 + gl) * 64];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                float v = 0.0f;
+                if (live) {
+                    const float* q = bp + (size_t)(32 * gl + j) * HWs;
+                    v = spool ? dl_pool(q, sWs) : q[0];
+                }
+                bn[j] = v;
+            }
+        };
+        fetch(0);
+#pragma unroll 1
+        for (int gl = 0; gl < sg; ++gl) {
+#pragma unroll
+            for (int m = 0; m < MT; ++m) ac[m] = an[m];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) bc[e] = cvh_pack2<CT>(bn[2 * e], bn[2 * e + 1]);
+            if (gl + 1 < sg) fetch(gl + 1);
+#pragma unroll
+            for (int m = 0; m < MT; ++m)
+                if (m < nm) acc[m] = cvh_mfma<CT>(ac[m], bc, acc[m]);
+        }
+        g0 += sg;
+    };
+#pragma unroll
+    for (int s = 0; s < DL_MAX_SRC_RES; ++s)
+        if (s < P.nsrc) source(P.src[s].p, P.src[s].C, P.src[s].pooled, P.src[s].Hs, P.src[s].Ws);
+    if (live) {
+        OT* __restrict__ oimg = reinterpret_cast<OT*>(P.out) + (size_t)n * Cout * HW;
+        float* __restrict__ o32 = P.out32 ? P.out32 + (size_t)n * Cout * HW : nullptr;
+        const int HWr = P.res_w ? P.res_h * P.res_w : HW;
+        const float* res = P.res ? P.res + (size_t)n * Cout * HWr + (P.res_w ? 2 * y * P.res_w + 2 * x : p) : nullptr;
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            if (m >= nm) continue;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int ch = 16 * (m0 + m) + 4 * kq + r;
+                float v = add_rn(mul_rn(acc[m][r], scale[ch]), shift[ch]);
+                if (res) v = add_rn(v, P.res_w ? dl_pool(res + (size_t)ch * HWr, P.res_w) : res[(size_t)ch * HWr]);
+                if (P.relu) v = relu_nan(v);
+                cv_store<OT>(oimg + (size_t)ch * HW + p, v);
+                if (o32) o32[(size_t)ch * HW + p] = v;
+            }
+        }
+    }
+}
+
 // ---- 7x7 (base_layer) -------------------------------------------------------------------------------------------------------
 struct DlaConv7Args {
     const void* in;          // [N, 3, H, W] of FT
@@ -500,9 +673,19 @@ dla_conv7x7_kernel(DlaConv7Args P) {
 }
 
 // ---- host: one launch each -------------------------------------------------------------------------------------------------
+// ctype: the compute type of kinds 5 and 6 (SMOT_FEAT_F16 or SMOT_FEAT_BF16); the other kinds do not read it
 static int dl_pack_launch(int kind, const float* w, const float* scale, const float* shift, int Cin, int Cout, float* packed,
-                          hipStream_t st) {
+                          hipStream_t st, int ctype = 0) {
     const long long total = dl_conv_floats(kind, Cin, Cout);
+    if (kind == 5 || kind == 6) {
+        const dim3 g((unsigned)((total + 255) / 256));
+        if (ctype == SMOT_FEAT_F16) {
+            SMOT_LAUNCH(dla_pack_half_kernel<SMOT_FEAT_F16>, g, dim3(256), 0, st, kind, w, scale, shift, Cin, Cout, total, packed);
+        } else {
+            SMOT_LAUNCH(dla_pack_half_kernel<SMOT_FEAT_BF16>, g, dim3(256), 0, st, kind, w, scale, shift, Cin, Cout, total, packed);
+        }
+        return check_launch("dla_pack_half");
+    }
     SMOT_LAUNCH(dla_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, kind, w, scale, shift, Cin, Cout, total,
                 packed);
     return check_launch("dla_pack");
@@ -560,10 +743,29 @@ static int dl_conv3_pick_split(const DlaConv3Args& P, int grid, hipStream_t st) 
     return check_launch("dla_conv3x3_split");
 }
 
+// The half compute mode's launch: the same wave split by the same rule (dl_conv3_wr), so a shape runs the same (WR, NM) in
+// every mode; stride 2 has no WR = 1 form here either.
+template <int CT, typename FT, int STRIDE>
+static int dl_conv3_pick_half(const DlaConv3Args& P, int grid, hipStream_t st) {
+    const int npairs = (P.Cout + 31) >> 5;
+    const int wr = dl_conv3_wr(STRIDE, P.Cout, grid);
+    const dim3 g(grid, (npairs + 4 / wr - 1) / (4 / wr));
+    if (P.Cout <= 16) {
+        SMOT_LAUNCH((dla_conv3x3_half_kernel<CT, FT, STRIDE, 4, 1>), g, dim3(256), 0, st, P);
+    } else if (wr == 4) {
+        SMOT_LAUNCH((dla_conv3x3_half_kernel<CT, FT, STRIDE, 4, 2>), g, dim3(256), 0, st, P);
+    } else if (wr == 2) {
+        SMOT_LAUNCH((dla_conv3x3_half_kernel<CT, FT, STRIDE, 2, 2>), g, dim3(256), 0, st, P);
+    } else {
+        if constexpr (STRIDE == 1) SMOT_LAUNCH((dla_conv3x3_half_kernel<CT, FT, 1, 1, 2>), g, dim3(256), 0, st, P);
+    }
+    return check_launch("dla_conv3x3_half");
+}
+
 // in [N, Cin, H, W] fp32 -> out [N, Cout, Ho, Wo]; the shapes were checked by the caller (dl_conv3_ok); split: w is a kind-4
-// image and Cin % 32 == 0
+// image and Cin % 32 == 0; ctype != 0 (SMOT_FEAT_F16 or SMOT_FEAT_BF16): w is a kind-5 image of that type and Cin % 32 == 0
 static int dl_conv3(const float* in, int N, int Cin, int H, int W, const float* w, int Cout, int stride, const float* res,
-                    int relu, float* out, hipStream_t st, int res_h = 0, int res_w = 0, bool split = false) {
+                    int relu, float* out, hipStream_t st, int res_h = 0, int res_w = 0, bool split = false, int ctype = 0) {
     DlaConv3Args P = {};
     P.in = in;
     P.w = w;
@@ -581,6 +783,10 @@ static int dl_conv3(const float* in, int N, int Cin, int H, int W, const float* 
     P.res_h = res_h;
     P.res_w = res_w;
     const int grid = P.tiles_per_image * N;
+    if (ctype == SMOT_FEAT_F16)
+        return stride == 2 ? dl_conv3_pick_half<SMOT_FEAT_F16, float, 2>(P, grid, st) : dl_conv3_pick_half<SMOT_FEAT_F16, float, 1>(P, grid, st);
+    if (ctype == SMOT_FEAT_BF16)
+        return stride == 2 ? dl_conv3_pick_half<SMOT_FEAT_BF16, float, 2>(P, grid, st) : dl_conv3_pick_half<SMOT_FEAT_BF16, float, 1>(P, grid, st);
     if (split) return stride == 2 ? dl_conv3_pick_split<float, 2>(P, grid, st) : dl_conv3_pick_split<float, 1>(P, grid, st);
     return stride == 2 ? dl_conv3_pick<float, 2>(P, grid, st) : dl_conv3_pick<float, 1>(P, grid, st);
 }
@@ -651,6 +857,54 @@ static int dl_conv1(const DlaSrc* src, int nsrc, int N, int H, int W, const floa
     return dl_conv1_launch<bf16_t>(P, grid, st);
 }
 
+// The half 1x1 kernel's M-tiles per workgroup: 4 (64 output channels: the B operand is read half as often) wherever that still
+// gives every CU a workgroup, else 2 (dla_conv1x1_res_kernel's block).  It does not touch an output's sum order.
+static int dl_conv1_half_mt(int Cout, long long tiles) {
+    return tiles * ((Cout / 16 + 3) / 4) >= DL_MIN_WORKGROUPS ? 4 : 2;
+}
+template <int CT, typename OT>
+static int dl_conv1_half_launch(const DlaConv1ResArgs& P, int grid, hipStream_t st) {
+    const int mt = P.Cout >> 4;
+    if (dl_conv1_half_mt(P.Cout, grid) == 4) {
+        SMOT_LAUNCH((dla_conv1x1_half_kernel<CT, OT, 4>), dim3(grid, (mt + 3) / 4), dim3(256), 0, st, P);
+    } else {
+        SMOT_LAUNCH((dla_conv1x1_half_kernel<CT, OT, 2>), dim3(grid, (mt + 1) / 2), dim3(256), 0, st, P);
+    }
+    return check_launch("dla_conv1x1_half");
+}
+// dl_conv1 in half compute mode: a: a kind-6 image of ctype; every source a multiple of 32 channels (the caller checked)
+static int dl_conv1_half(const DlaSrc* src, int nsrc, int N, int H, int W, const float* a, int Cout, int relu, void* out,
+                         int out_type, float* out32, hipStream_t st, const float* res, int res_h, int res_w, int ctype) {
+    DlaConv1ResArgs P = {};
+    int K = 0;
+    for (int s = 0; s < nsrc; ++s) {
+        P.src[s] = src[s];
+        K += src[s].C;
+    }
+    P.a = a;
+    P.out = out;
+    P.out32 = out32;
+    P.res = res;
+    P.nsrc = nsrc;
+    P.K = K;
+    P.Cout = Cout;
+    P.H = H;
+    P.W = W;
+    P.tiles_per_image = (int)(((long long)H * W + DL_POS - 1) / DL_POS);
+    P.relu = relu;
+    P.res_h = res ? res_h : 0;
+    P.res_w = res ? res_w : 0;
+    const int grid = P.tiles_per_image * N;
+    if (ctype == SMOT_FEAT_F16) {
+        if (out_type == SMOT_FEAT_F32) return dl_conv1_half_launch<SMOT_FEAT_F16, float>(P, grid, st);
+        if (out_type == SMOT_FEAT_F16) return dl_conv1_half_launch<SMOT_FEAT_F16, f16_t>(P, grid, st);
+        return dl_conv1_half_launch<SMOT_FEAT_F16, bf16_t>(P, grid, st);
+    }
+    if (out_type == SMOT_FEAT_F32) return dl_conv1_half_launch<SMOT_FEAT_BF16, float>(P, grid, st);
+    if (out_type == SMOT_FEAT_F16) return dl_conv1_half_launch<SMOT_FEAT_BF16, f16_t>(P, grid, st);
+    return dl_conv1_half_launch<SMOT_FEAT_BF16, bf16_t>(P, grid, st);
+}
+
 static int dl_conv7(const void* image, int in_type, int N, int H, int W, const float* a, int C0, float* out, hipStream_t st) {
     DlaConv7Args P = {};
     P.in = image;
@@ -678,7 +932,8 @@ struct DlaConv {
     long long off;           // first float in the packed image
 };
 struct DlaNet {
-    int n, k3;               // k3: the kind of the trees' 3x3 images (3; 4: split operands)
+    int n, k3;               // k3: the kind of the trees' 3x3 images (3; 4: split operands; 5: half compute mode)
+    int k1, ctype;           // k1: the kind of the trees' 1x1 images (1; 6: half compute mode, of compute type ctype)
     DlaConv conv[DL_MAX_CONVS];
     long long total;
 };
@@ -721,6 +976,8 @@ static int dla_net(const int* levels, const int* ch, DlaNet& net, const char* wh
     net.n = 0;
     net.total = 0;
     net.k3 = split ? 4 : 3;
+    net.k1 = 1;
+    net.ctype = 0;
     dl_add(net, 7, 3, ch[0]);
     dl_add(net, 3, ch[0], ch[0]);
     dl_add(net, 3, ch[0], ch[1]);
@@ -774,14 +1031,18 @@ static const float* dl_next(DlaCtx& c, int kind, int cin, int cout) {
 static void dl_run3(DlaCtx& c, int kind, const float* in, int Cin, int H, int W, int Cout, int stride, const float* res,
                     float* out, int res_h = 0, int res_w = 0) {
     const float* w = dl_next(c, kind, Cin, Cout);
-    if (!c.dry && !c.rc) c.rc = dl_conv3(in, c.N, Cin, H, W, w, Cout, stride, res, 1, out, c.st, res_h, res_w, kind == 4);
+    if (!c.dry && !c.rc)
+        c.rc = dl_conv3(in, c.N, Cin, H, W, w, Cout, stride, res, 1, out, c.st, res_h, res_w, kind == 4, kind == 5 ? c.net->ctype : 0);
 }
 static void dl_run1(DlaCtx& c, const DlaSrc* src, int nsrc, int H, int W, int Cout, int relu, void* out, int out_type, float* out32,
                     const float* res = nullptr, int res_h = 0, int res_w = 0) {
     int K = 0;
     for (int s = 0; s < nsrc; ++s) K += src[s].C;
-    const float* a = dl_next(c, 1, K, Cout);
-    if (!c.dry && !c.rc) c.rc = dl_conv1(src, nsrc, c.N, H, W, a, Cout, relu, out, out_type, out32, c.st, res, res_h, res_w);
+    const int k1 = c.net->k1;
+    const float* a = dl_next(c, k1, K, Cout);
+    if (c.dry || c.rc) return;
+    if (k1 == 6) c.rc = dl_conv1_half(src, nsrc, c.N, H, W, a, Cout, relu, out, out_type, out32, c.st, res, res_h, res_w, c.net->ctype);
+    else c.rc = dl_conv1(src, nsrc, c.N, H, W, a, Cout, relu, out, out_type, out32, c.st, res, res_h, res_w);
 }
 
 // A levels = 1 tree on x [N, cin, H, W] -> [N, cout, Ho, Wo] at `out` (of out_type; fp32 at out32 as well if non-null), or in
@@ -872,9 +1133,9 @@ static void dl_walk(DlaCtx& c, const void* image, int in_type, int H, int W, con
 static void dn_add_block(DlaNet& net, int block, int cin, int cout, int k3) {
     if (block == SMOT_DLA_BLOCK_BOTTLENECK) {
         const int mid = cout / 2;
-        dl_add(net, 1, cin, mid);
+        dl_add(net, net.k1, cin, mid);
         dl_add(net, k3, mid, mid);
-        dl_add(net, 1, mid, cout);
+        dl_add(net, net.k1, mid, cout);
     } else {
         dl_add(net, k3, cin, cout);
         dl_add(net, k3, cout, cout);
@@ -886,15 +1147,17 @@ static void dn_add_tree(DlaNet& net, int depth, int block, int cin, int cout, in
         dn_add_tree(net, depth - 1, block, cout, cout, root_extra + cout, k3);
         return;
     }
-    if (cin != cout) dl_add(net, 1, cin, cout);
+    if (cin != cout) dl_add(net, net.k1, cin, cout);
     dn_add_block(net, block, cin, cout, k3);
     dn_add_block(net, block, cout, cout, k3);
-    dl_add(net, 1, 2 * cout + root_extra, cout);
+    dl_add(net, net.k1, 2 * cout + root_extra, cout);
 }
 
 constexpr int DN_MAX_DEPTH = 5;                      // a root reads x2, x1, bottom and depth - 1 handed maps: 7 <= DL_MAX_SRC_RES
 
-static int dn_net(const int* levels, const int* ch, int block, DlaNet& net, const char* who, bool split = false) {
+// ctype != 0 (SMOT_FEAT_F16 or SMOT_FEAT_BF16, checked by the caller): half compute mode: the trees' images are kinds 5 and 6
+// (every tree convolution's Cin is a multiple of 32: channels[1..5], mid, and sums of them)
+static int dn_net(const int* levels, const int* ch, int block, DlaNet& net, const char* who, bool split = false, int ctype = 0) {
     if (!levels || !ch) {
         set_error("%s: null pointer", who);
         return SMOT_ERR_BAD_ARG;
@@ -916,7 +1179,9 @@ static int dn_net(const int* levels, const int* ch, int block, DlaNet& net, cons
     }
     net.n = 0;
     net.total = 0;
-    net.k3 = split ? 4 : 3;
+    net.k3 = ctype ? 5 : split ? 4 : 3;
+    net.k1 = ctype ? 6 : 1;
+    net.ctype = ctype;
     dl_add(net, 7, 3, ch[0]);
     dl_add(net, 3, ch[0], ch[0]);
     dl_add(net, 3, ch[0], ch[1]);
@@ -1053,7 +1318,7 @@ static int dla_pack_net(const DlaNet& net, const float* const* w, const float* c
                      "dla_pack: a tensor of convolution %d is null or not 4-byte aligned", i);
     for (int i = 0; i < net.n; ++i) {
         const DlaConv& c = net.conv[i];
-        const int rc = dl_pack_launch(c.kind, w[i], scale[i], shift[i], c.cin, c.cout, packed + c.off, (hipStream_t)stream);
+        const int rc = dl_pack_launch(c.kind, w[i], scale[i], shift[i], c.cin, c.cout, packed + c.off, (hipStream_t)stream, net.ctype);
         if (rc) return rc;
     }
     return SMOT_OK;
@@ -1191,7 +1456,7 @@ extern "C" int smot_dla_net_fwd(const void* image, int in_type, int num_images, 
 // ---- the three operators alone -------------------------------------------------------------------------------------------------
 static int dla_conv3x3_impl(const float* x, int num_images, int Cin, int H, int W, const float* w, const float* scale,
                             const float* shift, int Cout, int stride, const float* residual, int residual_h, int residual_w,
-                            int relu, float* packed, float* out, smot_stream_t stream, bool split) {
+                            int relu, float* packed, float* out, smot_stream_t stream, bool split, int ctype = 0) {
     SMOT_REQUIRE(dl_f32_ptr(x) && dl_f32_ptr(w) && dl_f32_ptr(scale) && dl_f32_ptr(shift) && dl_f32_ptr(out) &&
                      (!residual || dl_f32_ptr(residual)),
                  "dla_conv3x3: a null or misaligned pointer");
@@ -1202,7 +1467,7 @@ static int dla_conv3x3_impl(const float* x, int num_images, int Cin, int H, int 
     const bool rpool = residual && (residual_h != 0 || residual_w != 0);
     SMOT_REQUIRE(!rpool || (residual_h / 2 == Ho && residual_w / 2 == Wo),
                  "dla_conv3x3: a pooled residual of %d x %d for an output of %d x %d", residual_h, residual_w, Ho, Wo);
-    const int cstep = split ? CVS_IC : CV_IC;
+    const int cstep = split || ctype ? CVS_IC : CV_IC;
     if (Cin < cstep || Cin % cstep != 0 || Cin > 1024 || Cout < 16 || Cout % 16 != 0 || (Cout > 16 && Cout % 32 != 0) || Cout > 1024) {
         set_error("dla_conv3x3: Cin = %d, Cout = %d (supported: Cin a multiple of %d, Cout 16 or a multiple of 32, up to 1024)", Cin,
                   Cout, cstep);
@@ -1214,10 +1479,10 @@ static int dla_conv3x3_impl(const float* x, int num_images, int Cin, int H, int 
         return SMOT_ERR_UNSUPPORTED;
     }
     hipStream_t st = (hipStream_t)stream;
-    const int rp = dl_pack_launch(split ? 4 : 3, w, scale, shift, Cin, Cout, packed, st);
+    const int rp = dl_pack_launch(ctype ? 5 : split ? 4 : 3, w, scale, shift, Cin, Cout, packed, st, ctype);
     if (rp) return rp;
     return dl_conv3(x, num_images, Cin, H, W, packed, Cout, stride, residual, relu ? 1 : 0, out, st, rpool ? residual_h : 0,
-                    rpool ? residual_w : 0, split);
+                    rpool ? residual_w : 0, split, ctype);
 }
 extern "C" int smot_dla_conv3x3_fwd(const float* x, int num_images, int Cin, int H, int W, const float* w, const float* scale,
                                     const float* shift, int Cout, int stride, const float* residual, int residual_h,
@@ -1259,12 +1524,13 @@ extern "C" long long smot_dla_conv_split_packed_floats(int kernel_size, int Cin,
     return dl_conv_floats(4, Cin, Cout);
 }
 
-// max_sources: 4 for smot_dla_conv1x1_fwd (no residual), 8 for smot_dla_conv1x1_res_fwd
+// max_sources: 4 for smot_dla_conv1x1_fwd (no residual), 8 for smot_dla_conv1x1_res_fwd; ctype != 0: half compute mode (every
+// source a multiple of 32 channels, the kind-6 image, dla_conv1x1_half_kernel)
 static int dla_conv1x1_impl(const float* const* sources, const int* source_channels, const int* source_pooled,
                             const int* source_heights, const int* source_widths, int num_sources, int max_sources, int num_images,
                             int H, int W, const float* w, const float* scale, const float* shift, int Cout, int relu,
                             const float* residual, int residual_h, int residual_w, float* packed, void* out, int out_type,
-                            smot_stream_t stream) {
+                            smot_stream_t stream, int ctype = 0) {
     SMOT_REQUIRE(out_type == SMOT_FEAT_F32 || out_type == SMOT_FEAT_F16 || out_type == SMOT_FEAT_BF16,
                  "dla_conv1x1: out_type = %d (SMOT_FEAT_F32, _F16 or _BF16)", out_type);
     SMOT_REQUIRE(num_sources >= 1 && num_sources <= max_sources, "dla_conv1x1: %d sources (1 .. %d)", num_sources, max_sources);
@@ -1289,6 +1555,11 @@ static int dla_conv1x1_impl(const float* const* sources, const int* source_chann
         src[s] = DlaSrc{sources[s], source_channels[s], pooled, hs, wsrc};
         ok = ok && source_channels[s] >= 16 && source_channels[s] % 16 == 0 && source_channels[s] <= 1024;
         K += source_channels[s] > 0 ? source_channels[s] : 0;
+        if (ctype && source_channels[s] % 32 != 0) {
+            set_error("dla_conv1x1_half: source %d has %d channels (supported: every source a multiple of 32 channels: a K step "
+                      "of the 16-bit matrix instruction is 32 channels of one source)", s, source_channels[s]);
+            return SMOT_ERR_UNSUPPORTED;
+        }
         if ((long long)hs * wsrc * (source_channels[s] > 0 ? source_channels[s] : 1) >= (1LL << 31)) ok = false;
     }
     if (!ok || (long long)H * W * Cout >= (1LL << 31) || (long long)H * W / 64 * num_images >= (1LL << 31)) {
@@ -1297,8 +1568,11 @@ static int dla_conv1x1_impl(const float* const* sources, const int* source_chann
         return SMOT_ERR_UNSUPPORTED;
     }
     hipStream_t st = (hipStream_t)stream;
-    const int rp = dl_pack_launch(1, w, scale, shift, (int)K, Cout, packed, st);
+    const int rp = dl_pack_launch(ctype ? 6 : 1, w, scale, shift, (int)K, Cout, packed, st, ctype);
     if (rp) return rp;
+    if (ctype)
+        return dl_conv1_half(src, num_sources, num_images, H, W, packed, Cout, relu ? 1 : 0, out, out_type, nullptr, st, residual,
+                             rpool ? residual_h : 0, rpool ? residual_w : 0, ctype);
     return dl_conv1(src, num_sources, num_images, H, W, packed, Cout, relu ? 1 : 0, out, out_type, nullptr, st, residual,
                     rpool ? residual_h : 0, rpool ? residual_w : 0);
 }
@@ -1317,6 +1591,79 @@ extern "C" int smot_dla_conv1x1_res_fwd(const float* const* sources, const int* 
     return dla_conv1x1_impl(sources, source_channels, source_pooled, source_heights, source_widths, num_sources, DL_MAX_SRC_RES,
                             num_images, H, W, w, scale, shift, Cout, relu, residual, residual_h, residual_w, packed, out, out_type,
                             stream);
+}
+
+// ---- half compute mode (include/smot_emm.h, DLA BACKBONE, HALF COMPUTE) ---------------------------------------------------------
+static bool dl_ctype_ok(int t) { return t == SMOT_FEAT_F16 || t == SMOT_FEAT_BF16; }
+
+extern "C" long long smot_dla_half_packed_floats(const int* levels, const int* channels, int block, int residual_root,
+                                                 int compute_type) {
+    (void)residual_root;
+    DlaNet net;
+    if (!dl_ctype_ok(compute_type)) {
+        set_error("dla_half_packed_floats: compute_type = %d (SMOT_FEAT_F16 or SMOT_FEAT_BF16)", compute_type);
+        return -1;
+    }
+    if (dn_net(levels, channels, block, net, "dla_half_packed_floats", false, compute_type)) return -1;
+    return net.total;
+}
+
+extern "C" int smot_dla_half_pack(const int* levels, const int* channels, int block, int residual_root, int compute_type,
+                                  const float* const* w, const float* const* scale, const float* const* shift, int num_convs,
+                                  float* packed, smot_stream_t stream) {
+    (void)residual_root;
+    SMOT_REQUIRE(dl_ctype_ok(compute_type), "dla_half_pack: compute_type = %d (SMOT_FEAT_F16 or SMOT_FEAT_BF16)", compute_type);
+    DlaNet net;
+    const int rn = dn_net(levels, channels, block, net, "dla_half_pack", false, compute_type);
+    if (rn) return rn;
+    return dla_pack_net(net, w, scale, shift, num_convs, packed, stream);
+}
+
+// (the workspace is the fp32 mode's: smot_dla_net_ws_bytes)
+extern "C" int smot_dla_half_fwd(const void* image, int in_type, int num_images, int H, int W, const int* levels,
+                                 const int* channels, int block, int residual_root, int compute_type, const float* packed,
+                                 float* ws, void* const* out, int out_type, smot_stream_t stream) {
+    SMOT_REQUIRE(dl_ctype_ok(compute_type), "dla_half: compute_type = %d (SMOT_FEAT_F16 or SMOT_FEAT_BF16)", compute_type);
+    DlaNet net;
+    const int rn = dn_net(levels, channels, block, net, "dla_half", false, compute_type);
+    return dla_fwd_net(image, in_type, num_images, H, W, levels, channels, packed, ws, out, out_type, stream, net, rn,
+                       rn == SMOT_ERR_BAD_ARG ? 0 : block, residual_root);
+}
+
+extern "C" long long smot_dla_conv_half_packed_floats(int kernel_size, int Cin, int Cout) {
+    if (kernel_size == 7) return smot_dla_conv_packed_floats(kernel_size, Cin, Cout);
+    if ((kernel_size != 1 && kernel_size != 3) || Cin < 1 || Cin % 32 != 0 || Cout < 16 || Cout % 16 != 0) return -1;
+    return dl_conv_floats(kernel_size == 3 ? 5 : 6, Cin, Cout);
+}
+
+extern "C" int smot_dla_conv3x3_half_form(int num_images, int H, int W, int Cout, int stride) {
+    return smot_dla_conv3x3_form(num_images, H, W, Cout, stride);
+}
+
+// -> the M-tiles per workgroup (2 or 4) that smot_dla_conv1x1_half_fwd runs for this output
+extern "C" int smot_dla_conv1x1_half_form(int num_images, int H, int W, int Cout) {
+    if (num_images < 1 || H < 1 || W < 1 || Cout < 32 || Cout % 32 != 0) return -1;
+    return dl_conv1_half_mt(Cout, (((long long)H * W + DL_POS - 1) / DL_POS) * num_images);
+}
+
+extern "C" int smot_dla_conv3x3_half_fwd(const float* x, int num_images, int Cin, int H, int W, const float* w, const float* scale,
+                                         const float* shift, int Cout, int stride, const float* residual, int residual_h,
+                                         int residual_w, int relu, int compute_type, float* packed, float* out,
+                                         smot_stream_t stream) {
+    SMOT_REQUIRE(dl_ctype_ok(compute_type), "dla_conv3x3_half: compute_type = %d (SMOT_FEAT_F16 or SMOT_FEAT_BF16)", compute_type);
+    return dla_conv3x3_impl(x, num_images, Cin, H, W, w, scale, shift, Cout, stride, residual, residual_h, residual_w, relu, packed,
+                            out, stream, false, compute_type);
+}
+
+extern "C" int smot_dla_conv1x1_half_fwd(const float* const* sources, const int* source_channels, const int* source_pooled,
+                                         const int* source_heights, const int* source_widths, int num_sources, int num_images,
+                                         int H, int W, const float* w, const float* scale, const float* shift, int Cout, int relu,
+                                         const float* residual, int residual_h, int residual_w, int compute_type, float* packed,
+                                         void* out, int out_type, smot_stream_t stream) {
+    SMOT_REQUIRE(dl_ctype_ok(compute_type), "dla_conv1x1_half: compute_type = %d (SMOT_FEAT_F16 or SMOT_FEAT_BF16)", compute_type);
+    return dla_conv1x1_impl(sources, source_channels, source_pooled, source_heights, source_widths, num_sources, DL_MAX_SRC_RES,
+                            num_images, H, W, w, scale, shift, Cout, relu, residual, residual_h, residual_w, packed, out, out_type,
+                            stream, compute_type);
 }
 
 extern "C" long long smot_dla_stem_ws_bytes(int num_images, int H, int W, int c0, int c1) {

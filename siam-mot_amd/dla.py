@@ -17,7 +17,10 @@ Two forms of the operator live here:
   ``out_dtype`` half stores the stage maps rounded once; ``operands="split16"`` runs the trees' 3x3 convolutions on the
   16-bit matrix instruction with three-part bf16 operands and fp32 accumulation instead (fp32-grade results in another
   summation order, no dependence on the data's range).  ``DlaBasic`` networks with trees of depth <= 2
-  take ``ops.dla``, every other one ``ops.dla_net`` (INTEGRATION.md §3o);
+  take ``ops.dla``, every other one ``ops.dla_net``; ``compute_dtype=torch.float16`` or
+  ``torch.bfloat16`` runs EVERY tree convolution (3x3 and 1x1) with operands rounded to that type on the 16-bit matrix
+  instruction, fp32 accumulation and the fp32 epilogue (``ops.dla_half``): a half-precision result,
+  not an fp32-grade one;
 * ``dla_torch``: the same as a plain torch composition over the module tree.  It is the path for CPU tensors, images that
   are not contiguous NCHW, trainable parameters under grad mode and shapes beyond the capacities (counted in
   ``ops.FALLBACKS["dla_torch"]`` for device tensors), and the baseline of tools/dla_bench.py and
@@ -164,12 +167,26 @@ class DLA(nn.Module):
     the device path the packed weights are rebuilt when a parameter's or buffer's ``_version``, storage or device changes.
     ``operands``: "fp32" (the default) or "split16": which kernel the device path runs for the trees' 3x3 convolutions
     (module docstring); the torch composition, the ``state_dict`` and what ``kernel_ok`` admits do not depend on it.
-    ``block`` ("basic" or "bottleneck") and ``residual_root`` are upstream's, keyword-only."""
+    ``block`` ("basic" or "bottleneck") and ``residual_root`` are upstream's, keyword-only.
+    ``compute_dtype`` (keyword-only): None (the default: ``operands`` decides, nothing changes), ``torch.float16`` or
+    ``torch.bfloat16``: the device path runs every tree convolution, 3x3 and 1x1, with its input (as it is loaded) and its
+    filters (once, when packed) rounded to that type — ``tensor.to``'s rounding; an fp16 operand beyond 65,504 is +-inf —
+    with exact products and fp32 accumulation; the stem, the BN, the residuals and the maps between layers stay fp32, and
+    ``out_dtype`` keeps its meaning.  It excludes ``operands="split16"`` (two answers to one question).  The torch
+    composition ``dla_torch`` does not depend on it, exactly as it does not depend on ``operands``: CPU tensors and every
+    fallback give the bits of fp32 mode.  The ``state_dict`` and what ``kernel_ok`` admits do not depend on it either."""
 
-    def __init__(self, levels, channels, out_dtype=torch.float32, operands="fp32", *, block="basic", residual_root=False):
+    def __init__(self, levels, channels, out_dtype=torch.float32, operands="fp32", *, block="basic", residual_root=False,
+                 compute_dtype=None):
         super(DLA, self).__init__()
         if operands not in ops.DLA_OPERANDS:
             raise ValueError("DLA: operands must be \"fp32\" or \"split16\", got %r" % (operands,))
+        if compute_dtype is not None and compute_dtype not in ops.DLA_COMPUTE_TYPES:
+            raise ValueError("DLA: compute_dtype must be None, torch.float16 or torch.bfloat16, got %r" % (compute_dtype,))
+        if compute_dtype is not None and operands != "fp32":
+            raise ValueError("DLA: compute_dtype=%r excludes operands=%r: the half compute mode and the split operands are two "
+                             "answers to one question" % (compute_dtype, operands))
+        self.compute_dtype = compute_dtype
         if block not in BLOCKS:
             raise ValueError("DLA: block must be \"basic\" or \"bottleneck\", got %r" % (block,))
         self.operands, self.block, self.residual_root = operands, block, bool(residual_root)
@@ -222,11 +239,14 @@ class DLA(nn.Module):
 
     def packed(self):
         tensors = list(self.parameters()) + list(self.buffers())
-        key = (self.operands,) + tuple((t.data_ptr(), t._version, t.device) for t in tensors)
+        key = (self.operands, self.compute_dtype) + tuple((t.data_ptr(), t._version, t.device) for t in tensors)
         if key != self._packed_key:
             with torch.no_grad():
                 convs = [(c.weight.detach(),) + tuple(t.contiguous() for t in bn.scale_shift()) for c, bn in self.convs()]
-                if self._net:
+                if self.compute_dtype is not None:
+                    self._packed = ops.dla_half_pack(convs, self.levels, self.channels, self.compute_dtype, block=self.block,
+                                                     residual_root=self.residual_root)
+                elif self._net:
                     self._packed = ops.dla_net_pack(convs, self.levels, self.channels, block=self.block,
                                                     residual_root=self.residual_root, operands=self.operands)
                 else:
@@ -236,6 +256,9 @@ class DLA(nn.Module):
 
     def forward(self, images):
         if self.kernel_ok(images):
+            if self.compute_dtype is not None:
+                return ops.dla_half(images, self.packed(), self.levels, self.channels, self.compute_dtype, block=self.block,
+                                    residual_root=self.residual_root, out_dtype=self.out_dtype)
             if self._net:
                 return ops.dla_net(images, self.packed(), self.levels, self.channels, block=self.block,
                                    residual_root=self.residual_root, out_dtype=self.out_dtype, operands=self.operands)
@@ -248,26 +271,28 @@ class DLA(nn.Module):
         return out
 
 
-def dla_34(out_dtype=torch.float32, operands="fp32"):
-    return DLA((1, 1, 1, 2, 2, 1), (16, 32, 64, 128, 256, 512), out_dtype=out_dtype, operands=operands)
+def dla_34(out_dtype=torch.float32, operands="fp32", compute_dtype=None):
+    return DLA((1, 1, 1, 2, 2, 1), (16, 32, 64, 128, 256, 512), out_dtype=out_dtype, operands=operands, compute_dtype=compute_dtype)
 
 
-def dla_46_c(out_dtype=torch.float32, operands="fp32"):
-    return DLA((1, 1, 1, 2, 2, 1), (16, 32, 64, 64, 128, 256), out_dtype=out_dtype, operands=operands, block="bottleneck")
+def dla_46_c(out_dtype=torch.float32, operands="fp32", compute_dtype=None):
+    return DLA((1, 1, 1, 2, 2, 1), (16, 32, 64, 64, 128, 256), out_dtype=out_dtype, operands=operands, block="bottleneck",
+               compute_dtype=compute_dtype)
 
 
-def dla_60(out_dtype=torch.float32, operands="fp32"):
-    return DLA((1, 1, 1, 2, 3, 1), (16, 32, 128, 256, 512, 1024), out_dtype=out_dtype, operands=operands, block="bottleneck")
+def dla_60(out_dtype=torch.float32, operands="fp32", compute_dtype=None):
+    return DLA((1, 1, 1, 2, 3, 1), (16, 32, 128, 256, 512, 1024), out_dtype=out_dtype, operands=operands, block="bottleneck",
+               compute_dtype=compute_dtype)
 
 
-def dla_102(out_dtype=torch.float32, operands="fp32"):
+def dla_102(out_dtype=torch.float32, operands="fp32", compute_dtype=None):
     return DLA((1, 1, 1, 3, 4, 1), (16, 32, 128, 256, 512, 1024), out_dtype=out_dtype, operands=operands, block="bottleneck",
-               residual_root=True)
+               residual_root=True, compute_dtype=compute_dtype)
 
 
-def dla_169(out_dtype=torch.float32, operands="fp32"):
+def dla_169(out_dtype=torch.float32, operands="fp32", compute_dtype=None):
     return DLA((1, 1, 2, 3, 5, 1), (16, 32, 128, 256, 512, 1024), out_dtype=out_dtype, operands=operands, block="bottleneck",
-               residual_root=True)
+               residual_root=True, compute_dtype=compute_dtype)
 
 
 BODIES = {"DLA-34-FPN": dla_34, "DLA-46-C-FPN": dla_46_c, "DLA-60-FPN": dla_60, "DLA-102-FPN": dla_102, "DLA-169-FPN": dla_169}
@@ -275,7 +300,7 @@ BODIES = {"DLA-34-FPN": dla_34, "DLA-46-C-FPN": dla_46_c, "DLA-60-FPN": dla_60, 
 UNSUPPORTED_BODIES = ("DLA-46-XC-FPN", "DLA-60-RES2NET-FPN")
 
 
-def build_dla(cfg, out_dtype=torch.float32, operands="fp32"):
+def build_dla(cfg, out_dtype=torch.float32, operands="fp32", compute_dtype=None):
     """The body of the config's ``MODEL.BACKBONE.CONV_BODY``: one of ``BODIES``.  Any other body, any true entry of
     ``MODEL.DLA.STAGE_WITH_DCN`` (deformable convolutions) and stage widths in ``MODEL.DLA.DLA_STAGE*_OUT_CHANNELS`` that
     are not the body's raise a ``ValueError`` that names the body or the entry."""
@@ -289,7 +314,7 @@ def build_dla(cfg, out_dtype=torch.float32, operands="fp32"):
     if any(dcn):
         raise ValueError("build_dla: MODEL.DLA.STAGE_WITH_DCN = %r asks for deformable convolutions, which this package does "
                          "not have" % (dcn,))
-    body = BODIES[name](out_dtype=out_dtype, operands=operands)
+    body = BODIES[name](out_dtype=out_dtype, operands=operands, compute_dtype=compute_dtype)
     dla = cfg.MODEL.DLA
     stages = (dla.DLA_STAGE2_OUT_CHANNELS, dla.DLA_STAGE3_OUT_CHANNELS, dla.DLA_STAGE4_OUT_CHANNELS, dla.DLA_STAGE5_OUT_CHANNELS)
     if tuple(stages) != tuple(body.out_channels):

@@ -180,6 +180,16 @@ _SIGNATURES = {
     "smot_dla_net_fwd": (ctypes.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "smot_dla_conv1x1_res_fwd": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp,
                                                 _i, _vp]),
+    # DLA bodies in half compute mode: every tree convolution with fp16 / bf16 operands on the 16-bit matrix instruction
+    "smot_dla_half_packed_floats": (ctypes.c_longlong, [_vp, _vp, _i, _i, _i]),
+    "smot_dla_half_pack": (ctypes.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    "smot_dla_half_fwd": (ctypes.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    "smot_dla_conv_half_packed_floats": (ctypes.c_longlong, [_i, _i, _i]),
+    "smot_dla_conv3x3_half_fwd": (ctypes.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "smot_dla_conv3x3_half_form": (ctypes.c_int, [_i, _i, _i, _i, _i]),
+    "smot_dla_conv1x1_half_form": (ctypes.c_int, [_i, _i, _i, _i]),
+    "smot_dla_conv1x1_half_fwd": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp,
+                                                 _vp, _i, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 _DEBUG_SIGNATURES = {
@@ -1861,6 +1871,156 @@ def dla_net(images, packed, levels, channels, block="basic", residual_root=False
         rc = lib.smot_dla_net_fwd(_ptr(x), FEAT_TYPES[x.dtype], N, H, W, _cast(lv), _cast(ch), blk, rr, split, _ptr(packed),
                                   _ptr(ws), _cast(po), FEAT_TYPES[out_dtype], ln.stream)
     _check(rc, "dla_net")
+    return out
+
+
+# ``compute_dtype`` of the DLA bodies' half compute mode (include/smot_emm.h, DLA BACKBONE, HALF COMPUTE): every tree
+# convolution takes its operands rounded to this type, on the 16-bit matrix instruction, with fp32 accumulation
+DLA_COMPUTE_TYPES = (torch.float16, torch.bfloat16)
+
+
+def _dla_ctype(compute_dtype, who):
+    if compute_dtype not in DLA_COMPUTE_TYPES:
+        raise ValueError("siammot_amd.%s: compute_dtype must be torch.float16 or torch.bfloat16, got %r" % (who, compute_dtype))
+    return FEAT_TYPES[compute_dtype]
+
+
+def dla_half_pack(convs, levels, channels, compute_dtype, block="basic", residual_root=False):
+    """``dla_net_pack`` for ``dla_half`` (``smot_dla_half_pack``): the tree convolutions' filters rounded once to
+    ``compute_dtype`` (``tensor.to``'s rounding), the stem's and every ``scale`` / ``shift`` in fp32.  The tensor serves this
+    ``compute_dtype`` and no other mode."""
+    lib = _lib or load_library()
+    ct = _dla_ctype(compute_dtype, "dla_half_pack")
+    blk, rr = _dla_block(block, "dla_half_pack"), 1 if residual_root else 0
+    lv, ch = _int6(levels), _int6(channels)
+    n = lib.smot_dla_half_packed_floats(_cast(lv), _cast(ch), blk, rr, ct)
+    if n < 0:
+        _check(-2, "dla_half_pack")
+    ts = [[_chk(t, "dla_half_pack: convs[%d][%d]" % (i, j), tuple(t.shape)) for j, t in enumerate(c)] for i, c in enumerate(convs)]
+    packed = torch.empty((n,), dtype=_F32, device=ts[0][0].device)
+    arrays = [(ctypes.c_void_p * len(ts))(*[c[j].data_ptr() for c in ts]) for j in range(3)]
+    with _Launch(*[t for c in ts for t in c]) as ln:
+        rc = lib.smot_dla_half_pack(_cast(lv), _cast(ch), blk, rr, ct, _cast(arrays[0]), _cast(arrays[1]), _cast(arrays[2]),
+                                    len(ts), _ptr(packed), ln.stream)
+    _check(rc, "dla_half_pack")
+    return packed
+
+
+def dla_half(images, packed, levels, channels, compute_dtype, block="basic", residual_root=False, out_dtype=torch.float32):
+    """``dla_net`` in half compute mode (``smot_dla_half_fwd``): every tree convolution — 3x3 and 1x1 — multiplies operands
+    rounded to ``compute_dtype`` (activations as they are loaded, filters in ``dla_half_pack``) on the 16-bit matrix
+    instruction and accumulates in fp32; the stem, the BN, the residuals and the maps between layers stay fp32.  An fp16
+    operand beyond 65,504 in magnitude is +-inf.  Arguments and results otherwise as ``dla_net``'s; the same launches and
+    workspace."""
+    lib = _lib or load_library()
+    ct = _dla_ctype(compute_dtype, "dla_half")
+    blk, rr = _dla_block(block, "dla_half"), 1 if residual_root else 0
+    if out_dtype not in FEAT_TYPES:
+        raise RuntimeError("siammot_amd.dla_half: out_dtype must be float32, float16 or bfloat16, got %s" % (out_dtype,))
+    x = _dev_feat(images, "images")
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise RuntimeError("siammot_amd.dla_half: images has shape %s, expected [N, 3, H, W]" % (tuple(x.shape),))
+    N, H, W = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+    lv, ch = _int6(levels), _int6(channels)
+    nbytes = lib.smot_dla_net_ws_bytes(_cast(lv), _cast(ch), blk, rr, N, H, W)
+    if nbytes < 0:
+        _check(-2, "dla_half")
+    ws = torch.empty((max(nbytes // 4, 4),), dtype=_F32, device=x.device)
+    out = [torch.empty((N, int(channels[k]), H >> k, W >> k), dtype=out_dtype, device=x.device) for k in range(2, 6)]
+    po = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in out])
+    with _Launch(x, packed) as ln:
+        rc = lib.smot_dla_half_fwd(_ptr(x), FEAT_TYPES[x.dtype], N, H, W, _cast(lv), _cast(ch), blk, rr, ct, _ptr(packed),
+                                   _ptr(ws), _cast(po), FEAT_TYPES[out_dtype], ln.stream)
+    _check(rc, "dla_half")
+    return out
+
+
+def dla_conv3x3_half_form(N, H, W, Cout, stride):
+    """``dla_conv3x3_form`` for ``dla_conv3x3_half``'s launch site (``smot_dla_conv3x3_half_form``): ``(WR, NM)``."""
+    lib = _lib or load_library()
+    form = lib.smot_dla_conv3x3_half_form(int(N), int(H), int(W), int(Cout), int(stride))
+    if form < 0:
+        raise RuntimeError("siammot_amd.dla_conv3x3_half_form: bad argument")
+    return form // 10, form % 10
+
+
+def dla_conv3x3_half(x, w, scale, shift, stride, compute_dtype, residual=None, relu=True, residual_pooled=False):
+    """``dla_conv3x3`` in half compute mode (``smot_dla_conv3x3_half_fwd``): ``x`` and ``w`` rounded to ``compute_dtype``,
+    exact products, fp32 accumulation, the fp32 epilogue.  ``Cin`` a multiple of 32."""
+    lib = _lib or load_library()
+    ct = _dla_ctype(compute_dtype, "dla_conv3x3_half")
+    x = _dev_f32(x, "x")
+    N, Cin, H, W = (int(v) for v in x.shape)
+    Cout = int(w.shape[0])
+    w = _chk(w, "w", (Cout, Cin, 3, 3))
+    scale, shift = _chk(scale, "scale", (Cout,)), _chk(shift, "shift", (Cout,))
+    Ho, Wo = ((H - 1) // 2 + 1, (W - 1) // 2 + 1) if stride == 2 else (H, W)
+    rh = rw = 0
+    if residual is not None and residual_pooled:
+        rh, rw = int(residual.shape[-2]), int(residual.shape[-1])
+        residual = _chk(residual, "residual", (N, Cout, rh, rw))
+    elif residual is not None:
+        residual = _chk(residual, "residual", (N, Cout, Ho, Wo))
+    n = lib.smot_dla_conv_half_packed_floats(3, Cin, Cout)
+    packed = torch.empty((max(n, 4),), dtype=_F32, device=x.device)
+    out = torch.empty((N, Cout, Ho, Wo), dtype=_F32, device=x.device)
+    with _Launch(x, w, scale, shift, residual) as ln:
+        rc = lib.smot_dla_conv3x3_half_fwd(_ptr(x), N, Cin, H, W, _ptr(w), _ptr(scale), _ptr(shift), Cout, int(stride),
+                                           _ptr(residual), rh, rw, 1 if relu else 0, ct, _ptr(packed), _ptr(out), ln.stream)
+    _check(rc, "dla_conv3x3_half")
+    return out
+
+
+def dla_conv1x1_half_form(N, H, W, Cout):
+    """The M-tiles (of 16 output channels) per workgroup that ``dla_conv1x1_half`` runs for ``N`` outputs of ``H x W``
+    (``smot_dla_conv1x1_half_form``): 4, or 2 where 4 would leave CUs without a workgroup."""
+    lib = _lib or load_library()
+    form = lib.smot_dla_conv1x1_half_form(int(N), int(H), int(W), int(Cout))
+    if form < 0:
+        raise RuntimeError("siammot_amd.dla_conv1x1_half_form: bad argument")
+    return form
+
+
+def dla_conv1x1_half(sources, pooled, w, scale, shift, relu, compute_dtype, residual=None, residual_pooled=False,
+                     out_dtype=torch.float32):
+    """``dla_conv1x1_res`` in half compute mode (``smot_dla_conv1x1_half_fwd``): the sources' values (after the pool, where a
+    source is pooled) and ``w`` rounded to ``compute_dtype``, exact products, fp32 accumulation, the fp32 epilogue.  Every
+    source a multiple of 32 channels."""
+    lib = _lib or load_library()
+    ct = _dla_ctype(compute_dtype, "dla_conv1x1_half")
+    S = len(sources)
+    if S < 1 or len(pooled) != S:
+        raise RuntimeError("siammot_amd.dla_conv1x1_half: %d sources, %d pooled flags" % (S, len(pooled)))
+    if out_dtype not in FEAT_TYPES:
+        raise RuntimeError("siammot_amd.dla_conv1x1_half: out_dtype must be float32, float16 or bfloat16, got %s" % (out_dtype,))
+    src = [_dev_f32(t, "sources[%d]" % s) for s, t in enumerate(sources)]
+    N = int(src[0].shape[0])
+    H, W = (int(src[0].shape[2]) // 2, int(src[0].shape[3]) // 2) if pooled[0] else (int(src[0].shape[2]), int(src[0].shape[3]))
+    K = sum(int(t.shape[1]) for t in src)
+    Cout = int(w.shape[0])
+    w = _chk(w.reshape(Cout, -1), "w", (Cout, K))
+    scale, shift = _chk(scale, "scale", (Cout,)), _chk(shift, "shift", (Cout,))
+    for s, t in enumerate(src):
+        if t.dim() != 4 or t.shape[0] != N:
+            raise RuntimeError("siammot_amd.dla_conv1x1_half: sources[%d] has shape %s" % (s, tuple(t.shape)))
+    rh = rw = 0
+    if residual is not None and residual_pooled:                 # (its size is the library's to check)
+        rh, rw = int(residual.shape[-2]), int(residual.shape[-1])
+        residual = _chk(residual, "residual", (N, Cout, rh, rw))
+    elif residual is not None:
+        residual = _chk(residual, "residual", (N, Cout, H, W))
+    arr = lambda vals: (ctypes.c_int * S)(*[int(v) for v in vals])
+    sp = (ctypes.c_void_p * S)(*[t.data_ptr() for t in src])
+    sc, sf = arr(t.shape[1] for t in src), arr(1 if f else 0 for f in pooled)
+    sh, sw = arr(t.shape[2] for t in src), arr(t.shape[3] for t in src)
+    n = lib.smot_dla_conv_half_packed_floats(1, K, Cout)
+    packed = torch.empty((max(n, 4),), dtype=_F32, device=src[0].device)
+    out = torch.empty((N, Cout, H, W), dtype=out_dtype, device=src[0].device)
+    with _Launch(*(src + [w, scale, shift, residual])) as ln:
+        rc = lib.smot_dla_conv1x1_half_fwd(_cast(sp), _cast(sc), _cast(sf), _cast(sh), _cast(sw), S, N, H, W, _ptr(w),
+                                           _ptr(scale), _ptr(shift), Cout, 1 if relu else 0, _ptr(residual), rh, rw, ct,
+                                           _ptr(packed), _ptr(out), FEAT_TYPES[out_dtype], ln.stream)
+    _check(rc, "dla_conv1x1_half")
     return out
 
 
