@@ -64,7 +64,9 @@ typedef void* smot_stream_t; /* hipStream_t */
  *     smot_dla_conv_split_packed_floats, smot_dla_conv3x3_split_fwd, smot_dla_conv3x3_split_form;
  *     the bodies of either block type: smot_dla_net_*, smot_dla_conv1x1_res_fwd; the bodies in half compute mode:
  *     smot_dla_half_packed_floats, smot_dla_half_pack, smot_dla_half_fwd, smot_dla_conv_half_packed_floats,
- *     smot_dla_conv3x3_half_fwd, smot_dla_conv3x3_half_form, smot_dla_conv1x1_half_fwd.
+ *     smot_dla_conv3x3_half_fwd, smot_dla_conv3x3_half_form, smot_dla_conv1x1_half_fwd; the feature pyramid and the RPN head
+ *     in half compute mode: smot_fpn_half_packed_floats, smot_fpn_half_pack, smot_fpn_half_fwd,
+ *     smot_rpn_head_half_packed_floats, smot_rpn_head_half_pack, smot_rpn_head_half_fwd.
  */
 #define SMOT_ABI_VERSION 14
 
@@ -1107,6 +1109,39 @@ int smot_rpn_anchors_fwd(const float* const* cell_anchors, const int* num_anchor
                          const int* widths, int num_levels, float* const* out, smot_stream_t stream);
 
 /*
+ * RPN HEAD, HALF COMPUTE: the head above with its 3x3 convolution on the 16-bit matrix instruction
+ * (v_mfma_f32_16x16x32_f16 / _bf16).  Opt-in: the entry points above and their packed image are untouched.  The arguments are
+ * the fp32 twins' plus `compute_type` (SMOT_FEAT_F16 or SMOT_FEAT_BF16; anything else, SMOT_FEAT_F32 included, is
+ * SMOT_ERR_BAD_ARG, and smot_rpn_head_half_packed_floats returns -1 for it).
+ *
+ *   t   = relu(conv3x3(rnd(x), rnd(conv.weight), pad 1) + conv.bias)
+ *   obj = conv1x1(t, cls_logits.weight) + bias,  reg = conv1x1(t, bbox_pred.weight) + bias
+ *
+ *   rnd            tensor.to(compute_type)'s rounding: round to nearest even, an fp16 value beyond 65,504 becomes +-inf.  A
+ *                  map value is loaded, widened to fp32 and then rounded (an fp16 map in fp16 mode is exact); the filters are
+ *                  rounded once by smot_rpn_head_half_pack.  Products are exact, the accumulation is fp32, and the bias /
+ *                  ReLU epilogue is the fp32 mode's.
+ *   the heads      t stays fp32 on the chip and the two 1x1 heads run on it exactly as in the fp32 mode: fp32 matrix
+ *                  instruction, unrounded cls_logits / bbox_pred.  The mode is the 3x3's; there is no second, data-dependent
+ *                  rounding.
+ *   packed         smot_rpn_head_half_packed_floats(C, A, compute_type) floats, 16-byte aligned, written by
+ *                  smot_rpn_head_half_pack: the rounded filters two to a dword, everything behind them (biases, the heads'
+ *                  rows) fp32 as smot_rpn_head_pack lays it out.  An image serves its compute_type and no other mode.
+ *   contract       the fp32 mode's: one launch for all images and levels, no host synchronisation; a summation order fixed by
+ *                  (C, A): image i of a call equals the one-image call on it bit for bit; a NaN or infinite input cell (an
+ *                  fp16-mode value beyond 65,504 included) makes non-finite exactly the outputs whose 3x3 window covers it.
+ *   capacities     the fp32 mode's (C % 32 == 0 is the K step of the 16-bit instruction), also SMOT_ERR_UNSUPPORTED for a
+ *                  level of 2^26 cells or more.  Validation, refusals and "nothing is launched by a refused call" as above.
+ */
+long long smot_rpn_head_half_packed_floats(int C, int A, int compute_type);
+int smot_rpn_head_half_pack(const float* conv_w, const float* conv_b, const float* cls_w, const float* cls_b,
+                            const float* bbox_w, const float* bbox_b, int C, int A, int compute_type, float* packed,
+                            smot_stream_t stream);
+int smot_rpn_head_half_fwd(const void* const* feats, int feat_type, const int* heights, const int* widths, int num_levels,
+                           int num_images, int C, int A, int compute_type, const float* packed,
+                           float* const* objectness_out, float* const* regression_out, smot_stream_t stream);
+
+/*
  * FEATURE PYRAMID (csrc/fpn.hip): [UPSTREAM] maskrcnn_benchmark FPN.forward with the top-down path resized bilinearly to
  * the lateral's size (the stage maps need not halve exactly) — backbone stage maps to the pyramid's maps for every image of
  * a call in num_levels + 1 launches (one lateral launch per level, coarsest first, then ONE launch for the 3x3 convolutions
@@ -1150,6 +1185,41 @@ long long smot_fpn_ws_bytes(int num_levels, const int* heights, const int* width
 int smot_fpn_fwd(const void* const* stages, int stage_type, const int* in_channels, const int* heights, const int* widths,
                  int num_levels, int num_images, int C, const float* packed, float* ws, void* const* out, int out_type,
                  int top_block, smot_stream_t stream);
+
+/*
+ * FEATURE PYRAMID, HALF COMPUTE: the pyramid above with both convolutions on the 16-bit matrix instruction
+ * (v_mfma_f32_16x16x32_f16 / _bf16).  Opt-in: the entry points above and their packed image are untouched.  The arguments are
+ * the fp32 twins' plus `compute_type` (SMOT_FEAT_F16 or SMOT_FEAT_BF16; anything else, SMOT_FEAT_F32 included, is
+ * SMOT_ERR_BAD_ARG, and smot_fpn_half_packed_floats returns -1 for it).
+ *
+ *   last[l] = conv1x1(rnd(x[l]), rnd(inner_w)) + inner_b + resize(last[l+1] -> (H_l, W_l))    fp32, in the workspace
+ *   P[l]    = conv3x3(rnd(last[l]), rnd(layer_w), pad 1) + layer_b                            stored in out_type
+ *   P[L]    = P[L-1][:, :, ::2, ::2]                                                          stored with P[L-1]
+ *
+ *   rnd            tensor.to(compute_type)'s rounding: round to nearest even, an fp16 value beyond 65,504 becomes +-inf.  A
+ *                  value is loaded, widened to fp32 and then rounded (an fp16 stage map in fp16 mode is exact); the filters
+ *                  are rounded once by smot_fpn_half_pack.  Products are exact and the accumulation is fp32.  `last` is
+ *                  kept in fp32 and rounded AGAIN when the 3x3 stage loads it: that second rounding is part of the mode.
+ *                  The bias add, the bilinear sample (resize above, every operation rounded on its own, all four products)
+ *                  and the stores are the fp32 mode's expressions.
+ *   packed         smot_fpn_half_packed_floats(...) floats, 16-byte aligned, written by smot_fpn_half_pack: 16-bit operands
+ *                  two to a dword, the biases fp32.  An image serves its compute_type and no other mode.
+ *   ws             smot_fpn_ws_bytes(...) bytes as above: the mode's workspace is the fp32 mode's.
+ *   contract       the fp32 mode's: num_levels + 1 launches, no host synchronisation; a summation order fixed by
+ *                  (in_channels[l], C) and the position: image i of a call equals the one-image call on it bit for bit.  A
+ *                  non-finite cell (an fp16-mode value beyond 65,504 included) reaches exactly the outputs that the fp32
+ *                  mode's composition spreads it to.
+ *   capacities     the fp32 mode's, plus in_channels[l] % 32 == 0 for every level (a K step is 32 channels):
+ *                  SMOT_ERR_UNSUPPORTED beyond, naming the level; nothing is launched and the outputs are untouched.
+ *                  Validation and refusals otherwise as above.
+ */
+long long smot_fpn_half_packed_floats(int num_levels, const int* in_channels, int C, int compute_type);
+int smot_fpn_half_pack(const float* const* inner_w, const float* const* inner_b, const float* const* layer_w,
+                       const float* const* layer_b, int num_levels, const int* in_channels, int C, int compute_type,
+                       float* packed, smot_stream_t stream);
+int smot_fpn_half_fwd(const void* const* stages, int stage_type, const int* in_channels, const int* heights,
+                      const int* widths, int num_levels, int num_images, int C, int compute_type, const float* packed,
+                      float* ws, void* const* out, int out_type, int top_block, smot_stream_t stream);
 
 /*
  * DLA BACKBONE (csrc/dla.hip): [UPSTREAM] siammot/modelling/backbone/dla.py with DlaBasic blocks and maskrcnn_benchmark's

@@ -10,12 +10,12 @@ from .dla import build_dla
 from .fpn import build_fpn
 
 
-def build_backbone(cfg, out_dtype=torch.float32, operands="fp32", compute_dtype=None):
+def build_backbone(cfg, out_dtype=torch.float32, operands="fp32", compute_dtype=None, fpn_compute_dtype=None):
     """``out_dtype``: the element type of the FPN's maps; the body hands the pyramid fp32 stage maps.  ``operands``: the
-    body's operand mode (``dla.DLA``: "fp32" or "split16").  ``compute_dtype``: the body's half compute mode (``dla.DLA``:
-    None, ``torch.float16`` or ``torch.bfloat16``)."""
+    body's operand mode (``dla.DLA``: "fp32" or "split16").  ``compute_dtype``: the BODY's half compute mode (``dla.DLA``:
+    None, ``torch.float16`` or ``torch.bfloat16``), and the body's alone; ``fpn_compute_dtype``: the pyramid's (``fpn.FPN``)."""
     body = build_dla(cfg, operands=operands, compute_dtype=compute_dtype)
-    fpn = build_fpn(cfg, out_dtype=out_dtype)
+    fpn = build_fpn(cfg, out_dtype=out_dtype, compute_dtype=fpn_compute_dtype)
     if tuple(fpn.in_channels_list) != tuple(body.out_channels):
         raise ValueError("build_backbone: the body's stage widths %r are not the pyramid's inputs %r"
                          % (tuple(body.out_channels), tuple(fpn.in_channels_list)))

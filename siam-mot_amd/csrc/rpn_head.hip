@@ -28,7 +28,15 @@
 // outputs whose 3x3 window covers it.  An output's sum order is fixed by (C, A) — it does not depend on the image's
 // index, the number of images or the other levels of the call.
 // LDS: 128 x 144 x 4 = 73,728 B -> two workgroups per CU; launch bound 256 VGPRs.
-#include "roi_common.h"
+//
+// HALF COMPUTE MODE (the smot_rpn_head_half_* entry points; CT = SMOT_FEAT_F16 or SMOT_FEAT_BF16): rpn_head_half_kernel<CT, FT>
+// is the kernel above with the 3x3 stage on v_mfma_f32_16x16x32_f16 / _bf16 (conv3x3_mfma.h's cvh_block<CT, FT, 1, 1, 2>:
+// chunks of 32 input channels, x rounded to CT as it is staged, Wc rounded once by the pack kernel, exact products, fp32
+// accumulation; its two 12,288 B stage buffers lie under t as the fp32 buffers do).  t = relu(conv + bc) stays fp32 in LDS
+// and the two 1x1 heads run on it as above, on the fp32 matrix instruction with unrounded weights: the mode is the 3x3's,
+// and the result is "rounded operands, fp32 sum order" with no second, data-dependent rounding.  Same workgroups, barriers,
+// LDS and launch bound.
+#include "conv3x3_mfma.h"
 
 namespace smot {
 
@@ -257,6 +265,138 @@ rpn_head_kernel(RpnHeadArgs P) {
         }
 }
 
+// ---- half compute mode ----------------------------------------------------------------------------------------------------------
+// the half packed image: [cvh_pack_index image of conv.weight rounded to CT: 9 C^2 / 2 dwords][C conv biases][the heads' A
+// operand][the padded rows' biases]: everything behind the filters is fp32 and laid out as rpn_head_pack_kernel writes it
+__host__ __device__ inline long long rhh_off_bias(int C) { return cvh_packed_floats(C, C); }
+__host__ __device__ inline long long rhh_off_head(int C) { return rhh_off_bias(C) + C; }
+__host__ __device__ inline long long rhh_off_head_bias(int C, int A) { return rhh_off_head(C) + (long long)rh_head_rows(A) * C; }
+__host__ __device__ inline long long rhh_packed_floats(int C, int A) { return rhh_off_head_bias(C, A) + rh_head_rows(A); }
+
+template <int CT>
+__global__ void __launch_bounds__(256)
+rpn_head_half_pack_kernel(const float* __restrict__ conv_w, const float* __restrict__ conv_b, const float* __restrict__ cls_w,
+                          const float* __restrict__ cls_b, const float* __restrict__ bbox_w, const float* __restrict__ bbox_b,
+                          int C, int A, float* __restrict__ packed, long long total) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const long long ob = rhh_off_bias(C), oh = rhh_off_head(C), ohb = rhh_off_head_bias(C, A);
+    float v;
+    if (i < ob) {
+        const long long s = cvh_pack_index(i, C, C);           // (C % 32 == 0: no padded pair, s >= 0)
+        v = __uint_as_float(cvh_pack2<CT>(conv_w[s], conv_w[s + 9]));
+    } else if (i < oh) {
+        v = conv_b[i - ob];
+    } else if (i < ohb) {
+        const long long r = i - oh;
+        const int lane = (int)(r & 63);
+        const int ks = (int)((r >> 6) % (C / 4)), mh = (int)((r >> 6) / (C / 4));
+        const int row = 16 * mh + (lane & 15), k = 4 * ks + (lane >> 4);
+        v = row < A ? cls_w[(size_t)row * C + k] : (row < 5 * A ? bbox_w[(size_t)(row - A) * C + k] : 0.0f);
+    } else {
+        const int row = (int)(i - ohb);
+        v = row < A ? cls_b[row] : (row < 5 * A ? bbox_b[row - A] : 0.0f);
+    }
+    packed[i] = v;
+}
+
+static_assert(CvhGeom<1>::SMEM_SLOTS * 16 <= RH_SMEM_FLOATS * 4, "t lies over the two half stage buffers");
+
+template <int CT, typename FT>
+__global__ void __launch_bounds__(256, 2)
+rpn_head_half_kernel(RpnHeadArgs P) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int kq = lane >> 4, xl = lane & 15;
+    const int C = P.C, A = P.A;
+
+    // flat workgroup index -> (image, level, tile)
+    const int n = blockIdx.x / P.tiles_per_image;
+    const int rem = blockIdx.x - n * P.tiles_per_image;
+    RpnHeadLevel lv = P.lv[0];
+#pragma unroll
+    for (int k = 1; k < SMOT_MAX_LEVELS; ++k)
+        if (k < P.L && rem >= P.lv[k].tile0) lv = P.lv[k];
+    const int t = rem - lv.tile0;
+    const int ty = t / lv.tiles_x, tx = t - ty * lv.tiles_x;
+    const int y0 = ty * RH_TH, x0 = tx * RH_TW;
+    const int H = lv.H, W = lv.W, HW = H * W;
+    const FT* __restrict__ in = reinterpret_cast<const FT*>(lv.in) + (size_t)n * C * HW;
+
+    CvsPlan<1> pl;
+    cvs_plan<1>(pl, tid, y0, x0, H, W);
+    cvs_u32x4* stage = reinterpret_cast<cvs_u32x4*>(sm);   // the two stage buffers, under t
+
+    const int npairs = C >> 5, nmb = (npairs + 3) >> 2;
+    const int mht = rh_head_rows(A) >> 4;
+    const float* __restrict__ cbias = P.packed + rhh_off_bias(C);
+    const float* __restrict__ hw = P.packed + rhh_off_head(C);
+    const float* __restrict__ hbias = P.packed + rhh_off_head_bias(C, A);
+
+    f32x4 hacc[RH_MAX_HEAD_TILES][2];
+#pragma unroll
+    for (int mh = 0; mh < RH_MAX_HEAD_TILES; ++mh)
+        hacc[mh][0] = hacc[mh][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+    for (int mb = 0; mb < nmb; ++mb) {
+        const int pair = mb * 4 + wave;
+        const bool active = pair < npairs;                 // wave-uniform: C % 128 != 0 leaves waves of the last block idle
+        cv_f32x4 acc[2][RH_TH];
+        // (cvh_block stores its first chunk BEFORE its first barrier: every wave is past its last read of t — the barrier
+        // below the heads — and it ends behind a barrier: no wave reads a stage buffer when t is written over them)
+        cvh_block<CT, FT, 1, 1, 2>(stage, in, HW, C, pl, P.packed, pair, active, tid, 0, acc);
+        // ---- + bias, ReLU -> t[mid channel of the block][position] over the stage buffers ---------------------------
+        if (active) {
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int chl = (wave * 2 + m) * 16 + 4 * kq + r;
+                    const float bv = cbias[mb * RH_MID + chl];
+#pragma unroll
+                    for (int nt = 0; nt < RH_TH; ++nt) sm[chl * RH_TS + nt * RH_TW + xl] = relu_nan(acc[m][nt][r] + bv);
+                }
+        }
+        __syncthreads();
+        // ---- the two 1x1 heads over this block's mid channels: fp32, as rpn_head_kernel's -----------------------------
+        const int ksteps = min(RH_MID, C - mb * RH_MID) >> 2;
+        const float* tb = sm + kq * RH_TS + (2 * wave) * RH_TW + xl;
+        const float* hwp = hw + (size_t)(mb * (RH_MID / 4)) * 64 + lane;
+        for (int ks = 0; ks < ksteps; ++ks) {
+            const float b0 = tb[ks * 4 * RH_TS], b1 = tb[ks * 4 * RH_TS + RH_TW];
+#pragma unroll
+            for (int mh = 0; mh < RH_MAX_HEAD_TILES; ++mh)
+                if (mh < mht) {
+                    const float a = hwp[((size_t)mh * (C >> 2) + ks) * 64];
+                    hacc[mh][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b0, hacc[mh][0], 0, 0, 0);
+                    hacc[mh][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b1, hacc[mh][1], 0, 0, 0);
+                }
+        }
+        __syncthreads();                                   // t is read: the next block stages over it
+    }
+
+    // ---- + bias, masked stores: hacc[mh][j][r] = row 16 mh + 4 kq + r at tile row 2 wave + j, column xl --------------
+    const int x = x0 + xl;
+#pragma unroll
+    for (int mh = 0; mh < RH_MAX_HEAD_TILES; ++mh)
+        if (mh < mht) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int y = y0 + 2 * wave + j;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = 16 * mh + 4 * kq + r;
+                    if (y < H && x < W && row < 5 * A) {
+                        const float v = hacc[mh][j][r] + hbias[row];
+                        float* dst = row < A ? lv.obj + ((size_t)n * A + row) * HW : lv.reg + ((size_t)n * 4 * A + (row - A)) * HW;
+                        dst[y * W + x] = v;
+                    }
+                }
+            }
+        }
+}
+
 // ---- anchors: out_l[(h W + w) A + a] = cell_l[a] + (w s, h s, w s, h s), all levels in one launch ---------------------
 struct AnchorLevel {
     const float* cell;   // [A, 4]
@@ -306,6 +446,24 @@ static int rpn_head_launch(const RpnHeadArgs& P, int grid, hipStream_t st) {
     return check_launch("rpn_head");
 }
 
+template <int CT, typename FT>
+static int rpn_head_half_launch(const RpnHeadArgs& P, int grid, hipStream_t st) {
+    const size_t smem = (size_t)RH_SMEM_FLOATS * sizeof(float);
+    const int rco = ensure_lds_optin(reinterpret_cast<const void*>(&rpn_head_half_kernel<CT, FT>), smem, "rpn_head_half");
+    if (rco) return rco;
+    SMOT_LAUNCH((rpn_head_half_kernel<CT, FT>), dim3(grid), dim3(256), smem, st, P);
+    return check_launch("rpn_head_half");
+}
+
+template <int CT>
+static int rpn_head_half_pick(const RpnHeadArgs& P, int grid, int feat_type, hipStream_t st) {
+    if (feat_type == SMOT_FEAT_F32) return rpn_head_half_launch<CT, float>(P, grid, st);
+    if (feat_type == SMOT_FEAT_F16) return rpn_head_half_launch<CT, f16_t>(P, grid, st);
+    return rpn_head_half_launch<CT, bf16_t>(P, grid, st);
+}
+
+static bool rpn_head_ctype_ok(int ctype) { return ctype == SMOT_FEAT_F16 || ctype == SMOT_FEAT_BF16; }
+
 }  // namespace smot
 
 using namespace smot;
@@ -328,30 +486,32 @@ extern "C" int smot_rpn_head_pack(const float* conv_w, const float* conv_b, cons
     return check_launch("rpn_head_pack");
 }
 
-extern "C" int smot_rpn_head_fwd(const void* const* feats, int feat_type, const int* heights, const int* widths,
-                                 int num_levels, int num_images, int C, int A, const float* packed,
-                                 float* const* objectness_out, float* const* regression_out, smot_stream_t stream) {
-    const int rf = check_feat_type(feat_type, "rpn_head");
+// smot_rpn_head_fwd (ctype 0) and smot_rpn_head_half_fwd (ctype SMOT_FEAT_F16 / _BF16): the same checks, geometry and launch;
+// the mode selects the packed image's layout and the kernel
+static int rpn_head_fwd(const void* const* feats, int feat_type, const int* heights, const int* widths, int num_levels,
+                        int num_images, int C, int A, const float* packed, float* const* objectness_out,
+                        float* const* regression_out, smot_stream_t stream, int ctype, const char* who) {
+    const int rf = check_feat_type(feat_type, who);
     if (rf) return rf;
     if (feat_type & SMOT_FEAT_CHANNELS_LAST) {
-        set_error("rpn_head: channels-last maps are not read in place (pass contiguous NCHW maps)");
+        set_error("%s: channels-last maps are not read in place (pass contiguous NCHW maps)", who);
         return SMOT_ERR_UNSUPPORTED;
     }
-    SMOT_REQUIRE(num_levels >= 1 && num_levels <= SMOT_MAX_LEVELS, "rpn_head: num_levels = %d (1 .. %d)", num_levels,
+    SMOT_REQUIRE(num_levels >= 1 && num_levels <= SMOT_MAX_LEVELS, "%s: num_levels = %d (1 .. %d)", who, num_levels,
                  SMOT_MAX_LEVELS);
-    SMOT_REQUIRE(num_images >= 1 && num_images <= SMOT_MAX_IMAGES, "rpn_head: num_images = %d (1 .. %d)", num_images,
+    SMOT_REQUIRE(num_images >= 1 && num_images <= SMOT_MAX_IMAGES, "%s: num_images = %d (1 .. %d)", who, num_images,
                  SMOT_MAX_IMAGES);
-    const int rs = rpn_head_shape(C, A, "rpn_head");
+    const int rs = rpn_head_shape(C, A, who);
     if (rs) return rs;
-    SMOT_REQUIRE(feats && heights && widths && packed && objectness_out && regression_out, "rpn_head: null pointer");
-    SMOT_REQUIRE(((uintptr_t)packed & 15) == 0, "rpn_head: packed must be 16-byte aligned");
+    SMOT_REQUIRE(feats && heights && widths && packed && objectness_out && regression_out, "%s: null pointer", who);
+    SMOT_REQUIRE(((uintptr_t)packed & 15) == 0, "%s: packed must be 16-byte aligned", who);
     RpnHeadArgs P = {};
     long long tiles = 0;
     for (int l = 0; l < num_levels; ++l) {
-        SMOT_REQUIRE(feats[l] && objectness_out[l] && regression_out[l], "rpn_head: null tensor at level %d", l);
-        SMOT_REQUIRE(heights[l] >= 1 && widths[l] >= 1, "rpn_head: level %d is %d x %d", l, heights[l], widths[l]);
-        if ((long long)heights[l] * widths[l] * RH_IC >= (1LL << 31)) {
-            set_error("rpn_head: level %d (%d x %d) is beyond the kernel's 32-bit plane offsets", l, heights[l], widths[l]);
+        SMOT_REQUIRE(feats[l] && objectness_out[l] && regression_out[l], "%s: null tensor at level %d", who, l);
+        SMOT_REQUIRE(heights[l] >= 1 && widths[l] >= 1, "%s: level %d is %d x %d", who, l, heights[l], widths[l]);
+        if ((long long)heights[l] * widths[l] * (ctype ? CVS_IC : RH_IC) >= (1LL << 31)) {
+            set_error("%s: level %d (%d x %d) is beyond the kernel's 32-bit plane offsets", who, l, heights[l], widths[l]);
             return SMOT_ERR_UNSUPPORTED;
         }
         RpnHeadLevel& v = P.lv[l];
@@ -364,7 +524,7 @@ extern "C" int smot_rpn_head_fwd(const void* const* feats, int feat_type, const 
         v.tile0 = (int)tiles;
         tiles += (long long)v.tiles_x * ((v.H + RH_TH - 1) / RH_TH);
         if (tiles * num_images >= (1LL << 31)) {
-            set_error("rpn_head: %d images of these maps are more than 2^31 tiles", num_images);
+            set_error("%s: %d images of these maps are more than 2^31 tiles", who, num_images);
             return SMOT_ERR_UNSUPPORTED;
         }
     }
@@ -375,9 +535,57 @@ extern "C" int smot_rpn_head_fwd(const void* const* feats, int feat_type, const 
     P.tiles_per_image = (int)tiles;
     const int grid = (int)(tiles * num_images);
     hipStream_t st = (hipStream_t)stream;
+    if (ctype == SMOT_FEAT_F16) return rpn_head_half_pick<SMOT_FEAT_F16>(P, grid, feat_type, st);
+    if (ctype == SMOT_FEAT_BF16) return rpn_head_half_pick<SMOT_FEAT_BF16>(P, grid, feat_type, st);
     if (feat_type == SMOT_FEAT_F32) return rpn_head_launch<float>(P, grid, st);
     if (feat_type == SMOT_FEAT_F16) return rpn_head_launch<f16_t>(P, grid, st);
     return rpn_head_launch<bf16_t>(P, grid, st);
+}
+
+extern "C" int smot_rpn_head_fwd(const void* const* feats, int feat_type, const int* heights, const int* widths,
+                                 int num_levels, int num_images, int C, int A, const float* packed,
+                                 float* const* objectness_out, float* const* regression_out, smot_stream_t stream) {
+    return rpn_head_fwd(feats, feat_type, heights, widths, num_levels, num_images, C, A, packed, objectness_out, regression_out,
+                        stream, 0, "rpn_head");
+}
+
+// ---- half compute mode (include/smot_emm.h, RPN HEAD, HALF COMPUTE) ---------------------------------------------------------------
+extern "C" long long smot_rpn_head_half_packed_floats(int C, int A, int compute_type) {
+    if (!rpn_head_ctype_ok(compute_type)) {
+        set_error("rpn_head_half_packed_floats: compute_type = %d (SMOT_FEAT_F16 or SMOT_FEAT_BF16)", compute_type);
+        return -1;
+    }
+    if (rpn_head_shape(C, A, "rpn_head_half_packed_floats")) return -1;
+    return rhh_packed_floats(C, A);
+}
+
+extern "C" int smot_rpn_head_half_pack(const float* conv_w, const float* conv_b, const float* cls_w, const float* cls_b,
+                                       const float* bbox_w, const float* bbox_b, int C, int A, int compute_type, float* packed,
+                                       smot_stream_t stream) {
+    SMOT_REQUIRE(rpn_head_ctype_ok(compute_type), "rpn_head_half_pack: compute_type = %d (SMOT_FEAT_F16 or SMOT_FEAT_BF16)",
+                 compute_type);
+    const int rs = rpn_head_shape(C, A, "rpn_head_half_pack");
+    if (rs) return rs;
+    SMOT_REQUIRE(conv_w && conv_b && cls_w && cls_b && bbox_w && bbox_b && packed, "rpn_head_half_pack: null pointer");
+    SMOT_REQUIRE(((uintptr_t)packed & 15) == 0, "rpn_head_half_pack: packed must be 16-byte aligned");
+    const long long total = rhh_packed_floats(C, A);
+    const dim3 g((unsigned)((total + 255) / 256));
+    if (compute_type == SMOT_FEAT_F16)
+        hipLaunchKernelGGL(rpn_head_half_pack_kernel<SMOT_FEAT_F16>, g, dim3(256), 0, (hipStream_t)stream, conv_w, conv_b, cls_w,
+                           cls_b, bbox_w, bbox_b, C, A, packed, total);
+    else
+        hipLaunchKernelGGL(rpn_head_half_pack_kernel<SMOT_FEAT_BF16>, g, dim3(256), 0, (hipStream_t)stream, conv_w, conv_b, cls_w,
+                           cls_b, bbox_w, bbox_b, C, A, packed, total);
+    return check_launch("rpn_head_half_pack");
+}
+
+extern "C" int smot_rpn_head_half_fwd(const void* const* feats, int feat_type, const int* heights, const int* widths,
+                                      int num_levels, int num_images, int C, int A, int compute_type, const float* packed,
+                                      float* const* objectness_out, float* const* regression_out, smot_stream_t stream) {
+    SMOT_REQUIRE(rpn_head_ctype_ok(compute_type), "rpn_head_half: compute_type = %d (SMOT_FEAT_F16 or SMOT_FEAT_BF16)",
+                 compute_type);
+    return rpn_head_fwd(feats, feat_type, heights, widths, num_levels, num_images, C, A, packed, objectness_out, regression_out,
+                        stream, compute_type, "rpn_head_half");
 }
 
 extern "C" int smot_rpn_anchors_fwd(const float* const* cell_anchors, const int* num_anchors, const int* strides,

@@ -121,23 +121,28 @@ class DetectionHead(torch.nn.Module):
         return self.forward_stages(self.backbone.body(images), image_size)
 
 
-def build_detection_head(cfg, rpn_box_coder, in_channels, box_head=None, rpn_head=True, fpn=False, backbone=False):
+def build_detection_head(cfg, rpn_box_coder, in_channels, box_head=None, rpn_head=True, fpn=False, backbone=False,
+                         compute_dtype=None):
     """``DetectionHead`` from a config: the reference's RPN factory keys (``MODEL.RPN.*_TEST``) and the given box head or a
     fresh ``TrackBoxHead``.  ``rpn_head``: True for a fresh ``rpn.RPNHead`` and the config's anchor generator
     (``MODEL.RPN.ANCHOR_*``, ``ASPECT_RATIOS``), an ``RPNHead`` to use that one, False / None for a head that starts at the
     anchors (``forward`` only).  ``fpn``: True for the config's pyramid (``fpn.build_fpn``), an ``fpn.FPN`` to use that one,
     False / None for a head that starts at the FPN maps.  ``backbone``: True for the config's body and pyramid
     (``backbone.build_backbone``; it brings the pyramid, so ``fpn`` is not passed with it), a module with ``body`` and ``fpn``
-    to use that one."""
+    to use that one.  ``compute_dtype``: None, ``torch.float16`` or ``torch.bfloat16``: the half compute mode of whatever
+    this builder creates itself — the fresh ``RPNHead``, ``build_fpn``'s pyramid, ``build_backbone``'s body and pyramid
+    (INTEGRATION.md §3q); modules passed in are left as they are."""
     if box_head is None:
         box_head = TrackBoxHead(cfg, in_channels).eval()
     head, generator = None, None
     if rpn_head:
         generator = make_anchor_generator(cfg)
-        head = RPNHead(cfg, in_channels, generator.num_anchors_per_location()[0]) if rpn_head is True else rpn_head
+        head = (RPNHead(cfg, in_channels, generator.num_anchors_per_location()[0], compute_dtype=compute_dtype)
+                if rpn_head is True else rpn_head)
     if backbone and fpn:
         raise ValueError("build_detection_head: a backbone brings its pyramid; pass `backbone` or `fpn`, not both")
-    pyramid = (build_fpn(cfg) if fpn is True else fpn) if fpn else None
-    trunk = (build_backbone(cfg) if backbone is True else backbone) if backbone else None
+    pyramid = (build_fpn(cfg, compute_dtype=compute_dtype) if fpn is True else fpn) if fpn else None
+    trunk = ((build_backbone(cfg, compute_dtype=compute_dtype, fpn_compute_dtype=compute_dtype) if backbone is True else backbone)
+             if backbone else None)
     return DetectionHead(make_rpn_postprocessor(cfg, rpn_box_coder, is_train=False).eval(), box_head, head, generator,
                          pyramid, trunk).eval()

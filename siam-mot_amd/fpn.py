@@ -11,7 +11,8 @@ Two forms of the operator live here:
 
 * ``FPN.forward`` in eval mode on device maps within ``ops.fpn``'s capacities: the laterals (one launch per level) and the
   3x3 convolutions of all levels and images (one launch) on the fp32 matrix cores, no host synchronisation; ``out_dtype``
-  half stores the maps the head and poolers read fastest with no cast in between;
+  half stores the maps the head and poolers read fastest with no cast in between; ``compute_dtype=torch.float16`` or
+  ``torch.bfloat16`` (opt-in) runs both convolutions on the 16-bit matrix cores instead (``ops.fpn_half``, INTEGRATION.md §3q);
 * ``fpn_torch``: the same as a plain torch composition.  It is the path for CPU tensors, training, GroupNorm / ReLU conv
   blocks, ``LastLevelP6P7``, a skipped level (``in_channels`` 0) and shapes beyond the capacities (counted in
   ``ops.FALLBACKS["fpn_torch"]`` for device tensors), and the baseline of tools/fpn_bench.py.
@@ -95,10 +96,18 @@ class FPN(nn.Module):
     convolutions (``conv_with_kaiming_uniform()``).  ``forward(x)``: the stage maps, finest first -> a tuple of maps, finest
     first (+ the top block's).  A level whose ``in_channels`` is 0 has no blocks and its stage map is not read, as upstream.
     ``out_dtype``: the element type of the returned maps (float32, float16 or bfloat16: the fp32 result rounded once).
+    ``compute_dtype`` (keyword-only): None (the default: nothing changes), ``torch.float16`` or ``torch.bfloat16``: the half
+    compute mode — the laterals and the 3x3 convolutions multiply operands rounded to that type (stage maps and the fp32
+    ``last`` maps as they are loaded, filters when packed) with fp32 accumulation; every ``Cin_l`` a multiple of 32, else the
+    torch composition.  CPU tensors and every fallback give the bits of the fp32 mode.  The ``state_dict`` is the same.
     On the device path the packed weights are rebuilt when a parameter's ``_version``, storage or device changes."""
 
-    def __init__(self, in_channels_list, out_channels, conv_block=None, top_blocks=None, out_dtype=torch.float32):
+    def __init__(self, in_channels_list, out_channels, conv_block=None, top_blocks=None, out_dtype=torch.float32, *,
+                 compute_dtype=None):
         super(FPN, self).__init__()
+        if compute_dtype is not None and compute_dtype not in ops.DLA_COMPUTE_TYPES:
+            raise ValueError("FPN: compute_dtype must be None, torch.float16 or torch.bfloat16, got %r" % (compute_dtype,))
+        self.compute_dtype = compute_dtype
         if conv_block is None:
             conv_block = conv_with_kaiming_uniform()
         self.inner_blocks, self.layer_blocks = [], []
@@ -143,21 +152,29 @@ class FPN(nn.Module):
         if not (1 <= N <= ops.RPN_MAX_IMAGES and all(t.device == dev and t.dtype is dt and t.shape[0] == N and t.numel() > 0
                                                      and t.shape[1] == c for t, c in zip(x, self.in_channels))):
             return False
+        if self.compute_dtype is not None:
+            return ops.fpn_half_shapes_ok(self.in_channels, self.out_channels)
         return ops.fpn_shapes_ok(self.in_channels, self.out_channels)
 
     def packed(self):
         inner, layer = self._blocks()
         params = [p for m in inner + layer for p in (m.weight, m.bias)]
-        key = tuple((p.data_ptr(), p._version, p.device) for p in params)
+        key = (self.compute_dtype,) + tuple((p.data_ptr(), p._version, p.device) for p in params)
         if key != self._packed_key:
-            self._packed = ops.fpn_pack([(m.weight.detach(), m.bias.detach()) for m in inner],
-                                        [(m.weight.detach(), m.bias.detach()) for m in layer])
+            blocks = ([(m.weight.detach(), m.bias.detach()) for m in inner], [(m.weight.detach(), m.bias.detach()) for m in layer])
+            if self.compute_dtype is not None:
+                self._packed = ops.fpn_half_pack(*blocks, self.compute_dtype)
+            else:
+                self._packed = ops.fpn_pack(*blocks)
             self._packed_key = key
         return self._packed
 
     def forward(self, x):
         x = list(x)
         if self.kernel_ok(x):
+            if self.compute_dtype is not None:
+                return tuple(ops.fpn_half(x, self.packed(), self.in_channels, self.out_channels, self.compute_dtype,
+                                          out_dtype=self.out_dtype, top_block=self.top_blocks is not None))
             return tuple(ops.fpn(x, self.packed(), self.in_channels, self.out_channels, out_dtype=self.out_dtype,
                                  top_block=self.top_blocks is not None))
         if any(isinstance(t, torch.Tensor) and t.is_cuda for t in x):
@@ -169,12 +186,13 @@ class FPN(nn.Module):
         return tuple(results)
 
 
-def build_fpn(cfg, out_dtype=torch.float32):
+def build_fpn(cfg, out_dtype=torch.float32, compute_dtype=None):
     """The pyramid of the config's backbone, as the reference builds it: DLA-34 stages ``MODEL.DLA.DLA_STAGE{2..5}_OUT_CHANNELS``
     -> ``MODEL.DLA.BACKBONE_OUT_CHANNELS`` channels, plain or GroupNorm / ReLU conv blocks by ``MODEL.FPN.USE_GN`` /
-    ``USE_RELU``, and a ``LastLevelMaxPool``."""
+    ``USE_RELU``, and a ``LastLevelMaxPool``.  ``compute_dtype``: the pyramid's half compute mode (``FPN``)."""
     dla = cfg.MODEL.DLA
     stages = [dla.DLA_STAGE2_OUT_CHANNELS, dla.DLA_STAGE3_OUT_CHANNELS, dla.DLA_STAGE4_OUT_CHANNELS, dla.DLA_STAGE5_OUT_CHANNELS]
     gn = cfg.MODEL.GROUP_NORM
     block = conv_with_kaiming_uniform(cfg.MODEL.FPN.USE_GN, cfg.MODEL.FPN.USE_RELU, num_groups=gn.NUM_GROUPS, eps=gn.EPSILON)
-    return FPN(stages, dla.BACKBONE_OUT_CHANNELS, block, top_blocks=LastLevelMaxPool(), out_dtype=out_dtype)
+    return FPN(stages, dla.BACKBONE_OUT_CHANNELS, block, top_blocks=LastLevelMaxPool(), out_dtype=out_dtype,
+               compute_dtype=compute_dtype)

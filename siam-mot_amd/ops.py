@@ -190,6 +190,13 @@ _SIGNATURES = {
     "smot_dla_conv1x1_half_form": (ctypes.c_int, [_i, _i, _i, _i]),
     "smot_dla_conv1x1_half_fwd": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp,
                                                  _vp, _i, _vp]),
+    # FPN and RPN head in half compute mode: the fp32 twins' arguments + compute_type
+    "smot_fpn_half_packed_floats": (ctypes.c_longlong, [_i, _vp, _i, _i]),
+    "smot_fpn_half_pack": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
+    "smot_fpn_half_fwd": (ctypes.c_int, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
+    "smot_rpn_head_half_packed_floats": (ctypes.c_longlong, [_i, _i, _i]),
+    "smot_rpn_head_half_pack": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "smot_rpn_head_half_fwd": (ctypes.c_int, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 _DEBUG_SIGNATURES = {
@@ -1460,41 +1467,52 @@ def rpn_head_shapes_ok(C, A):
     return C >= 32 and C % RPN_HEAD_CHANNEL_STEP == 0 and C <= RPN_HEAD_MAX_CHANNELS and 1 <= A and 5 * A <= RPN_HEAD_MAX_ROWS
 
 
-def rpn_head_pack(conv_w, conv_b, cls_w, cls_b, bbox_w, bbox_b):
-    """The RPN head's parameters (upstream's ``conv`` ``[C, C, 3, 3]``, ``cls_logits`` ``[A, C, 1, 1]``, ``bbox_pred``
-    ``[4A, C, 1, 1]`` and their biases, fp32 device tensors) in the operand order of ``rpn_head`` (``smot_rpn_head_pack``:
-    one launch, no synchronisation).  -> fp32 ``[smot_rpn_head_packed_floats(C, A)]``."""
+def _rpn_head_pack(who, ct, conv_w, conv_b, cls_w, cls_b, bbox_w, bbox_b):
     lib = _lib or load_library()
     C, A = int(conv_w.shape[0]), int(cls_w.shape[0])
     ts = [_chk(conv_w, "conv.weight", (C, C, 3, 3)), _chk(conv_b, "conv.bias", (C,)),
           _chk(cls_w.reshape(A, -1), "cls_logits.weight", (A, C)), _chk(cls_b, "cls_logits.bias", (A,)),
           _chk(bbox_w.reshape(4 * A, -1), "bbox_pred.weight", (4 * A, C)), _chk(bbox_b, "bbox_pred.bias", (4 * A,))]
-    n = lib.smot_rpn_head_packed_floats(C, A)
+    n = lib.smot_rpn_head_packed_floats(C, A) if ct is None else lib.smot_rpn_head_half_packed_floats(C, A, ct)
     if n < 0:
-        _check(-2, "rpn_head_pack")
+        _check(-2, who)
     packed = torch.empty((n,), dtype=_F32, device=conv_w.device)
     with _Launch(*ts) as ln:
-        rc = lib.smot_rpn_head_pack(*([_ptr(t) for t in ts] + [C, A, _ptr(packed), ln.stream]))
-    _check(rc, "rpn_head_pack")
+        if ct is None:
+            rc = lib.smot_rpn_head_pack(*([_ptr(t) for t in ts] + [C, A, _ptr(packed), ln.stream]))
+        else:
+            rc = lib.smot_rpn_head_half_pack(*([_ptr(t) for t in ts] + [C, A, ct, _ptr(packed), ln.stream]))
+    _check(rc, who)
     return packed
 
 
-def rpn_head(features, packed, C, A):
-    """Upstream's ``RPNHead.forward`` on all images and levels of a call in one launch (``smot_rpn_head_fwd``), free of host
-    synchronisation.  features: L maps ``[N, C, H_l, W_l]`` of one dtype (fp32, fp16 or bf16; a half call returns the bits
-    of the call on ``.float()``); anything but contiguous NCHW (channels-last, strided views) is copied.  packed:
-    ``rpn_head_pack``'s tensor.  -> (objectness: L fp32 ``[N, A, H_l, W_l]``, regression: L fp32 ``[N, 4A, H_l, W_l]``)."""
+def rpn_head_pack(conv_w, conv_b, cls_w, cls_b, bbox_w, bbox_b):
+    """The RPN head's parameters (upstream's ``conv`` ``[C, C, 3, 3]``, ``cls_logits`` ``[A, C, 1, 1]``, ``bbox_pred``
+    ``[4A, C, 1, 1]`` and their biases, fp32 device tensors) in the operand order of ``rpn_head`` (``smot_rpn_head_pack``:
+    one launch, no synchronisation).  -> fp32 ``[smot_rpn_head_packed_floats(C, A)]``."""
+    return _rpn_head_pack("rpn_head_pack", None, conv_w, conv_b, cls_w, cls_b, bbox_w, bbox_b)
+
+
+def rpn_head_half_pack(conv_w, conv_b, cls_w, cls_b, bbox_w, bbox_b, compute_dtype):
+    """``rpn_head_pack`` for ``rpn_head_half`` (``smot_rpn_head_half_pack``): ``conv.weight`` rounded once to
+    ``compute_dtype`` (``tensor.to``'s rounding), every bias and the two 1x1 heads' rows in fp32.  The tensor serves this
+    ``compute_dtype`` and no other mode."""
+    ct = _dla_ctype(compute_dtype, "rpn_head_half_pack")
+    return _rpn_head_pack("rpn_head_half_pack", ct, conv_w, conv_b, cls_w, cls_b, bbox_w, bbox_b)
+
+
+def _rpn_head(who, ct, features, packed, C, A):
     lib = _lib or load_library()
     L = len(features)
     if L < 1:
-        raise RuntimeError("siammot_amd.rpn_head: no feature level")
+        raise RuntimeError("siammot_amd.%s: no feature level" % who)
     feats = [_dev_feat(f, "features[%d]" % l) for l, f in enumerate(features)]
     ft = _feat_type(feats)
     N = feats[0].shape[0]
     for l, f in enumerate(feats):
         if f.dim() != 4 or f.shape[0] != N or f.shape[1] != C:
-            raise RuntimeError("siammot_amd.rpn_head: features[%d] has shape %s, expected [%d, %d, H, W]"
-                               % (l, tuple(f.shape), N, C))
+            raise RuntimeError("siammot_amd.%s: features[%d] has shape %s, expected [%d, %d, H, W]"
+                               % (who, l, tuple(f.shape), N, C))
     dev = feats[0].device
     obj = [torch.empty((N, A) + tuple(f.shape[2:]), dtype=_F32, device=dev) for f in feats]
     reg = [torch.empty((N, 4 * A) + tuple(f.shape[2:]), dtype=_F32, device=dev) for f in feats]
@@ -1504,10 +1522,31 @@ def rpn_head(features, packed, C, A):
     ih = (ctypes.c_int * L)(*[f.shape[2] for f in feats])
     iw = (ctypes.c_int * L)(*[f.shape[3] for f in feats])
     with _Launch(*(feats + [packed])) as ln:
-        rc = lib.smot_rpn_head_fwd(_cast(fp), ft, _cast(ih), _cast(iw), L, N, int(C), int(A), _ptr(packed), _cast(po),
-                                   _cast(pr), ln.stream)
-    _check(rc, "rpn_head")
+        if ct is None:
+            rc = lib.smot_rpn_head_fwd(_cast(fp), ft, _cast(ih), _cast(iw), L, N, int(C), int(A), _ptr(packed), _cast(po),
+                                       _cast(pr), ln.stream)
+        else:
+            rc = lib.smot_rpn_head_half_fwd(_cast(fp), ft, _cast(ih), _cast(iw), L, N, int(C), int(A), ct, _ptr(packed),
+                                            _cast(po), _cast(pr), ln.stream)
+    _check(rc, who)
     return obj, reg
+
+
+def rpn_head(features, packed, C, A):
+    """Upstream's ``RPNHead.forward`` on all images and levels of a call in one launch (``smot_rpn_head_fwd``), free of host
+    synchronisation.  features: L maps ``[N, C, H_l, W_l]`` of one dtype (fp32, fp16 or bf16; a half call returns the bits
+    of the call on ``.float()``); anything but contiguous NCHW (channels-last, strided views) is copied.  packed:
+    ``rpn_head_pack``'s tensor.  -> (objectness: L fp32 ``[N, A, H_l, W_l]``, regression: L fp32 ``[N, 4A, H_l, W_l]``)."""
+    return _rpn_head("rpn_head", None, features, packed, C, A)
+
+
+def rpn_head_half(features, packed, C, A, compute_dtype):
+    """``rpn_head`` in half compute mode (``smot_rpn_head_half_fwd``): the 3x3 convolution multiplies the maps and
+    ``conv.weight`` rounded to ``compute_dtype`` (maps as they are loaded, filters in ``rpn_head_half_pack``) on the 16-bit
+    matrix instruction and accumulates in fp32; its bias / ReLU result stays fp32 on the chip and the two 1x1 heads run on
+    it as in ``rpn_head``, unrounded.  An fp16 operand beyond 65,504 in magnitude is +-inf.  Arguments and results
+    otherwise as ``rpn_head``'s; the same single launch.  packed: ``rpn_head_half_pack``'s tensor of this ``compute_dtype``."""
+    return _rpn_head("rpn_head_half", _dla_ctype(compute_dtype, "rpn_head_half"), features, packed, C, A)
 
 
 # capacities of ``fpn`` (include/smot_emm.h): beyond them ``siammot_amd.fpn.FPN`` takes its torch composition
@@ -1523,14 +1562,19 @@ def fpn_shapes_ok(in_channels, C):
             and all(16 <= c <= FPN_MAX_IN_CHANNELS and c % FPN_IN_CHANNEL_STEP == 0 for c in in_channels))
 
 
-def fpn_pack(inner, layer):
-    """The pyramid's parameters (per level, finest first: ``inner[l]`` = upstream's ``fpn_inner{l+1}`` ``(weight [C, Cin_l,
-    1, 1], bias [C])``, ``layer[l]`` = ``fpn_layer{l+1}`` ``(weight [C, C, 3, 3], bias [C])``, fp32 device tensors) in the
-    operand order of ``fpn`` (``smot_fpn_pack``: one launch, no synchronisation).  -> fp32 ``[smot_fpn_packed_floats]``."""
+# the half compute mode's K step (``fpn_half``): every level's input channels in multiples of 32
+FPN_HALF_IN_CHANNEL_STEP = 32
+
+
+def fpn_half_shapes_ok(in_channels, C):
+    return fpn_shapes_ok(in_channels, C) and all(c % FPN_HALF_IN_CHANNEL_STEP == 0 for c in in_channels)
+
+
+def _fpn_pack(who, ct, inner, layer):
     lib = _lib or load_library()
     L = len(inner)
     if L < 1 or len(layer) != L:
-        raise RuntimeError("siammot_amd.fpn_pack: %d lateral and %d output blocks" % (L, len(layer)))
+        raise RuntimeError("siammot_amd.%s: %d lateral and %d output blocks" % (who, L, len(layer)))
     C = int(inner[0][0].shape[0])
     cin = [int(w.shape[1]) for w, _ in inner]
     iw = [_chk(w.reshape(C, -1), "fpn_inner%d.weight" % (l + 1), (C, cin[l])) for l, (w, _) in enumerate(inner)]
@@ -1538,15 +1582,71 @@ def fpn_pack(inner, layer):
     lw = [_chk(w, "fpn_layer%d.weight" % (l + 1), (C, C, 3, 3)) for l, (w, _) in enumerate(layer)]
     lb = [_chk(b, "fpn_layer%d.bias" % (l + 1), (C,)) for l, (_, b) in enumerate(layer)]
     ic = (ctypes.c_int * L)(*cin)
-    n = lib.smot_fpn_packed_floats(L, _cast(ic), C)
+    n = lib.smot_fpn_packed_floats(L, _cast(ic), C) if ct is None else lib.smot_fpn_half_packed_floats(L, _cast(ic), C, ct)
     if n < 0:
-        _check(-2, "fpn_pack")
+        _check(-2, who)
     packed = torch.empty((n,), dtype=_F32, device=iw[0].device)
     arrays = [(ctypes.c_void_p * L)(*[t.data_ptr() for t in ts]) for ts in (iw, ib, lw, lb)]
     with _Launch(*(iw + ib + lw + lb)) as ln:
-        rc = lib.smot_fpn_pack(*([_cast(a) for a in arrays] + [L, _cast(ic), C, _ptr(packed), ln.stream]))
-    _check(rc, "fpn_pack")
+        if ct is None:
+            rc = lib.smot_fpn_pack(*([_cast(a) for a in arrays] + [L, _cast(ic), C, _ptr(packed), ln.stream]))
+        else:
+            rc = lib.smot_fpn_half_pack(*([_cast(a) for a in arrays] + [L, _cast(ic), C, ct, _ptr(packed), ln.stream]))
+    _check(rc, who)
     return packed
+
+
+def fpn_pack(inner, layer):
+    """The pyramid's parameters (per level, finest first: ``inner[l]`` = upstream's ``fpn_inner{l+1}`` ``(weight [C, Cin_l,
+    1, 1], bias [C])``, ``layer[l]`` = ``fpn_layer{l+1}`` ``(weight [C, C, 3, 3], bias [C])``, fp32 device tensors) in the
+    operand order of ``fpn`` (``smot_fpn_pack``: one launch, no synchronisation).  -> fp32 ``[smot_fpn_packed_floats]``."""
+    return _fpn_pack("fpn_pack", None, inner, layer)
+
+
+def fpn_half_pack(inner, layer, compute_dtype):
+    """``fpn_pack`` for ``fpn_half`` (``smot_fpn_half_pack``): both convolutions' filters rounded once to ``compute_dtype``
+    (``tensor.to``'s rounding), the biases in fp32.  The tensor serves this ``compute_dtype`` and no other mode."""
+    return _fpn_pack("fpn_half_pack", _dla_ctype(compute_dtype, "fpn_half_pack"), inner, layer)
+
+
+def _fpn(who, ct, stages, packed, in_channels, C, out_dtype, top_block):
+    lib = _lib or load_library()
+    L = len(stages)
+    if L < 1 or len(in_channels) != L:
+        raise RuntimeError("siammot_amd.%s: %d stage maps for %d levels" % (who, L, len(in_channels)))
+    if out_dtype not in FEAT_TYPES:
+        raise RuntimeError("siammot_amd.%s: out_dtype must be float32, float16 or bfloat16, got %s" % (who, out_dtype))
+    feats = [_dev_feat(f, "stages[%d]" % l) for l, f in enumerate(stages)]
+    ft = _feat_type(feats)
+    N = feats[0].shape[0]
+    for l, f in enumerate(feats):
+        if f.dim() != 4 or f.shape[0] != N or f.shape[1] != in_channels[l]:
+            raise RuntimeError("siammot_amd.%s: stages[%d] has shape %s, expected [%d, %d, H, W]"
+                               % (who, l, tuple(f.shape), N, in_channels[l]))
+    dev = feats[0].device
+    sizes = [(int(f.shape[2]), int(f.shape[3])) for f in feats]
+    ic = (ctypes.c_int * L)(*[int(c) for c in in_channels])
+    ih = (ctypes.c_int * L)(*[s[0] for s in sizes])
+    iw = (ctypes.c_int * L)(*[s[1] for s in sizes])
+    nbytes = lib.smot_fpn_ws_bytes(L, _cast(ih), _cast(iw), N, int(C))
+    if nbytes < 0:
+        raise RuntimeError("siammot_amd.%s: %d levels of %d images (at most %d levels, %d images, no empty map)"
+                           % (who, L, N, FPN_MAX_LEVELS, RPN_MAX_IMAGES))
+    ws = torch.empty((max(nbytes // 4, 4),), dtype=_F32, device=dev)
+    if top_block:
+        sizes = sizes + [((sizes[-1][0] + 1) // 2, (sizes[-1][1] + 1) // 2)]
+    out = [torch.empty((N, int(C), h, w), dtype=out_dtype, device=dev) for (h, w) in sizes]
+    fp = (ctypes.c_void_p * L)(*[t.data_ptr() for t in feats])
+    po = (ctypes.c_void_p * len(out))(*[t.data_ptr() for t in out])
+    with _Launch(*(feats + [packed])) as ln:
+        if ct is None:
+            rc = lib.smot_fpn_fwd(_cast(fp), ft, _cast(ic), _cast(ih), _cast(iw), L, N, int(C), _ptr(packed), _ptr(ws),
+                                  _cast(po), FEAT_TYPES[out_dtype], 1 if top_block else 0, ln.stream)
+        else:
+            rc = lib.smot_fpn_half_fwd(_cast(fp), ft, _cast(ic), _cast(ih), _cast(iw), L, N, int(C), ct, _ptr(packed), _ptr(ws),
+                                       _cast(po), FEAT_TYPES[out_dtype], 1 if top_block else 0, ln.stream)
+    _check(rc, who)
+    return out
 
 
 def fpn(stages, packed, in_channels, C, out_dtype=torch.float32, top_block=True):
@@ -1555,39 +1655,16 @@ def fpn(stages, packed, in_channels, C, out_dtype=torch.float32, top_block=True)
     one dtype (fp32, fp16 or bf16; a half call returns the bits of the call on ``.float()``); anything but contiguous NCHW
     is copied.  packed: ``fpn_pack``'s tensor.  -> L (+ 1 with ``top_block``: ``LastLevelMaxPool``) contiguous NCHW maps
     ``[N, C, H_l, W_l]`` of ``out_dtype`` (a half output is the fp32 value rounded to nearest even)."""
-    lib = _lib or load_library()
-    L = len(stages)
-    if L < 1 or len(in_channels) != L:
-        raise RuntimeError("siammot_amd.fpn: %d stage maps for %d levels" % (L, len(in_channels)))
-    if out_dtype not in FEAT_TYPES:
-        raise RuntimeError("siammot_amd.fpn: out_dtype must be float32, float16 or bfloat16, got %s" % (out_dtype,))
-    feats = [_dev_feat(f, "stages[%d]" % l) for l, f in enumerate(stages)]
-    ft = _feat_type(feats)
-    N = feats[0].shape[0]
-    for l, f in enumerate(feats):
-        if f.dim() != 4 or f.shape[0] != N or f.shape[1] != in_channels[l]:
-            raise RuntimeError("siammot_amd.fpn: stages[%d] has shape %s, expected [%d, %d, H, W]"
-                               % (l, tuple(f.shape), N, in_channels[l]))
-    dev = feats[0].device
-    sizes = [(int(f.shape[2]), int(f.shape[3])) for f in feats]
-    ic = (ctypes.c_int * L)(*[int(c) for c in in_channels])
-    ih = (ctypes.c_int * L)(*[s[0] for s in sizes])
-    iw = (ctypes.c_int * L)(*[s[1] for s in sizes])
-    nbytes = lib.smot_fpn_ws_bytes(L, _cast(ih), _cast(iw), N, int(C))
-    if nbytes < 0:
-        raise RuntimeError("siammot_amd.fpn: %d levels of %d images (at most %d levels, %d images, no empty map)"
-                           % (L, N, FPN_MAX_LEVELS, RPN_MAX_IMAGES))
-    ws = torch.empty((max(nbytes // 4, 4),), dtype=_F32, device=dev)
-    if top_block:
-        sizes = sizes + [((sizes[-1][0] + 1) // 2, (sizes[-1][1] + 1) // 2)]
-    out = [torch.empty((N, int(C), h, w), dtype=out_dtype, device=dev) for (h, w) in sizes]
-    fp = (ctypes.c_void_p * L)(*[t.data_ptr() for t in feats])
-    po = (ctypes.c_void_p * len(out))(*[t.data_ptr() for t in out])
-    with _Launch(*(feats + [packed])) as ln:
-        rc = lib.smot_fpn_fwd(_cast(fp), ft, _cast(ic), _cast(ih), _cast(iw), L, N, int(C), _ptr(packed), _ptr(ws), _cast(po),
-                              FEAT_TYPES[out_dtype], 1 if top_block else 0, ln.stream)
-    _check(rc, "fpn")
-    return out
+    return _fpn("fpn", None, stages, packed, in_channels, C, out_dtype, top_block)
+
+
+def fpn_half(stages, packed, in_channels, C, compute_dtype, out_dtype=torch.float32, top_block=True):
+    """``fpn`` in half compute mode (``smot_fpn_half_fwd``): the laterals and the 3x3 convolutions multiply operands rounded
+    to ``compute_dtype`` (stage maps and the fp32 ``last`` maps as they are loaded, filters in ``fpn_half_pack``) on the
+    16-bit matrix instruction and accumulate in fp32; the bias adds, the bilinear top-down path, ``last`` in the workspace and
+    the stores are ``fpn``'s.  An fp16 operand beyond 65,504 in magnitude is +-inf.  Every ``Cin_l`` a multiple of 32
+    (``fpn_half_shapes_ok``).  Arguments and results otherwise as ``fpn``'s; the same L + 1 launches and workspace."""
+    return _fpn("fpn_half", _dla_ctype(compute_dtype, "fpn_half"), stages, packed, in_channels, C, out_dtype, top_block)
 
 
 # capacities of ``dla`` (include/smot_emm.h, DLA BACKBONE): beyond them ``siammot_amd.dla.DLA`` takes its torch composition

@@ -291,10 +291,16 @@ class RPNHead(torch.nn.Module):
     ``cls_logits`` (1x1, C -> A), ``bbox_pred`` (1x1, C -> 4A), normal(std 0.01) weights, zero biases.
     ``forward(features) -> (objectness list, regression list)``.  In eval mode on device maps within ``ops.rpn_head``'s
     capacities: one launch for all images and levels; the packed weights are rebuilt when a parameter's ``_version``, storage
-    or device changes."""
+    or device changes.  ``compute_dtype`` (keyword-only): None (the default: nothing changes), ``torch.float16`` or
+    ``torch.bfloat16``: the half compute mode (``ops.rpn_head_half``) — the 3x3 convolution multiplies
+    the maps and ``conv.weight`` rounded to that type with fp32 accumulation; the two 1x1 heads stay fp32.  CPU tensors and
+    every fallback give the bits of the fp32 mode; the ``state_dict`` is the same."""
 
-    def __init__(self, cfg, in_channels, num_anchors):
+    def __init__(self, cfg, in_channels, num_anchors, *, compute_dtype=None):
         super(RPNHead, self).__init__()
+        if compute_dtype is not None and compute_dtype not in ops.DLA_COMPUTE_TYPES:
+            raise ValueError("RPNHead: compute_dtype must be None, torch.float16 or torch.bfloat16, got %r" % (compute_dtype,))
+        self.compute_dtype = compute_dtype
         self.conv = torch.nn.Conv2d(in_channels, in_channels, kernel_size=3, stride=1, padding=1)
         self.cls_logits = torch.nn.Conv2d(in_channels, num_anchors, kernel_size=1, stride=1)
         self.bbox_pred = torch.nn.Conv2d(in_channels, num_anchors * 4, kernel_size=1, stride=1)
@@ -326,15 +332,20 @@ class RPNHead(torch.nn.Module):
 
     def packed(self):
         params = self._params()
-        key = tuple((p.data_ptr(), p._version, p.device) for p in params)
+        key = (self.compute_dtype,) + tuple((p.data_ptr(), p._version, p.device) for p in params)
         if key != self._packed_key:
-            self._packed = ops.rpn_head_pack(*[p.detach() for p in params])
+            if self.compute_dtype is not None:
+                self._packed = ops.rpn_head_half_pack(*[p.detach() for p in params], self.compute_dtype)
+            else:
+                self._packed = ops.rpn_head_pack(*[p.detach() for p in params])
             self._packed_key = key
         return self._packed
 
     def forward(self, features):
         features = list(features)
         if self.kernel_ok(features):
+            if self.compute_dtype is not None:
+                return ops.rpn_head_half(features, self.packed(), self.in_channels, self.num_anchors, self.compute_dtype)
             return ops.rpn_head(features, self.packed(), self.in_channels, self.num_anchors)
         if any(isinstance(f, torch.Tensor) and f.is_cuda for f in features):
             ops.FALLBACKS["rpn_head_torch"] += 1
@@ -345,12 +356,12 @@ class RPNModule(torch.nn.Module):
     """Upstream's ``RPNModule`` at inference: FPN maps -> proposals.  ``forward(images_or_sizes, features)`` -> one ``BoxList``
     per image (field ``objectness``); images_or_sizes as ``AnchorGenerator.forward`` takes them.  ``state_dict`` keys are those
     of ``rpn.*`` in a reference checkpoint (``anchor_generator.cell_anchors.{l}``, ``head.conv.*``, ``head.cls_logits.*``,
-    ``head.bbox_pred.*``)."""
+    ``head.bbox_pred.*``).  ``compute_dtype`` (keyword-only): the head's half compute mode (``RPNHead``)."""
 
-    def __init__(self, cfg, in_channels):
+    def __init__(self, cfg, in_channels, *, compute_dtype=None):
         super(RPNModule, self).__init__()
         self.anchor_generator = make_anchor_generator(cfg)
-        self.head = RPNHead(cfg, in_channels, self.anchor_generator.num_anchors_per_location()[0])
+        self.head = RPNHead(cfg, in_channels, self.anchor_generator.num_anchors_per_location()[0], compute_dtype=compute_dtype)
         self.box_selector_test = make_rpn_postprocessor(cfg, BoxCoder(weights=(1.0, 1.0, 1.0, 1.0)), is_train=False)
 
     def forward(self, images_or_sizes, features, targets=None):
