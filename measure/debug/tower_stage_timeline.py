@@ -1,5 +1,7 @@
-"""One stage of the bf16 x 3 tower loop as a per-wave timeline (SMOT_WINO_ABL=15, measurement library): s_memtime stamps of
-stage 9 (block 2, stage 1) for all eight waves of every workgroup.  JSON: mean cycles from the stage's first stamp of wave 0."""
+"""One stage of the split (fp16 x 2) tower loop as a per-wave timeline (SMOT_WINO_ABL=15, measurement library): s_memtime stamps of
+stage 9 (block 2, stage 1) for all eight waves of every workgroup.  JSON: mean cycles from the stage's first stamp of wave 0.
+Slot 2 was "raw planes stored" while the planes went through registers; since they go to LDS by direct-to-LDS loads nothing
+is stored there and the slot is the point right behind the first barrier (its distance to slot 1 is the stamp's own cost)."""
 import json, os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "..")); sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "..", "tests"))
@@ -24,6 +26,6 @@ t = tr.view(grid, 8, 8).cpu().numpy().astype(np.float64)
 t = t[t[:, 0, 5] != 0]
 base = t[:, :, 0].min(axis=1)[:, None, None]
 rel = (t[:, :, :6] - base)
-names = ["before_barrier1", "after_barrier1", "raw_planes_stored", "vector_phase_done", "after_vmcnt0_and_barrier2", "matrix_and_fetches_issued"]
+names = ["before_barrier1", "after_barrier1", "behind_barrier1_no_store", "vector_phase_done", "after_vmcnt0_and_barrier2", "matrix_and_fetches_issued"]
 print(json.dumps({"tracks": n, "workgroups": int(t.shape[0]), "slots": names,
                   "mean_cycles_by_wave": {("wave%d" % w): [round(float(x), 0) for x in rel[:, w, :].mean(0)] for w in range(8)}}))

@@ -26,6 +26,7 @@ for n in [int(t) for t in os.environ.get("TRACKS", "30").split(",")]:
             rows.append({"workgroups": int(t.shape[0]), "start_offset_mean": float((t[:, 0] - t0).mean()), "start_offset_max": float((t[:, 0] - t0).max()),
                          "duration_mean": float((t[:, 5] - t[:, 0]).mean()), "duration_min": float((t[:, 5] - t[:, 0]).min()), "duration_max": float((t[:, 5] - t[:, 0]).max()),
                          "first_start_to_last_end": float(t[:, 5].max() - t0),
+                         "phase_mean": [round(float(x)) for x in np.diff(t[:, :6], axis=1).mean(0)],
                          "phase_max": [float(x) for x in np.diff(t[:, :6], axis=1).max(0)], "phase_p90": [float(x) for x in np.percentile(np.diff(t[:, :6], axis=1), 90, axis=0)]})
         lib.smot_debug_trace(ops._ptr(None))
         ts = []

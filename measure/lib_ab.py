@@ -1,5 +1,5 @@
 """A/B of two builds of the product library (e.g. another compiler flag), same session, interleaved: frame pair and
-tracking loop.    python measure/lib_ab.py measure/libsmot_emm_preload.so"""
+tracking loop.    python measure/lib_ab.py measure/libsmot_emm_preload.so [ALTERNATIONS, default 3]"""
 import json, os, sys
 import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -24,7 +24,7 @@ emm = EMM(cfg, build_track_utils(cfg)).eval()
 bench.init_predictor(emm.predictor, boxes.cpu())
 emm = emm.to(dev)
 ref = None
-for rep in range(3):
+for rep in range(int(sys.argv[2]) if len(sys.argv) > 2 else 3):
     for name, lib in (("product", base), ("variant", other)):
         ops._lib = lib
         with torch.no_grad():

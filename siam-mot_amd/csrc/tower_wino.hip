@@ -26,6 +26,10 @@
 //               8 operands.  The transformed input never exists in memory.
 //   LDS       = raw response planes only (8 channels per stage, zero-haloed 18 x 24 rows, plane stride 448),
 //               ring of four stages, one barrier per stage; two further stages are in flight in registers.
+//               The split form of the 16 x 16 map (BF3, the product's) has no register in between: a plane is ONE
+//               direct-to-LDS instruction (1 KB, unscaled, no column halo, rows in a bank-conflict-free order, a zeroed
+//               gap behind it for the rows -1 and 16), three stages in flight in the ring itself; the column halo comes
+//               from the neighbouring lanes (DPP) and the track's scale is applied in the operand transform.
 //   epilogue  = output transform (column half in registers, row half across the waves through LDS), two-pass
 //               GroupNorm + affine + ReLU, fused partial heads exactly as in predictor.hip.
 #include "tower_common.h"
@@ -39,6 +43,13 @@ constexpr int W_PLANE = 448;              // 18 rows * 24 = 432, padded: plane s
 constexpr int W_STAGE_IC = 8;             // input channels per LDS stage (2 k-steps)
 constexpr int W_RING = 4;                 // stage buffers
 constexpr int W_BUF = W_STAGE_IC * W_PLANE;      // 3840 floats
+// Split form of the 16 x 16 towers (BF3, not BLOCKED): a plane is the 1 KB that ONE direct-to-LDS instruction writes, its 64
+// 16-byte chunks (row, column chunk) in the order D_READ documents, followed by a 256-byte gap that no fetch writes: the
+// zero rows -1 and 16 of the plane (the gap is zeroed once per workgroup).
+constexpr int D_PLANE = 320;              // floats: 256 of the plane + 64 of the gap; 1280 B = 0 (mod 64) banks
+constexpr int D_GAP_LO = 256 + 48;        // row -1 at bytes 1216 = 192 (mod 256), row 16 at bytes 1024 = 0 (mod 256): see D_READ
+constexpr int D_GAP_HI = 256;
+constexpr int D_BUF = W_STAGE_IC * D_PLANE;      // 2560 floats per stage: the ring of four is 40 KB of the 56 KB it owns
 constexpr int W_XOC = 68;                 // oc stride of the exchange image (4*68 = 16 mod 64 banks)
 constexpr int W_X_FLOATS = 4 * 2 * 16 * W_XOC;   // 8704
 constexpr int W_PL_OFF = W_X_FLOATS;             // head planes [16][336]
@@ -162,8 +173,8 @@ __device__ __forceinline__ void heads_group(const float (&hw)[9], const float (&
                                                                   (G * 36 + E) % 16, 0)), ...);
 }
 
-// ABL (timing ablations for profiles/, wrong results): 1 = no raw staging inside the loop, 2 = no A-operand
-// loads inside the loop, 3 = no LDS reads / operand transform, 4 = no MFMAs, 5 = MFMAs + barriers only,
+// ABL (timing ablations for profiles/, wrong results): 1 = no raw staging inside the loop (split form: 9 = no plane
+// DMA and no A-part DMA inside the loop), 2 = no A-operand loads inside the loop, 3 = no LDS reads / operand transform, 4 = no MFMAs, 5 = MFMAs + barriers only,
 // 6 = MFMAs only.  Instantiated in the measurement library only (knobs.h: SMOT_WINO_ABL).
 // BHO > 0: BLOCKED mode for a response map of BHO x BHO (16 < BHO <= 32; the second yaml family's 29 x 29): the map is
 // covered by four overlapping 16 x 16 output blocks with origins {0, BHO - 16}^2 and a workgroup convolves ONE block of
@@ -196,6 +207,7 @@ tower_wino_kernel(const float* __restrict__ resp, const float* __restrict__ pack
     constexpr int NT = 256 * OCT;             // threads
     constexpr int NP = 2 / OCT;               // tile-row halves (pairs of N-tiles) per wave
     constexpr bool BLOCKED = BHO > 0;
+    constexpr bool DMA = BF3 && !BLOCKED;     // response planes global -> LDS with no register in between (see dma_plane)
     constexpr int MAP = BLOCKED ? BHO * BHO : 256;                    // positions of a response plane
     constexpr int RAW4 = 512 / NT;            // float4 per thread and stage of raw response
     constexpr int RAWB = (W_STAGE_IC * 324 + NT - 1) / NT;            // BLOCKED: dwords per thread and stage (18 x 18 windows)
@@ -309,9 +321,15 @@ tower_wino_kernel(const float* __restrict__ resp, const float* __restrict__ pack
     // (round 6: a stage's fetches stay in flight across the stage's end; see WB_STAGE)
     typedef int i32x4 __attribute__((ext_vector_type(4)));
     const unsigned long long pin = reinterpret_cast<unsigned long long>(in);
+    // DMA: the resource ends with the LAUNCH's response (what is left of its N C 256 floats from this track on): an offset
+    // past it reads zeros instead of someone else's memory
+    const unsigned long long in_left = (unsigned long long)(N - n) * (unsigned)C * (MAP * 4ull);
     const i32x4 rs_in_words = {__builtin_amdgcn_readfirstlane((int)(unsigned)pin),
                                __builtin_amdgcn_readfirstlane((int)((unsigned)(pin >> 32) & 0xffffu)),
-                               BLOCKED ? (int)((unsigned)C * MAP * 4u) : 0x7fffffff, 0x00020000};
+                               BLOCKED ? (int)((unsigned)C * MAP * 4u)
+                                       : (DMA ? __builtin_amdgcn_readfirstlane((int)(in_left < 0x7fffffffull ? in_left : 0x7fffffffull))
+                                              : 0x7fffffff),
+                               0x00020000};
     auto load_raw_asm = [&](int st, float4* pr) __attribute__((always_inline)) {
         const int soff = __builtin_amdgcn_readfirstlane(st * (W_STAGE_IC * MAP * 4));
         if constexpr (!BLOCKED) {
@@ -388,6 +406,20 @@ tower_wino_kernel(const float* __restrict__ resp, const float* __restrict__ pack
         dma_part(q, kbp, 0);
         dma_part(q, kbp, 1);
     };
+    // DMA: plane `wave` of stage st (1 KB of the plain [N, C, 16, 16] response) -> ring slot `slot`, one direct-to-LDS
+    // instruction per wave and stage.  The instruction writes LDS linearly (M0 base + lane * 16 B), the SOURCE offset of a lane
+    // is free: lane L fills chunk L = 4 pos + xc of the plane's image with the four floats of columns 4 xc .. 4 xc + 3 of
+    // row(pos) = the inverse of D_READ's row order, pos = row[3] row[0] row[2] row[1] (bits).
+    const unsigned pl_voff = (unsigned)((((((lane >> 2) & 3) << 1) | ((lane >> 4) & 1) | ((lane >> 5) << 3)) * 4 + (lane & 3)) * 16);
+    const int pl_soff = __builtin_amdgcn_readfirstlane(wave * 1024);
+    const unsigned pl_dst = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_float*)sm + (unsigned)(wave * D_PLANE) * 4u);
+    auto dma_plane = [&](int st, int slot) __attribute__((always_inline)) {
+        const int soff = __builtin_amdgcn_readfirstlane(st * (W_STAGE_IC * 256 * 4) + pl_soff);
+        const unsigned dst = __builtin_amdgcn_readfirstlane(pl_dst + (unsigned)(slot * D_BUF) * 4u);
+        unsigned keep;
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "s"(dst), "v"(pl_voff), "s"(rs_in_words), "s"(soff) : "memory");
+    };
     auto load_al = [&](int q, u32x4 (*dst)[2]) __attribute__((always_inline)) {
         const float* src = sm + W_RING * W_BUF + q * W_A_SLOT + al_row + lane * 4;
 #pragma unroll
@@ -404,9 +436,15 @@ tower_wino_kernel(const float* __restrict__ resp, const float* __restrict__ pack
 #pragma unroll
             for (int t = 0; t < 2 * NP; ++t) acc[o][q][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    load_raw(0, prs[0]);
-    load_raw(1, prs[1]);
-    if constexpr (BF3) {                       // columns 0 and 1 of the first block: consumed in the stages 0 and 1
+    if constexpr (DMA) {                       // stages 0-2 go to the ring's slots 0-2 at entry; the loop fetches from stage 3 on
+        dma_plane(0, 0);
+        dma_plane(1, 1);
+        dma_plane(2, 2);
+    } else {
+        load_raw(0, prs[0]);
+        load_raw(1, prs[1]);
+    }
+    if constexpr (BF3) {                     // columns 0 and 1 of the first block: consumed in the stages 0 and 1
         dma_slot(0, 0);
         dma_slot(1, 0);
     }
@@ -428,7 +466,13 @@ tower_wino_kernel(const float* __restrict__ resp, const float* __restrict__ pack
         __builtin_amdgcn_sched_barrier(0);
     }
     // (first global loads are in flight: their latency covers the fill and the weight fetch)
-    {   // zero the stage buffers once: the halos stay zero for the whole main loop (a halo-only fill was measured
+    if constexpr (DMA) {
+        // the gaps behind the ring's 32 planes (rows -1 and 16 of every plane): one ds_write_b128 per thread.  No fetch ever
+        // writes a gap, so the fill needs no order against the fetches above; the barrier in front of the loop publishes it.
+        static_assert(W_RING * W_STAGE_IC * 16 == NT, "one 16-byte piece of the gaps per thread");
+        *reinterpret_cast<float4*>(sm + (tid >> 4) * D_PLANE + 256 + (tid & 15) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+        // zero the stage buffers once: the halos stay zero for the whole main loop (a halo-only fill was measured
         // slower: its scattered ds_write_b32 and index arithmetic cost more than 14 ds_write_b128 per thread)
         float4* z = reinterpret_cast<float4*>(sm);
         for (int e = tid; e < W_RING * W_BUF / 4; e += NT) z[e] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -461,14 +505,22 @@ tower_wino_kernel(const float* __restrict__ resp, const float* __restrict__ pack
         }
     }
 
-    __syncthreads();                       // zero fill complete before interior writes
-    // BF3: the first A parts are in LDS (the first raw planes are needed here anyway; waiting BEFORE the next fetches are
-    // issued keeps their latency out of this wait)
-    if constexpr (BF3) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    store_raw(sm, prs[0]);
-    store_raw(sm + W_BUF, prs[1]);
-    load_raw(min(2, nstages - 1), prs[0]);
-    load_raw(min(3, nstages - 1), prs[1]);
+    // DMA: the scale multiplies the row combinations (WB_XFORM), from a scalar register
+    const float sv_s = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(sv)));
+    if constexpr (!DMA) {
+        __syncthreads();                       // zero fill complete before interior writes
+        // BF3: the first A parts are in LDS (the first raw planes are needed here anyway; waiting BEFORE the next fetches are
+        // issued keeps their latency out of this wait)
+        if constexpr (BF3) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        store_raw(sm, prs[0]);
+        store_raw(sm + W_BUF, prs[1]);
+        load_raw(min(2, nstages - 1), prs[0]);
+        load_raw(min(3, nstages - 1), prs[1]);
+    } else {
+        // this wave's planes of the stages 0-2 and its A parts of the columns 0 and 1 are in LDS; the barrier below publishes
+        // them and the gaps to the other waves.  ONE barrier in front of the loop (before: zero fill | stores | loop).
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
     // GroupNorm's affine parameters of the thread's epilogue channel: requested here (two registers through the loop);
     // fetched where they are used, their cold round trip stood in the epilogue (the barrier behind the exchange drains vmcnt)
     float ga = 0.0f, be = 0.0f;
@@ -491,6 +543,25 @@ tower_wino_kernel(const float* __restrict__ resp, const float* __restrict__ pack
     // OCT = 1: the wave walks p = 0, 1;  OCT = 2: the wave owns p = nh.
     const int patch0 = kq * W_PLANE + (2 * (xl >> 2) + (OCT == 2 ? 8 * nh : 0)) * W_ROW + 4 * (xl & 3);
     int ia = patch0 + row_a * W_ROW, ib = patch0 + row_b * W_ROW;
+    if constexpr (DMA) {
+        // D_READ: the lane's OWN four columns 4 xc .. 4 xc + 3 of its two patch rows, one ds_read_b128 each; the columns -1
+        // and +4 come from the neighbouring lanes (WB_XFORM).  Map row r of a plane lies at float 16 pos(r), pos = r[3] r[0]
+        // r[2] r[1] (bits): the 16 lanes of a b128 group are one plane x 4 tile rows (map rows r0, r0 + 2, r0 + 4, r0 + 6)
+        // x 4 column chunks = 16-byte chunks 4 pos + xc, and pos % 4 = (r >> 1) % 4 takes four different values for either
+        // parity of r0: 16 different chunks modulo 16 = all 64 banks once.  (In plain row order the rows r0 and r0 + 4 lie 64
+        // floats apart: two-way.)  Rows -1 and 16 are the plane's gap, at chunks = 12 + xc and xc (mod 16): the classes the
+        // other three tile rows of the group (rows 1, 3, 5: classes 0-2; rows 10, 12, 14: classes 1-3) leave free.
+        auto d_row = [](int r) {
+            return r < 0 ? D_GAP_LO : (r > 15 ? D_GAP_HI : 16 * ((((r >> 3) & 1) << 3) | ((r & 1) << 2) | ((r >> 1) & 3)));
+        };
+        // Lane order of this form: tile row = xl % 4, column chunk xc = xl / 4 (the other forms: the other way round), so
+        // that the lanes of the chunks xc - 1 and xc + 1 are the lanes -4 and +4 of the DPP row and the map's edge is the
+        // row's edge (WB_XFORM).  The N index of the matrix instruction is permuted with it: the epilogue's exchange image is
+        // written at the other forms' index 4 (xl % 4) + xl / 4.
+        const int r0 = 2 * ((xl & 3) + 4 * nh) - 1;       // map row of patch row 0
+        ia = kq * D_PLANE + d_row(r0 + row_a) + 4 * (xl >> 2);
+        ib = kq * D_PLANE + d_row(r0 + row_b) + 4 * (xl >> 2);
+    }
     asm volatile("" : "+v"(ia), "+v"(ib));   // two base registers; every (stage, k-step, pair) offset is an immediate
 
     // Main loop.  Stage = 8 input channels = 2 k-steps; ring of four stage buffers; one barrier per stage.
@@ -612,8 +683,8 @@ tower_wino_kernel(const float* __restrict__ resp, const float* __restrict__ pack
     // (tools/ubench/mfma_residual.hip checks 2^28 values per exponent pattern bit for bit against the vector form, bf16
     // there).  A column's four operands (two tiles x two k-steps) are one such group: 4 conversions + 1 matrix instruction.
     //
-    // The schedule: the two waves of a SIMD in ANTI-PHASE.  A stage is a vector phase P1 (raw store, operand transform, LDS
-    // reads of the next stage, split) and a matrix phase P2 (the column's 12 instructions, the stage's fetches in their
+    // The schedule: the two waves of a SIMD in ANTI-PHASE.  A stage is a vector phase P1 (BLOCKED: raw store; operand transform,
+    // LDS reads of the next stage, split) and a matrix phase P2 (the column's 12 instructions, the stage's fetches in their
     // shadow).  tools/ubench/mfma_residual.hip ("pingpong"): a wave that issues only matrix instructions is not slowed by a
     // partner issuing only vector instructions, and the partner keeps ~55 % of its rate.  So the waves 4-7 (nh = 1; wave w
     // and w + 4 share a SIMD) run ONE INTERVAL behind the waves 0-3: a barrier between P1 and P2, one extra barrier for the
@@ -624,6 +695,13 @@ tower_wino_kernel(const float* __restrict__ resp, const float* __restrict__ pack
     // + 1) [X 2s + 2]; the slot's last readers were in P1(s - 3).  A parts of column (s + 2) % 4 are requested in P2(s) [X 2s
     // + 1, Y 2s + 2], confirmed by the issuing wave's vmcnt(0) at the end of P1(s + 1) [Y: end of 2s + 3], read in P2(s + 2)
     // [X 2s + 5]; the slot's last readers were in P2(s - 2) [Y 2s - 2].  The tail keeps the cadence (three pseudo-stages).
+    // DMA form (16 x 16 map: no registers, no store): the planes of stage s + 3 are requested in P2(s) [X 2s + 1, Y 2s + 2] into
+    // the slot of stage s - 1, whose last readers were in P1(s - 2) [Y 2s - 3]; each wave's plane is confirmed by that wave's
+    // vmcnt(0) at the end of P1(s + 1) [X 2s + 2, Y 2s + 3] and published by the barrier behind it; first read in P1(s + 2) [X
+    // 2s + 4, Y 2s + 5] — one barrier more than "wait, barrier, read" needs, because the halves run staggered.  The stages 0-2
+    // are requested at entry and published by the one barrier in front of the loop; a stage past the last is not requested
+    // (the tail fetches only the A parts it uses).  The gaps (rows -1 and 16) are written once, before that barrier, and lie
+    // outside every fetch's destination.
     // Fetches are inline asm (hipcc's waitcnt pass does not count them; through the builtins it drains vmcnt at the next
     // LDS read): issued at the start of a matrix phase, waited for with ONE s_waitcnt vmcnt(0) at the end of the next vector
     // phase — a full stage later, and with no assumption on the order in which direct-to-LDS and register loads retire (a
@@ -686,11 +764,39 @@ tower_wino_kernel(const float* __restrict__ resp, const float* __restrict__ pack
     // the row combination d_a +- d_b as one fused multiply-add with the wave's sign in a scalar register (exact: the
     // factor is +-1): ONE copy of the loop for all four xi rows, which leaves the instruction cache room for unrolling it
     const float sgn = __uint_as_float(__builtin_amdgcn_readfirstlane(xi == 1 ? 0x3f800000u : 0xbf800000u));
+    // DMA: columns 1..4 of the combination are the lane's own (scaled here by the track's power of two: LDS holds the
+    // response as it is in memory; (a +- b) 2^kv = a 2^kv +- b 2^kv bit for bit, nothing here is near the ends of the
+    // exponent range); column 0 = column 4 of the lane to the left, column 5 = column 1 of the lane to the right — the same
+    // tile row, patch rows and sign, so the same bits the old image held twice — as the DPP operand (row_shr:4 / row_shl:4
+    // with bound_ctrl) of the subtraction that consumes it: no instruction of its own, and the lanes whose neighbour lies
+    // outside the row of 16 — the map's first / last chunk — read an exact 0 (not a product with 0: a non-finite neighbour
+    // must not become NaN).  Per k-step: 2 packed FMAs + 2 packed multiplies + 8 adds (before: 6 FMAs + 8 adds).
+#define WB_DPP(V, CTRL) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(V), (CTRL), 0xf, 0xf, true))
+#define D_READ(BUFI, Q, RD)                                                                      \
+    {                                                                                            \
+        const float* oa = sm + ia + ((BUFI) * D_BUF + (Q) * 4 * D_PLANE);                        \
+        const float* ob = sm + ib + ((BUFI) * D_BUF + (Q) * 4 * D_PLANE);                        \
+        f32x4 a4 = *reinterpret_cast<const f32x4*>(oa);     /* (through a pointer variable: the cast of an expression */ \
+        f32x4 b4 = *reinterpret_cast<const f32x4*>(ob);     /* on the array keeps the array's 4-byte alignment) */       \
+        asm volatile("" : "+v"(a4), "+v"(b4));                                                   \
+        _Pragma("unroll") for (int c = 0; c < 4; ++c) { RD[0][c + 1][0] = a4[c]; RD[0][c + 1][1] = b4[c]; } \
+    }
+#define WB_READ(BUFI, Q, RD) if constexpr (DMA) D_READ(BUFI, Q, RD) else { W_READ(BUFI, Q, RD) }
 #define WB_XFORM(RD, BOP)                                                                        \
     _Pragma("unroll") for (int p = 0; p < NP; ++p) {                                             \
         float w[6];                                                                              \
-        _Pragma("unroll") for (int c = 0; c < 6; ++c) w[c] = __builtin_fmaf(sgn, RD[p][c][1], RD[p][c][0]); \
-        BOP[0][2 * p] = w[0] - w[2];                                                             \
+        if constexpr (DMA) {                                                                     \
+            const f32x2 w12 = __builtin_elementwise_fma((f32x2){sgn, sgn}, (f32x2){RD[p][1][1], RD[p][2][1]},     \
+                                                        (f32x2){RD[p][1][0], RD[p][2][0]}) * (f32x2){sv_s, sv_s}; \
+            const f32x2 w34 = __builtin_elementwise_fma((f32x2){sgn, sgn}, (f32x2){RD[p][3][1], RD[p][4][1]},     \
+                                                        (f32x2){RD[p][3][0], RD[p][4][0]}) * (f32x2){sv_s, sv_s}; \
+            w[1] = w12[0]; w[2] = w12[1]; w[3] = w34[0]; w[4] = w34[1];                          \
+            w[0] = WB_DPP(w[4], 0x114);                    /* row_shr:4: column 4 of chunk xc - 1 */ \
+            w[5] = WB_DPP(w[1], 0x104);                    /* row_shl:4: column 1 of chunk xc + 1 */ \
+        } else {                                                                                 \
+            _Pragma("unroll") for (int c = 0; c < 6; ++c) w[c] = __builtin_fmaf(sgn, RD[p][c][1], RD[p][c][0]); \
+        }                                                                                        \
+        BOP[0][2 * p] = w[0] - w[2];                                                         \
         BOP[1][2 * p] = w[1] + w[2];                                                             \
         BOP[2][2 * p] = w[2] - w[1];                                                             \
         BOP[3][2 * p] = w[1] - w[3];                                                             \
@@ -700,25 +806,25 @@ tower_wino_kernel(const float* __restrict__ resp, const float* __restrict__ pack
         BOP[3][2 * p + 1] = w[3] - w[5];                                                         \
     }
     // ABL 15: timeline of ONE stage (KB 2, J 1) per wave: trace[(workgroup * 8 + wave) * 8 + slot], slots: 0 before the stage's
-    // first barrier, 1 behind it, 2 raw planes stored, 3 transform + reads + split done, 4 behind the second barrier, 5 matrix
+    // first barrier, 1 behind it, 2 raw planes stored (DMA form: nothing is stored, the same point again), 3 transform + reads + split done, 4 behind the second barrier, 5 matrix
     // instructions and fetches issued, 6 behind vmcnt(N)
 #define WB_STAMP(J, KB, SLOT) if (ABL == 15 && (KB) == 2 && (J) == 1 && trace && lane == 0) \
         trace[((size_t)blockIdx.x * 8 + wave) * 8 + (SLOT)] = (long long)__builtin_amdgcn_s_memtime();
 #define WB_STAGE(J, KB)                                                                          \
     {                                                                                            \
-        /* P1, vector phase: raw store, operand transform, next stage's LDS reads, split, this column's A parts requested */ \
+        /* P1, vector phase: (BLOCKED: raw store,) operand transform, next stage's LDS reads, split, this column's A parts read */ \
         WB_STAMP(J, KB, 0)                                                                       \
         asm volatile("s_barrier" ::: "memory");                                                  \
         WB_STAMP(J, KB, 1)                                                                       \
-        store_raw(sm + (((J) + 2) & 3) * W_BUF, prs[(J) & 1]);                                   \
+        if constexpr (!DMA) store_raw(sm + (((J) + 2) & 3) * W_BUF, prs[(J) & 1]);               \
         W_FENCE                                                                                  \
-        WB_STAMP(J, KB, 2)                                                                       \
+        WB_STAMP(J, KB, 2)                             /* DMA: nothing stored, = slot 1 */       \
         float ba[4][2 * NP], bb[4][2 * NP];                                                      \
         u32x4 AB[OCT][2];                                                                        \
         WB_XFORM(rd, ba)                               /* k-step 2s */                           \
-        W_READ(((J) + 1) & 3, 0, rd)                   /* k-step 2(s+1): next stage's buffer */  \
+        WB_READ(((J) + 1) & 3, 0, rd)                  /* k-step 2(s+1): next stage's buffer */  \
         WB_XFORM(rdb, bb)                              /* k-step 2s+1 */                         \
-        W_READ(((J) + 1) & 3, 1, rdb)                                                            \
+        WB_READ(((J) + 1) & 3, 1, rdb)                                                           \
         WB_SPLIT(J, ba, bb)                                                                      \
         load_al(J, AB);                                                                          \
         W_FENCE                                                                                  \
@@ -726,8 +832,10 @@ tower_wino_kernel(const float* __restrict__ resp, const float* __restrict__ pack
         /* everything this wave fetched in the last matrix phase has arrived (no assumption on the order in which direct-to- \
            LDS and register loads retire): the A parts of column (J + 1) % 4, read after the next stage's second barrier, and  \
            the raw planes stored at the start of the next stage.  The raw stores above are behind at least the 12 LDS reads    \
-           (LDS operations of a wave complete in order). */                                    \
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(12)\n\ts_barrier" ::: "memory");                \
+           (LDS operations of a wave complete in order).  DMA form: this wave's plane of stage s + 2, read from the stage after \
+           the next on; it has no LDS write to order, so no lgkmcnt. */                        \
+        if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");         \
+        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(12)\n\ts_barrier" ::: "memory");           \
         W_FENCE                                                                                  \
         WB_STAMP(J, KB, 4)                                                                       \
         /* (the next stage's LDS reads issued HERE instead of in the vector phase were measured: loop 25.2 k against 23.3 k    \
@@ -736,7 +844,9 @@ tower_wino_kernel(const float* __restrict__ resp, const float* __restrict__ pack
            wait above); slot (J + 2) % 4 was consumed two stages ago, its next use is two stages ahead */ \
         WB_TERM(J, 1, 0)                                                                         \
         W_FENCE                                                                                  \
-        if (ABL != 9) load_raw_asm(min(4 * (KB) + (J) + 4, nstages - 1), prs[(J) & 1]);          \
+        if constexpr (DMA) {                           /* stage s + 3 -> the slot of stage s - 1 */ \
+            if (ABL != 9 && 4 * (KB) + (J) + 3 < 4 * nkb) dma_plane(4 * (KB) + (J) + 3, ((J) + 3) & 3); \
+        } else if (ABL != 9) load_raw_asm(min(4 * (KB) + (J) + 4, nstages - 1), prs[(J) & 1]);   \
         if (ABL != 9) dma_part(((J) + 2) & 3, (KB) + ((J) >= 2 ? 1 : 0), 0);                     \
         W_FENCE                                                                                  \
         WB_TERM(J, 0, 1)                                                                         \
@@ -749,8 +859,8 @@ tower_wino_kernel(const float* __restrict__ resp, const float* __restrict__ pack
     }
 #define WB_BLOCK(KB) WB_STAGE(0, KB) WB_STAGE(1, KB) WB_STAGE(2, KB) WB_STAGE(3, KB)
 #define WB_LOOP                                                                                  \
-    W_READ(0, 0, rd)                                                                             \
-    W_READ(0, 1, rdb)                                                                            \
+    WB_READ(0, 0, rd)                                                                            \
+    WB_READ(0, 1, rdb)                                                                           \
     if (nh == 1) asm volatile("s_barrier" ::: "memory");            /* the late half: one interval behind */ \
     if (nkb == 4) {        /* C = 128 unrolled: no loop-carried register shuffle */              \
         WB_BLOCK(0) WB_BLOCK(1) WB_BLOCK(2) WB_BLOCK(3)                                          \
@@ -767,8 +877,10 @@ tower_wino_kernel(const float* __restrict__ resp, const float* __restrict__ pack
     WB_Q(0)                                                                                      \
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                             \
     /* the loop's last raw fetches (re-fetches of the last stage, never stored) have landed: their registers may die */ \
-    _Pragma("unroll") for (int j = 0; j < NRAW; ++j) asm volatile("" :: "v"(prs[0][j].x), "v"(prs[0][j].y), "v"(prs[0][j].z), "v"(prs[0][j].w), \
-                                                                    "v"(prs[1][j].x), "v"(prs[1][j].y), "v"(prs[1][j].z), "v"(prs[1][j].w)); \
+    if constexpr (!DMA) {                                                                        \
+        _Pragma("unroll") for (int j = 0; j < NRAW; ++j) asm volatile("" :: "v"(prs[0][j].x), "v"(prs[0][j].y), "v"(prs[0][j].z), "v"(prs[0][j].w), \
+                                                                        "v"(prs[1][j].x), "v"(prs[1][j].y), "v"(prs[1][j].z), "v"(prs[1][j].w)); \
+    }                                                                                            \
     asm volatile("s_barrier\n\ts_barrier" ::: "memory");                                         \
     WB_Q(1)                                                                                      \
     asm volatile("s_barrier\n\ts_barrier" ::: "memory");                                         \
@@ -794,6 +906,9 @@ tower_wino_kernel(const float* __restrict__ resp, const float* __restrict__ pack
 #undef WB_STAMP
 #undef WB_BLOCK
 #undef WB_XFORM
+#undef WB_READ
+#undef D_READ
+#undef WB_DPP
 #undef WB_Q
 #undef WB_QM
 #undef WB_TERM
@@ -820,7 +935,7 @@ tower_wino_kernel(const float* __restrict__ resp, const float* __restrict__ pack
                 const float p0 = (acc[o][0][t][r] + acc[o][1][t][r]) + acc[o][2][t][r];
                 const float p1 = (acc[o][1][t][r] - acc[o][2][t][r]) - acc[o][3][t][r];
                 float* dst = sm + o * W_EPI_FLOATS + ((xi * 2) * 16 + (kq * 4 + r)) * W_XOC +
-                             16 * (t + (OCT == 2 ? 2 * nh : 0)) + xl;
+                             16 * (t + (OCT == 2 ? 2 * nh : 0)) + (DMA ? ((xl & 3) << 2) | (xl >> 2) : xl);
                 dst[0] = p0;
                 dst[16 * W_XOC] = p1;
             }
