@@ -237,22 +237,26 @@ class DLA(nn.Module):
         N, _, H, W = images.shape
         return N >= 1 and ops.dla_shapes_ok(self.levels, self.channels, H, W, N, self.block)
 
+    def _pack(self):
+        with torch.no_grad():
+            convs = [(c.weight.detach(),) + tuple(t.contiguous() for t in bn.scale_shift()) for c, bn in self.convs()]
+            if self.compute_dtype is not None:
+                return ops.dla_half_pack(convs, self.levels, self.channels, self.compute_dtype, block=self.block,
+                                         residual_root=self.residual_root)
+            if self._net:
+                return ops.dla_net_pack(convs, self.levels, self.channels, block=self.block, residual_root=self.residual_root,
+                                        operands=self.operands)
+            return ops.dla_pack(convs, self.levels, self.channels, operands=self.operands)
+
     def packed(self):
+        """The packed weights for a launch on the current stream: packed on the stream of the first call after a change and
+        ordered for every other stream by ``ops.StreamImage`` (an event wait on the device, no host synchronisation)."""
         tensors = list(self.parameters()) + list(self.buffers())
         key = (self.operands, self.compute_dtype) + tuple((t.data_ptr(), t._version, t.device) for t in tensors)
         if key != self._packed_key:
-            with torch.no_grad():
-                convs = [(c.weight.detach(),) + tuple(t.contiguous() for t in bn.scale_shift()) for c, bn in self.convs()]
-                if self.compute_dtype is not None:
-                    self._packed = ops.dla_half_pack(convs, self.levels, self.channels, self.compute_dtype, block=self.block,
-                                                     residual_root=self.residual_root)
-                elif self._net:
-                    self._packed = ops.dla_net_pack(convs, self.levels, self.channels, block=self.block,
-                                                    residual_root=self.residual_root, operands=self.operands)
-                else:
-                    self._packed = ops.dla_pack(convs, self.levels, self.channels, operands=self.operands)
+            self._packed = ops.StreamImage(self._pack, tensors[0].device)
             self._packed_key = key
-        return self._packed
+        return self._packed.get()
 
     def forward(self, images):
         if self.kernel_ok(images):

@@ -157,17 +157,19 @@ class FPN(nn.Module):
         return ops.fpn_shapes_ok(self.in_channels, self.out_channels)
 
     def packed(self):
+        """The packed weights for a launch on the current stream: packed on the stream of the first call after a change and
+        ordered for every other stream by ``ops.StreamImage`` (an event wait on the device, no host synchronisation)."""
         inner, layer = self._blocks()
         params = [p for m in inner + layer for p in (m.weight, m.bias)]
         key = (self.compute_dtype,) + tuple((p.data_ptr(), p._version, p.device) for p in params)
         if key != self._packed_key:
             blocks = ([(m.weight.detach(), m.bias.detach()) for m in inner], [(m.weight.detach(), m.bias.detach()) for m in layer])
             if self.compute_dtype is not None:
-                self._packed = ops.fpn_half_pack(*blocks, self.compute_dtype)
+                self._packed = ops.StreamImage(lambda: ops.fpn_half_pack(*blocks, self.compute_dtype), params[0].device)
             else:
-                self._packed = ops.fpn_pack(*blocks)
+                self._packed = ops.StreamImage(lambda: ops.fpn_pack(*blocks), params[0].device)
             self._packed_key = key
-        return self._packed
+        return self._packed.get()
 
     def forward(self, x):
         x = list(x)

@@ -372,6 +372,32 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
+class StreamImage(object):
+    """A device image that is computed once and kept (packed weights, anchor grids), ordered for every stream that reads it.
+    ``produce()`` enqueues the image on the current stream of ``device`` and returns its tensor or list of tensors; the image
+    carries that stream's raw handle and an event recorded right behind the producing launch.  ``get()`` returns the
+    tensor(s) for a consumer that launches on the current stream: on the producing stream that is one raw-stream lookup and
+    an integer compare; on any other stream the stream first waits for the event (on the device: no host synchronisation)
+    and the tensors are marked as used by it (``Tensor.record_stream``), so that dropping the image on a repack cannot hand
+    its block out again under a kernel that still reads it."""
+    __slots__ = ("value", "device", "stream", "event")
+
+    def __init__(self, produce, device):
+        self.device = device
+        self.stream = _stream(device).value
+        self.value = produce()
+        self.event = torch.cuda.Event()
+        self.event.record(torch.cuda.current_stream(device))
+
+    def get(self):
+        if _stream(self.device).value != self.stream:
+            current = torch.cuda.current_stream(self.device)
+            current.wait_event(self.event)
+            for t in (self.value if isinstance(self.value, (list, tuple)) else (self.value,)):
+                t.record_stream(current)
+        return self.value
+
+
 class _Launch(object):
     """Launch context of one binding: every tensor must live on ONE device, that device is made current for
     the duration of the call (hipLaunchKernelGGL launches on the CURRENT device — a stream handle of another
@@ -1489,14 +1515,17 @@ def _rpn_head_pack(who, ct, conv_w, conv_b, cls_w, cls_b, bbox_w, bbox_b):
 def rpn_head_pack(conv_w, conv_b, cls_w, cls_b, bbox_w, bbox_b):
     """The RPN head's parameters (upstream's ``conv`` ``[C, C, 3, 3]``, ``cls_logits`` ``[A, C, 1, 1]``, ``bbox_pred``
     ``[4A, C, 1, 1]`` and their biases, fp32 device tensors) in the operand order of ``rpn_head`` (``smot_rpn_head_pack``:
-    one launch, no synchronisation).  -> fp32 ``[smot_rpn_head_packed_floats(C, A)]``."""
+    one launch, no synchronisation).  -> fp32 ``[smot_rpn_head_packed_floats(C, A)]``.
+    The image is ordered on the current stream only: a caller who packs on one stream and consumes on another orders the two
+    himself (the modules do it through ``StreamImage``)."""
     return _rpn_head_pack("rpn_head_pack", None, conv_w, conv_b, cls_w, cls_b, bbox_w, bbox_b)
 
 
 def rpn_head_half_pack(conv_w, conv_b, cls_w, cls_b, bbox_w, bbox_b, compute_dtype):
     """``rpn_head_pack`` for ``rpn_head_half`` (``smot_rpn_head_half_pack``): ``conv.weight`` rounded once to
     ``compute_dtype`` (``tensor.to``'s rounding), every bias and the two 1x1 heads' rows in fp32.  The tensor serves this
-    ``compute_dtype`` and no other mode."""
+    ``compute_dtype`` and no other mode.  One launch, no synchronisation, ordered on the current stream only, as
+    ``rpn_head_pack``."""
     ct = _dla_ctype(compute_dtype, "rpn_head_half_pack")
     return _rpn_head_pack("rpn_head_half_pack", ct, conv_w, conv_b, cls_w, cls_b, bbox_w, bbox_b)
 
@@ -1599,13 +1628,16 @@ def _fpn_pack(who, ct, inner, layer):
 def fpn_pack(inner, layer):
     """The pyramid's parameters (per level, finest first: ``inner[l]`` = upstream's ``fpn_inner{l+1}`` ``(weight [C, Cin_l,
     1, 1], bias [C])``, ``layer[l]`` = ``fpn_layer{l+1}`` ``(weight [C, C, 3, 3], bias [C])``, fp32 device tensors) in the
-    operand order of ``fpn`` (``smot_fpn_pack``: one launch, no synchronisation).  -> fp32 ``[smot_fpn_packed_floats]``."""
+    operand order of ``fpn`` (``smot_fpn_pack``: one launch, no synchronisation).  -> fp32 ``[smot_fpn_packed_floats]``.
+    The image is ordered on the current stream only: a caller who packs on one stream and consumes on another orders the two
+    himself (the modules do it through ``StreamImage``)."""
     return _fpn_pack("fpn_pack", None, inner, layer)
 
 
 def fpn_half_pack(inner, layer, compute_dtype):
     """``fpn_pack`` for ``fpn_half`` (``smot_fpn_half_pack``): both convolutions' filters rounded once to ``compute_dtype``
-    (``tensor.to``'s rounding), the biases in fp32.  The tensor serves this ``compute_dtype`` and no other mode."""
+    (``tensor.to``'s rounding), the biases in fp32.  The tensor serves this ``compute_dtype`` and no other mode.  One launch, no
+    synchronisation, ordered on the current stream only, as ``fpn_pack``."""
     return _fpn_pack("fpn_half_pack", _dla_ctype(compute_dtype, "fpn_half_pack"), inner, layer)
 
 
@@ -1719,7 +1751,9 @@ def dla_pack(convs, levels, channels, operands="fp32"):
     """The body's parameters in the operand order of ``dla`` (``smot_dla_pack``, or ``smot_dla_split_pack`` for ``operands``
     "split16": the image of one mode does not serve the other; one launch per convolution, no synchronisation).  convs: ``(weight [Cout, Cin, k, k], scale [Cout], shift [Cout])`` per convolution in LAUNCH ORDER
     (include/smot_emm.h; ``dla.DLA.convs()``), fp32 device tensors, ``scale`` / ``shift`` the frozen BN's.  -> fp32
-    ``[smot_dla_packed_floats]``."""
+    ``[smot_dla_packed_floats]``.
+    The image is ordered on the current stream only: a caller who packs on one stream and consumes on another orders the two
+    himself (the modules do it through ``StreamImage``)."""
     lib = _lib or load_library()
     split = _dla_split(operands, "dla_pack")
     lv, ch = _int6(levels), _int6(channels)
@@ -1906,7 +1940,8 @@ def dla_net_ws_bytes(levels, channels, N, H, W, block="basic", residual_root=Fal
 
 def dla_net_pack(convs, levels, channels, block="basic", residual_root=False, operands="fp32"):
     """``dla_pack`` for ``dla_net`` (``smot_dla_net_pack``): convs in LAUNCH ORDER (``dla.DLA.convs()``).  With basic blocks and
-    trees of depth <= 2 the tensor is ``dla_pack``'s."""
+    trees of depth <= 2 the tensor is ``dla_pack``'s.  No synchronisation, ordered on the current stream only, as
+    ``dla_pack``."""
     lib = _lib or load_library()
     split = 1 if _dla_split(operands, "dla_net_pack") else 0
     blk, rr = _dla_block(block, "dla_net_pack"), 1 if residual_root else 0
@@ -1965,7 +2000,7 @@ def _dla_ctype(compute_dtype, who):
 def dla_half_pack(convs, levels, channels, compute_dtype, block="basic", residual_root=False):
     """``dla_net_pack`` for ``dla_half`` (``smot_dla_half_pack``): the tree convolutions' filters rounded once to
     ``compute_dtype`` (``tensor.to``'s rounding), the stem's and every ``scale`` / ``shift`` in fp32.  The tensor serves this
-    ``compute_dtype`` and no other mode."""
+    ``compute_dtype`` and no other mode.  No synchronisation, ordered on the current stream only, as ``dla_pack``."""
     lib = _lib or load_library()
     ct = _dla_ctype(compute_dtype, "dla_half_pack")
     blk, rr = _dla_block(block, "dla_half_pack"), 1 if residual_root else 0
@@ -2130,7 +2165,8 @@ def dla_stem(images, layers):
 def rpn_anchors(cell_anchors, strides, grid_sizes):
     """Upstream's ``AnchorGenerator.grid_anchors`` for all levels in one launch (``smot_rpn_anchors_fwd``).  cell_anchors: L
     fp32 device tensors ``[A_l, 4]``; strides: L ints; grid_sizes: L pairs ``(H_l, W_l)``.  -> L fp32 ``[H_l*W_l*A_l, 4]``
-    in the flattened order (h*W + w)*A + a."""
+    in the flattened order (h*W + w)*A + a.  No synchronisation; the grids are ordered on the current stream only, as
+    ``rpn_head_pack``'s image."""
     lib = _lib or load_library()
     L = len(cell_anchors)
     if L < 1 or len(strides) != L or len(grid_sizes) != L:

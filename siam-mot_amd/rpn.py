@@ -259,8 +259,9 @@ class AnchorGenerator(torch.nn.Module):
         if hit is None:
             if len(self._grids) >= self._CACHE_ENTRIES:
                 self._grids.clear()
-            hit = self._grids[key] = ops.rpn_anchors(cells, self.strides, grid_sizes)
-        return hit
+            # (computed on the current stream, ordered for every other one: an event wait on the device, no host synchronisation)
+            hit = self._grids[key] = ops.StreamImage(lambda: ops.rpn_anchors(cells, self.strides, grid_sizes), cells[0].device)
+        return hit.get()
 
     def forward(self, image_sizes, feature_maps):
         grid_sizes = [(int(f.shape[-2]), int(f.shape[-1])) for f in feature_maps]
@@ -331,15 +332,18 @@ class RPNHead(torch.nn.Module):
         return ops.rpn_head_shapes_ok(self.in_channels, self.num_anchors)
 
     def packed(self):
+        """The packed weights for a launch on the current stream: packed on the stream of the first call after a change and
+        ordered for every other stream by ``ops.StreamImage`` (an event wait on the device, no host synchronisation)."""
         params = self._params()
         key = (self.compute_dtype,) + tuple((p.data_ptr(), p._version, p.device) for p in params)
         if key != self._packed_key:
+            tensors = [p.detach() for p in params]
             if self.compute_dtype is not None:
-                self._packed = ops.rpn_head_half_pack(*[p.detach() for p in params], self.compute_dtype)
+                self._packed = ops.StreamImage(lambda: ops.rpn_head_half_pack(*tensors, self.compute_dtype), params[0].device)
             else:
-                self._packed = ops.rpn_head_pack(*[p.detach() for p in params])
+                self._packed = ops.StreamImage(lambda: ops.rpn_head_pack(*tensors), params[0].device)
             self._packed_key = key
-        return self._packed
+        return self._packed.get()
 
     def forward(self, features):
         features = list(features)
