@@ -66,7 +66,9 @@ typedef void* smot_stream_t; /* hipStream_t */
  *     smot_dla_half_packed_floats, smot_dla_half_pack, smot_dla_half_fwd, smot_dla_conv_half_packed_floats,
  *     smot_dla_conv3x3_half_fwd, smot_dla_conv3x3_half_form, smot_dla_conv1x1_half_fwd; the feature pyramid and the RPN head
  *     in half compute mode: smot_fpn_half_packed_floats, smot_fpn_half_pack, smot_fpn_half_fwd,
- *     smot_rpn_head_half_packed_floats, smot_rpn_head_half_pack, smot_rpn_head_half_fwd.
+ *     smot_rpn_head_half_packed_floats, smot_rpn_head_half_pack, smot_rpn_head_half_fwd; the bodies in half compute mode with
+ *     the maps between layers stored in the compute type: smot_dla_half_storage_ws_bytes, smot_dla_half_storage_fwd,
+ *     smot_dla_conv3x3_half_storage_fwd, smot_dla_conv1x1_half_storage_fwd.
  */
 #define SMOT_ABI_VERSION 14
 
@@ -1436,6 +1438,49 @@ int smot_dla_conv1x1_half_fwd(const float* const* sources, const int* source_cha
                               const float* w, const float* scale, const float* shift, int Cout, int relu, const float* residual,
                               int residual_h, int residual_w, int compute_type, float* packed, void* out, int out_type,
                               smot_stream_t stream);
+
+/* DLA BACKBONE, HALF STORAGE: the half compute mode above with every map that a TREE convolution writes STORED in the compute
+ * type: block intermediates, block outputs, project outputs, roots and the four returned stage maps.
+ *   stored value the fp32 epilogue value (acc * scale + shift, + residual, ReLU) rounded once to compute_type, round to nearest
+ *                even as torch's tensor.to(dtype); an fp16 value beyond 65,504 in magnitude is stored as +-inf, a NaN stays.
+ *   operands     unchanged: half compute mode rounds an activation to compute_type as it loads it, rounding a stored value
+ *                again gives the stored bits, and the 2 x 2 max-pool commutes with a monotone rounding.  What changes: a
+ *                residual that is a stored map is added as the rounded value, and the returned maps are the stored maps.
+ *   fp32 stays   the stem (base_layer, level0, level1) and its output x1 in the workspace: read as a convolution's input it
+ *                changes nothing; as a residual (channels[1] == channels[2] only) its fp32 value is added.  Products,
+ *                accumulation, scale / shift and the residual add stay fp32.  The packed image is smot_dla_half_pack's.
+ *   contract     an operator here returns, bit for bit, what the half-mode operator (smot_dla_conv3x3_half_fwd /
+ *                smot_dla_conv1x1_half_fwd) returns on the inputs and the residual widened to fp32, rounded once to
+ *                compute_type: the same forms by the same rules, the same sum order.  Image i of a call equals the one-image
+ *                call; no host synchronisation, no allocation; the launches are half mode's (37 / 48 / 63 / 105 / 168).
+ *   types        in_type and res_type are each SMOT_FEAT_F32 or compute_type (anything else: SMOT_ERR_BAD_ARG, as a
+ *                compute_type that is neither SMOT_FEAT_F16 nor SMOT_FEAT_BF16); a pointer must be aligned for its type (4 / 2
+ *                bytes).  All sources of one 1x1 call have in_type.  res_type is not read where residual is null.
+ *   smot_dla_half_storage_ws_bytes   the workspace of smot_dla_half_storage_fwd (-1 where smot_dla_net_ws_bytes is -1 or the
+ *                compute_type is bad): x1 and the stem's two full-resolution maps in fp32, the tree maps in 2 bytes per
+ *                element, no fp32 twin of a returned map.  Never above smot_dla_net_ws_bytes, and below it wherever a tree
+ *                is that form's peak (where the stem's two fp32 maps and x1 are the peak of both forms, as for DLA-34, the
+ *                two answers are equal); never below the stem's need plus x1.
+ *   smot_dla_half_storage_fwd        smot_dla_half_fwd's arguments, checks and refusals without out_type: out[0..3] are
+ *                [N, channels[k], H >> k, W >> k], k = 2 .. 5, of compute_type, 2-byte aligned.
+ *   smot_dla_conv3x3_half_storage_fwd / smot_dla_conv1x1_half_storage_fwd   smot_dla_conv3x3_half_fwd's /
+ *                smot_dla_conv1x1_half_fwd's arguments, checks and refusals with in_type behind x / sources and res_type behind
+ *                residual, and without out_type: out is of compute_type.  A refused call launches nothing.
+ */
+long long smot_dla_half_storage_ws_bytes(const int* levels, const int* channels, int block, int residual_root, int compute_type,
+                                         int num_images, int H, int W);
+int smot_dla_half_storage_fwd(const void* image, int in_type, int num_images, int H, int W, const int* levels, const int* channels,
+                              int block, int residual_root, int compute_type, const float* packed, float* ws, void* const* out,
+                              smot_stream_t stream);
+int smot_dla_conv3x3_half_storage_fwd(const void* x, int in_type, int num_images, int Cin, int H, int W, const float* w,
+                                      const float* scale, const float* shift, int Cout, int stride, const void* residual,
+                                      int res_type, int residual_h, int residual_w, int relu, int compute_type, float* packed,
+                                      void* out, smot_stream_t stream);
+int smot_dla_conv1x1_half_storage_fwd(const void* const* sources, int in_type, const int* source_channels, const int* source_pooled,
+                                      const int* source_heights, const int* source_widths, int num_sources, int num_images, int H,
+                                      int W, const float* w, const float* scale, const float* shift, int Cout, int relu,
+                                      const void* residual, int res_type, int residual_h, int residual_w, int compute_type,
+                                      float* packed, void* out, smot_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -524,8 +524,12 @@ __host__ __device__ inline long long cvh_packed_floats(int Cin, int Cout) {
     return (long long)((Cout + 31) / 32) * (Cin / CVS_IC) * 9 * 2 * 256;
 }
 
-// cvs_block with one part: sm: CvhGeom<STRIDE>::SMEM_SLOTS 16-byte slots; pl: cvs_plan's; packed: the cvh_pack_index image
-template <int CT, typename FT, int STRIDE, int WR, int NM>
+// cvs_block with one part: sm: CvhGeom<STRIDE>::SMEM_SLOTS 16-byte slots; pl: cvs_plan's; packed: the cvh_pack_index image.
+// FT: the input's element type (fp32, or f16_t / bf16_t: a stored value widens exactly and rounds to CT back to its own bits).
+// USER: names the calling kernel family and is not read: the staging lambdas below are functions of their own per
+// instantiation, and a second kernel that shared one would change how the compiler inlines them into the first (measured: the
+// stride-1 half kernels took 3 - 6 more registers and one lost a wave of occupancy), so each family takes its own copy.
+template <int CT, typename FT, int STRIDE, int WR, int NM, int USER = 0>
 __device__ __forceinline__ void cvh_block(cvs_u32x4* sm, const FT* __restrict__ in, int HW, int Cin, const CvsPlan<STRIDE>& pl,
                                           const float* __restrict__ packed, int pair, bool active, int tid, int row0,
                                           cv_f32x4 (&acc)[NM][CV_TH / WR]) {

@@ -316,6 +316,101 @@ dla_conv3x3_half_kernel(DlaConv3Args P) {
     if (active && x < P.Wo) dl_conv3_store<NM, ROWS>(acc, pair, kq, x, y0, row0, Cout, P.Ho, P.Wo, HWo, P.res_w, HWr, P.relu, scale, shift, res, out);
 }
 
+// ---- HALF STORAGE: the half compute mode with the maps between layers stored in the compute type -----------------------------
+// (the smot_dla_half_storage_* entry points).  A map type is the element type of the compute type: f16_t or bf16_t.  Widening
+// a stored value is exact and monotone, so rounding it again on load gives the stored bits and the max-pool of widened values
+// is the widened max-pool: an operator here returns what the half-mode operator returns on the widened maps, rounded once.
+template <int CT>
+struct DlMapOf {
+    using type = f16_t;
+};
+template <>
+struct DlMapOf<SMOT_FEAT_BF16> {
+    using type = bf16_t;
+};
+// dl_pool over a map of any type
+template <typename RT>
+__device__ __forceinline__ float dl_pool_of(const RT* __restrict__ q, int Ws) {
+    return dl_pool_step(dl_pool_step(dl_pool_step(feat_ld<RT>(q), feat_ld<RT>(q + 1)), feat_ld<RT>(q + Ws)), feat_ld<RT>(q + Ws + 1));
+}
+// the residual at element `o` (plain) or through the 2 x 2 pool at `op` of a row of Ws; f32: (wave-uniform) it is an fp32 map
+template <typename MT_>
+__device__ __forceinline__ float dl_res_of(const void* __restrict__ res, int f32, int Ws, size_t o, size_t op) {
+    if (f32) {
+        const float* __restrict__ r = reinterpret_cast<const float*>(res);
+        return Ws ? dl_pool(r + op, Ws) : r[o];
+    }
+    const MT_* __restrict__ r = reinterpret_cast<const MT_*>(res);
+    return Ws ? dl_pool_of<MT_>(r + op, Ws) : feat_ld<MT_>(r + o);
+}
+
+struct DlaConv3HsArgs {
+    const void* in;          // [N, Cin, H, W] of the kernel's FT
+    const float* w;          // the convolution's kind-5 packed image
+    const void* res;         // as DlaConv3Args', of fp32 (res_f32) or the map type
+    void* out;               // [N, Cout, Ho, Wo] of the map type
+    int Cin, Cout, H, W, Ho, Wo;
+    int tiles_x, tiles_per_image, relu, res_h, res_w, res_f32;
+};
+
+// dla_conv3x3_hs_kernel<CT, FT, STRIDE, WR, NM>: dla_conv3x3_half_kernel's workgroup, stage (cvh_block) and sum order with the
+//   input of type FT (fp32 or CT's map type), the residual of either type (a wave-uniform switch in the epilogue) and the
+//   output stored rounded once to CT.  LDS as dla_conv3x3_half_kernel's.
+template <int CT, typename FT, int STRIDE, int WR, int NM>
+__global__ void __launch_bounds__(256, 2)
+dla_conv3x3_hs_kernel(DlaConv3HsArgs P) {
+    using Hh = CvhGeom<STRIDE>;
+    using MapT = typename DlMapOf<CT>::type;
+    constexpr int WP = 4 / WR, ROWS = CV_TH / WR;
+    __shared__ __attribute__((aligned(16))) cvs_u32x4 sm[Hh::SMEM_SLOTS];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int kq = lane >> 4, xl = lane & 15;
+    const int n = blockIdx.x / P.tiles_per_image;
+    const int t = blockIdx.x - n * P.tiles_per_image;
+    const int ty = t / P.tiles_x, tx = t - ty * P.tiles_x;
+    const int y0 = ty * CV_TH, x0 = tx * CV_TW;
+    const int HW = P.H * P.W, HWo = P.Ho * P.Wo, Cout = P.Cout;
+    const FT* __restrict__ in = reinterpret_cast<const FT*>(P.in) + (size_t)n * P.Cin * HW;
+    const int npairs = (Cout + 31) >> 5;
+    const float* __restrict__ scale = P.w + cvh_packed_floats(P.Cin, Cout);
+    const float* __restrict__ shift = scale + 32 * npairs;
+    const int HWr = P.res_w ? P.res_h * P.res_w : HWo;
+    const size_t rimg = (size_t)n * Cout * HWr;                 // the image's first residual element
+    MapT* __restrict__ out = reinterpret_cast<MapT*>(P.out) + (size_t)n * Cout * HWo;
+    const int wp = WR == 1 ? wave : wave % WP, row0 = WR == 1 ? 0 : (wave / WP) * ROWS;
+
+    CvsPlan<STRIDE> pl;
+    cvs_plan<STRIDE>(pl, tid, y0, x0, P.H, P.W);
+    const int x = x0 + xl;
+    const int pair = blockIdx.y * WP + wp;                      // grid.y: the blocks of 32 WP output channels
+    const bool active = pair < npairs;
+    cv_f32x4 acc[NM][ROWS];
+    cvh_block<CT, FT, STRIDE, WR, NM, 1>(sm, in, HW, P.Cin, pl, P.w, pair, active, tid, row0, acc);
+    if (active && x < P.Wo) {
+#pragma unroll
+        for (int m = 0; m < NM; ++m)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int ch = 32 * pair + 16 * m + 4 * kq + r;
+                if (ch >= Cout) continue;
+                const float sc = scale[ch], sh = shift[ch];
+#pragma unroll
+                for (int nt = 0; nt < ROWS; ++nt) {
+                    const int y = y0 + row0 + nt;
+                    if (y < P.Ho) {
+                        const int o = ch * HWo + y * P.Wo + x;
+                        float v = add_rn(mul_rn(acc[m][nt][r], sc), sh);
+                        if (P.res)
+                            v = add_rn(v, dl_res_of<MapT>(P.res, P.res_f32, P.res_w, rimg + o,
+                                                          rimg + (size_t)ch * HWr + 2 * y * P.res_w + 2 * x));
+                        cv_store<MapT>(out + o, P.relu ? relu_nan(v) : v);
+                    }
+                }
+            }
+    }
+}
+
 // ---- 1x1 over a virtual concatenation ---------------------------------------------------------------------------------------
 struct DlaSrc {
     const float* p;          // [N, C, Hs, Ws]
@@ -597,6 +692,100 @@ dla_conv1x1_half_kernel(DlaConv1ResArgs P) {
     }
 }
 
+// dla_conv1x1_hs_kernel<CT, ST, MT>: dla_conv1x1_half_kernel's workgroup, K order and k-loop in HALF STORAGE: every source of
+//   this launch is of type ST (fp32, or CT's map type: a lane then loads its eight channels as eight 2-byte values, sixteen
+//   consecutive positions of a lane group are 32 bytes per channel), widened in registers — exact — and rounded to CT as the
+//   half kernel rounds, which gives the stored bits back; the residual is fp32 or of the map type (a wave-uniform switch in
+//   the epilogue); the output is stored rounded once to CT and no fp32 copy exists.  No LDS.
+struct DlaConv1HsArgs {
+    DlaSrc src[DL_MAX_SRC_RES];   // (p: of the launch's source type ST)
+    const float* a;          // the convolution's kind-6 packed image
+    void* out;               // [N, Cout, H, W] of the map type
+    const void* res;         // as DlaConv1ResArgs', of fp32 (res_f32) or the map type
+    int nsrc, K, Cout, H, W, tiles_per_image, relu, res_h, res_w, res_f32;
+};
+
+template <int CT, typename ST, int MT>
+__global__ void __launch_bounds__(256, 2)
+dla_conv1x1_hs_kernel(DlaConv1HsArgs P) {
+    using MapT = typename DlMapOf<CT>::type;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int kq = lane >> 4, xl = lane & 15;
+    const int Cout = P.Cout, HW = P.H * P.W;
+    const int n = blockIdx.x / P.tiles_per_image;
+    const int tile = blockIdx.x - n * P.tiles_per_image;
+    const int p = tile * DL_POS + wave * 16 + xl;
+    const bool live = p < HW;
+    const int y = live ? p / P.W : 0, x = live ? p - y * P.W : 0;
+    const int ng = P.K >> 5;
+    const float* __restrict__ scale = P.a + (size_t)Cout * P.K / 2;
+    const float* __restrict__ shift = scale + Cout;
+    const int m0 = blockIdx.y * MT;
+    const int nm = min(MT, (Cout >> 4) - m0);                   // (block-uniform) the M-tiles this block has
+    const cvs_u32x4* __restrict__ ap = reinterpret_cast<const cvs_u32x4*>(P.a) + (size_t)m0 * ng * 64 + lane;
+    cv_f32x4 acc[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) acc[m] = (cv_f32x4){0.f, 0.f, 0.f, 0.f};
+    cvs_u32x4 an[MT], ac[MT], bc;
+    float bn[8];
+    int g0 = 0;
+    auto source = [&](const float* sp, int sC, int spool, int sHs, int sWs) {
+        const int sg = sC >> 5;
+        const int HWs = spool ? sHs * sWs : HW;
+        const ST* bp = reinterpret_cast<const ST*>(sp) + ((size_t)n * sC + 8 * kq) * HWs + (spool ? (2 * y) * sWs + 2 * x : p);
+        auto fetch = [&](int gl) {
+#pragma unroll
+            for (int m = 0; m < MT; ++m)
+                if (m < nm) an[m] = ap[((size_t)m * ng + g0 + gl) * 64];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                float v = 0.0f;
+                if (live) {
+                    const ST* q = bp + (size_t)(32 * gl + j) * HWs;
+                    v = spool ? dl_pool_of<ST>(q, sWs) : feat_ld<ST>(q);
+                }
+                bn[j] = v;
+            }
+        };
+        fetch(0);
+#pragma unroll 1
+        for (int gl = 0; gl < sg; ++gl) {
+#pragma unroll
+            for (int m = 0; m < MT; ++m) ac[m] = an[m];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) bc[e] = cvh_pack2<CT>(bn[2 * e], bn[2 * e + 1]);
+            if (gl + 1 < sg) fetch(gl + 1);
+#pragma unroll
+            for (int m = 0; m < MT; ++m)
+                if (m < nm) acc[m] = cvh_mfma<CT>(ac[m], bc, acc[m]);
+        }
+        g0 += sg;
+    };
+#pragma unroll
+    for (int s = 0; s < DL_MAX_SRC_RES; ++s)
+        if (s < P.nsrc) source(P.src[s].p, P.src[s].C, P.src[s].pooled, P.src[s].Hs, P.src[s].Ws);
+    if (live) {
+        MapT* __restrict__ oimg = reinterpret_cast<MapT*>(P.out) + (size_t)n * Cout * HW;
+        const int HWr = P.res_w ? P.res_h * P.res_w : HW;
+        const size_t r0 = (size_t)n * Cout * HWr;               // the image's first residual element
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            if (m >= nm) continue;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int ch = 16 * (m0 + m) + 4 * kq + r;
+                float v = add_rn(mul_rn(acc[m][r], scale[ch]), shift[ch]);
+                if (P.res)
+                    v = add_rn(v, dl_res_of<MapT>(P.res, P.res_f32, P.res_w, r0 + (size_t)ch * HWr + p,
+                                                  r0 + (size_t)ch * HWr + 2 * y * P.res_w + 2 * x));
+                if (P.relu) v = relu_nan(v);
+                cv_store<MapT>(oimg + (size_t)ch * HW + p, v);
+            }
+        }
+    }
+}
+
 // ---- 7x7 (base_layer) -------------------------------------------------------------------------------------------------------
 struct DlaConv7Args {
     const void* in;          // [N, 3, H, W] of FT
@@ -791,6 +980,55 @@ static int dl_conv3(const float* in, int N, int Cin, int H, int W, const float* 
     return stride == 2 ? dl_conv3_pick<float, 2>(P, grid, st) : dl_conv3_pick<float, 1>(P, grid, st);
 }
 
+// Half storage: the half mode's wave split by the same rule, so a shape runs the same (WR, NM) and sum order
+template <int CT, typename FT, int STRIDE>
+static int dl_conv3_pick_hs(const DlaConv3HsArgs& P, int grid, hipStream_t st) {
+    const int npairs = (P.Cout + 31) >> 5;
+    const int wr = dl_conv3_wr(STRIDE, P.Cout, grid);
+    const dim3 g(grid, (npairs + 4 / wr - 1) / (4 / wr));
+    if (P.Cout <= 16) {
+        SMOT_LAUNCH((dla_conv3x3_hs_kernel<CT, FT, STRIDE, 4, 1>), g, dim3(256), 0, st, P);
+    } else if (wr == 4) {
+        SMOT_LAUNCH((dla_conv3x3_hs_kernel<CT, FT, STRIDE, 4, 2>), g, dim3(256), 0, st, P);
+    } else if (wr == 2) {
+        SMOT_LAUNCH((dla_conv3x3_hs_kernel<CT, FT, STRIDE, 2, 2>), g, dim3(256), 0, st, P);
+    } else {
+        if constexpr (STRIDE == 1) SMOT_LAUNCH((dla_conv3x3_hs_kernel<CT, FT, 1, 1, 2>), g, dim3(256), 0, st, P);
+    }
+    return check_launch("dla_conv3x3_hs");
+}
+template <int CT>
+static int dl_conv3_hs_of(const DlaConv3HsArgs& P, int in_type, int stride, int grid, hipStream_t st) {
+    using MapT = typename DlMapOf<CT>::type;
+    if (in_type == SMOT_FEAT_F32)
+        return stride == 2 ? dl_conv3_pick_hs<CT, float, 2>(P, grid, st) : dl_conv3_pick_hs<CT, float, 1>(P, grid, st);
+    return stride == 2 ? dl_conv3_pick_hs<CT, MapT, 2>(P, grid, st) : dl_conv3_pick_hs<CT, MapT, 1>(P, grid, st);
+}
+// dl_conv3 in half storage: in of in_type, res of res_type (each fp32 or ctype), out of ctype; w a kind-5 image of ctype
+static int dl_conv3_hs(const void* in, int in_type, int N, int Cin, int H, int W, const float* w, int Cout, int stride,
+                       const void* res, int res_type, int relu, void* out, hipStream_t st, int res_h, int res_w, int ctype) {
+    DlaConv3HsArgs P = {};
+    P.in = in;
+    P.w = w;
+    P.res = res;
+    P.out = out;
+    P.Cin = Cin;
+    P.Cout = Cout;
+    P.H = H;
+    P.W = W;
+    P.Ho = stride == 2 ? (H - 1) / 2 + 1 : H;
+    P.Wo = stride == 2 ? (W - 1) / 2 + 1 : W;
+    P.tiles_x = (P.Wo + CV_TW - 1) / CV_TW;
+    P.tiles_per_image = P.tiles_x * ((P.Ho + CV_TH - 1) / CV_TH);
+    P.relu = relu;
+    P.res_h = res ? res_h : 0;
+    P.res_w = res ? res_w : 0;
+    P.res_f32 = res_type == SMOT_FEAT_F32 ? 1 : 0;
+    const int grid = P.tiles_per_image * N;
+    if (ctype == SMOT_FEAT_F16) return dl_conv3_hs_of<SMOT_FEAT_F16>(P, in_type, stride, grid, st);
+    return dl_conv3_hs_of<SMOT_FEAT_BF16>(P, in_type, stride, grid, st);
+}
+
 template <typename OT>
 static int dl_conv1_launch(const DlaConv1Args& P, int grid, hipStream_t st) {
     SMOT_LAUNCH(dla_conv1x1_kernel<OT>, dim3(grid, (P.Cout >> 4) / DL_MT), dim3(256), 0, st, P);
@@ -905,6 +1143,48 @@ static int dl_conv1_half(const DlaSrc* src, int nsrc, int N, int H, int W, const
     return dl_conv1_half_launch<SMOT_FEAT_BF16, bf16_t>(P, grid, st);
 }
 
+// Half storage: the half mode's M-tiles per workgroup by the same rule (dl_conv1_half_mt)
+template <int CT, typename ST>
+static int dl_conv1_hs_launch(const DlaConv1HsArgs& P, int grid, hipStream_t st) {
+    const int mt = P.Cout >> 4;
+    if (dl_conv1_half_mt(P.Cout, grid) == 4) {
+        SMOT_LAUNCH((dla_conv1x1_hs_kernel<CT, ST, 4>), dim3(grid, (mt + 3) / 4), dim3(256), 0, st, P);
+    } else {
+        SMOT_LAUNCH((dla_conv1x1_hs_kernel<CT, ST, 2>), dim3(grid, (mt + 1) / 2), dim3(256), 0, st, P);
+    }
+    return check_launch("dla_conv1x1_hs");
+}
+// dl_conv1_half in half storage: every source of src_type, res of res_type (each fp32 or ctype), out of ctype
+static int dl_conv1_hs(const DlaSrc* src, int nsrc, int src_type, int N, int H, int W, const float* a, int Cout, int relu,
+                       void* out, hipStream_t st, const void* res, int res_type, int res_h, int res_w, int ctype) {
+    DlaConv1HsArgs P = {};
+    int K = 0;
+    for (int s = 0; s < nsrc; ++s) {
+        P.src[s] = src[s];
+        K += src[s].C;
+    }
+    P.a = a;
+    P.out = out;
+    P.res = res;
+    P.nsrc = nsrc;
+    P.K = K;
+    P.Cout = Cout;
+    P.H = H;
+    P.W = W;
+    P.tiles_per_image = (int)(((long long)H * W + DL_POS - 1) / DL_POS);
+    P.relu = relu;
+    P.res_h = res ? res_h : 0;
+    P.res_w = res ? res_w : 0;
+    P.res_f32 = res_type == SMOT_FEAT_F32 ? 1 : 0;
+    const int grid = P.tiles_per_image * N;
+    if (ctype == SMOT_FEAT_F16) {
+        if (src_type == SMOT_FEAT_F32) return dl_conv1_hs_launch<SMOT_FEAT_F16, float>(P, grid, st);
+        return dl_conv1_hs_launch<SMOT_FEAT_F16, f16_t>(P, grid, st);
+    }
+    if (src_type == SMOT_FEAT_F32) return dl_conv1_hs_launch<SMOT_FEAT_BF16, float>(P, grid, st);
+    return dl_conv1_hs_launch<SMOT_FEAT_BF16, bf16_t>(P, grid, st);
+}
+
 static int dl_conv7(const void* image, int in_type, int N, int H, int W, const float* a, int C0, float* out, hipStream_t st) {
     DlaConv7Args P = {};
     P.in = image;
@@ -1016,6 +1296,7 @@ struct DlaCtx {
     int N, rc;
     hipStream_t st;
     int block, rroot;        // dn_walk's: the block type (SMOT_DLA_BLOCK_*) and "every root adds its first source"
+    int mt;                  // dn_walk's: the element type of the TREE maps: SMOT_FEAT_F32 (= 0), or the compute type in half storage
 };
 static float* dl_alloc(DlaCtx& c, long long floats) {
     float* p = c.dry ? nullptr : c.ws + c.bump;
@@ -1023,26 +1304,41 @@ static float* dl_alloc(DlaCtx& c, long long floats) {
     if (c.bump > c.peak) c.peak = c.bump;
     return p;
 }
+static int dl_type_bytes(int type) { return type == SMOT_FEAT_F32 ? 4 : 2; }
+// a tree map of `elems` elements of c.mt: carved in bytes of that type, in units of 16 bytes (fp32 maps: dl_alloc's answer)
+static void* dl_alloc_map(DlaCtx& c, long long elems) {
+    return dl_alloc(c, (elems * dl_type_bytes(c.mt) + 3) / 4);
+}
 static const float* dl_next(DlaCtx& c, int kind, int cin, int cout) {
     const DlaConv& v = c.net->conv[c.ci++];
     if (v.kind != kind || v.cin != cin || v.cout != cout) c.rc = SMOT_ERR_BAD_ARG;      // (the two walks disagree: a bug)
     return c.dry ? nullptr : c.packed + v.off;
 }
-static void dl_run3(DlaCtx& c, int kind, const float* in, int Cin, int H, int W, int Cout, int stride, const float* res,
-                    float* out, int res_h = 0, int res_w = 0) {
+// in_type, res_type: read in half storage (c.mt != SMOT_FEAT_F32) only, where a tree convolution's input and residual are
+// of fp32 (x1) or of c.mt and its output is of c.mt; everywhere else every map is fp32
+static void dl_run3(DlaCtx& c, int kind, const void* in, int Cin, int H, int W, int Cout, int stride, const void* res,
+                    void* out, int res_h = 0, int res_w = 0, int in_type = SMOT_FEAT_F32, int res_type = SMOT_FEAT_F32) {
     const float* w = dl_next(c, kind, Cin, Cout);
-    if (!c.dry && !c.rc)
-        c.rc = dl_conv3(in, c.N, Cin, H, W, w, Cout, stride, res, 1, out, c.st, res_h, res_w, kind == 4, kind == 5 ? c.net->ctype : 0);
+    if (c.dry || c.rc) return;
+    if (kind == 5 && c.mt != SMOT_FEAT_F32)
+        c.rc = dl_conv3_hs(in, in_type, c.N, Cin, H, W, w, Cout, stride, res, res_type, 1, out, c.st, res_h, res_w, c.net->ctype);
+    else
+        c.rc = dl_conv3((const float*)in, c.N, Cin, H, W, w, Cout, stride, (const float*)res, 1, (float*)out, c.st, res_h, res_w,
+                        kind == 4, kind == 5 ? c.net->ctype : 0);
 }
+// (half storage: out_type and out32 are not read: the output is of c.mt; src_type: the type of every source)
 static void dl_run1(DlaCtx& c, const DlaSrc* src, int nsrc, int H, int W, int Cout, int relu, void* out, int out_type, float* out32,
-                    const float* res = nullptr, int res_h = 0, int res_w = 0) {
+                    const void* res = nullptr, int res_h = 0, int res_w = 0, int src_type = SMOT_FEAT_F32,
+                    int res_type = SMOT_FEAT_F32) {
     int K = 0;
     for (int s = 0; s < nsrc; ++s) K += src[s].C;
     const int k1 = c.net->k1;
     const float* a = dl_next(c, k1, K, Cout);
     if (c.dry || c.rc) return;
-    if (k1 == 6) c.rc = dl_conv1_half(src, nsrc, c.N, H, W, a, Cout, relu, out, out_type, out32, c.st, res, res_h, res_w, c.net->ctype);
-    else c.rc = dl_conv1(src, nsrc, c.N, H, W, a, Cout, relu, out, out_type, out32, c.st, res, res_h, res_w);
+    if (k1 == 6 && c.mt != SMOT_FEAT_F32)
+        c.rc = dl_conv1_hs(src, nsrc, src_type, c.N, H, W, a, Cout, relu, out, c.st, res, res_type, res_h, res_w, c.net->ctype);
+    else if (k1 == 6) c.rc = dl_conv1_half(src, nsrc, c.N, H, W, a, Cout, relu, out, out_type, out32, c.st, (const float*)res, res_h, res_w, c.net->ctype);
+    else c.rc = dl_conv1(src, nsrc, c.N, H, W, a, Cout, relu, out, out_type, out32, c.st, (const float*)res, res_h, res_w);
 }
 
 // A levels = 1 tree on x [N, cin, H, W] -> [N, cout, Ho, Wo] at `out` (of out_type; fp32 at out32 as well if non-null), or in
@@ -1192,22 +1488,24 @@ static int dn_net(const int* levels, const int* ch, int block, DlaNet& net, cons
 // One block on x [N, cin, H, W] -> out [N, cout, H / stride, W / stride] fp32, + res (res_w != 0: through the pool) before the
 // last ReLU.  Its intermediate maps are released when it returns (every launch is on one stream: a later launch that reuses
 // the memory runs after the ones that read it).
-static void dn_block(DlaCtx& c, const float* x, int cin, int H, int W, int cout, int stride, const float* res, int res_h, int res_w,
-                     float* out) {
+// The maps are of c.mt (fp32 outside half storage); x and res are of x_type and res_type: c.mt, or fp32 where they are the
+// stem's x1.  (A DlaSrc carries its map as `const float*` whatever the type: the launch knows the type of its sources.)
+static void dn_block(DlaCtx& c, const void* x, int x_type, int cin, int H, int W, int cout, int stride, const void* res, int res_type,
+                     int res_h, int res_w, void* out) {
     const int Ho = H / stride, Wo = W / stride, k3 = c.net->k3;
     const long long mark = c.bump;
     if (c.block == SMOT_DLA_BLOCK_BOTTLENECK) {      // conv1 at the input's resolution, the stride on the 3x3, as upstream
         const int mid = cout / 2;
-        float* m1 = dl_alloc(c, (long long)c.N * mid * H * W);
-        float* m2 = dl_alloc(c, (long long)c.N * mid * Ho * Wo);
-        const DlaSrc s1 = {x, cin, 0, H, W}, s3 = {m2, mid, 0, Ho, Wo};
-        dl_run1(c, &s1, 1, H, W, mid, 1, m1, SMOT_FEAT_F32, nullptr);
-        dl_run3(c, k3, m1, mid, H, W, mid, stride, nullptr, m2);
-        dl_run1(c, &s3, 1, Ho, Wo, cout, 1, out, SMOT_FEAT_F32, nullptr, res, res_h, res_w);
+        void* m1 = dl_alloc_map(c, (long long)c.N * mid * H * W);
+        void* m2 = dl_alloc_map(c, (long long)c.N * mid * Ho * Wo);
+        const DlaSrc s1 = {(const float*)x, cin, 0, H, W}, s3 = {(const float*)m2, mid, 0, Ho, Wo};
+        dl_run1(c, &s1, 1, H, W, mid, 1, m1, SMOT_FEAT_F32, nullptr, nullptr, 0, 0, x_type);
+        dl_run3(c, k3, m1, mid, H, W, mid, stride, nullptr, m2, 0, 0, c.mt);
+        dl_run1(c, &s3, 1, Ho, Wo, cout, 1, out, SMOT_FEAT_F32, nullptr, res, res_h, res_w, c.mt, res_type);
     } else {
-        float* t = dl_alloc(c, (long long)c.N * cout * Ho * Wo);
-        dl_run3(c, k3, x, cin, H, W, cout, stride, nullptr, t);
-        dl_run3(c, k3, t, cout, Ho, Wo, cout, 1, res, out, res_h, res_w);
+        void* t = dl_alloc_map(c, (long long)c.N * cout * Ho * Wo);
+        dl_run3(c, k3, x, cin, H, W, cout, stride, nullptr, t, 0, 0, x_type);
+        dl_run3(c, k3, t, cout, Ho, Wo, cout, 1, res, out, res_h, res_w, c.mt, res_type);
     }
     c.bump = mark;
 }
@@ -1221,40 +1519,44 @@ struct DlaDst {
 // tree(depth) on x [N, cin, H, W] -> dst, which the caller owns.  handed: what the parent handed down.  Everything the
 // subtree allocates is released when its root has been written: a depth-n tree holds n - 1 tree1 results, one depth-1
 // tree's maps (project, x1, x2) and one block's intermediates at a time, whatever the number of blocks.
-static void dn_tree(DlaCtx& c, int depth, const float* x, int cin, int H, int W, int cout, int stride, bool level_root,
+// x is of x_type: c.mt, or fp32 for the stem's x1 under level 2 (which has no level_root: x1 joins no root, so every source of
+// a root is of c.mt; x1 is read alone by a project and by tree1's first convolution, and added as a residual where cin == cout).
+static void dn_tree(DlaCtx& c, int depth, const void* x, int x_type, int cin, int H, int W, int cout, int stride, bool level_root,
                     const DlaSrc* handed, int nhanded, const DlaDst& dst) {
     const int Ho = H / stride, Wo = W / stride;
     const long long on = (long long)c.N * cout * Ho * Wo, mark = c.bump;
-    const DlaSrc bottom = {x, cin, stride == 2 ? 1 : 0, H, W};
+    const DlaSrc bottom = {(const float*)x, cin, stride == 2 ? 1 : 0, H, W};
     DlaSrc src[DL_MAX_SRC_RES];
     int ns = 0;
     if (depth > 1) {
-        float* t = dl_alloc(c, on);
-        dn_tree(c, depth - 1, x, cin, H, W, cout, stride, false, nullptr, 0, DlaDst{t, SMOT_FEAT_F32, nullptr});
+        void* t = dl_alloc_map(c, on);
+        dn_tree(c, depth - 1, x, x_type, cin, H, W, cout, stride, false, nullptr, 0, DlaDst{t, SMOT_FEAT_F32, nullptr});
         if (level_root) src[ns++] = bottom;
         for (int e = 0; e < nhanded; ++e) src[ns++] = handed[e];
-        src[ns++] = DlaSrc{t, cout, 0, Ho, Wo};
-        dn_tree(c, depth - 1, t, cout, Ho, Wo, cout, 1, false, src, ns, dst);
+        src[ns++] = DlaSrc{(const float*)t, cout, 0, Ho, Wo};
+        dn_tree(c, depth - 1, t, c.mt, cout, Ho, Wo, cout, 1, false, src, ns, dst);
         c.bump = mark;
         return;
     }
-    const float* residual = x;
+    const void* residual = x;
+    int res_type = x_type;
     if (cin != cout) {
-        float* r = dl_alloc(c, on);
-        dl_run1(c, &bottom, 1, Ho, Wo, cout, 0, r, SMOT_FEAT_F32, nullptr);
+        void* r = dl_alloc_map(c, on);
+        dl_run1(c, &bottom, 1, Ho, Wo, cout, 0, r, SMOT_FEAT_F32, nullptr, nullptr, 0, 0, x_type);
         residual = r;
+        res_type = c.mt;
     }
     // (cin == cout at stride 2: the residual is the pooled input itself, read through the pool)
     const bool rpool = cin == cout && stride == 2;
-    float* x1 = dl_alloc(c, on);
-    float* x2 = dl_alloc(c, on);
-    dn_block(c, x, cin, H, W, cout, stride, residual, rpool ? H : 0, rpool ? W : 0, x1);
-    dn_block(c, x1, cout, Ho, Wo, cout, 1, x1, 0, 0, x2);
-    src[ns++] = DlaSrc{x2, cout, 0, Ho, Wo};
-    src[ns++] = DlaSrc{x1, cout, 0, Ho, Wo};
+    void* x1 = dl_alloc_map(c, on);
+    void* x2 = dl_alloc_map(c, on);
+    dn_block(c, x, x_type, cin, H, W, cout, stride, residual, res_type, rpool ? H : 0, rpool ? W : 0, x1);
+    dn_block(c, x1, c.mt, cout, Ho, Wo, cout, 1, x1, c.mt, 0, 0, x2);
+    src[ns++] = DlaSrc{(const float*)x2, cout, 0, Ho, Wo};
+    src[ns++] = DlaSrc{(const float*)x1, cout, 0, Ho, Wo};
     if (level_root) src[ns++] = bottom;
     for (int e = 0; e < nhanded; ++e) src[ns++] = handed[e];
-    dl_run1(c, src, ns, Ho, Wo, cout, 1, dst.out, dst.out_type, dst.out32, c.rroot ? x2 : nullptr);
+    dl_run1(c, src, ns, Ho, Wo, cout, 1, dst.out, dst.out_type, dst.out32, c.rroot ? x2 : nullptr, 0, 0, c.mt, c.mt);
     c.bump = mark;
 }
 
@@ -1264,22 +1566,28 @@ static void dn_walk(DlaCtx& c, const void* image, int in_type, int H, int W, con
     float* x1 = dl_alloc(c, (long long)c.N * ch[1] * (H / 2) * (W / 2));
     long long mark = c.bump;
     dl_stem(c, image, in_type, H, W, ch[0], ch[1], x1);
-    const float* x = x1;
+    const void* x = x1;
+    int x_type = SMOT_FEAT_F32;
+    const bool hs = c.mt != SMOT_FEAT_F32;                       // half storage: out_type is c.mt and the next level reads the
+                                                                 // returned map itself: no fp32 twin exists
     int h = H / 2, w = W / 2;
     for (int k = 2; k < 6; ++k) {
         c.bump = mark;
         const int cout = ch[k], ho = h / 2, wo = w / 2;
-        float* out32 = (out_type != SMOT_FEAT_F32 && k < 5) ? dl_alloc(c, (long long)c.N * cout * ho * wo) : nullptr;
+        float* out32 = (!hs && out_type != SMOT_FEAT_F32 && k < 5) ? dl_alloc(c, (long long)c.N * cout * ho * wo) : nullptr;
         mark = c.bump;
         void* o = c.dry ? nullptr : out[k - 2];
-        dn_tree(c, levels[k], x, ch[k - 1], h, w, cout, 2, k > 2, nullptr, 0, DlaDst{o, out_type, out32});
-        x = out_type == SMOT_FEAT_F32 ? (const float*)o : out32;
+        dn_tree(c, levels[k], x, x_type, ch[k - 1], h, w, cout, 2, k > 2, nullptr, 0, DlaDst{o, out_type, out32});
+        x = hs || out_type == SMOT_FEAT_F32 ? (const void*)o : out32;
+        x_type = c.mt;
         h = ho;
         w = wo;
     }
 }
 
 static int dl_f32_ptr(const void* p) { return p && ((uintptr_t)p & 3) == 0; }
+// non-null and aligned for elements of `type` (SMOT_FEAT_*)
+static int dl_map_ptr(const void* p, int type) { return p && ((uintptr_t)p & (type == SMOT_FEAT_F32 ? 3 : 1)) == 0; }
 
 }  // namespace smot
 
@@ -1348,7 +1656,7 @@ extern "C" long long smot_dla_ws_bytes(const int* levels, const int* channels, i
 // described with the code rn
 static int dla_fwd_net(const void* image, int in_type, int num_images, int H, int W, const int* levels, const int* channels,
                        const float* packed, float* ws, void* const* out, int out_type, smot_stream_t stream, const DlaNet& net,
-                       int rn, int block, int residual_root);
+                       int rn, int block, int residual_root, int map_type = SMOT_FEAT_F32);
 static int dla_fwd_impl(const void* image, int in_type, int num_images, int H, int W, const int* levels, const int* channels,
                         const float* packed, float* ws, void* const* out, int out_type, smot_stream_t stream, bool split) {
     DlaNet net;
@@ -1357,7 +1665,7 @@ static int dla_fwd_impl(const void* image, int in_type, int num_images, int H, i
 }
 static int dla_fwd_net(const void* image, int in_type, int num_images, int H, int W, const int* levels, const int* channels,
                        const float* packed, float* ws, void* const* out, int out_type, smot_stream_t stream, const DlaNet& net,
-                       int rn, int block, int residual_root) {
+                       int rn, int block, int residual_root, int map_type) {
     SMOT_REQUIRE(in_type == SMOT_FEAT_F32 || in_type == SMOT_FEAT_F16 || in_type == SMOT_FEAT_BF16,
                  "dla: in_type = %d (SMOT_FEAT_F32, _F16 or _BF16, NCHW)", in_type);
     SMOT_REQUIRE(out_type == SMOT_FEAT_F32 || out_type == SMOT_FEAT_F16 || out_type == SMOT_FEAT_BF16,
@@ -1390,6 +1698,7 @@ static int dla_fwd_net(const void* image, int in_type, int num_images, int H, in
     c.st = (hipStream_t)stream;
     c.block = block;
     c.rroot = residual_root ? 1 : 0;
+    c.mt = map_type;                                 // (half storage: dn_walk alone, and out_type == map_type)
     if (block < 0) dl_walk(c, image, in_type, H, W, levels, channels, out, out_type);
     else dn_walk(c, image, in_type, H, W, levels, channels, out, out_type);
     return c.rc;
@@ -1454,11 +1763,13 @@ extern "C" int smot_dla_net_fwd(const void* image, int in_type, int num_images, 
 }
 
 // ---- the three operators alone -------------------------------------------------------------------------------------------------
-static int dla_conv3x3_impl(const float* x, int num_images, int Cin, int H, int W, const float* w, const float* scale,
-                            const float* shift, int Cout, int stride, const float* residual, int residual_h, int residual_w,
-                            int relu, float* packed, float* out, smot_stream_t stream, bool split, int ctype = 0) {
-    SMOT_REQUIRE(dl_f32_ptr(x) && dl_f32_ptr(w) && dl_f32_ptr(scale) && dl_f32_ptr(shift) && dl_f32_ptr(out) &&
-                     (!residual || dl_f32_ptr(residual)),
+// hs: half storage (ctype != 0): x of in_type, residual of res_type, out of ctype; otherwise all three are fp32
+static int dla_conv3x3_impl(const void* x, int num_images, int Cin, int H, int W, const float* w, const float* scale,
+                            const float* shift, int Cout, int stride, const void* residual, int residual_h, int residual_w,
+                            int relu, float* packed, void* out, smot_stream_t stream, bool split, int ctype = 0, bool hs = false,
+                            int in_type = SMOT_FEAT_F32, int res_type = SMOT_FEAT_F32) {
+    SMOT_REQUIRE(dl_map_ptr(x, in_type) && dl_f32_ptr(w) && dl_f32_ptr(scale) && dl_f32_ptr(shift) &&
+                     dl_map_ptr(out, hs ? ctype : SMOT_FEAT_F32) && (!residual || dl_map_ptr(residual, res_type)),
                  "dla_conv3x3: a null or misaligned pointer");
     SMOT_REQUIRE(packed && ((uintptr_t)packed & 15) == 0, "dla_conv3x3: packed must be 16-byte aligned");
     SMOT_REQUIRE(num_images >= 1 && num_images <= SMOT_MAX_IMAGES && H >= 1 && W >= 1 && (stride == 1 || stride == 2),
@@ -1481,8 +1792,11 @@ static int dla_conv3x3_impl(const float* x, int num_images, int Cin, int H, int 
     hipStream_t st = (hipStream_t)stream;
     const int rp = dl_pack_launch(ctype ? 5 : split ? 4 : 3, w, scale, shift, Cin, Cout, packed, st, ctype);
     if (rp) return rp;
-    return dl_conv3(x, num_images, Cin, H, W, packed, Cout, stride, residual, relu ? 1 : 0, out, st, rpool ? residual_h : 0,
-                    rpool ? residual_w : 0, split, ctype);
+    if (hs)
+        return dl_conv3_hs(x, in_type, num_images, Cin, H, W, packed, Cout, stride, residual, res_type, relu ? 1 : 0, out, st,
+                           rpool ? residual_h : 0, rpool ? residual_w : 0, ctype);
+    return dl_conv3((const float*)x, num_images, Cin, H, W, packed, Cout, stride, (const float*)residual, relu ? 1 : 0, (float*)out,
+                    st, rpool ? residual_h : 0, rpool ? residual_w : 0, split, ctype);
 }
 extern "C" int smot_dla_conv3x3_fwd(const float* x, int num_images, int Cin, int H, int W, const float* w, const float* scale,
                                     const float* shift, int Cout, int stride, const float* residual, int residual_h,
@@ -1526,15 +1840,17 @@ extern "C" long long smot_dla_conv_split_packed_floats(int kernel_size, int Cin,
 
 // max_sources: 4 for smot_dla_conv1x1_fwd (no residual), 8 for smot_dla_conv1x1_res_fwd; ctype != 0: half compute mode (every
 // source a multiple of 32 channels, the kind-6 image, dla_conv1x1_half_kernel)
-static int dla_conv1x1_impl(const float* const* sources, const int* source_channels, const int* source_pooled,
+// hs: half storage (ctype != 0): every source of in_type, residual of res_type, out_type == ctype
+static int dla_conv1x1_impl(const void* const* sources, const int* source_channels, const int* source_pooled,
                             const int* source_heights, const int* source_widths, int num_sources, int max_sources, int num_images,
                             int H, int W, const float* w, const float* scale, const float* shift, int Cout, int relu,
-                            const float* residual, int residual_h, int residual_w, float* packed, void* out, int out_type,
-                            smot_stream_t stream, int ctype = 0) {
+                            const void* residual, int residual_h, int residual_w, float* packed, void* out, int out_type,
+                            smot_stream_t stream, int ctype = 0, bool hs = false, int in_type = SMOT_FEAT_F32,
+                            int res_type = SMOT_FEAT_F32) {
     SMOT_REQUIRE(out_type == SMOT_FEAT_F32 || out_type == SMOT_FEAT_F16 || out_type == SMOT_FEAT_BF16,
                  "dla_conv1x1: out_type = %d (SMOT_FEAT_F32, _F16 or _BF16)", out_type);
     SMOT_REQUIRE(num_sources >= 1 && num_sources <= max_sources, "dla_conv1x1: %d sources (1 .. %d)", num_sources, max_sources);
-    SMOT_REQUIRE(!residual || dl_f32_ptr(residual), "dla_conv1x1: the residual is misaligned");
+    SMOT_REQUIRE(!residual || dl_map_ptr(residual, res_type), "dla_conv1x1: the residual is misaligned");
     const bool rpool = residual && (residual_h != 0 || residual_w != 0);
     SMOT_REQUIRE(!rpool || (residual_h / 2 == H && residual_w / 2 == W),
                  "dla_conv1x1: a pooled residual of %d x %d for an output of %d x %d", residual_h, residual_w, H, W);
@@ -1548,11 +1864,11 @@ static int dla_conv1x1_impl(const float* const* sources, const int* source_chann
     long long K = 0;
     bool ok = Cout >= 32 && Cout % 32 == 0 && Cout <= 1024 && !(rpool && (long long)residual_h * residual_w * Cout >= (1LL << 31));
     for (int s = 0; s < num_sources; ++s) {
-        SMOT_REQUIRE(dl_f32_ptr(sources[s]), "dla_conv1x1: source %d is null or misaligned", s);
-        const int pooled = source_pooled[s] ? 1 : 0, hs = source_heights[s], wsrc = source_widths[s];
-        SMOT_REQUIRE(pooled ? (hs / 2 == H && wsrc / 2 == W) : (hs == H && wsrc == W),
-                     "dla_conv1x1: source %d is %d x %d for an output of %d x %d (pooled: %d)", s, hs, wsrc, H, W, pooled);
-        src[s] = DlaSrc{sources[s], source_channels[s], pooled, hs, wsrc};
+        SMOT_REQUIRE(dl_map_ptr(sources[s], in_type), "dla_conv1x1: source %d is null or misaligned", s);
+        const int pooled = source_pooled[s] ? 1 : 0, hsrc = source_heights[s], wsrc = source_widths[s];
+        SMOT_REQUIRE(pooled ? (hsrc / 2 == H && wsrc / 2 == W) : (hsrc == H && wsrc == W),
+                     "dla_conv1x1: source %d is %d x %d for an output of %d x %d (pooled: %d)", s, hsrc, wsrc, H, W, pooled);
+        src[s] = DlaSrc{(const float*)sources[s], source_channels[s], pooled, hsrc, wsrc};
         ok = ok && source_channels[s] >= 16 && source_channels[s] % 16 == 0 && source_channels[s] <= 1024;
         K += source_channels[s] > 0 ? source_channels[s] : 0;
         if (ctype && source_channels[s] % 32 != 0) {
@@ -1560,7 +1876,7 @@ static int dla_conv1x1_impl(const float* const* sources, const int* source_chann
                       "of the 16-bit matrix instruction is 32 channels of one source)", s, source_channels[s]);
             return SMOT_ERR_UNSUPPORTED;
         }
-        if ((long long)hs * wsrc * (source_channels[s] > 0 ? source_channels[s] : 1) >= (1LL << 31)) ok = false;
+        if ((long long)hsrc * wsrc * (source_channels[s] > 0 ? source_channels[s] : 1) >= (1LL << 31)) ok = false;
     }
     if (!ok || (long long)H * W * Cout >= (1LL << 31) || (long long)H * W / 64 * num_images >= (1LL << 31)) {
         set_error("dla_conv1x1: Cout = %d over %lld concatenated channels (supported: Cout a multiple of 32 up to 1024, every source a "
@@ -1570,17 +1886,20 @@ static int dla_conv1x1_impl(const float* const* sources, const int* source_chann
     hipStream_t st = (hipStream_t)stream;
     const int rp = dl_pack_launch(ctype ? 6 : 1, w, scale, shift, (int)K, Cout, packed, st, ctype);
     if (rp) return rp;
+    if (hs)
+        return dl_conv1_hs(src, num_sources, in_type, num_images, H, W, packed, Cout, relu ? 1 : 0, out, st, residual, res_type,
+                           rpool ? residual_h : 0, rpool ? residual_w : 0, ctype);
     if (ctype)
-        return dl_conv1_half(src, num_sources, num_images, H, W, packed, Cout, relu ? 1 : 0, out, out_type, nullptr, st, residual,
-                             rpool ? residual_h : 0, rpool ? residual_w : 0, ctype);
-    return dl_conv1(src, num_sources, num_images, H, W, packed, Cout, relu ? 1 : 0, out, out_type, nullptr, st, residual,
-                    rpool ? residual_h : 0, rpool ? residual_w : 0);
+        return dl_conv1_half(src, num_sources, num_images, H, W, packed, Cout, relu ? 1 : 0, out, out_type, nullptr, st,
+                             (const float*)residual, rpool ? residual_h : 0, rpool ? residual_w : 0, ctype);
+    return dl_conv1(src, num_sources, num_images, H, W, packed, Cout, relu ? 1 : 0, out, out_type, nullptr, st,
+                    (const float*)residual, rpool ? residual_h : 0, rpool ? residual_w : 0);
 }
 extern "C" int smot_dla_conv1x1_fwd(const float* const* sources, const int* source_channels, const int* source_pooled,
                                     const int* source_heights, const int* source_widths, int num_sources, int num_images, int H,
                                     int W, const float* w, const float* scale, const float* shift, int Cout, int relu,
                                     float* packed, void* out, int out_type, smot_stream_t stream) {
-    return dla_conv1x1_impl(sources, source_channels, source_pooled, source_heights, source_widths, num_sources, DL_MAX_SRC,
+    return dla_conv1x1_impl((const void* const*)sources, source_channels, source_pooled, source_heights, source_widths, num_sources, DL_MAX_SRC,
                             num_images, H, W, w, scale, shift, Cout, relu, nullptr, 0, 0, packed, out, out_type, stream);
 }
 extern "C" int smot_dla_conv1x1_res_fwd(const float* const* sources, const int* source_channels, const int* source_pooled,
@@ -1588,7 +1907,7 @@ extern "C" int smot_dla_conv1x1_res_fwd(const float* const* sources, const int* 
                                         int H, int W, const float* w, const float* scale, const float* shift, int Cout, int relu,
                                         const float* residual, int residual_h, int residual_w, float* packed, void* out,
                                         int out_type, smot_stream_t stream) {
-    return dla_conv1x1_impl(sources, source_channels, source_pooled, source_heights, source_widths, num_sources, DL_MAX_SRC_RES,
+    return dla_conv1x1_impl((const void* const*)sources, source_channels, source_pooled, source_heights, source_widths, num_sources, DL_MAX_SRC_RES,
                             num_images, H, W, w, scale, shift, Cout, relu, residual, residual_h, residual_w, packed, out, out_type,
                             stream);
 }
@@ -1661,9 +1980,73 @@ extern "C" int smot_dla_conv1x1_half_fwd(const float* const* sources, const int*
                                          const float* residual, int residual_h, int residual_w, int compute_type, float* packed,
                                          void* out, int out_type, smot_stream_t stream) {
     SMOT_REQUIRE(dl_ctype_ok(compute_type), "dla_conv1x1_half: compute_type = %d (SMOT_FEAT_F16 or SMOT_FEAT_BF16)", compute_type);
-    return dla_conv1x1_impl(sources, source_channels, source_pooled, source_heights, source_widths, num_sources, DL_MAX_SRC_RES,
+    return dla_conv1x1_impl((const void* const*)sources, source_channels, source_pooled, source_heights, source_widths, num_sources, DL_MAX_SRC_RES,
                             num_images, H, W, w, scale, shift, Cout, relu, residual, residual_h, residual_w, packed, out, out_type,
                             stream, compute_type);
+}
+
+// ---- half storage (include/smot_emm.h, DLA BACKBONE, HALF STORAGE) ---------------------------------------------------------------
+// fp32 or the compute type
+static bool dl_hs_type_ok(int t, int ctype) { return t == SMOT_FEAT_F32 || t == ctype; }
+
+extern "C" long long smot_dla_half_storage_ws_bytes(const int* levels, const int* channels, int block, int residual_root,
+                                                    int compute_type, int num_images, int H, int W) {
+    if (!dl_ctype_ok(compute_type)) {
+        set_error("dla_half_storage_ws_bytes: compute_type = %d (SMOT_FEAT_F16 or SMOT_FEAT_BF16)", compute_type);
+        return -1;
+    }
+    DlaNet net;
+    if (dn_net(levels, channels, block, net, "dla_half_storage_ws_bytes", false, compute_type) ||
+        dla_size_ok(num_images, H, W, "dla_half_storage_ws_bytes"))
+        return -1;
+    DlaCtx c = {};
+    c.net = &net;
+    c.dry = true;
+    c.N = num_images;
+    c.block = block;
+    c.rroot = residual_root ? 1 : 0;
+    c.mt = compute_type;
+    dn_walk(c, nullptr, SMOT_FEAT_F32, H, W, levels, channels, nullptr, compute_type);
+    return c.rc ? -1 : c.peak * (long long)sizeof(float);
+}
+
+extern "C" int smot_dla_half_storage_fwd(const void* image, int in_type, int num_images, int H, int W, const int* levels,
+                                         const int* channels, int block, int residual_root, int compute_type, const float* packed,
+                                         float* ws, void* const* out, smot_stream_t stream) {
+    SMOT_REQUIRE(dl_ctype_ok(compute_type), "dla_half_storage: compute_type = %d (SMOT_FEAT_F16 or SMOT_FEAT_BF16)", compute_type);
+    DlaNet net;
+    const int rn = dn_net(levels, channels, block, net, "dla_half_storage", false, compute_type);
+    return dla_fwd_net(image, in_type, num_images, H, W, levels, channels, packed, ws, out, compute_type, stream, net, rn,
+                       rn == SMOT_ERR_BAD_ARG ? 0 : block, residual_root, compute_type);
+}
+
+extern "C" int smot_dla_conv3x3_half_storage_fwd(const void* x, int in_type, int num_images, int Cin, int H, int W, const float* w,
+                                                 const float* scale, const float* shift, int Cout, int stride,
+                                                 const void* residual, int res_type, int residual_h, int residual_w, int relu,
+                                                 int compute_type, float* packed, void* out, smot_stream_t stream) {
+    SMOT_REQUIRE(dl_ctype_ok(compute_type), "dla_conv3x3_half_storage: compute_type = %d (SMOT_FEAT_F16 or SMOT_FEAT_BF16)",
+                 compute_type);
+    SMOT_REQUIRE(dl_hs_type_ok(in_type, compute_type) && (!residual || dl_hs_type_ok(res_type, compute_type)),
+                 "dla_conv3x3_half_storage: in_type = %d, res_type = %d (each SMOT_FEAT_F32 or the compute type %d)", in_type,
+                 res_type, compute_type);
+    return dla_conv3x3_impl(x, num_images, Cin, H, W, w, scale, shift, Cout, stride, residual, residual_h, residual_w, relu, packed,
+                            out, stream, false, compute_type, true, in_type, residual ? res_type : SMOT_FEAT_F32);
+}
+
+extern "C" int smot_dla_conv1x1_half_storage_fwd(const void* const* sources, int in_type, const int* source_channels,
+                                                 const int* source_pooled, const int* source_heights, const int* source_widths,
+                                                 int num_sources, int num_images, int H, int W, const float* w, const float* scale,
+                                                 const float* shift, int Cout, int relu, const void* residual, int res_type,
+                                                 int residual_h, int residual_w, int compute_type, float* packed, void* out,
+                                                 smot_stream_t stream) {
+    SMOT_REQUIRE(dl_ctype_ok(compute_type), "dla_conv1x1_half_storage: compute_type = %d (SMOT_FEAT_F16 or SMOT_FEAT_BF16)",
+                 compute_type);
+    SMOT_REQUIRE(dl_hs_type_ok(in_type, compute_type) && (!residual || dl_hs_type_ok(res_type, compute_type)),
+                 "dla_conv1x1_half_storage: in_type = %d, res_type = %d (each SMOT_FEAT_F32 or the compute type %d)", in_type,
+                 res_type, compute_type);
+    return dla_conv1x1_impl(sources, source_channels, source_pooled, source_heights, source_widths, num_sources, DL_MAX_SRC_RES,
+                            num_images, H, W, w, scale, shift, Cout, relu, residual, residual_h, residual_w, packed, out,
+                            compute_type, stream, compute_type, true, in_type, residual ? res_type : SMOT_FEAT_F32);
 }
 
 extern "C" long long smot_dla_stem_ws_bytes(int num_images, int H, int W, int c0, int c1) {

@@ -122,7 +122,7 @@ class DetectionHead(torch.nn.Module):
 
 
 def build_detection_head(cfg, rpn_box_coder, in_channels, box_head=None, rpn_head=True, fpn=False, backbone=False,
-                         compute_dtype=None):
+                         compute_dtype=None, half_storage=False):
     """``DetectionHead`` from a config: the reference's RPN factory keys (``MODEL.RPN.*_TEST``) and the given box head or a
     fresh ``TrackBoxHead``.  ``rpn_head``: True for a fresh ``rpn.RPNHead`` and the config's anchor generator
     (``MODEL.RPN.ANCHOR_*``, ``ASPECT_RATIOS``), an ``RPNHead`` to use that one, False / None for a head that starts at the
@@ -131,7 +131,8 @@ def build_detection_head(cfg, rpn_box_coder, in_channels, box_head=None, rpn_hea
     (``backbone.build_backbone``; it brings the pyramid, so ``fpn`` is not passed with it), a module with ``body`` and ``fpn``
     to use that one.  ``compute_dtype``: None, ``torch.float16`` or ``torch.bfloat16``: the half compute mode of whatever
     this builder creates itself — the fresh ``RPNHead``, ``build_fpn``'s pyramid, ``build_backbone``'s body and pyramid
-    (INTEGRATION.md §3q); modules passed in are left as they are."""
+    (INTEGRATION.md §3q); modules passed in are left as they are.  ``half_storage``: handed to the ``build_backbone`` this
+    builder creates itself (the body's maps between layers in ``compute_dtype``)."""
     if box_head is None:
         box_head = TrackBoxHead(cfg, in_channels).eval()
     head, generator = None, None
@@ -142,7 +143,7 @@ def build_detection_head(cfg, rpn_box_coder, in_channels, box_head=None, rpn_hea
     if backbone and fpn:
         raise ValueError("build_detection_head: a backbone brings its pyramid; pass `backbone` or `fpn`, not both")
     pyramid = (build_fpn(cfg, compute_dtype=compute_dtype) if fpn is True else fpn) if fpn else None
-    trunk = ((build_backbone(cfg, compute_dtype=compute_dtype, fpn_compute_dtype=compute_dtype) if backbone is True else backbone)
-             if backbone else None)
+    trunk = ((build_backbone(cfg, compute_dtype=compute_dtype, fpn_compute_dtype=compute_dtype, half_storage=half_storage)
+              if backbone is True else backbone) if backbone else None)
     return DetectionHead(make_rpn_postprocessor(cfg, rpn_box_coder, is_train=False).eval(), box_head, head, generator,
                          pyramid, trunk).eval()

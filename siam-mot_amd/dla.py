@@ -174,10 +174,20 @@ class DLA(nn.Module):
     with exact products and fp32 accumulation; the stem, the BN, the residuals and the maps between layers stay fp32, and
     ``out_dtype`` keeps its meaning.  It excludes ``operands="split16"`` (two answers to one question).  The torch
     composition ``dla_torch`` does not depend on it, exactly as it does not depend on ``operands``: CPU tensors and every
-    fallback give the bits of fp32 mode.  The ``state_dict`` and what ``kernel_ok`` admits do not depend on it either."""
+    fallback give the bits of fp32 mode.  The ``state_dict`` and what ``kernel_ok`` admits do not depend on it either.
+    ``half_storage`` (keyword-only, default False): a refinement of ``compute_dtype``, which it needs, with ``out_dtype``
+    given as that same type: the device path stores every map a tree convolution writes — block intermediates and outputs,
+    ``project`` outputs, roots, the four stage maps — in ``compute_dtype``, the fp32 epilogue value rounded once
+    (``ops.dla_half_storage``).  No convolution operand changes by a bit against half compute mode
+    (rounding a stored value again is idempotent, the max-pool commutes with the rounding); a residual that is a stored map
+    is added as the rounded value, and the returned stage maps ARE the stored maps (no copy, no second rounding).  The
+    stem and its output ``x1`` stay fp32.  The ``state_dict``, ``kernel_ok``, the packed weights (``ops.dla_half_pack``'s)
+    and the launches do not depend on it; CPU tensors and every fallback give fp32 mode's result ``.to(out_dtype)``.
+    NOT RECOMMENDED FOR SPEED: measured, it is 1.15 ... 1.86 x slower than half compute mode without it in every case
+    (DESIGN.md §7); what it buys is the smaller workspace and half stage maps for the pyramid without a conversion."""
 
     def __init__(self, levels, channels, out_dtype=torch.float32, operands="fp32", *, block="basic", residual_root=False,
-                 compute_dtype=None):
+                 compute_dtype=None, half_storage=False):
         super(DLA, self).__init__()
         if operands not in ops.DLA_OPERANDS:
             raise ValueError("DLA: operands must be \"fp32\" or \"split16\", got %r" % (operands,))
@@ -186,7 +196,13 @@ class DLA(nn.Module):
         if compute_dtype is not None and operands != "fp32":
             raise ValueError("DLA: compute_dtype=%r excludes operands=%r: the half compute mode and the split operands are two "
                              "answers to one question" % (compute_dtype, operands))
-        self.compute_dtype = compute_dtype
+        if half_storage and compute_dtype is None:
+            raise ValueError("DLA: half_storage=True needs compute_dtype=torch.float16 or torch.bfloat16: it stores the maps "
+                             "between layers in the compute type")
+        if half_storage and out_dtype is not compute_dtype:
+            raise ValueError("DLA: half_storage=True returns the stored maps themselves, so out_dtype must be given as the "
+                             "compute_dtype %r, got out_dtype=%r" % (compute_dtype, out_dtype))
+        self.compute_dtype, self.half_storage = compute_dtype, bool(half_storage)
         if block not in BLOCKS:
             raise ValueError("DLA: block must be \"basic\" or \"bottleneck\", got %r" % (block,))
         self.operands, self.block, self.residual_root = operands, block, bool(residual_root)
@@ -260,6 +276,9 @@ class DLA(nn.Module):
 
     def forward(self, images):
         if self.kernel_ok(images):
+            if self.compute_dtype is not None and self.half_storage:
+                return ops.dla_half_storage(images, self.packed(), self.levels, self.channels, self.compute_dtype, block=self.block,
+                                            residual_root=self.residual_root)
             if self.compute_dtype is not None:
                 return ops.dla_half(images, self.packed(), self.levels, self.channels, self.compute_dtype, block=self.block,
                                     residual_root=self.residual_root, out_dtype=self.out_dtype)
@@ -275,28 +294,29 @@ class DLA(nn.Module):
         return out
 
 
-def dla_34(out_dtype=torch.float32, operands="fp32", compute_dtype=None):
-    return DLA((1, 1, 1, 2, 2, 1), (16, 32, 64, 128, 256, 512), out_dtype=out_dtype, operands=operands, compute_dtype=compute_dtype)
+def dla_34(out_dtype=torch.float32, operands="fp32", compute_dtype=None, half_storage=False):
+    return DLA((1, 1, 1, 2, 2, 1), (16, 32, 64, 128, 256, 512), out_dtype=out_dtype, operands=operands, compute_dtype=compute_dtype,
+               half_storage=half_storage)
 
 
-def dla_46_c(out_dtype=torch.float32, operands="fp32", compute_dtype=None):
+def dla_46_c(out_dtype=torch.float32, operands="fp32", compute_dtype=None, half_storage=False):
     return DLA((1, 1, 1, 2, 2, 1), (16, 32, 64, 64, 128, 256), out_dtype=out_dtype, operands=operands, block="bottleneck",
-               compute_dtype=compute_dtype)
+               compute_dtype=compute_dtype, half_storage=half_storage)
 
 
-def dla_60(out_dtype=torch.float32, operands="fp32", compute_dtype=None):
+def dla_60(out_dtype=torch.float32, operands="fp32", compute_dtype=None, half_storage=False):
     return DLA((1, 1, 1, 2, 3, 1), (16, 32, 128, 256, 512, 1024), out_dtype=out_dtype, operands=operands, block="bottleneck",
-               compute_dtype=compute_dtype)
+               compute_dtype=compute_dtype, half_storage=half_storage)
 
 
-def dla_102(out_dtype=torch.float32, operands="fp32", compute_dtype=None):
+def dla_102(out_dtype=torch.float32, operands="fp32", compute_dtype=None, half_storage=False):
     return DLA((1, 1, 1, 3, 4, 1), (16, 32, 128, 256, 512, 1024), out_dtype=out_dtype, operands=operands, block="bottleneck",
-               residual_root=True, compute_dtype=compute_dtype)
+               residual_root=True, compute_dtype=compute_dtype, half_storage=half_storage)
 
 
-def dla_169(out_dtype=torch.float32, operands="fp32", compute_dtype=None):
+def dla_169(out_dtype=torch.float32, operands="fp32", compute_dtype=None, half_storage=False):
     return DLA((1, 1, 2, 3, 5, 1), (16, 32, 128, 256, 512, 1024), out_dtype=out_dtype, operands=operands, block="bottleneck",
-               residual_root=True, compute_dtype=compute_dtype)
+               residual_root=True, compute_dtype=compute_dtype, half_storage=half_storage)
 
 
 BODIES = {"DLA-34-FPN": dla_34, "DLA-46-C-FPN": dla_46_c, "DLA-60-FPN": dla_60, "DLA-102-FPN": dla_102, "DLA-169-FPN": dla_169}
@@ -304,7 +324,7 @@ BODIES = {"DLA-34-FPN": dla_34, "DLA-46-C-FPN": dla_46_c, "DLA-60-FPN": dla_60, 
 UNSUPPORTED_BODIES = ("DLA-46-XC-FPN", "DLA-60-RES2NET-FPN")
 
 
-def build_dla(cfg, out_dtype=torch.float32, operands="fp32", compute_dtype=None):
+def build_dla(cfg, out_dtype=torch.float32, operands="fp32", compute_dtype=None, half_storage=False):
     """The body of the config's ``MODEL.BACKBONE.CONV_BODY``: one of ``BODIES``.  Any other body, any true entry of
     ``MODEL.DLA.STAGE_WITH_DCN`` (deformable convolutions) and stage widths in ``MODEL.DLA.DLA_STAGE*_OUT_CHANNELS`` that
     are not the body's raise a ``ValueError`` that names the body or the entry."""
@@ -318,7 +338,7 @@ def build_dla(cfg, out_dtype=torch.float32, operands="fp32", compute_dtype=None)
     if any(dcn):
         raise ValueError("build_dla: MODEL.DLA.STAGE_WITH_DCN = %r asks for deformable convolutions, which this package does "
                          "not have" % (dcn,))
-    body = BODIES[name](out_dtype=out_dtype, operands=operands, compute_dtype=compute_dtype)
+    body = BODIES[name](out_dtype=out_dtype, operands=operands, compute_dtype=compute_dtype, half_storage=half_storage)
     dla = cfg.MODEL.DLA
     stages = (dla.DLA_STAGE2_OUT_CHANNELS, dla.DLA_STAGE3_OUT_CHANNELS, dla.DLA_STAGE4_OUT_CHANNELS, dla.DLA_STAGE5_OUT_CHANNELS)
     if tuple(stages) != tuple(body.out_channels):

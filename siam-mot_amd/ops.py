@@ -190,6 +190,13 @@ _SIGNATURES = {
     "smot_dla_conv1x1_half_form": (ctypes.c_int, [_i, _i, _i, _i]),
     "smot_dla_conv1x1_half_fwd": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp,
                                                  _vp, _i, _vp]),
+    # DLA bodies in half compute mode with the maps between layers stored in the compute type
+    "smot_dla_half_storage_ws_bytes": (ctypes.c_longlong, [_vp, _vp, _i, _i, _i, _i, _i, _i]),
+    "smot_dla_half_storage_fwd": (ctypes.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "smot_dla_conv3x3_half_storage_fwd": (ctypes.c_int, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i,
+                                                         _vp, _vp, _vp]),
+    "smot_dla_conv1x1_half_storage_fwd": (ctypes.c_int, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i,
+                                                         _i, _i, _i, _vp, _vp, _vp]),
     # FPN and RPN head in half compute mode: the fp32 twins' arguments + compute_type
     "smot_fpn_half_packed_floats": (ctypes.c_longlong, [_i, _vp, _i, _i]),
     "smot_fpn_half_pack": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
@@ -2133,6 +2140,133 @@ def dla_conv1x1_half(sources, pooled, w, scale, shift, relu, compute_dtype, resi
                                            _ptr(scale), _ptr(shift), Cout, 1 if relu else 0, _ptr(residual), rh, rw, ct,
                                            _ptr(packed), _ptr(out), FEAT_TYPES[out_dtype], ln.stream)
     _check(rc, "dla_conv1x1_half")
+    return out
+
+
+# ---- half storage: half compute mode with the maps between layers stored in ``compute_dtype`` (include/smot_emm.h, DLA
+# BACKBONE, HALF STORAGE).  A map is float32 or ``compute_dtype``; every result is ``compute_dtype``.
+def _dla_hs_map(t, name, compute_dtype, who):
+    t = _dev_feat(t, name)
+    if t.dtype is not torch.float32 and t.dtype is not compute_dtype:
+        raise RuntimeError("siammot_amd.%s: %s must be float32 or the compute type %s, got %s" % (who, name, compute_dtype, t.dtype))
+    return t
+
+
+def _shaped(t, name, shape):
+    if tuple(t.shape) != shape:
+        raise RuntimeError("siammot_amd: %s has shape %s, expected %s" % (name, tuple(t.shape), shape))
+    return t
+
+
+def dla_half_storage_ws_bytes(levels, channels, N, H, W, compute_dtype, block="basic", residual_root=False):
+    """The bytes of workspace ``dla_half_storage`` takes (``smot_dla_half_storage_ws_bytes``; no device needed): ``x1`` and the
+    stem's two full-resolution maps in fp32, the tree maps in two bytes per element, no fp32 twin of a returned map.  -1
+    exactly where ``dla_net_ws_bytes`` is."""
+    lib = _lib or load_library()
+    ct = _dla_ctype(compute_dtype, "dla_half_storage_ws_bytes")
+    return int(lib.smot_dla_half_storage_ws_bytes(_cast(_int6(levels)), _cast(_int6(channels)),
+                                                  _dla_block(block, "dla_half_storage_ws_bytes"), 1 if residual_root else 0, ct,
+                                                  int(N), int(H), int(W)))
+
+
+def dla_half_storage(images, packed, levels, channels, compute_dtype, block="basic", residual_root=False):
+    """``dla_half`` with every map a tree convolution writes stored in ``compute_dtype`` (``smot_dla_half_storage_fwd``): the
+    fp32 epilogue value rounded once (``tensor.to``'s rounding; an fp16 value beyond 65,504 is +-inf).  No convolution
+    operand changes by a bit against ``dla_half``; a residual that is a stored map is added as the rounded value, and the
+    four returned maps, of ``compute_dtype``, ARE the stored maps.  packed: ``dla_half_pack``'s tensor; the same launches."""
+    lib = _lib or load_library()
+    ct = _dla_ctype(compute_dtype, "dla_half_storage")
+    blk, rr = _dla_block(block, "dla_half_storage"), 1 if residual_root else 0
+    x = _dev_feat(images, "images")
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise RuntimeError("siammot_amd.dla_half_storage: images has shape %s, expected [N, 3, H, W]" % (tuple(x.shape),))
+    N, H, W = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+    lv, ch = _int6(levels), _int6(channels)
+    nbytes = lib.smot_dla_half_storage_ws_bytes(_cast(lv), _cast(ch), blk, rr, ct, N, H, W)
+    if nbytes < 0:
+        _check(-2, "dla_half_storage")
+    ws = torch.empty((max(nbytes // 4, 4),), dtype=_F32, device=x.device)
+    out = [torch.empty((N, int(channels[k]), H >> k, W >> k), dtype=compute_dtype, device=x.device) for k in range(2, 6)]
+    po = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in out])
+    with _Launch(x, packed) as ln:
+        rc = lib.smot_dla_half_storage_fwd(_ptr(x), FEAT_TYPES[x.dtype], N, H, W, _cast(lv), _cast(ch), blk, rr, ct, _ptr(packed),
+                                           _ptr(ws), _cast(po), ln.stream)
+    _check(rc, "dla_half_storage")
+    return out
+
+
+def dla_conv3x3_half_storage(x, w, scale, shift, stride, compute_dtype, residual=None, relu=True, residual_pooled=False):
+    """``dla_conv3x3_half`` in half storage (``smot_dla_conv3x3_half_storage_fwd``): ``x`` and ``residual`` each float32 or
+    ``compute_dtype``; -> ``compute_dtype``: bit for bit ``dla_conv3x3_half(x.float(), ..., residual.float(), ...)
+    .to(compute_dtype)``."""
+    lib = _lib or load_library()
+    who = "dla_conv3x3_half_storage"
+    ct = _dla_ctype(compute_dtype, who)
+    x = _dla_hs_map(x, "x", compute_dtype, who)
+    N, Cin, H, W = (int(v) for v in x.shape)
+    Cout = int(w.shape[0])
+    w = _chk(w, "w", (Cout, Cin, 3, 3))
+    scale, shift = _chk(scale, "scale", (Cout,)), _chk(shift, "shift", (Cout,))
+    Ho, Wo = ((H - 1) // 2 + 1, (W - 1) // 2 + 1) if stride == 2 else (H, W)
+    rh = rw = 0
+    if residual is not None:
+        residual = _dla_hs_map(residual, "residual", compute_dtype, who)
+        if residual_pooled:
+            rh, rw = int(residual.shape[-2]), int(residual.shape[-1])
+        _shaped(residual, "residual", (N, Cout, rh, rw) if residual_pooled else (N, Cout, Ho, Wo))
+    n = lib.smot_dla_conv_half_packed_floats(3, Cin, Cout)
+    packed = torch.empty((max(n, 4),), dtype=_F32, device=x.device)
+    out = torch.empty((N, Cout, Ho, Wo), dtype=compute_dtype, device=x.device)
+    with _Launch(x, w, scale, shift, residual) as ln:
+        rc = lib.smot_dla_conv3x3_half_storage_fwd(_ptr(x), FEAT_TYPES[x.dtype], N, Cin, H, W, _ptr(w), _ptr(scale), _ptr(shift),
+                                                   Cout, int(stride), _ptr(residual),
+                                                   FEAT_TYPES[residual.dtype] if residual is not None else 0, rh, rw,
+                                                   1 if relu else 0, ct, _ptr(packed), _ptr(out), ln.stream)
+    _check(rc, who)
+    return out
+
+
+def dla_conv1x1_half_storage(sources, pooled, w, scale, shift, relu, compute_dtype, residual=None, residual_pooled=False):
+    """``dla_conv1x1_half`` in half storage (``smot_dla_conv1x1_half_storage_fwd``): the sources all float32 or all
+    ``compute_dtype``, ``residual`` of either; -> ``compute_dtype``: bit for bit ``dla_conv1x1_half`` on the widened sources
+    and residual, ``.to(compute_dtype)``."""
+    lib = _lib or load_library()
+    who = "dla_conv1x1_half_storage"
+    ct = _dla_ctype(compute_dtype, who)
+    S = len(sources)
+    if S < 1 or len(pooled) != S:
+        raise RuntimeError("siammot_amd.%s: %d sources, %d pooled flags" % (who, S, len(pooled)))
+    src = [_dla_hs_map(t, "sources[%d]" % s, compute_dtype, who) for s, t in enumerate(sources)]
+    if any(t.dtype is not src[0].dtype for t in src):
+        raise RuntimeError("siammot_amd.%s: the sources of one call have one type, got %s" % (who, [t.dtype for t in src]))
+    N = int(src[0].shape[0])
+    H, W = (int(src[0].shape[2]) // 2, int(src[0].shape[3]) // 2) if pooled[0] else (int(src[0].shape[2]), int(src[0].shape[3]))
+    K = sum(int(t.shape[1]) for t in src)
+    Cout = int(w.shape[0])
+    w = _chk(w.reshape(Cout, -1), "w", (Cout, K))
+    scale, shift = _chk(scale, "scale", (Cout,)), _chk(shift, "shift", (Cout,))
+    for s, t in enumerate(src):
+        if t.dim() != 4 or t.shape[0] != N:
+            raise RuntimeError("siammot_amd.%s: sources[%d] has shape %s" % (who, s, tuple(t.shape)))
+    rh = rw = 0
+    if residual is not None:                                     # (a pooled residual's size is the library's to check)
+        residual = _dla_hs_map(residual, "residual", compute_dtype, who)
+        if residual_pooled:
+            rh, rw = int(residual.shape[-2]), int(residual.shape[-1])
+        _shaped(residual, "residual", (N, Cout, rh, rw) if residual_pooled else (N, Cout, H, W))
+    arr = lambda vals: (ctypes.c_int * S)(*[int(v) for v in vals])
+    sp = (ctypes.c_void_p * S)(*[t.data_ptr() for t in src])
+    sc, sf = arr(t.shape[1] for t in src), arr(1 if f else 0 for f in pooled)
+    sh, sw = arr(t.shape[2] for t in src), arr(t.shape[3] for t in src)
+    n = lib.smot_dla_conv_half_packed_floats(1, K, Cout)
+    packed = torch.empty((max(n, 4),), dtype=_F32, device=src[0].device)
+    out = torch.empty((N, Cout, H, W), dtype=compute_dtype, device=src[0].device)
+    with _Launch(*(src + [w, scale, shift, residual])) as ln:
+        rc = lib.smot_dla_conv1x1_half_storage_fwd(_cast(sp), FEAT_TYPES[src[0].dtype], _cast(sc), _cast(sf), _cast(sh), _cast(sw),
+                                                   S, N, H, W, _ptr(w), _ptr(scale), _ptr(shift), Cout, 1 if relu else 0,
+                                                   _ptr(residual), FEAT_TYPES[residual.dtype] if residual is not None else 0,
+                                                   rh, rw, ct, _ptr(packed), _ptr(out), ln.stream)
+    _check(rc, who)
     return out
 
 
