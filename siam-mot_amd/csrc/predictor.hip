@@ -633,7 +633,11 @@ int predictor_impl(const float* resp, int N, int C, int Ho, const float* cls_tow
     H.reg_w = reg_w;
     H.reg_b = reg_b;
     const size_t hsmem = (size_t)H_IC * (Ho + 2) * (Ho + 2) * sizeof(float);
-    SMOT_REQUIRE(hsmem <= 64 * 1024, "predictor: Ho=%d too large for the heads kernel", Ho);
+    SMOT_REQUIRE(hsmem <= 160 * 1024, "predictor: Ho=%d too large for the heads kernel", Ho);
+    if (hsmem > 64 * 1024) {             // Ho = 31, 32 (the entry guard admits 1024 positions): 69,696 and 73,984 B
+        const int rco = ensure_lds_optin(reinterpret_cast<const void*>(&heads_kernel<1>), hsmem, "predictor heads");
+        if (rco) return rco;
+    }
     // one position per thread, position chunks of 256 on grid z: 4x the workgroups of the former 4-positions-per-
     // thread form for a 29x29 map (60 workgroups left three quarters of the chip idle: 177 us)
     hipLaunchKernelGGL(heads_kernel<1>, dim3(N, 2, (Ho * Ho + 255) / 256), dim3(256), hsmem, st,

@@ -97,7 +97,7 @@ xcorr_dw_patch2_kernel(const float* __restrict__ x, const float* __restrict__ z,
 // per plane, thread = (output row, group of four output columns).  The template's RZ*RZ taps live in registers; a
 // window row is read once per thread as 4 + RZ - 1 contiguous floats (LDS rows padded to a multiple of four floats,
 // zero filled) and feeds 4 * RZ FMAs — 0.4 LDS reads per FMA instead of the generic kernel's two.  Taps accumulate
-// u-major / v-minor in one fmaf chain per output: the generic kernel's (and the oracle's) order, bit for bit.
+// u-major / v-minor in one fmaf chain per output: the oracle's order (and the two-planes-per-wave kernel's), bit for bit.
 template <int RX, int RZ>
 __global__ void __launch_bounds__(256)
 xcorr_dw_rowpatch_kernel(const float* __restrict__ x, const float* __restrict__ z, float* __restrict__ out) {
@@ -146,7 +146,10 @@ xcorr_dw_rowpatch_kernel(const float* __restrict__ x, const float* __restrict__ 
         if (4 * jq + o < HO) dst[o] = acc[o];
 }
 
-// Any (Rx, Rz): one workgroup per plane, plane and template in LDS, one thread per output.
+// Any (Rx, Rz): one workgroup per plane, plane and template in LDS, one thread per output.  Every template row is its own
+// fmaf chain and the RZ row sums are added in row order: the rounding error grows with 2 RZ steps instead of RZ * RZ (one
+// chain over 225 taps of smooth, pooled planes reaches 1.06e-6 * sum |x z|, above the 1e-6 the project states for this
+// operator; the row form stays below 3e-7 there).  Exact data, NaN / inf and zero planes come out as from one chain.
 __global__ void __launch_bounds__(256)
 xcorr_dw_generic_kernel(const float* __restrict__ x, const float* __restrict__ z,
                         float* __restrict__ out, int RX, int RZ) {
@@ -163,8 +166,11 @@ xcorr_dw_generic_kernel(const float* __restrict__ x, const float* __restrict__ z
     for (int o = threadIdx.x; o < HO * HO; o += blockDim.x) {
         const int i = o / HO, j = o - i * HO;
         float acc = 0.0f;
-        for (int u = 0; u < RZ; ++u)
-            for (int v = 0; v < RZ; ++v) acc = fmaf(xs[(i + u) * RX + j + v], zs[u * RZ + v], acc);
+        for (int u = 0; u < RZ; ++u) {
+            float row = 0.0f;
+            for (int v = 0; v < RZ; ++v) row = fmaf(xs[(i + u) * RX + j + v], zs[u * RZ + v], row);
+            acc += row;
+        }
         out[plane * HO * HO + o] = acc;
     }
 }
@@ -198,6 +204,10 @@ extern "C" int smot_xcorr_dw_fwd(const float* x, const float* z, float* out, int
     } else {
         const size_t smem = (size_t)(Rx * Rx + Rz * Rz) * sizeof(float);
         SMOT_REQUIRE(smem <= 160 * 1024, "xcorr: plane too large for LDS (Rx=%d Rz=%d)", Rx, Rz);
+        if (smem > 64 * 1024) {              // above the default dynamic-LDS limit of a launch: opt in, as the other launch sites do
+            const int rco = ensure_lds_optin(reinterpret_cast<const void*>(&xcorr_dw_generic_kernel), smem, "xcorr");
+            if (rco) return rco;
+        }
         SMOT_LAUNCH(xcorr_dw_generic_kernel, dim3(planes), dim3(256), smem, st, x, z, out, Rx, Rz);
     }
     timer_mark(0, 1, st);
